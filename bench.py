@@ -8,7 +8,13 @@ over 1 000 synthetic segments per GPU that are already resident in HBM (BASELINE
 configs[1]); with N > 1 each rank owns its own 1 000-segment shard (weak scaling) and the only
 collective is the gather of the packed top-k rows to rank 0.  Prints ONE JSON line on rank 0.
 
-`value` is the first timed region of exactly K steps (barrier + synchronise on both sides, max over ranks);
+`value` is the first timed region of exactly K steps (barrier + synchronise on both sides, max over ranks) and
+`ms_per_step` the milliseconds one of its steps took.  A plain run does only that: set-up, warm-up, the K timed steps
+and the line.  `--dump-outputs DIR` then writes what the last timed step computed (logits, top-k indices and
+confidences) as DIR/<name>.npy, float32 / float64, so that two builds can be compared output for output on
+identical seeded inputs.
+
+The fields of this paragraph come with `--full` only (the first region then also carries the HIP profiling events):
 `repeats` holds four more K-step regions and the median of the five.
 `roofline` is the dominant kernel (largest total time in the timed region): one of the fused
 MBConv kernels, priced in ALGORITHMIC flops (2 x MACs of the block's expand + depthwise +
@@ -152,9 +158,9 @@ class ClockSampler:
 
 def c4_child_leg(precision):
     """The Perch-sized model (BASELINE configs[3]) in a process of its own, bounded to a few steps, so that the DRIVER's line times it
-    (VERDICT r5 next #3: C4 numbers were builder-side only): `bench.py --config c4 --steps 5 --warmup 2` without its extra legs."""
+    (VERDICT r5 next #3: C4 numbers were builder-side only): `bench.py --config c4 --steps 5 --warmup 2 --full` without its extra legs."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", "c4", "--steps", "5", "--warmup", "2", "--no-extra-legs", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", "c4", "--steps", "5", "--warmup", "2", "--full", "--no-extra-legs", "--no-cpu-baseline"]
     if precision in ("auto", "f16x3", "f32"):
         cmd += ["--precision", precision]
     t0 = time.perf_counter()
@@ -164,7 +170,7 @@ def c4_child_leg(precision):
         d = json.loads(line)
         return {"value": d["value"], "unit": d["unit"], "metric": d["metric"], "steps": d["steps"], "ms_per_step": d["ms_per_step"],
                 "median_of_5": d["repeats"]["median_of_5"], "fused_blocks": d["config"]["fused_blocks"], "roofline": d.get("roofline"),
-                "wall_s": round(time.perf_counter() - t0, 1), "what": "bench.py --config c4 --steps 5 --warmup 2 in a child process: " + d["config"]["workload"]}
+                "wall_s": round(time.perf_counter() - t0, 1), "what": "bench.py --config c4 --steps 5 --warmup 2 --full in a child process: " + d["config"]["workload"]}
     except Exception as e:   # noqa: BLE001 -- the headline line must not die with this leg
         return {"value": None, "error": str(e)[:200], "wall_s": round(time.perf_counter() - t0, 1)}
 
@@ -531,6 +537,29 @@ def analyse(clf, m, info, fused, stage_tot, layer_tot, segs_done, steps, slices_
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def write_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy (float32 / float64).  Beyond DUMP_LIMIT_BYTES in all, the largest
+    array keeps a fixed seeded sample of its rows, and DIR/<name>_rows.npy says which rows those are."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    assert all(v.dtype in (np.float32, np.float64) for v in arrays.values())
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        big = max(arrays, key=lambda k: arrays[k].nbytes)
+        v = arrays[big]
+        room = DUMP_LIMIT_BYTES - (total - v.nbytes) - 4096
+        keep = max(1, min(v.shape[0], room // (v.nbytes // v.shape[0] + 8)))
+        rows = np.sort(np.random.default_rng(0).choice(v.shape[0], size=keep, replace=False))
+        arrays[big] = v[rows]
+        arrays[big + "_rows"] = rows.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+
+
 def torch_gather_rows(rows, n_total, rank, world, on_host):
     """The one collective of the path: packed int32 top-k rows of every rank to rank 0, in segment order
     (all_gather_into_tensor over RCCL; gloo gather in the CPU tests and the 1-GPU dry run)."""
@@ -705,8 +734,13 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--micro-batch", type=int, default=int(os.environ.get("BIRDA_HIP_MICRO_BATCH", "1000")))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the f32, H2D-inclusive and end-to-end legs (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline region: four more regions, clocks, rooflines and per-stage times, the extra legs and the "
+                         "CPU baseline (a plain run does set-up, warm-up, the timed steps and the line only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the f32, H2D-inclusive and end-to-end legs (profiling runs)")
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c4", "c5"],
                     help="BASELINE.json configs: c2 = configs[1] (the bench line), c3 = 10 000 segments as 8 shards through bh_multi_*, "
                          "c4 = Perch-sized model, c5 = mixed-rate input -> resampler -> f16 MFMA")
@@ -841,6 +875,8 @@ def main():
         else:
             forward_all(x.data_ptr())
 
+    gathered = {"rows": None}      # rank 0: the packed top-k rows of the whole job, as the last step's gather returned them
+
     def step():
         local_step()
         if world > 1:
@@ -856,7 +892,7 @@ def main():
                 read = torch.cuda.Event()
                 read.record(cur)
                 ctx_stream.wait_event(read)               # the next forward's top-k must not overwrite them earlier
-            torch_gather_rows(packed.cpu() if dryrun else packed, n_total, rank, world, dryrun)
+            gathered["rows"] = torch_gather_rows(packed.cpu() if dryrun else packed, n_total, rank, world, dryrun)
 
     def sync_all():
         ctx.synchronize()
@@ -889,21 +925,35 @@ def main():
         step()
     sync_all()
 
-    ctx.set_profiling(True)     # HIP events around every launch, on the context stream
-    with ClockSampler(local_rank) as clocks:      # which mode the box is in WHILE the contract's region runs (host-side sysfs reads)
-        elapsed = timed_region(args.steps)
-    stage_tot = {k: [ms, n] for k, (ms, n) in ctx.stage_ms().items()}
-    layer_tot = [[ms, n] for (ms, n) in ctx.layer_ms()]
-    ctx.set_profiling(False)
-    # four more K-step regions: median of 5; `value` stays the first, the contract's region
-    more = [timed_region(args.steps) for _ in range(4)]
-    all_values = [n_total * args.steps / e for e in [elapsed] + more]
-
-    if args.config == "c5":
-        first = logits[inv[:16]].cpu().numpy()            # list order
+    if args.full:
+        ctx.set_profiling(True)     # HIP events around every launch, on the context stream
+        with ClockSampler(local_rank) as clocks:      # which mode the box is in WHILE the contract's region runs (host-side sysfs reads)
+            elapsed = timed_region(args.steps)
+        stage_tot = {k: [ms, n] for k, (ms, n) in ctx.stage_ms().items()}
+        layer_tot = [[ms, n] for (ms, n) in ctx.layer_ms()]
+        ctx.set_profiling(False)
     else:
-        first = logits[:64].cpu().numpy()                 # every distinct segment of the timed batch
-    hip_logits = {args.precision: first} if rank == 0 else None   # segments 0.. of the global list
+        elapsed = timed_region(args.steps)
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left in the result buffers, in the order of the segment list
+        order_ = inv if args.config == "c5" else slice(None)
+        arrays = {"topk_index": tk_idx[order_].cpu().numpy().astype(np.float64), "topk_confidence": tk_conf[order_].cpu().numpy()}
+        if args.config != "c3":       # (c3's logits are one micro-batch of scratch rows; its callers receive the top-k rows)
+            arrays["logits"] = logits[order_].cpu().numpy()
+        if gathered["rows"] is not None:
+            rows = gathered["rows"].cpu()
+            arrays["gathered_topk_index"] = rows[:, :5].numpy().astype(np.float64)
+            arrays["gathered_topk_confidence"] = rows[:, 5:].contiguous().view(torch.float32).numpy()
+        write_outputs(args.dump_outputs, arrays)
+    if args.full:
+        # four more K-step regions: median of 5; `value` stays the first, the contract's region
+        more = [timed_region(args.steps) for _ in range(4)]
+        all_values = [n_total * args.steps / e for e in [elapsed] + more]
+        if args.config == "c5":
+            first = logits[inv[:16]].cpu().numpy()            # list order
+        else:
+            first = logits[:64].cpu().numpy()                 # every distinct segment of the timed batch
+        hip_logits = {args.precision: first} if rank == 0 else None   # segments 0.. of the global list
     value = n_total * args.steps / elapsed
     segs_done = n_local * args.steps
     slices_per_step = max(1, -(-n_local // args.micro_batch))
@@ -926,17 +976,18 @@ def main():
                    "segments_per_gpu": n_local, "micro_batch": args.micro_batch, "pre_warm_s": round(pre_warm_s, 2),
                    "gflop_per_segment": round((2 * info.macs_per_segment + info.mel_flops_per_segment) / 1e9, 3),
                    "fused_blocks": len(fused), "precision": args.precision, "dtype_note": DTYPE[args.precision],
-                   **clocks.summary(),
+                   **(clocks.summary() if args.full else {}),
                    "gemm": {"f32": "v_mfma_f32_16x16x4_f32 (exact f32 fmaf chains)",
                             "f16x3": "f32 operands split into f16 hi + lo, 3 x v_mfma_f32_16x16x32_f16 per product, f32 "
                                      "accumulate (|err| ~1e-7 of sum|a b|, same fp32 logit tolerance as the f32 MFMA path, "
                                      "tests/test_parity_gpu.py)",
                             "f16": "operands rounded to f16, v_mfma_f32_16x16x32_f16, f32 accumulate"}["f16x3" if args.precision == "auto" else args.precision]},
-        "repeats": {"values": [round(v, 1) for v in all_values], "median_of_5": round(statistics.median(all_values), 1),
-                    "note": "five regions of exactly --steps steps each; `value` is the first"},
     }
-    out.update(analyse(clf, m, info, fused, stage_tot, layer_tot, segs_done, args.steps, slices_per_step, args.precision))
-    extra = rank == 0 and world == 1 and not args.no_extra_legs
+    if args.full:
+        out["repeats"] = {"values": [round(v, 1) for v in all_values], "median_of_5": round(statistics.median(all_values), 1),
+                          "note": "five regions of exactly --steps steps each; `value` is the first"}
+        out.update(analyse(clf, m, info, fused, stage_tot, layer_tot, segs_done, args.steps, slices_per_step, args.precision))
+    extra = args.full and rank == 0 and world == 1 and not args.no_extra_legs
     if extra and args.config in ("c2", "c4"):
         # what birda's own batch sizes reach (-b 1..512, constants.rs:44,55; bh_default_batch_size = 256): the same 1 000 resident
         # segments through micro-batches of 256 and 512
@@ -977,12 +1028,12 @@ def main():
         f32.update(analyse(clf, m, info, clf.fused_blocks(), st2, ly2, n_local * args.steps, args.steps, slices_per_step, "f32"))
         out["f32_mfma_path"] = f32
         hip_logits["f32"] = logits[:64].cpu().numpy()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if args.config == "c5":       # the checker's path for this workload: oracle resampler -> oracle forward on the first segments
             out["cpu_baseline"] = cpu_baseline_c5(model_path, m, hip_logits)
         else:
             out["cpu_baseline"] = cpu_baseline(model_path, m.sample_count, m.sample_rate, hip_logits)
-    elif rank == 0:
+    elif args.full and rank == 0:
         out["cpu_baseline"] = None
     ctx.close()
     clf.close()
@@ -1028,6 +1079,19 @@ def cpu_baseline_c5(model_path, m, hip_logits):
             "max_abs_dlogit_vs_oracle": parity}
 
 
+def dump_results(out_dir, c_res, n):
+    """--dump-outputs for the bh_multi_* path: the bh_result rows of one step as arrays (entries past n_pred: index -1, 0)."""
+    import numpy as np
+    from birda_amd._lib import BH_MAX_TOP_K
+    rec = np.frombuffer(c_res, dtype=np.dtype([("n_pred", "<u4"), ("index", "<i4", BH_MAX_TOP_K), ("confidence", "<f4", BH_MAX_TOP_K)]),
+                        count=n)
+    valid = np.arange(BH_MAX_TOP_K)[None, :] < rec["n_pred"][:, None]
+    k = max(1, int(rec["n_pred"].max()))
+    write_outputs(out_dir, {"n_pred": rec["n_pred"].astype(np.float64),
+                            "topk_index": np.where(valid, rec["index"], -1)[:, :k].astype(np.float64),
+                            "topk_confidence": np.where(valid, rec["confidence"], 0.0).astype(np.float32)[:, :k]})
+
+
 def bench_inproc_multi(args, m, model_path, tmp, devices, n_total, scaling, workload):
     """Several shards in ONE process through the C ABI (bh_multi_forward_device: one host thread + context + stream per
     shard, packed top-k gather by RCCL all-gather when every shard has its own device, else hipMemcpyDtoH per shard).
@@ -1065,14 +1129,14 @@ def bench_inproc_multi(args, m, model_path, tmp, devices, n_total, scaling, work
     def sync_all():
         for d in sorted(set(devices)):
             torch.cuda.synchronize(d)
-    res = mc.forward_device(ptrs, counts)
+    res = mc.forward_device(ptrs, counts) if args.full else None
     pre_warm_s = pre_warm(step, sync_all)      # the chips at their sustained clock before the contract's region (see main())
     for _ in range(max(1, args.warmup)):
         step()
     clf0, ctx0 = mc.shard_classifier(0), mc.shard_context(0)
     vals, stage_tot, layer_tot = [], None, None
-    for rep in range(5):
-        if rep == 0:
+    for rep in range(5 if args.full else 1):
+        if rep == 0 and args.full:
             ctx0.set_profiling(True)     # HIP events around shard 0's launches, on its own stream
         sync_all()
         t0 = time.perf_counter()
@@ -1080,7 +1144,9 @@ def bench_inproc_multi(args, m, model_path, tmp, devices, n_total, scaling, work
             step()
         sync_all()
         vals.append(n_total * args.steps / (time.perf_counter() - t0))
-        if rep == 0:
+        if rep == 0 and args.dump_outputs:      # the bh_result rows the last timed step unpacked, in segment order
+            dump_results(args.dump_outputs, c_res, n_total)
+        if rep == 0 and args.full:
             stage_tot = {k: [ms, n] for k, (ms, n) in ctx0.stage_ms().items()}
             layer_tot = [[ms, n] for (ms, n) in ctx0.layer_ms()]
             ctx0.set_profiling(False)
@@ -1094,10 +1160,14 @@ def bench_inproc_multi(args, m, model_path, tmp, devices, n_total, scaling, work
                       "gather_backend": mc.gather_backend(), "precision": args.precision,
                       "gflop_per_segment": round((2 * mc.info.macs_per_segment + mc.info.mel_flops_per_segment) / 1e9, 3),
                       "note": ("one shard per GPU" if n_gpus == G else
-                               "shards that share a GPU are logical devices: this measures the sharding machinery, not multi-GPU scaling")},
-           "repeats": {"values": [round(v, 1) for v in vals], "median_of_5": round(statistics.median(vals), 1),
-                       "note": "five regions of exactly --steps steps each; `value` is the first (the one that carries the profiling events)"},
-           "checks": {"results": len(res), "segments_with_predictions": sum(1 for r in res if r.predictions)}}
+                               "shards that share a GPU are logical devices: this measures the sharding machinery, not multi-GPU scaling")}}
+    if not args.full:
+        mc.close()
+        print(json.dumps(out), flush=True)
+        return
+    out["repeats"] = {"values": [round(v, 1) for v in vals], "median_of_5": round(statistics.median(vals), 1),
+                      "note": "five regions of exactly --steps steps each; `value` is the first (the one that carries the profiling events)"}
+    out["checks"] = {"results": len(res), "segments_with_predictions": sum(1 for r in res if r.predictions)}
     fused = clf0.fused_blocks()
     out.update(analyse(clf0, m, mc.info, fused, stage_tot, layer_tot, counts[0] * args.steps, args.steps,
                        max(1, -(-counts[0] // max_batch)), args.precision))

@@ -23,7 +23,7 @@ swap_in() { cp birda_amd/libbirda_hip.so /tmp/libbirda_hip_keep.so; cp "$1" bird
 swap_out() { cp /tmp/libbirda_hip_keep.so birda_amd/libbirda_hip.so; }
 [ -n "$LIBX" ] && [ "$mode" != lib ] && swap_in tools/ab/libbirda_hip_x.so
 row() {   # label -> one line: value, median of five, mel, mbconv, per-block times
-  python bench.py --no-cpu-baseline --no-extra-legs --steps ${STEPS:-10} --warmup 2 $BENCH_ARGS "${@:2}" 2>/tmp/ab_err.txt | python -c "
+  python bench.py --full --no-cpu-baseline --no-extra-legs --steps ${STEPS:-10} --warmup 2 $BENCH_ARGS "${@:2}" 2>/tmp/ab_err.txt | python -c "
 import json,sys
 t=sys.stdin.read()
 if not t.strip(): print('$1 | bench.py FAILED:', open('/tmp/ab_err.txt').read()[-300:].replace(chr(10),' '), file=sys.stderr); sys.exit(0)
@@ -58,7 +58,7 @@ libs) # tools/ab.sh libs tagA tagB ...: tools/ab/libbirda_hip_<tag>.so in turn (
       for rep in $(seq 1 ${REPS:-2}); do for tag in "$@"; do cp tools/ab/libbirda_hip_$tag.so birda_amd/libbirda_hip.so; row $tag; done; done
       cp /tmp/libbirda_hip_new.so birda_amd/libbirda_hip.so; medians ;;
 legs) for set in "$@"; do
-        env $set python bench.py --no-cpu-baseline --steps ${STEPS:-5} --warmup 2 $BENCH_ARGS 2>/dev/null | python -c "
+        env $set python bench.py --full --no-cpu-baseline --steps ${STEPS:-5} --warmup 2 $BENCH_ARGS 2>/dev/null | python -c "
 import json,sys
 d=json.load(sys.stdin); h=d.get('h2d_inclusive',{}); e=d.get('end_to_end',{})
 g=lambda x,k: round(x[k]['value']) if isinstance(x.get(k),dict) and 'value' in x[k] else None
