@@ -241,6 +241,11 @@ HOST_SYMBOLS = [
     ("bhh_project_scores", C.c_int, [_VP, _SZ, _VP, _VP, _SZ, _VP, _SZ, C.c_float, _VP, C.POINTER(_SZ), C.POINTER(_SZ)]),
 ]
 
+# include/birda_hip_audit.h: the plans the library makes at create, for the tests that hold them to the forward pass
+AUDIT_SYMBOLS = [
+    ("bh_audit_arena_plan", C.c_int, [_VP, _VP, _SZ, _VP, _VP, _VP, _SZ]),
+]
+
 _lib = None
 
 
@@ -253,7 +258,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

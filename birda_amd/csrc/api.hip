@@ -136,7 +136,7 @@ int ctx_create(bh_classifier *c, size_t max_batch, bool keep, bh_batch_context *
     HIPCHK(hipMalloc((void **)&ctx->d_input, in_bytes));
     HIPCHK(hipMalloc((void **)&ctx->d_minmax, max_batch * 16 * sizeof(float)));
     HIPCHK(hipMalloc((void **)&ctx->d_inbad, max_batch * 8 * sizeof(unsigned)));
-    plan_arena(m, c->fused_at, c->se, c->head_gap, max_batch, keep, ctx->t_off, ctx->arena_floats);
+    plan_arena(m, c->fused_at, c->se, c->head_gap, c->gap_gate, max_batch, keep, ctx->t_off, ctx->arena_floats);
     // (slack for the lanes: the plans of a slice's sub-slices, side by side, exceed the whole slice's plan by up to 64 floats of
     //  alignment per tensor and sub-plan; the automatic split makes up to 9 sub-slices, bh_batch_context_set_sub_slices more --
     //  16 sub-plans fit, beyond that lanes_begin falls back to one stream and counts it: bh_batch_context_lane_fallbacks)
@@ -208,9 +208,6 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
     float *const d_minmax = ctx->d_minmax + (lane ? lane->seg0 * 16 : 0);
     unsigned *const d_inbad = ctx->d_inbad + (lane ? lane->seg0 * 8 : 0);
     auto T = [&](uint32_t t) { return arena + t_off[t]; };
-#ifndef BH_SE_GATE16_MIN
-#define BH_SE_GATE16_MIN 577
-#endif
     const uint32_t nl = (uint32_t)m.layers.size();
     bh::TraceRange tr_slice("bh_forward_slice");   // ROCTx ranges (BIRDA_HIP_ROCTX=1): the slice, its front end, every layer group
     ctx_mark(ctx, -1);
@@ -248,6 +245,26 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
                 // never exists; D crosses HBM once each way.
                 const auto &S = c->se[c->fused_at[i]];
                 const auto &G1 = m.layers[S.iPw1], &G2 = m.layers[S.iPw2], &LP = m.layers[S.iP];
+                // (the gate: one launch, a workgroup per segment (se_gate_kernel), or the pool + the two dense layers as GEMMs over all
+                //  segments, through the arena slots of the layers they stand for.  Either way every sum runs in a fixed order.)
+                // (which of the two a BLOCK takes depends on its width alone, never on the launch: up to 576 expanded channels the
+                //  one-launch kernel is the faster one -- three launches cost ~27 us per 1 000 segments whatever their size, measured
+                //  13-36 against 27-50 us; beyond, its per-segment re-read of both weight matrices is: 59-490 against 37-143 us)
+                // (round 6: beyond 576 channels two launches of sixteen-segment workgroups -- the pooled rows x W1 split over channel
+                //  slices, then hidden x W2 -- instead of pool + two GEMMs of a handful of tiles: kernels_conv.hip se_hidden_kernel)
+                // (one selection for whole launches and for the groups below: a segment's bits do not depend on how its launch is cut)
+                static const bool gate1 = [] { const char *e = BH_XENV("BIRDA_HIP_SE_GATE1"); return e && e[0] == '1'; }();
+                auto launch_gate = [&](const float *part, int tiles, int P, float *pooled, float *hidden, float *gate, size_t ns) {
+                    if (!gate1 && d.Cexp >= BH_SE_GATE16_MIN && bh::se_gate16_supports(d.Cexp, (int)G1.cout))
+                        bh::launch_se_gate16(part, tiles, P, pooled, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
+                                             c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+                    else if (!gate1 && d.Cexp > 576)
+                        bh::launch_se_gate_gemm(part, tiles, P, pooled, hidden, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
+                                                c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+                    else
+                        bh::launch_se_gate(part, tiles, P, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
+                                           c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+                };
                 // Round 6 (VERDICT r5 next #3a): a block whose D is large -- the early stages: 1.5-2.3 MB a segment -- runs its three
                 // launches per GROUP of segments, so that the D pass A writes is still in the 256 MB Infinity Cache when the gated
                 // project GEMM reads it (at 1 000 segments a launch it crosses HBM both ways).  The tiling -- hence every pooled sum's
@@ -274,14 +291,7 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
                             g.dblk = blocked;
                             bh::launch_mbconv(g, (int)ng, s);
                             float *gg = gate + s0 * d.Cexp;
-                            static const bool gate1g = [] { const char *e = BH_XENV("BIRDA_HIP_SE_GATE1"); return e && e[0] == '1'; }();
-                            if (!gate1g && d.Cexp > 576)
-                                bh::launch_se_gate_gemm(g.pool_part, (int)tiles, (int)P, T(S.iGap + 1) + s0 * d.Cexp, T(S.iPw1 + 1) + s0 * G1.cout, c->d_w[S.iPw1], c->d_blob + G1.b_off,
-                                                        c->ldw[S.iPw1], (int)G1.act, c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gg, (int)ng,
-                                                        d.Cexp, (int)G1.cout, s);
-                            else
-                                bh::launch_se_gate(g.pool_part, (int)tiles, (int)P, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
-                                                   c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gg, (int)ng, d.Cexp, (int)G1.cout, s);
+                            launch_gate(g.pool_part, (int)tiles, (int)P, T(S.iGap + 1) + s0 * d.Cexp, T(S.iPw1 + 1) + s0 * G1.cout, gg, ng);
                             float *yg = y + s0 * P * d.Cout;
                             const float *rg = r ? r + s0 * P * d.Cout : nullptr;
                             if (c->d_w16[S.iP])
@@ -314,25 +324,7 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
                 ctx_mark(ctx, ST_MBCONV, (int)i);
                 float *gate = T(S.iPw2 + 1);
                 const int P = d.Ho * d.Wo;
-                // (the gate: one launch, a workgroup per segment (se_gate_kernel), or the pool + the two dense layers as GEMMs over all
-                //  segments, through the arena slots of the layers they stand for.  Either way every sum runs in a fixed order.)
-                // (which of the two a BLOCK takes depends on its width alone, never on the launch: up to 576 expanded channels the
-                //  one-launch kernel is the faster one -- three launches cost ~27 us per 1 000 segments whatever their size, measured
-                //  13-36 against 27-50 us; beyond, its per-segment re-read of both weight matrices is: 59-490 against 37-143 us)
-                static const bool gate1 = [] { const char *e = BH_XENV("BIRDA_HIP_SE_GATE1"); return e && e[0] == '1'; }();
-                // (round 6: beyond 576 channels two launches of sixteen-segment workgroups -- the pooled rows x W1 split over channel
-                //  slices, then hidden x W2 -- instead of pool + two GEMMs of a handful of tiles: kernels_conv.hip se_hidden_kernel)
-                if (!gate1 && d.Cexp >= BH_SE_GATE16_MIN && bh::se_gate16_supports(d.Cexp, (int)G1.cout))
-                    bh::launch_se_gate16(d.pool_part, d.tiles_x * d.tiles_y, P, T(S.iGap + 1), c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1],
-                                         (int)G1.act, c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)n, d.Cexp,
-                                         (int)G1.cout, s);
-                else if (!gate1 && d.Cexp > 576)
-                    bh::launch_se_gate_gemm(d.pool_part, d.tiles_x * d.tiles_y, P, T(S.iGap + 1), T(S.iPw1 + 1), c->d_w[S.iPw1], c->d_blob + G1.b_off,
-                                            c->ldw[S.iPw1], (int)G1.act, c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)n,
-                                            d.Cexp, (int)G1.cout, s);
-                else
-                bh::launch_se_gate(d.pool_part, d.tiles_x * d.tiles_y, P, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
-                                   c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)n, d.Cexp, (int)G1.cout, s);
+                launch_gate(d.pool_part, d.tiles_x * d.tiles_y, P, T(S.iGap + 1), T(S.iPw1 + 1), gate, n);
                 ctx_mark(ctx, ST_GAP, (int)S.iGap);
                 float *y = (S.iP == nl - 1) ? d_logits : T(S.iP + 1);
                 const float *r = LP.res_tensor != bh::NO_TENSOR ? T(LP.res_tensor) : nullptr;
@@ -419,24 +411,17 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
             // 160).  On a small image the two gate launches of the fused path take the whole chain: se_hidden_kernel pools the
             // depthwise output itself (its "tiles" are the image's pixels, in order), the pool layer's own tensor holds the partial
             // sums.  Which path a block takes depends on its shapes alone.
-            const bool small_image = L.in_h * L.in_w <= 64 && L.cout >= BH_SE_GATE16_MIN;
-            if (small_image && !ctx->keep_tensors && i + 2 < nl) {
+            // (the chain's shapes are checked once, at create: gap_gate_chain; the arena plan keeps the pool layer's tensor, which
+            //  holds the partial sums, apart from the gate's.  A model that ENDS in such a gate gets it in d_logits.)
+            if (!ctx->keep_tensors && c->gap_gate[i]) {
                 const auto &G1 = m.layers[i + 1], &G2 = m.layers[i + 2];
-                bool ok = G1.op == bh::OP_PWCONV && G2.op == bh::OP_PWCONV && G1.in_h * G1.in_w == 1 && G2.in_h * G2.in_w == 1 &&
-                          G1.in_tensor == i + 1 && G2.in_tensor == i + 2 && G1.res_tensor == bh::NO_TENSOR && G2.res_tensor == bh::NO_TENSOR &&
-                          G1.cin == L.cout && G2.cin == G1.cout && G2.cout == L.cout && m.h.embedding_tensor != i + 1 && m.h.embedding_tensor != i + 2 &&
-                          bh::se_gate16_supports((int)L.cout, (int)G1.cout);
-                for (uint32_t j = i + 1; ok && j < nl; j++)          // nobody else may read the pooled or the hidden tensor
-                    if ((j > i + 1 && m.layers[j].in_tensor == i + 1) || (j > i + 2 && m.layers[j].in_tensor == i + 2) ||
-                        m.layers[j].res_tensor == i + 1 || m.layers[j].res_tensor == i + 2) ok = false;
-                if (ok) {
-                    const int P = (int)(L.in_h * L.in_w);
-                    bh::launch_se_gate16(in, P, P, out, c->d_w[i + 1], c->d_blob + G1.b_off, c->ldw[i + 1], (int)G1.act, c->d_w[i + 2],
-                                         c->d_blob + G2.b_off, c->ldw[i + 2], (int)G2.act, T(i + 3), (int)n, (int)L.cout, (int)G1.cout, s);
-                    ctx_mark(ctx, ST_GAP, (int)i);
-                    i += 2;          // the two dense layers of the gate are done
-                    break;
-                }
+                const int P = (int)(L.in_h * L.in_w);
+                float *gate = (i + 2 == nl - 1) ? d_logits : T(i + 3);
+                bh::launch_se_gate16(in, P, P, out, c->d_w[i + 1], c->d_blob + G1.b_off, c->ldw[i + 1], (int)G1.act, c->d_w[i + 2],
+                                     c->d_blob + G2.b_off, c->ldw[i + 2], (int)G2.act, gate, (int)n, (int)L.cout, (int)G1.cout, s);
+                ctx_mark(ctx, ST_GAP, (int)i);
+                i += 2;          // the two dense layers of the gate are done
+                break;
             }
             bh::launch_gap(in, out, (int)n, (int)(L.in_h * L.in_w), (int)L.cout, s);
             ctx_mark(ctx, ST_GAP, (int)i);
@@ -712,7 +697,7 @@ bool lanes_begin(bh_classifier *c, bh_batch_context *ctx, const std::vector<size
         auto it = ctx->plans.find(ns);
         if (it == ctx->plans.end()) {
             bh_batch_context::ArenaPlan p;
-            plan_arena(c->model, c->fused_at, c->se, c->head_gap, ns, false, p.t_off, p.total);
+            plan_arena(c->model, c->fused_at, c->se, c->head_gap, c->gap_gate, ns, false, p.t_off, p.total);
             it = ctx->plans.emplace(ns, std::move(p)).first;
         }
         if (base + it->second.total > ctx->arena_cap) { lanes.clear(); ctx->lane_fallbacks++; return false; }
@@ -1136,6 +1121,8 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
             if (!other_reader) c->head_gap[i] = 1;
         }
     }
+    c->gap_gate.assign(m.layers.size(), 0);
+    for (size_t i = 0; i < m.layers.size(); i++) c->gap_gate[i] = gap_gate_chain(m, i) ? 1 : 0;
     if (const char *e = BH_XENV("BIRDA_HIP_MB_NARROW_MAX")) c->narrow_max_workgroups = atoi(e);   // (A/B aid: 0 = never)
     if (const char *e = getenv("BIRDA_HIP_SE_GROUP_MB")) c->se_group_bytes = (size_t)atol(e) << 20;   // (MB of D per group of segments; 0: whole launches)
     if (const char *st = BH_XENV("BIRDA_HIP_MB_STAMPS"); st && st[0] == '1' && !c->mb.empty()) {
@@ -1547,6 +1534,41 @@ int bh_debug_read_tensor(bh_classifier *c, bh_batch_context *ctx, uint32_t tenso
     const float *src = (tensor == c->model.layers.size()) ? ctx->last_logits : ctx->d_arena + ctx->t_off[tensor];
     HIPCHK(hipMemcpy(host, src, nfl * sizeof(float), hipMemcpyDeviceToHost));
     return BH_OK;
+} catch (...) { return on_exception(); }
+
+int bh_audit_arena_plan(bh_classifier *c, bh_batch_context *ctx, size_t n, uint64_t *off_floats, uint64_t *size_floats, uint8_t *path,
+                        size_t cap) try {
+    int rc = check_ctx(c, ctx);
+    if (rc != BH_OK) return rc;
+    const auto &m = c->model;
+    const size_t nl = m.layers.size(), nt = nl + 1;
+    if (!off_floats || !size_floats || !path || cap < nt) return fail(BH_ERR_INVALID, "arena_plan: %zu entries needed", nt);
+    const bool keep = ctx->keep_tensors;
+    std::vector<size_t> off, sz;
+    size_t total = 0;
+    // n == 0: the context's own plan (what its forwards of max_batch segments use); else the plan a lane of n segments gets
+    plan_arena(m, c->fused_at, c->se, c->head_gap, c->gap_gate, n ? n : ctx->max_batch, keep, off, total, &sz);
+    if (!n) off = ctx->t_off;
+    for (size_t t = 0; t < nt; t++) { off_floats[t] = off[t]; size_floats[t] = sz[t]; }
+    // the path forward_slice takes at each layer (its dispatch, in its order)
+    for (size_t i = 0; i < cap; i++) path[i] = BH_PATH_INNER;
+    for (size_t i = 0; i < nl; i++) {
+        const auto &L = m.layers[i];
+        if ((!keep || ctx->keep_fused) && c->fused_at[i] >= 0) {
+            const auto &S = c->se[c->fused_at[i]];
+            const bool se = S.iP != 0;
+            path[i] = se ? BH_PATH_FUSED_SE : BH_PATH_FUSED;
+            i = se ? S.iP : c->mb[c->fused_at[i]].noexp ? i + 1 : i + 2;
+        } else if (!keep && L.op == bh::OP_PWCONV && c->head_gap[i]) {
+            path[i] = BH_PATH_HEAD_GAP;
+            i += 1;
+        } else if (!keep && L.op == bh::OP_GAP && c->gap_gate[i]) {
+            path[i] = BH_PATH_SE_GATE;
+            i += 2;
+        } else
+            path[i] = BH_PATH_LAYER;
+    }
+    return (int)nt;
 } catch (...) { return on_exception(); }
 
 int bh_batch_context_layer_ms(bh_batch_context *ctx, float *ms, uint32_t *launches, size_t n_layers) try {

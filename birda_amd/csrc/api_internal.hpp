@@ -27,6 +27,7 @@
 
 #include "../../include/birda_hip.h"
 #include "../../include/birda_hip_debug.h"
+#include "../../include/birda_hip_audit.h"
 #include "kernels.hpp"
 #include "trace.hpp"
 #include "model.hpp"
@@ -53,6 +54,11 @@ enum Stage { ST_MINMAX = 0, ST_MEL, ST_STEM, ST_DW, ST_PW, ST_GAP, ST_DENSE, ST_
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// squeeze-excite gates of at least this many channels take the two-launch gate (launch_se_gate16) where it supports their shape
+#ifndef BH_SE_GATE16_MIN
+#define BH_SE_GATE16_MIN 577
+#endif
+
 
 }  // namespace bhi
 
@@ -68,6 +74,10 @@ struct bh_classifier {
     std::vector<void *> d_w16;               // per layer: f16 hi / lo fragment planes (pw / dense outside fused blocks), or null
     std::vector<float> w16_unscale;          // per layer: 2^-s of those planes (they hold W * 2^s, kernels.hpp f16_scale_exponent)
     std::vector<char> head_gap;              // per layer: 1 = this 1x1 conv + GELU and the global average pool after it run as one launch
+    // per layer: 1 = this pool layer and the two 1x1 layers after it (a squeeze-excite gate of a block that runs layer by layer) run as
+    // the two gate launches (launch_se_gate16): the pool layer's tensor holds the hidden partial sums until the gate is written.  Decided
+    // once, at create (gap_gate_chain), and read by the forward (api.hip forward_slice) and the arena plan (api_plan.hip plan_arena).
+    std::vector<char> gap_gate;
     std::vector<float *> d_owned;            // re-laid buffers to free
     bh::FrontendParams fe{};
     bh::FrontendParams *d_fe = nullptr;      // device copy read by the mel kernel
@@ -249,8 +259,10 @@ namespace bhi {
 uint16_t f32_to_f16(float f);
 float f16_to_f32(uint16_t h);
 std::vector<float> build_gf(const bh::BranchRec &b, const float *W, int nm_pad, int prec, int *scale_exp);
-void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std::vector<bh_classifier::SeInfo> &se, const std::vector<char> &head_gap, size_t max_batch,
-                bool keep, std::vector<size_t> &off, size_t &total);
+void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std::vector<bh_classifier::SeInfo> &se, const std::vector<char> &head_gap,
+                const std::vector<char> &gap_gate, size_t max_batch, bool keep, std::vector<size_t> &off, size_t &total,
+                std::vector<size_t> *sizes = nullptr);
+bool gap_gate_chain(const bh::Model &m, size_t i);
 bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, size_t i, int precision, int force_cfg, bh::MbDesc &d);
 std::vector<int> tensor_readers(const bh::Model &m);
 int plan_fusion(bh_classifier *c);

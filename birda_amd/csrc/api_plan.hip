@@ -92,8 +92,9 @@ std::vector<float> build_gf(const bh::BranchRec &b, const float *W, int nm_pad, 
 }
 // liveness-based arena plan: tensor t is born at step t (tensor 0 = front-end) and dies after
 // the last layer that reads it; the embedding tensor and the logits live to the end.
-void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std::vector<bh_classifier::SeInfo> &se, const std::vector<char> &head_gap, size_t max_batch,
-                bool keep, std::vector<size_t> &off, size_t &total) {
+void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std::vector<bh_classifier::SeInfo> &se, const std::vector<char> &head_gap,
+                const std::vector<char> &gap_gate, size_t max_batch, bool keep, std::vector<size_t> &off, size_t &total,
+                std::vector<size_t> *sizes) {
     const size_t nt = m.layers.size() + 1;
     std::vector<size_t> last(nt, 0), sz(nt);
     for (size_t t = 0; t < nt; t++) { last[t] = t; sz[t] = align_up(m.tensor_floats[t] * max_batch, 64); }
@@ -137,8 +138,19 @@ void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std:
                 last[m.layers[i].in_tensor] = std::max(last[m.layers[i].in_tensor], i + 2);
                 sz[i + 1] = 0;
             }
+    if (!keep)
+        for (size_t i = 0; i + 2 < gap_gate.size(); i++)
+            if (gap_gate[i]) {
+                // the gate of a block that runs layer by layer in two launches (gap_gate_chain): se_hidden_kernel writes its partial
+                // sums into the pool layer's tensor (i+1), se_gate16_kernel reads them while it writes the gate (tensor i+3, the
+                // same n x C floats): both tensors of the gate's inputs live through the gate's step, or first-fit hands the
+                // gate the partial sums' bytes
+                last[i + 1] = std::max(last[i + 1], i + 3);
+                last[i + 2] = std::max(last[i + 2], i + 3);
+            }
     last[m.h.embedding_tensor] = nt;
     last[nt - 1] = nt;
+    if (sizes) *sizes = sz;
     off.assign(nt, 0);
     total = 0;
     if (keep) {
@@ -162,6 +174,25 @@ void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std:
         total = std::max(total, pos + sz[t]);
     }
 }
+// The pool layer i opens a squeeze-excite gate that runs as the two gate launches (se_hidden_kernel, se_gate16_kernel) instead of pool
+// + two GEMMs: an image of at most 64 pixels, at least BH_SE_GATE16_MIN channels, pool -> 1x1 (C -> Cr) -> 1x1 (Cr -> C) with no
+// other reader of the pooled or the hidden tensor, and a shape se_gate16 supports.  Shapes alone decide; the forward
+// (forward_slice) and the arena plan (plan_arena) both read the answer from bh_classifier::gap_gate.
+bool gap_gate_chain(const bh::Model &m, size_t i) {
+    const size_t nl = m.layers.size();
+    if (i + 2 >= nl) return false;
+    const auto &L = m.layers[i], &G1 = m.layers[i + 1], &G2 = m.layers[i + 2];
+    if (L.op != bh::OP_GAP || L.in_h * L.in_w > 64 || L.cout < BH_SE_GATE16_MIN) return false;
+    bool ok = G1.op == bh::OP_PWCONV && G2.op == bh::OP_PWCONV && G1.in_h * G1.in_w == 1 && G2.in_h * G2.in_w == 1 &&
+              G1.in_tensor == i + 1 && G2.in_tensor == i + 2 && G1.res_tensor == bh::NO_TENSOR && G2.res_tensor == bh::NO_TENSOR &&
+              G1.cin == L.cout && G2.cin == G1.cout && G2.cout == L.cout && m.h.embedding_tensor != i + 1 && m.h.embedding_tensor != i + 2 &&
+              bh::se_gate16_supports((int)L.cout, (int)G1.cout);
+    for (size_t j = i + 1; ok && j < nl; j++)          // nobody else may read the pooled or the hidden tensor
+        if ((j > i + 1 && m.layers[j].in_tensor == i + 1) || (j > i + 2 && m.layers[j].in_tensor == i + 2) ||
+            m.layers[j].res_tensor == i + 1 || m.layers[j].res_tensor == i + 2) ok = false;
+    return ok;
+}
+
 // IEEE binary16 round-to-nearest-even of a float, and back (host side of the hi/lo operand split)
 uint16_t f32_to_f16(float f) {
     uint32_t x; memcpy(&x, &f, 4);

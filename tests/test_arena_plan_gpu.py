@@ -1,0 +1,253 @@
+"""The activation arena's plan against what the forward pass actually reads and writes.
+
+plan_arena (birda_amd/csrc/api_plan.hip) gives every tensor bytes of one arena by liveness: a tensor is born at its layer's step
+and its bytes go to the next tensor once its last reader has run.  Several paths of forward_slice (birda_amd/csrc/api.hip) do not
+follow that picture -- a launch that stands for several layers writes tensors earlier, or reads them later, than their layers
+would -- and each of them needs its own liveness patch in the planner.  A missing one is silent: the bytes are shared, a late
+workgroup reads what an early one wrote over its input, and the logits come out wrong and finite.  Whether that shows on the GPU
+depends on how many workgroups are resident at once, so this file does not run a forward at all: it asks the library for its
+plan (bh_audit_arena_plan: offsets, planned sizes, and the path the forward takes at every layer) and replays the launches of
+forward_slice, restated here from reading it, over the planned bytes:
+
+  * no launch writes bytes that the same launch reads or writes as another tensor;
+  * every read finds its tensor's bytes untouched since the launch that wrote that tensor.
+
+The restatement per path (tensor t = output of layer t-1, tensor 0 = the spectrogram):
+  plain layer        reads its input (+ residual), writes its output;
+  fused block        one launch: reads the block input (+ the project's residual), writes the project's output;
+  fused SE block     pass A reads the block input, writes the depthwise output D (not for a block without an expand conv, which
+                     computes D again later) and the per-tile channel sums (the OP_SCALE output's slot); the gate launch reads the
+                     sums and writes the gate (the second 1x1's slot) and, beyond 576 channels, scratch in the slots of the pool
+                     and the first 1x1; the gated project GEMM reads D (or the block input again), the gate and the residual;
+  head conv + pool   one launch: reads the conv's input, writes the pooled tensor;
+  gate fast path     se_hidden_kernel reads the pool's input and writes partial sums into the pool's slot (i+1), then
+                     se_gate16_kernel reads those and writes the gate (i+3);
+and the embedding tensor is read back after the forward.  The last layer's output goes to the caller's logits buffer.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+# include/birda_hip_audit.h
+PATH_LAYER, PATH_FUSED, PATH_FUSED_SE, PATH_HEAD_GAP, PATH_SE_GATE, PATH_INNER = range(6)
+PATH_NAMES = {PATH_LAYER: "layer", PATH_FUSED: "fused block", PATH_FUSED_SE: "fused SE block", PATH_HEAD_GAP: "head conv + pool",
+              PATH_SE_GATE: "gate fast path", PATH_INNER: "inner"}
+
+# The mini front-end (12 000 samples, 32 mels, one branch) down to 2 x 8 = 16 pixels, then a 640-channel stage with squeeze-excite
+# gates: its blocks run layer by layer, and both gates -- 112 -> 672 (Cr 28) and 640 -> 3 840 (Cr 160, the v3.0-sized block) --
+# take the gate fast path (pool -> 1x1 -> 1x1 as se_hidden_kernel + se_gate16_kernel).
+WIDE_GATE_PLAN = dict(sr=48000, n=12000, branches=[(512, 100, 32, 0.0, 3000.0)], stem=16, act=3, se=True, head=128, classes=50,
+                      stages=[(1, 3, 1, 16, 1), (6, 3, 2, 24, 1), (6, 3, 2, 40, 1), (6, 3, 2, 112, 1), (6, 3, 1, 640, 2)])
+# The same front-end down to 4 x 15 = 60 pixels and a 112 -> 672 squeeze-excite block that the planner fuses in every precision:
+# its gate is se_gate16 on the fused path (more than 576 expanded channels).
+FUSED_WIDE_SE_PLAN = dict(WIDE_GATE_PLAN, stages=[(1, 3, 1, 16, 1), (6, 3, 2, 24, 1), (6, 3, 2, 40, 1), (6, 3, 1, 112, 1), (6, 3, 1, 112, 1)])
+RANDOM_SEEDS = range(12)
+BATCHES = (0, 1, 16, 300, 4096)    # 0: the context's own plan (max_batch 16); the others: the plan an n-segment lane gets
+
+
+def build_models(d):
+    """name -> (.bhm path, model): every model this file and tests/test_launch_scale_gpu.py audit."""
+    from birda_amd import modelfile as mf, synth
+    models = {k: synth.build_model(k) for k in ("mini", "mini_b0", "mini_hg", "mini_se")}
+    models["wide_gate"] = synth.build_model("custom", plan=WIDE_GATE_PLAN)
+    models["fused_wide_se"] = synth.build_model("custom", plan=FUSED_WIDE_SE_PLAN)
+    models["tail_gate"] = tail_gate_model()
+    for seed in RANDOM_SEEDS:
+        p = synth.random_plan(seed)
+        p["se"] = True
+        models[f"random{seed}"] = synth.build_model("custom", plan=p)
+    out = {}
+    for k, m in models.items():
+        path = os.path.join(str(d), f"{k}.bhm")
+        mf.write_model(path, m)
+        out[k] = (path, m)
+    return out
+
+
+def tail_gate_model():
+    """A model that ENDS in a gate chain (the last three layers: pool of a 2 x 8 = 16-pixel, 640-channel tensor -> 1x1 640 -> 160,
+    swish -> 1x1 160 -> 640, sigmoid; 640 classes): the wide-gate plan cut after its last block, the head replaced by the chain.  The
+    gate fast path takes it, and its output is the logits."""
+    from birda_amd import modelfile as mf, synth
+    m = synth.build_model("custom", plan=WIDE_GATE_PLAN)
+    b = synth._Builder(np.random.default_rng(0x7A11))
+    b.chunks, b.off, b.layers = [m.blob], int(m.blob.size), list(m.layers[:-3])     # (without head conv, pool, dense)
+    last = b.layers[-1]
+    t, h, w, c = len(b.layers), last.out_h, last.out_w, last.cout
+    assert (h * w, c) == (16, 640)
+    g = b.gap(t, h, w, c)
+    g = b.pwconv(g, 1, 1, c, 160, mf.ACT_SWISH)
+    b.pwconv(g, 1, 1, 160, c, mf.ACT_SIGMOID)
+    return mf.Model(m.family, m.sample_rate, m.sample_count, m.segment_duration, c, h * w * c, mf.OUT_NONE, t, m.spec_h, m.spec_w,
+                    m.norm_eps, m.branches, b.layers, np.concatenate(b.chunks))
+
+
+def arena_plan(clf, ctx, n):
+    """(offsets, planned sizes) per tensor in floats, and the path tag per layer, of `ctx`'s plan (n == 0) or an n-segment lane's."""
+    from birda_amd import _lib
+    cap = 4096
+    off = (C.c_uint64 * cap)()
+    sz = (C.c_uint64 * cap)()
+    path = (C.c_uint8 * cap)()
+    nt = _lib.load().bh_audit_arena_plan(clf._h, ctx._h, n, off, sz, path, cap)
+    _lib.check(0 if nt > 0 else nt)
+    return np.array(off[:nt], np.uint64), np.array(sz[:nt], np.uint64), list(path[:nt - 1])
+
+
+def tensor_floats(m, t):
+    if t == 0:
+        return len(m.branches) * m.spec_h * m.spec_w
+    L = m.layers[t - 1]
+    return L.out_h * L.out_w * L.cout
+
+
+def schedule(m, path):
+    """forward_slice's launches in stream order: (name, tensors read, tensors written, tensors written as a layer's output).
+    None stands for the caller's logits buffer."""
+    from birda_amd import modelfile as mf
+    nl = len(m.layers)
+    out = lambda t: None if t == nl else t
+    res = lambda L: [] if L.res_tensor == mf.NO_TENSOR else [L.res_tensor]
+    launches = [("front end", [], [0], [0])]
+    i = 0
+    while i < nl:
+        L, tag = m.layers[i], path[i]
+        assert tag != PATH_INNER, f"layer {i} starts a launch but is tagged as inside an earlier one"
+        if tag == PATH_LAYER:
+            launches.append((f"layer {i}", [L.in_tensor] + res(L), [out(i + 1)], [out(i + 1)]))
+            i += 1
+        elif tag == PATH_FUSED:
+            ip = i + 1 if L.op == mf.OP_DWCONV else i + 2
+            assert m.layers[ip].op == mf.OP_PWCONV and all(m.layers[k].in_tensor == k for k in range(i + 1, ip + 1)), i
+            assert all(p == PATH_INNER for p in path[i + 1:ip + 1]), (i, path[i:ip + 1])
+            launches.append((f"fused block {i}..{ip}", [L.in_tensor] + res(m.layers[ip]), [out(ip + 1)], [out(ip + 1)]))
+            i = ip + 1
+        elif tag == PATH_FUSED_SE:
+            iD = i if L.op == mf.OP_DWCONV else i + 1
+            iGap, iPw1, iPw2, iScale, iP = iD + 1, iD + 2, iD + 3, iD + 4, iD + 5
+            ops = [m.layers[k].op for k in (iD, iGap, iPw1, iPw2, iScale, iP)]
+            assert ops == [mf.OP_DWCONV, mf.OP_GAP, mf.OP_PWCONV, mf.OP_PWCONV, mf.OP_SCALE, mf.OP_PWCONV], (i, ops)
+            assert m.layers[iScale].in_tensor == iD + 1 and m.layers[iScale].res_tensor == iPw2 + 1 and m.layers[iP].in_tensor == iScale + 1
+            assert all(p == PATH_INNER for p in path[i + 1:iP + 1]), (i, path[i:iP + 1])
+            noexp = iD == i
+            C_ = m.layers[iD].cout
+            launches.append((f"SE block {i}..{iP}: pass A", [L.in_tensor], ([] if noexp else [iD + 1]) + [iScale + 1], []))
+            scratch = [iGap + 1, iPw1 + 1] if C_ > 576 else []
+            launches.append((f"SE block {i}..{iP}: gate", [iScale + 1], scratch + [iPw2 + 1], []))
+            launches.append((f"SE block {i}..{iP}: gated project", ([L.in_tensor] if noexp else [iD + 1]) + [iPw2 + 1] + res(m.layers[iP]),
+                             [out(iP + 1)], [out(iP + 1)]))
+            i = iP + 1
+        elif tag == PATH_HEAD_GAP:
+            G = m.layers[i + 1]
+            assert L.op == mf.OP_PWCONV and G.op == mf.OP_GAP and G.in_tensor == i + 1 and path[i + 1] == PATH_INNER, i
+            launches.append((f"head conv + pool {i}..{i + 1}", [L.in_tensor], [out(i + 2)], [out(i + 2)]))
+            i += 2
+        elif tag == PATH_SE_GATE:
+            G1, G2 = m.layers[i + 1], m.layers[i + 2]
+            assert L.op == mf.OP_GAP and G1.op == mf.OP_PWCONV and G2.op == mf.OP_PWCONV and G1.in_tensor == i + 1 and G2.in_tensor == i + 2, i
+            assert path[i + 1] == PATH_INNER and path[i + 2] == PATH_INNER, i
+            launches.append((f"gate {i}..{i + 2}: se_hidden_kernel", [L.in_tensor], [i + 1], []))
+            launches.append((f"gate {i}..{i + 2}: se_gate16_kernel", [i + 1], [out(i + 3)], [out(i + 3)]))
+            i += 3
+        else:
+            raise AssertionError(f"layer {i}: unknown path tag {tag}")
+    if m.embedding_tensor != nl:
+        launches.append(("embedding read-back", [m.embedding_tensor], [], []))
+    return launches
+
+
+def audit(m, off, sz, path, n):
+    """The problems of one plan, as strings (empty: the plan is sound for these launches)."""
+    rng = lambda t: (int(off[t]), int(off[t]) + int(sz[t]))
+    overlap = lambda a, b: rng(a)[0] < rng(b)[1] and rng(b)[0] < rng(a)[1]
+    problems = []
+    written_at, writes = {}, []
+    for k, (name, reads, wr, outputs) in enumerate(schedule(m, path)):
+        wr = [t for t in wr if t is not None]
+        for t in set(reads) | set(wr):
+            if sz[t] == 0:
+                problems.append(f"{name}: touches T({t}), which the plan gives no bytes")
+        for t in outputs:
+            if t is not None and sz[t] < tensor_floats(m, t) * n:
+                problems.append(f"{name}: T({t}) needs {tensor_floats(m, t) * n} floats, the plan gives {sz[t]}")
+        for t in reads:
+            if t not in written_at:
+                problems.append(f"{name}: reads T({t}) before any launch wrote it")
+                continue
+            for (k2, u) in writes:
+                if k2 > written_at[t] and u != t and overlap(t, u):
+                    problems.append(f"{name}: reads T({t}) at {rng(t)}, overwritten since by T({u}) at {rng(u)} ({schedule_name(m, path, k2)})")
+        touched = set(reads) | set(wr)
+        for t in wr:
+            for u in touched - {t}:
+                if overlap(t, u):
+                    problems.append(f"{name}: writes T({t}) at {rng(t)} over T({u}) at {rng(u)}, which the same launch "
+                                    f"{'reads' if u in reads else 'writes'}")
+        for t in wr:
+            written_at[t] = k
+            writes.append((k, t))
+    return problems
+
+
+def schedule_name(m, path, k):
+    return schedule(m, path)[k][0]
+
+
+@pytest.fixture(scope="module")
+def models(tmp_path_factory):
+    return build_models(tmp_path_factory.mktemp("arena_models"))
+
+
+@pytest.fixture(scope="module")
+def perch(tmp_path_factory):
+    from birda_amd import modelfile as mf, synth
+    m = synth.build_model("perch_v2")
+    path = str(tmp_path_factory.mktemp("arena_perch") / "perch_v2.bhm")
+    mf.write_model(path, m)
+    return path, m
+
+
+def _audit_model(path, m, precision):
+    from birda_amd.classifier import BirdClassifier
+    clf = BirdClassifier(path, None, precision=precision)
+    ctx = clf.create_batch_context(16)
+    tags = None
+    try:
+        failures = []
+        for n in BATCHES:
+            off, sz, tags = arena_plan(clf, ctx, n)
+            assert len(off) == len(m.layers) + 1
+            for p in audit(m, off, sz, tags, n or 16):
+                failures.append(f"[{precision}, n={n or '16 (context)'}] {p}")
+        return tags, failures
+    finally:
+        ctx.close()
+        clf.close()
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3"])
+@pytest.mark.parametrize("name", ["mini", "mini_b0", "mini_hg", "mini_se", "wide_gate", "fused_wide_se", "tail_gate"] +
+                         [f"random{s}" for s in RANDOM_SEEDS])
+def test_arena_plan_keeps_every_launchs_tensors_apart(models, name, precision):
+    path, m = models[name]
+    tags, failures = _audit_model(path, m, precision)
+    used = sorted({PATH_NAMES[t] for t in tags if t != PATH_INNER})
+    print(f"{name} [{precision}]: {len(m.layers)} layers, paths {used}, {len(failures)} problem(s)")
+    assert not failures, "\n".join(failures[:20])
+    if name == "wide_gate":     # the chains this plan exists for: both gates of the 640-channel stage on the fast path
+        gated = [m.layers[i].cout for i, t in enumerate(tags) if t == PATH_SE_GATE]
+        assert 3840 in gated and 672 in gated, (precision, gated)
+    if name == "tail_gate":
+        assert tags[len(m.layers) - 3] == PATH_SE_GATE, (precision, tags[-3:])
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3"])
+def test_arena_plan_of_the_perch_sized_model(perch, precision):
+    path, m = perch
+    tags, failures = _audit_model(path, m, precision)
+    assert PATH_FUSED_SE in tags, (precision, sorted(set(tags)))
+    assert not failures, "\n".join(failures[:20])

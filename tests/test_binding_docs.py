@@ -153,3 +153,22 @@ def test_ctypes_mirror_matches_the_header(header):
             assert len(args) == len(want_args), name
             for i, (a, b) in enumerate(zip(args, want_args)):
                 assert _eq_ctypes(A.ctypes_class(a), b), (name, i, a, b)
+
+
+def test_audit_table_matches_its_header():
+    """include/birda_hip_audit.h (the plan introspection the arena / launch-scale tests call) against its ctypes table, the
+    library's exports and the path tags tests/test_arena_plan_gpu.py restates the forward pass by."""
+    from birda_amd import _lib
+    _, functions, defines = A.parse_c_header(os.path.join(ROOT, "include", "birda_hip_audit.h"))
+    assert {n for n, _, _ in _lib.AUDIT_SYMBOLS} == set(functions) == {"bh_audit_arena_plan"}
+    for name, res, args in _lib.AUDIT_SYMBOLS:
+        want_ret, want_args = functions[name]
+        assert _eq_ctypes(A.ctypes_class(res), want_ret), name
+        assert len(args) == len(want_args), name
+        for i, (a, b) in enumerate(zip(args, want_args)):
+            assert _eq_ctypes(A.ctypes_class(a), b), (name, i, a, b)
+        assert hasattr(_lib.load(), name), f"{name} declared in include/birda_hip_audit.h but not exported"
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import test_arena_plan_gpu as T
+    for k in ("LAYER", "FUSED", "FUSED_SE", "HEAD_GAP", "SE_GATE", "INNER"):
+        assert getattr(T, "PATH_" + k) == defines["BH_PATH_" + k], k
