@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbirda_hip.so")
 BH_MAX_TOP_K = 32
 BH_N_STAGES = 9
+# ("stem": every full convolution -- the unfused NCHW stem and the k x k group-1 layers past it, e.g. Fused-MBConv expands)
 STAGE_NAMES = ["minmax", "mel", "stem", "depthwise", "pointwise", "pool", "dense", "topk", "mbconv"]
 
 

@@ -451,15 +451,17 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             if a is None or b is None:
                 # MatMul + Add(bias): handled with the MatMul below
                 raise ConvertError(f"Add of {n.inputs}: operands are not both activations on the path")
-            # residual: one operand is a 1x1 conv's output (latest layer, no residual yet), the other an older tensor
+            # residual: one operand is a 1x1 or a full NHWC conv's output (latest layer, no residual yet; a full convolution is
+            # the Fused-MBConv residual Add(act(conv(x)), x), never the NCHW stem), the other an older tensor
             for y, r in ((a, b), (b, a)):
                 L = layers[y[0] - 1] if y[0] > 0 else None
-                if L is not None and L.op == mf.OP_PWCONV and L.res_tensor == mf.NO_TENSOR and r[0] < y[0] and r[1:] == y[1:]:
+                conv = L is not None and (L.op == mf.OP_PWCONV or (L.op == mf.OP_CONV and L.in_layout == 0))
+                if conv and L.res_tensor == mf.NO_TENSOR and r[0] < y[0] and r[1:] == y[1:]:
                     L.res_tensor = r[0]
                     tmap[n.outputs[0]] = y
                     break
             else:
-                raise ConvertError(f"Add of {n.inputs}: no 1x1 convolution to fold the residual into")
+                raise ConvertError(f"Add of {n.inputs}: no convolution to fold the residual into")
         elif op in ("GlobalAveragePool", "ReduceMean"):
             t = tmap.get(n.inputs[0])
             if t is None:

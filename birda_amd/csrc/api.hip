@@ -67,6 +67,22 @@ std::vector<uint16_t> w16_planes(const float *W, int K, int N, float *unscale) {
     return planes;
 }
 
+bh::ConvParams conv_params(const bh::LayerRec &L) {
+    return bh::ConvParams{(int)L.in_h, (int)L.in_w, (int)L.out_h, (int)L.out_w, (int)L.cin, (int)L.cout, (int)L.kh, (int)L.kw,
+                          (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l, (int)L.in_layout, (int)L.act};
+}
+
+// A full convolution's [kh][kw][cin][cout] weights as the implicit GEMM's K x ld rows: the channels of every tap padded to whole
+// 32-deep steps (K = kh kw align_up(cin, 32)), the columns to ld; zero in the padding
+std::vector<float> conv_gemm_rows(const float *W, const bh::LayerRec &L, int ld) {
+    const size_t cpad = align_up(L.cin, 32), taps = (size_t)L.kh * L.kw;
+    std::vector<float> w(taps * cpad * ld, 0.0f);
+    for (size_t t = 0; t < taps; t++)
+        for (uint32_t ch = 0; ch < L.cin; ch++)
+            memcpy(&w[(t * cpad + ch) * ld], W + (t * L.cin + ch) * L.cout, L.cout * sizeof(float));
+    return w;
+}
+
 int upload(const void *src, size_t bytes, float **dst) {
     HIPCHK(hipMalloc((void **)dst, bytes ? bytes : 4));
     if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
@@ -371,7 +387,14 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
         }
         switch (L.op) {
         case bh::OP_CONV:
-            bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
+            // the NCHW stem on the direct kernel (when it is not fused into the first block); every NHWC full convolution is an
+            // implicit GEMM on the MFMA (kernels_conv.hip), split-f16 where it has planes
+            if (L.in_layout == 1)
+                bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
+            else if (!ctx->keep_tensors && c->d_w16[i])
+                bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->precision == 3 ? 3 : 1, c->w16_unscale[i], s);
+            else
+                bh::launch_conv_gemm(in, c->d_w[i], bias, res, out, p, (int)n, c->ldw[i], s);
             ctx_mark(ctx, ST_STEM, (int)i);
             break;
         case bh::OP_DWCONV:
@@ -1066,15 +1089,36 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
         } else if (L.op == bh::OP_DWCONV) {
             if (L.cout % 4 || L.kh != L.kw || L.sh != L.sw || !((L.kh == 3 || L.kh == 5) && (L.sh == 1 || L.sh == 2)))
                 return fail(BH_ERR_UNSUPPORTED, "layer %zu: depthwise %ux%u stride %u channels %u not built", i, L.kh, L.kw, L.sh, L.cout);
-        } else if (L.op == bh::OP_CONV) {
+        } else if (L.op == bh::OP_CONV && L.in_layout == 1) {   // the NCHW stem: the direct kernel, weights in LDS
             if (L.cout % 4 || (size_t)L.kh * L.kw * L.cin * L.cout * 4 > 64 * 1024)
                 return fail(BH_ERR_UNSUPPORTED, "layer %zu: direct conv shape not built", i);
+        } else if (L.op == bh::OP_CONV) {   // NHWC: the implicit GEMM, W rows padded per tap to whole 32-deep steps
+            const bh::ConvParams p = conv_params(L);
+            if (!bh::conv_gemm_supports(p))
+                return fail(BH_ERR_UNSUPPORTED, "layer %zu: full convolution %ux%u stride %ux%u, %u -> %u channels, layout %u not built "
+                            "(kernel 1..7, stride 1 / 2, channels multiples of 4, NHWC)", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout, L.in_layout);
+            const int ld = (int)align_up(L.cout, 4);
+            c->ldw[i] = ld;
+            const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, L, ld);
+            float *d = nullptr;
+            rc = upload(w.data(), w.size() * sizeof(float), &d);
+            if (rc != BH_OK) return rc;
+            c->d_owned.push_back(d);
+            c->d_w[i] = d;
         } else if (L.op == bh::OP_GAP || L.op == bh::OP_SCALE) {
             if (L.cout % 4) return fail(BH_ERR_UNSUPPORTED, "layer %zu: channels %u not a multiple of 4", i, L.cout);
         }
     }
     if (m.layers.empty() || m.layers.back().cout != m.h.n_classes)
         return fail(BH_ERR_IO, "model: last layer width != n_classes");
+    // a residual on a layer whose kernel cannot add one is refused, not dropped: depthwise and pool layers (a fused block's
+    // residual sits on its project convolution; the planner fuses no depthwise layer that carries one) and the NCHW stem
+    for (size_t i = 0; i < m.layers.size(); i++) {
+        const auto &L = m.layers[i];
+        if (L.res_tensor != bh::NO_TENSOR && (L.op == bh::OP_DWCONV || L.op == bh::OP_GAP || (L.op == bh::OP_CONV && L.in_layout == 1)))
+            return fail(BH_ERR_UNSUPPORTED, "layer %zu: a residual on a %s layer is not supported (only convolutions, 1x1 and full NHWC, "
+                        "and dense layers add one)", i, L.op == bh::OP_DWCONV ? "depthwise" : L.op == bh::OP_GAP ? "pool" : "stem convolution");
+    }
     rc = plan_fusion(c.get());
     if (rc != BH_OK) return rc;
     // f16 operand planes for the GEMM layers that stay outside the fused blocks (head conv, dense)
@@ -1096,6 +1140,21 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
             }
         for (size_t i = 0; i < m.layers.size(); i++) {
             const auto &L = m.layers[i];
+            if (L.op == bh::OP_CONV && L.in_layout == 0) {   // a full convolution: planes over the per-tap padded K
+                // (64 output channels or fewer stay on the f32 MFMA: the split-f16 kernel's 128-column tile would idle half or more
+                //  of its MFMAs there, and the f32 kernel is the faster -- 1.08 against 2.22 ms for 3x3 32 -> 32 at 64 x 249 x 256
+                //  segments, profiles/conv_gemm.txt -- and exact; shapes alone decide)
+                if (!bh::conv_gemm16_supports(conv_params(L)) || L.cout <= 64) continue;
+                const uint32_t cpad = (uint32_t)align_up(L.cin, 32);
+                const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, L, (int)L.cout);
+                const std::vector<uint16_t> planes = w16_planes(w.data(), (int)(L.kh * L.kw * cpad), (int)L.cout, &c->w16_unscale[i]);
+                float *d = nullptr;
+                rc = upload(planes.data(), planes.size() * sizeof(uint16_t), &d);
+                if (rc != BH_OK) return rc;
+                c->d_owned.push_back(d);
+                c->d_w16[i] = d;
+                continue;
+            }
             if (in_block[i] || (L.op != bh::OP_PWCONV && L.op != bh::OP_DENSE)) continue;
             if (!(se_project[i] ? (L.cin % 4 == 0 && L.act == bh::ACT_NONE) : bh::pw_gemm16_supports((int)L.cin, (int)L.act))) continue;
             const std::vector<uint16_t> planes = w16_planes(m.blob.data() + L.w_off, (int)L.cin, (int)L.cout, &c->w16_unscale[i]);

@@ -358,9 +358,18 @@ void launch_mel(const float *x, const float *minmax, float *spec, const Frontend
 struct ConvParams {
     int in_h, in_w, out_h, out_w, cin, cout, kh, kw, sh, sw, pad_t, pad_l, in_layout, act;
 };
-// direct conv for the small-Cin stem; w [kh][kw][cin][cout]
+// direct conv for the small-Cin NCHW stem; w [kh][kw][cin][cout]
 void launch_conv_direct(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
                         int n_seg, hipStream_t s);
+// full convolution NHWC (group 1) as an implicit GEMM: out = act(im2col(in) . W + b) (+ R).  W is K x N with K = kh kw cpad,
+// cpad = align_up(cin, 32), the channels of every tap zero-padded to whole 32-deep steps: f32 rows [K][ldw] (ldw % 4 == 0), or
+// the split-f16 planes of launch_pw_gemm16 over that K.  kh, kw 1 .. 7, strides 1 / 2, cin and cout multiples of 4, NHWC input.
+bool conv_gemm_supports(const ConvParams &p);
+bool conv_gemm16_supports(const ConvParams &p);   // ... and an activation the f16 epilogue is instantiated for
+void launch_conv_gemm(const float *in, const float *W, const float *b, const float *R, float *out, const ConvParams &p, int n_seg,
+                      int ldw, hipStream_t s);
+void launch_conv_gemm16(const float *in, const void *Wf, const float *b, const float *R, float *out, const ConvParams &p, int n_seg,
+                        int terms, float w_unscale, hipStream_t s);
 // depthwise conv NHWC; w [kh][kw][c]
 void launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
                    int n_seg, hipStream_t s);

@@ -5,7 +5,8 @@
 // activation, residual Add, GlobalAveragePool, Gemm.
 //   * pointwise 1x1 conv and the dense head: LDS-tiled GEMM on v_mfma_f32_16x16x4_f32
 //   * depthwise kxk: direct NHWC conv, 4 channels per lane (16-B loads/stores)
-//   * stem conv (tiny Cin): direct conv, weights in LDS, 8 output channels per lane
+//   * stem conv (tiny Cin, NCHW): direct conv, weights in LDS, 8 output channels per lane
+//   * full kxk convolutions (NHWC, group 1): implicit GEMM on the same MFMAs as the pointwise layers
 #include "kernels.hpp"
 
 namespace bh {
@@ -1321,6 +1322,304 @@ void launch_conv_direct(const float *in, const float *w, const float *b, float *
     const size_t smem = (size_t)p.kh * p.kw * p.cin * p.cout * sizeof(float);
     if (nc == 8) hipLaunchKernelGGL(conv_direct_kernel<8>, dim3((unsigned)blocks), dim3(256), smem, s, in, w, b, out, p, n_seg);
     else hipLaunchKernelGGL(conv_direct_kernel<4>, dim3((unsigned)blocks), dim3(256), smem, s, in, w, b, out, p, n_seg);
+}
+
+// ---------------------------------------------------------------------------------------
+// Full convolution (group 1, NHWC, any layer but the NCHW stem) as an implicit GEMM:
+//     C[m][n] = act(im2col(X)[m][:] . W[:][n] + bias[n]) (+ R[m][n]),  m = (segment, oy, ox)
+// W keeps the loaders' [kh][kw][cin][cout] layout read as K x N, with the channels of every tap padded on the host to whole
+// 32-deep steps (cpad = align_up(cin, 32), zero rows): K = kh kw cpad, and a k step never straddles two taps.  The im2col
+// matrix never exists: the A loader walks the steps tap by tap (dy, dx, channel step) and gathers each row's input pixel
+// (oy sh - pad_t + dy, ox sw - pad_l + dx); taps outside the image and channels past cin read as zero.
+// Two kernels, one per operand precision, each the twin of a pointwise GEMM (the same tiles, MFMAs, k order inside a step
+// and epilogue; the same plane layout): conv_gemm_kernel of pw_gemm_kernel (f32 MFMA, LDS-staged 32-deep chunks) and
+// conv_gemm16_kernel of pw_gemm16_kernel (split-f16 MFMA, register-direct).  They are kernels of their own rather than an
+// A-loader mode of the pointwise ones because the gather carries per-row state (the row's segment base and image origin)
+// and a per-step tap walk that the pointwise loaders do not: kept apart, the pointwise instantiations -- and their names,
+// which the profiles and tools match -- stay exactly what they were.
+// Per output element the k order is fixed (tap-major, channels ascending): no split-K, so a segment's bits do not depend
+// on the launch it runs in.  Offsets into X, R and C are 64-bit.
+// ---------------------------------------------------------------------------------------
+struct ConvRows {   // one output row's gather origin: its segment's image and the top-left input pixel of its window
+    const float *x;
+    int iy0, ix0;
+};
+__device__ __forceinline__ ConvRows conv_row(const float *X, const ConvParams &p, int m) {
+    const int opix = p.out_h * p.out_w;
+    const int seg = m / opix, r = m - seg * opix;
+    const int oy = r / p.out_w, ox = r - oy * p.out_w;
+    return ConvRows{X + (size_t)seg * p.in_h * p.in_w * p.cin, oy * p.sh - p.pad_t, ox * p.sw - p.pad_l};
+}
+// four consecutive channels ch .. ch + 3 of tap (dy, dx) of a row (cin % 4 == 0: a float4 is wholly inside or wholly past cin)
+__device__ __forceinline__ float4 conv_gather4(const ConvRows &r, const ConvParams &p, int dy, int dx, int ch) {
+    const int iy = r.iy0 + dy, ix = r.ix0 + dx;
+    if ((unsigned)iy >= (unsigned)p.in_h || (unsigned)ix >= (unsigned)p.in_w || ch >= p.cin) return make_float4(0.f, 0.f, 0.f, 0.f);
+    return *reinterpret_cast<const float4 *>(r.x + ((size_t)iy * p.in_w + ix) * p.cin + ch);
+}
+// the tap walk: (channel step, dx, dy) advanced one 32-deep step at a time, in the order the steps are loaded
+struct ConvTap {
+    int cs = 0, dx = 0, dy = 0;
+    __device__ __forceinline__ void next(int csteps, int kw) {
+        if (++cs == csteps) { cs = 0; if (++dx == kw) { dx = 0; ++dy; } }
+    }
+};
+
+template <int BM, int NT>
+__global__ __launch_bounds__(256) void conv_gemm_kernel(const float *__restrict__ X, const float *__restrict__ W,
+                                                         const float *__restrict__ bias, const float *__restrict__ R,
+                                                         float *__restrict__ C, ConvParams p, int M, int ldw) {
+    constexpr int BN = NT * 16;
+    constexpr int WM = BM / 4;
+    constexpr int MT = WM / 16;
+    constexpr int AS = PW_BK + 4;
+    constexpr int BS = BN + 4;
+    constexpr int A4 = BM * PW_BK / 4 / 256;
+    constexpr int B4 = (PW_BK * BN / 4 + 255) / 256;
+    __shared__ __attribute__((aligned(16))) float As[2][BM * AS];
+    __shared__ __attribute__((aligned(16))) float Bs[2][PW_BK * BS];
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, kq = lane >> 4;
+    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
+    const int N = p.cout, csteps = (p.cin + 31) >> 5;
+    const int K = p.kh * p.kw * csteps * PW_BK;
+
+    ConvRows rows[A4];
+#pragma unroll
+    for (int i = 0; i < A4; i++) rows[i] = conv_row(X, p, min(m0 + ((tid + 256 * i) >> 3), M - 1));   // rows past M: clamped, never stored
+    ConvTap tap;
+    float4 pa[A4], pb[B4];
+    auto load_chunk = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < A4; i++) pa[i] = conv_gather4(rows[i], p, tap.dy, tap.dx, tap.cs * PW_BK + ((tid & 7) << 2));
+        tap.next(csteps, p.kw);
+#pragma unroll
+        for (int i = 0; i < B4; i++) {
+            const int f = tid + 256 * i;
+            const int row = f / (BN / 4), nc = (f % (BN / 4)) << 2;
+            const int gn = n0 + nc;
+            pb[i] = (f < PW_BK * BN / 4 && gn < ldw) ? *reinterpret_cast<const float4 *>(W + (size_t)(k0 + row) * ldw + gn)
+                                                     : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    };
+    auto store_chunk = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < A4; i++) {
+            const int f = tid + 256 * i;
+            *reinterpret_cast<float4 *>(&As[buf][(f >> 3) * AS + ((f & 7) << 2)]) = pa[i];
+        }
+#pragma unroll
+        for (int i = 0; i < B4; i++) {
+            const int f = tid + 256 * i;
+            if (f < PW_BK * BN / 4) {
+                const int row = f / (BN / 4), nc = (f % (BN / 4)) << 2;
+                *reinterpret_cast<float4 *>(&Bs[buf][row * BS + nc]) = pb[i];
+            }
+        }
+    };
+
+    f32x4 acc[MT][NT];
+#pragma unroll
+    for (int i = 0; i < MT; i++)
+#pragma unroll
+        for (int j = 0; j < NT; j++) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    load_chunk(0);
+    store_chunk(0);
+    __syncthreads();
+
+    const int nchunks = K / PW_BK;
+    for (int c = 0; c < nchunks; c++) {
+        const int buf = c & 1;
+        if (c + 1 < nchunks) load_chunk((c + 1) * PW_BK);
+        const float *as = &As[buf][(wave * WM + li) * AS + 4 * kq];
+        const float *bs = &Bs[buf][(4 * kq) * BS + li];
+#pragma unroll
+        for (int g = 0; g < 2; g++) {
+            float4 a4[MT];
+#pragma unroll
+            for (int i = 0; i < MT; i++) a4[i] = *reinterpret_cast<const float4 *>(as + i * 16 * AS + g * 16);
+#pragma unroll
+            for (int cc = 0; cc < 4; cc++) {
+                float b[NT];
+#pragma unroll
+                for (int j = 0; j < NT; j++) b[j] = bs[(g * 16 + cc) * BS + j * 16];
+#pragma unroll
+                for (int i = 0; i < MT; i++) {
+                    const float a = cc == 0 ? a4[i].x : cc == 1 ? a4[i].y : cc == 2 ? a4[i].z : a4[i].w;
+#pragma unroll
+                    for (int j = 0; j < NT; j++)
+                        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b[j], acc[i][j], 0, 0, 0);
+                }
+            }
+        }
+        if (c + 1 < nchunks) store_chunk(buf ^ 1);
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int j = 0; j < NT; j++) {
+        const int col = n0 + j * 16 + li;
+        if (col >= N) continue;
+        const float bv = bias[col];
+#pragma unroll
+        for (int i = 0; i < MT; i++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int row = m0 + wave * WM + i * 16 + kq * 4 + r;
+                if (row < M) {
+                    float v = act_apply(acc[i][j][r] + bv, p.act);
+                    if (R) v += R[(size_t)row * N + col];
+                    C[(size_t)row * N + col] = v;
+                }
+            }
+    }
+}
+
+// Split-f16 twin.  Block = 4 waves as 2 x 2, wave tile 64 x 64, block tile 128 rows x 8 column tiles; a lane loads 8
+// consecutive channels of its four rows' tap straight into registers one step ahead and splits them there.  Blocks run
+// column block fastest: the blocks that read the same rows of X are adjacent (X is gathered kh kw times per row; those
+// re-reads come from L2), and W -- at most a few MB -- stays in L2 for all of them.
+template <int TERMS, int ACT>
+__global__ __launch_bounds__(256) void conv_gemm16_kernel(const float *__restrict__ X, const f16x8 *__restrict__ Wf,
+                                                           const float *__restrict__ bias, const float *__restrict__ R,
+                                                           float *__restrict__ C, ConvParams p, int M, int n_tiles, float w_unscale) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int li = lane & 15, kq = lane >> 4;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int n_xb = (n_tiles + 7) / 8;
+    const int yb = (int)(blockIdx.x / (unsigned)n_xb), xb = (int)(blockIdx.x % (unsigned)n_xb);
+    const int m0 = yb * 128 + wm * 64, t0 = xb * 8 + wn * 4;   // first row, first column tile
+    const int N = p.cout, csteps = (p.cin + 31) >> 5;
+    const int steps = p.kh * p.kw * csteps;
+
+    f32x4 acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 4; j++) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    ConvRows rows[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) rows[i] = conv_row(X, p, min(m0 + i * 16 + li, M - 1));   // rows past M: clamped, never stored
+    ConvTap tap;
+
+    float4 ra0[4][2], ra1[4][2];
+    f16x8 bh0[4], bl0[4], bh1[4], bl1[4];
+    auto load = [&](int st, float4 (&ra)[4][2], f16x8 (&bh)[4], f16x8 (&bl)[4]) {
+        const int ch = tap.cs * 32 + 8 * kq;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            ra[i][0] = conv_gather4(rows[i], p, tap.dy, tap.dx, ch);
+            ra[i][1] = conv_gather4(rows[i], p, tap.dy, tap.dx, ch + 4);
+        }
+        tap.next(csteps, p.kw);
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            const int t = min(t0 + j, n_tiles - 1);
+            bh[j] = Wf[(((size_t)st * n_tiles + t) * 2 + 0) * 64 + lane];
+            if (TERMS == 3) bl[j] = Wf[(((size_t)st * n_tiles + t) * 2 + 1) * 64 + lane];
+        }
+    };
+    auto step = [&](const float4 (&ra)[4][2], const f16x8 (&bh)[4], const f16x8 (&bl)[4]) {
+        f16x8 ah[4], al[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            const float v[8] = {ra[i][0].x, ra[i][0].y, ra[i][0].z, ra[i][0].w, ra[i][1].x, ra[i][1].y, ra[i][1].z, ra[i][1].w};
+            bh_split8(v, ah[i], al[i]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+                if (TERMS == 3) {
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
+                }
+            }
+    };
+    load(0, ra0, bh0, bl0);
+    for (int st = 0; st < steps; st += 2) {
+        if (st + 1 < steps) load(st + 1, ra1, bh1, bl1);
+        __builtin_amdgcn_sched_barrier(0);
+        step(ra0, bh0, bl0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (st + 2 < steps) load(st + 2, ra0, bh0, bl0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (st + 1 < steps) step(ra1, bh1, bl1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int col = (t0 + j) * 16 + li;
+        if (col >= N) continue;
+        const float bv = bias[col];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int row = m0 + i * 16 + kq * 4 + r;
+                if (row < M) {
+                    float v = __builtin_fmaf(acc[i][j][r], w_unscale, bv);   // the planes hold W / w_unscale
+                    v = bh_act<ACT>(v);
+                    if (R) v += R[(size_t)row * N + col];
+                    C[(size_t)row * N + col] = v;
+                }
+            }
+    }
+}
+
+bool conv_gemm_supports(const ConvParams &p) {
+    return p.in_layout == 0 && p.cin % 4 == 0 && p.cout % 4 == 0 && p.cin > 0 && p.cout > 0 && p.kh >= 1 && p.kh <= 7 && p.kw >= 1 &&
+           p.kw <= 7 && (p.sh == 1 || p.sh == 2) && (p.sw == 1 || p.sw == 2) && p.pad_t >= 0 && p.pad_l >= 0;
+}
+bool conv_gemm16_supports(const ConvParams &p) { return conv_gemm_supports(p) && (p.act == ACT_NONE || act_is_templated(p.act)); }
+
+template <int BM, int NT>
+static void conv_launch(const float *X, const float *W, const float *bias, const float *R, float *C, const ConvParams &p, int M, int ldw,
+                        hipStream_t s) {
+    dim3 grid((p.cout + NT * 16 - 1) / (NT * 16), (M + BM - 1) / BM), block(256);
+    hipLaunchKernelGGL((conv_gemm_kernel<BM, NT>), grid, block, 0, s, X, W, bias, R, C, p, M, ldw);
+}
+
+void launch_conv_gemm(const float *X, const float *W, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
+                      int ldw, hipStream_t s) {
+    const int M = n_seg * p.out_h * p.out_w;
+    if (M <= 0) return;
+    const int nt = pick_nt(p.cout);
+    const long blocks128 = (long)((M + 127) / 128) * ((p.cout + nt * 16 - 1) / (nt * 16));
+    const bool small = blocks128 < 512;   // the tile is the layer's shape alone: the same bits at any launch size either way
+#define BH_CG_CASE(NTV)                                                                       \
+    case NTV:                                                                                 \
+        if (small) conv_launch<64, NTV>(X, W, bias, R, C, p, M, ldw, s);                     \
+        else conv_launch<128, NTV>(X, W, bias, R, C, p, M, ldw, s);                          \
+        break;
+    switch (nt) {
+        BH_CG_CASE(1) BH_CG_CASE(2) BH_CG_CASE(3) BH_CG_CASE(4)
+        BH_CG_CASE(5) BH_CG_CASE(6) BH_CG_CASE(7) BH_CG_CASE(8)
+    }
+#undef BH_CG_CASE
+}
+
+void launch_conv_gemm16(const float *X, const void *Wf, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
+                        int terms, float w_unscale, hipStream_t s) {
+    const int M = n_seg * p.out_h * p.out_w;
+    if (M <= 0) return;
+    const int n_tiles = (p.cout + 15) / 16;
+    const dim3 grid((unsigned)(((n_tiles + 7) / 8) * ((M + 127) / 128))), block(256);
+#define BH_CG16(T, ACTV) hipLaunchKernelGGL((conv_gemm16_kernel<T, ACTV>), grid, block, 0, s, X, (const f16x8 *)Wf, bias, R, C, p, M, n_tiles, w_unscale)
+#define BH_CG16A(T)                                                  \
+    switch (p.act) {                                                 \
+    case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF); break;              \
+    case ACT_SWISH: BH_CG16(T, ACT_SWISH); break;                    \
+    case ACT_RELU6: BH_CG16(T, ACT_RELU6); break;                    \
+    default: BH_CG16(T, ACT_NONE); break;                            \
+    }
+    if (terms == 3) { BH_CG16A(3) } else { BH_CG16A(1) }
+#undef BH_CG16A
+#undef BH_CG16
 }
 
 // ---------------------------------------------------------------------------------------

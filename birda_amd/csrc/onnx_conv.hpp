@@ -413,13 +413,15 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 const T &y = side ? b : a, &r = side ? a : b;
                 if (y.idx == 0) continue;
                 LayerRec &L = layers[y.idx - 1];
-                if (L.op == OP_PWCONV && L.res_tensor == NO_TENSOR && r.idx < y.idx && r.c == y.c && r.h == y.h && r.w == y.w) {
+                // (a 1x1 or a full NHWC convolution: Add(act(conv(x)), x), the Fused-MBConv residual; never the NCHW stem)
+                const bool conv = L.op == OP_PWCONV || (L.op == OP_CONV && L.in_layout == 0);
+                if (conv && L.res_tensor == NO_TENSOR && r.idx < y.idx && r.c == y.c && r.h == y.h && r.w == y.w) {
                     L.res_tensor = r.idx;
                     tmap[n.out[0]] = y;
                     done = true;
                 }
             }
-            if (!done) return fail("Add of '" + n.in[0] + "', '" + n.in[1] + "': no 1x1 convolution to fold the residual into");
+            if (!done) return fail("Add of '" + n.in[0] + "', '" + n.in[1] + "': no convolution to fold the residual into");
         } else if (op == "GlobalAveragePool" || op == "ReduceMean") {
             T t;
             if (!find(n.in[0], t)) return fail(op + ": input not on the path");

@@ -85,11 +85,13 @@ class _Builder:
         self.layers.append(L)
         return len(self.layers)  # tensor index of this layer's output
 
-    def conv(self, tin, h, w, cin, cout, k, s, act, in_layout=0):
+    def conv(self, tin, h, w, cin, cout, k, s, act, in_layout=0, res=mf.NO_TENSOR, gain=1.0):
         oh, pt = _same_pad(h, k, s)
         ow, pl = _same_pad(w, k, s)
         wt = self.he((k, k, cin, cout), k * k * cin)
-        L = mf.Layer(mf.OP_CONV, act, tin, mf.NO_TENSOR, cin, cout, k, k, s, s, pt, pl, h, w, oh, ow,
+        if gain != 1.0:
+            wt = wt * np.float32(gain)
+        L = mf.Layer(mf.OP_CONV, act, tin, res, cin, cout, k, k, s, s, pt, pl, h, w, oh, ow,
                      in_layout, self.put(wt), self.put(self.bias(cout)))
         return self.add(L), oh, ow
 
@@ -132,9 +134,14 @@ _B3_STAGES = [(1, 3, 1, 24, 2), (6, 3, 2, 32, 3), (6, 5, 2, 48, 3), (6, 3, 2, 96
 # BirdNET v3.0 at its PUBLISHED size (manifests/BirdNET-v3.0-Models.models.json: 557 212 256 bytes = 139 M float32 parameters, a
 # 1 280-d embedding, 11 560 classes).  [EXT] The trunk is not published offline; what fits those three numbers is EfficientNetV2-L
 # (Tan & Le 2021: 119 M parameters, 1 280 final features) under an 11 560 x 1 280 head (14.8 M).  V2-L's first three stages are
-# fused-MBConv (a 3x3 FULL convolution as expand); this library's conv stack has 3x3 full convolutions for the stem only, so they
-# are spelled as MBConv here and four more blocks in the 384-channel stage make up for their weights: 139.0 M parameters.
+# fused-MBConv (a 3x3 FULL convolution as expand).  'birdnet_v30_v2l' builds that plan as it is (_V2L_FUSED_STAGES: 132 M
+# parameters, 31.6 GFLOP per segment, 12.9 of them in the full convolutions); 'birdnet_v30_sized' -- written before the library
+# ran full convolutions past the stem -- spells the three fused stages as MBConv and adds four blocks to the 384-channel stage
+# to make up for their weights (139.0 M parameters), and stays as it was.
 _V2L_STAGES = [(1, 3, 1, 32, 4), (4, 3, 2, 64, 7), (4, 3, 2, 96, 7), (4, 3, 2, 192, 10), (6, 3, 1, 224, 19), (6, 3, 2, 384, 29), (6, 3, 1, 640, 7)]
+# EfficientNetV2-L's own plan: (expand, kernel, stride, cout, repeats, fused) -- a sixth element True makes the stage Fused-MBConv
+_V2L_FUSED_STAGES = [(1, 3, 1, 32, 4, True), (4, 3, 2, 64, 7, True), (4, 3, 2, 96, 7, True), (4, 3, 2, 192, 10), (6, 3, 1, 224, 19),
+                     (6, 3, 2, 384, 25), (6, 3, 1, 640, 7)]
 # a two-stage toy stack for CPU-speed tests (same op mix: conv, dw s1/s2 k3/k5, pw, residual)
 _TINY_STAGES = [(1, 3, 1, 8, 1), (4, 5, 2, 16, 2), (4, 3, 2, 24, 1)]
 
@@ -152,7 +159,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     v2.4-shaped model's conv stack; the published file is 413 MB and runs 4.4x slower than v2.4 on the reference's CPU, see below),
     'perch_v2_tiny' (the same front-end and head on the B0 stage plan with GELU: 89 MB, 1.0 GFLOP; rounds 1-2's "perch_v2"),
     'birdnet_v30' (the v3.0 contract of the reference's manifest: 5 s / 32 kHz, 11 560 classes with the sigmoid inside the model,
-    1 280-d embedding; trunk and front-end [EXT]: B0 on the 128-mel front-end).
+    1 280-d embedding; trunk and front-end [EXT]: B0 on the 128-mel front-end),
+    'birdnet_v30_sized' (the same contract on a trunk of the published file's size, every stage MBConv),
+    'birdnet_v30_v2l' (the same contract on EfficientNetV2-L's stage plan: three Fused-MBConv stages, 132 M parameters).
+    A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
     rng = np.random.default_rng(seed)
@@ -183,6 +193,13 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
         sr, n, dur = 32000, 160000, 5.0
         branches = [mf.Branch(1024, 320, 128, (n - 1024) // 320 + 1, 60.0, 16000.0, 1.23)]
         stages, stem, head, ncls, family, out_act = _B0_STAGES, 32, 1280, 11560, 2, mf.OUT_NONE
+    elif kind == "birdnet_v30_v2l":
+        # the v3.0 contract on EfficientNetV2-L's actual stage plan: three Fused-MBConv stages (a k x k full convolution as the
+        # expand, no gate), then MBConv with squeeze-excite; swish
+        sr, n, dur = 32000, 160000, 5.0
+        branches = [mf.Branch(1024, 320, 128, (n - 1024) // 320 + 1, 60.0, 16000.0, 1.23)]
+        stages, stem, head, ncls, family, out_act = _V2L_FUSED_STAGES, 32, 1280, 11560, 2, mf.OUT_NONE
+        act = mf.ACT_SWISH
     elif kind == "birdnet_v30_sized":
         # the v3.0 contract (above) on a trunk of the published file's SIZE (VERDICT r5 missing #3: the B0 stand-in is a quarter of a
         # percent of it): _V2L_STAGES with swish and squeeze-excite gates
@@ -206,7 +223,7 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     elif kind == "custom":
         # any inverted-residual stack on any spectrogram (round 6: plans this repo did not write -- tests/test_random_plans_gpu.py,
         # tools/plan_coverage.py): `plan` = {sr, n, branches: [(frame_length, hop, n_mels, fmin, fmax)], stem, stages: [(expand,
-        # kernel, stride, cout, repeats)], head, classes, act, se, out_act, family, hidden, stem_stride, project_act}
+        # kernel, stride, cout, repeats[, fused])], head, classes, act, se, out_act, family, hidden, stem_stride, project_act}
         P = dict(plan or {})
         sr, n = int(P.get("sr", 48000)), int(P.get("n", 12000))
         dur = n / float(sr)
@@ -230,7 +247,7 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     # EfficientNet-B3, whose every MBConv block carries a gate between the depthwise and the project convolution (se_ratio 0.25 of
     # the block's INPUT channels; rounded down to a multiple of 4 here, the kernels' channel granularity: 40 -> 8, 24 -> 4,
     # 32 -> 8, 48 -> 12, 96 -> 24, 136 -> 32, 232 -> 56, 384 -> 96).  'perch_v2_tiny' (B0 plan, GELU) stays gate-free.
-    se = kind in ("mini_se", "perch_v2", "birdnet_v30_sized")
+    se = kind in ("mini_se", "perch_v2", "birdnet_v30_sized", "birdnet_v30_v2l")
     if se:
         act = mf.ACT_SWISH      # the EfficientNet original: swish activations, squeeze-excite in every block
     stem_stride, se_div = 2, 4
@@ -241,10 +258,26 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     h, w_, c = branches[0].n_mels, branches[0].n_frames, len(branches)
     t, h, w_ = b.conv(0, h, w_, c, stem, 3, stem_stride, act, in_layout=1)
     c = stem
-    for (e, k, s, cout, reps) in stages:
+    for st in stages:
+        (e, k, s, cout, reps), fused = st[:5], len(st) > 5 and bool(st[5])
         for r in range(reps):
             stride = s if r == 0 else 1
             tin, cin = t, c
+            if fused:
+                # Fused-MBConv (EfficientNetV2): a k x k full convolution as the expand (or the whole block at expand ratio 1),
+                # then a 1x1 project; no squeeze-excite gate.  Residual branches damped as below, and every fused branch by half
+                # again, standing in for the gate's sigmoid (~0.5): at MBConv's gains the three fused stages of EfficientNetV2-L
+                # handed the MBConv stages a trunk ten times the size they see in birdnet_v30_sized, which those carried past the
+                # f16 range (and made the logits hypersensitive to rounding)
+                res = tin if (stride == 1 and cin == cout) else mf.NO_TENSOR
+                gain = 0.25 if res != mf.NO_TENSOR else 0.5
+                if e == 1:
+                    t, h, w_ = b.conv(t, h, w_, c, cout, k, stride, act, res=res, gain=gain if res != mf.NO_TENSOR else 1.0)
+                else:
+                    t, h, w_ = b.conv(t, h, w_, c, c * e, k, stride, act)
+                    t = b.pwconv(t, h, w_, c * e, cout, mf.ACT_NONE, res, gain=gain)
+                c = cout
+                continue
             if e != 1:
                 t = b.pwconv(t, h, w_, c, c * e, act)
                 c = c * e
@@ -266,7 +299,7 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
         t = b.dense(t, head, hidden, act=act, logits=False)
         t = b.dense(t, hidden, ncls, gain=1.5)
     else:
-        t = b.dense(t, head, ncls, gain=1.5, act=mf.ACT_SIGMOID if kind in ("birdnet_v30", "birdnet_v30_sized") else mf.ACT_NONE)
+        t = b.dense(t, head, ncls, gain=1.5, act=mf.ACT_SIGMOID if kind in ("birdnet_v30", "birdnet_v30_sized", "birdnet_v30_v2l") else mf.ACT_NONE)
     blob = np.concatenate(b.chunks) if b.chunks else np.zeros(0, np.float32)
     m = mf.Model(family, sr, n, dur, ncls, head, out_act, emb_t, branches[0].n_mels,
                  branches[0].n_frames, 1e-6, branches, b.layers, blob)
@@ -324,6 +357,17 @@ def random_plan(seed: int, big: bool = False) -> dict:
     return {"sr": sr, "n": n, "branches": brs, "stem": stem, "stages": stages, "head": ri(8, 40) * 8, "classes": ri(20, 120),
             "act": act, "se": bool(rng.integers(0, 2)), "out_act": int(rng.choice([mf.OUT_SIGMOID, mf.OUT_SOFTMAX, mf.OUT_SIGMOID])),
             "stem_stride": int(rng.choice([1, 2, 2])), "mag_scale": float(rng.uniform(0.8, 1.5)), "se_div": int(rng.choice([4, 2, 6]))}
+
+
+def random_fused_plan(seed: int, big: bool = False) -> dict:
+    """random_plan(seed, big) with its first one to three stages turned into Fused-MBConv stages (a sixth stage element True: a
+    k x k full convolution as the expand, then the 1x1 project; no gate), how many drawn from a generator of its own so that
+    random_plan's draws stay what they are.  Feed to build_model("custom", plan=...)."""
+    P = random_plan(seed, big)
+    rng = np.random.default_rng(0xF05ED + seed)
+    n_fused = int(rng.integers(1, min(3, len(P["stages"])) + 1))
+    P["stages"] = [tuple(st) + (True,) if i < n_fused else tuple(st) for i, st in enumerate(P["stages"])]
+    return P
 
 
 # The five plans the round-5 judge ran the planner on (VERDICT r5 missing #1): widths one step away from this repo's own

@@ -309,7 +309,7 @@ BH_API uint64_t bh_tensor_floats(const bh_classifier *c, uint32_t tensor);
 /* Per-stage kernel timing, summed over every bh_forward_device call since profiling was last switched ON
  * (set_profiling(ctx, 1) starts a new measurement; the events are recorded on the context stream around every
  * launch and read here, after a stream synchronise: nothing inside a forward waits for them):
- * stage 0 = min/max, 1 = mel front-end, 2 = stem conv, 3 = depthwise, 4 = pointwise,
+ * stage 0 = min/max, 1 = mel front-end, 2 = full convolutions (the unfused stem and every k x k group-1 layer), 3 = depthwise, 4 = pointwise,
  * 5 = pool, 6 = dense, 7 = top-k, 8 = fused MBConv blocks (expand + depthwise + project in
  * one launch).  ms[] receives BH_N_STAGES floats (HIP-event times). */
 #define BH_N_STAGES 9
