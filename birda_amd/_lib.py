@@ -247,6 +247,12 @@ AUDIT_SYMBOLS = [
     ("bh_audit_arena_plan", C.c_int, [_VP, _VP, _SZ, _VP, _VP, _VP, _SZ]),
 ]
 
+# include/birda_hip_layer_debug.h: the layer kernels alone, for the tests that hold them to float64
+LAYER_DEBUG_SYMBOLS = [
+    ("bh_debug_conv_gemm", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, C.c_int, C.c_int, _VP, _SZ]),
+    ("bh_debug_layer_gemm", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ, _SZ, _SZ, _SZ, C.c_int, C.c_int, _VP, _SZ]),
+]
+
 _lib = None
 
 
@@ -259,7 +265,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

@@ -74,12 +74,19 @@ bh::ConvParams conv_params(const bh::LayerRec &L) {
 
 // A full convolution's [kh][kw][cin][cout] weights as the implicit GEMM's K x ld rows: the channels of every tap padded to whole
 // 32-deep steps (K = kh kw align_up(cin, 32)), the columns to ld; zero in the padding
-std::vector<float> conv_gemm_rows(const float *W, const bh::LayerRec &L, int ld) {
-    const size_t cpad = align_up(L.cin, 32), taps = (size_t)L.kh * L.kw;
+std::vector<float> conv_gemm_rows(const float *W, const bh::ConvParams &p, int ld) {
+    const size_t cpad = align_up((size_t)p.cin, 32), taps = (size_t)p.kh * p.kw;
     std::vector<float> w(taps * cpad * ld, 0.0f);
     for (size_t t = 0; t < taps; t++)
-        for (uint32_t ch = 0; ch < L.cin; ch++)
-            memcpy(&w[(t * cpad + ch) * ld], W + (t * L.cin + ch) * L.cout, L.cout * sizeof(float));
+        for (size_t ch = 0; ch < (size_t)p.cin; ch++)
+            memcpy(&w[(t * cpad + ch) * ld], W + (t * p.cin + ch) * p.cout, p.cout * sizeof(float));
+    return w;
+}
+
+// A pointwise / dense layer's [K][N] weights with the rows padded to ld = align_up(N, 4) (the f32 GEMM's 16-B loads); zero in the padding
+std::vector<float> pw_gemm_rows(const float *W, size_t K, size_t N, size_t ld) {
+    std::vector<float> w(K * ld, 0.0f);
+    for (size_t k = 0; k < K; k++) memcpy(&w[k * ld], W + k * N, N * sizeof(float));
     return w;
 }
 
@@ -1077,9 +1084,7 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
             const int ld = (int)align_up(L.cout, 4);
             c->ldw[i] = ld;
             if (ld != (int)L.cout) {  // pad rows so 16-B loads stay aligned
-                std::vector<float> w((size_t)L.cin * ld, 0.0f);
-                for (uint32_t k = 0; k < L.cin; k++)
-                    memcpy(&w[(size_t)k * ld], m.blob.data() + L.w_off + (size_t)k * L.cout, L.cout * sizeof(float));
+                const std::vector<float> w = pw_gemm_rows(m.blob.data() + L.w_off, L.cin, L.cout, (size_t)ld);
                 float *d = nullptr;
                 rc = upload(w.data(), w.size() * sizeof(float), &d);
                 if (rc != BH_OK) return rc;
@@ -1099,7 +1104,7 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
                             "(kernel 1..7, stride 1 / 2, channels multiples of 4, NHWC)", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout, L.in_layout);
             const int ld = (int)align_up(L.cout, 4);
             c->ldw[i] = ld;
-            const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, L, ld);
+            const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, p, ld);
             float *d = nullptr;
             rc = upload(w.data(), w.size() * sizeof(float), &d);
             if (rc != BH_OK) return rc;
@@ -1146,7 +1151,7 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
                 //  segments, profiles/conv_gemm.txt -- and exact; shapes alone decide)
                 if (!bh::conv_gemm16_supports(conv_params(L)) || L.cout <= 64) continue;
                 const uint32_t cpad = (uint32_t)align_up(L.cin, 32);
-                const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, L, (int)L.cout);
+                const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, conv_params(L), (int)L.cout);
                 const std::vector<uint16_t> planes = w16_planes(w.data(), (int)(L.kh * L.kw * cpad), (int)L.cout, &c->w16_unscale[i]);
                 float *d = nullptr;
                 rc = upload(planes.data(), planes.size() * sizeof(uint16_t), &d);
@@ -1761,6 +1766,131 @@ int bh_debug_gated_gemm(int device, const float *A, const float *gate, const flo
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(C, dC.p, M * N * 4, hipMemcpyDeviceToHost));
     return BH_OK;
+} catch (...) { return on_exception(); }
+
+namespace {
+
+// A device buffer inside 64 KiB guard bands, for the layer-kernel diagnostics below.  The input guards hold a quiet NaN, so a read
+// past an operand shows up as NaN in the output (the guards lie inside the allocation: such a read cannot fault); the output buffer,
+// guards and body alike, holds a second NaN payload before the launch, so an element the kernel never wrote keeps it and a write
+// past C is found by comparing the guards afterwards.
+constexpr uint32_t kGuardNaN = 0x7fc00000u, kUnwrittenNaN = 0x7fc0beefu;
+struct Guarded {
+    static constexpr size_t G = 64 * 1024;
+    char *base = nullptr;
+    size_t bytes = 0;
+    ~Guarded() { if (base) (void)hipFree(base); }
+    void *p() const { return base + G; }
+    // body = src (bytes of it), or the fill pattern too when src is null
+    bool put(const void *src, size_t n, uint32_t fill) {
+        bytes = (n + 3) & ~(size_t)3;
+        std::vector<uint32_t> h((2 * G + bytes) / 4, fill);
+        if (src) memcpy((char *)h.data() + G, src, n);
+        if (hipMalloc((void **)&base, h.size() * 4) != hipSuccess) { base = nullptr; return false; }
+        return hipMemcpy(base, h.data(), h.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    int guards_intact(uint32_t fill, bool *intact) const {
+        std::vector<uint32_t> h(G / 4);
+        *intact = true;
+        for (const char *g : {base, base + G + bytes}) {
+            HIPCHK(hipMemcpy(h.data(), g, G, hipMemcpyDeviceToHost));
+            for (uint32_t v : h) *intact = *intact && v == fill;
+        }
+        return BH_OK;
+    }
+};
+
+const char *act_name(int act) {
+    static const char *const names[] = {"none", "relu", "relu6", "swish", "gelu", "gelu_tanh", "sigmoid"};
+    return act >= 0 && act <= bh::ACT_SIGMOID ? names[act] : "?";
+}
+
+// the launch's end: wait, check C's guards, copy C and the kernel's name out
+int finish_debug_launch(const char *who, const char *name, const Guarded &dC, float *C, size_t c_floats, char *kernel, size_t kernel_cap) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    bool intact = false;
+    int rc = dC.guards_intact(kUnwrittenNaN, &intact);
+    if (rc != BH_OK) return rc;
+    if (!intact) return fail(BH_ERR_INTERNAL, "%s: %s wrote outside C", who, name ? name : "the kernel");
+    HIPCHK(hipMemcpy(C, dC.p(), c_floats * 4, hipMemcpyDeviceToHost));
+    if (kernel && kernel_cap) snprintf(kernel, kernel_cap, "%s", name ? name : "");
+    return BH_OK;
+}
+
+}  // namespace
+
+// One full convolution on the implicit-GEMM kernels, on operands of the caller's, with the weight preparation create does
+// (conv_gemm_rows, w16_planes) -- tests drive every shape, precision and epilogue instantiation without a model around it.
+int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
+                       const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap) try {
+    if (!X || !W || !bias || !C || !shape || !n_seg || (terms != 0 && terms != 1 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
+        return fail(BH_ERR_INVALID, "debug_conv_gemm: bad arguments");
+    const bh::ConvParams p{shape[0], shape[1], shape[2], shape[3], shape[4], shape[5], shape[6], shape[7], shape[8], shape[9],
+                           shape[10], shape[11], 0, act};
+    if (p.in_h < 1 || p.in_w < 1 || p.out_h < 1 || p.out_w < 1)
+        return fail(BH_ERR_INVALID, "debug_conv_gemm: image %dx%d -> %dx%d", p.in_h, p.in_w, p.out_h, p.out_w);
+    if (terms ? !bh::conv_gemm16_supports(p) : !bh::conv_gemm_supports(p))
+        return fail(BH_ERR_UNSUPPORTED, "debug_conv_gemm: %dx%d stride %dx%d pad %d,%d, %d -> %d channels, %s not built for terms %d",
+                    p.kh, p.kw, p.sh, p.sw, p.pad_t, p.pad_l, p.cin, p.cout, act_name(act), terms);
+    const size_t M = n_seg * (size_t)p.out_h * p.out_w, x_floats = n_seg * (size_t)p.in_h * p.in_w * p.cin;
+    if (M * (size_t)p.cout > (size_t)INT32_MAX || x_floats > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_conv_gemm: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    const size_t K = (size_t)p.kh * p.kw * align_up((size_t)p.cin, 32);
+    const int ld = terms ? p.cout : (int)align_up((size_t)p.cout, 4);
+    const std::vector<float> w = conv_gemm_rows(W, p, ld);
+    float unscale = 1.0f;
+    std::vector<uint16_t> planes;
+    if (terms) planes = w16_planes(w.data(), (int)K, p.cout, &unscale);
+    Guarded dX, dW, dB, dR, dC;
+    if (!dX.put(X, x_floats * 4, kGuardNaN) ||
+        !(terms ? dW.put(planes.data(), planes.size() * 2, kGuardNaN) : dW.put(w.data(), w.size() * 4, kGuardNaN)) ||
+        !dB.put(bias, (size_t)p.cout * 4, kGuardNaN) || (R && !dR.put(R, M * p.cout * 4, kGuardNaN)) ||
+        !dC.put(nullptr, M * p.cout * 4, kUnwrittenNaN))
+        return fail(BH_ERR_HIP, "debug_conv_gemm: device memory");
+    const float *dr = R ? (const float *)dR.p() : nullptr;
+    const char *name = terms ? bh::launch_conv_gemm16((const float *)dX.p(), dW.p(), (const float *)dB.p(), dr, (float *)dC.p(), p,
+                                                      (int)n_seg, terms, unscale, nullptr)
+                             : bh::launch_conv_gemm((const float *)dX.p(), (const float *)dW.p(), (const float *)dB.p(), dr,
+                                                    (float *)dC.p(), p, (int)n_seg, ld, nullptr);
+    return finish_debug_launch("debug_conv_gemm", name, dC, C, M * p.cout, kernel, kernel_cap);
+} catch (...) { return on_exception(); }
+
+// A pointwise / dense layer (pool_rows == 0) or the fused head convolution + pool (pool_rows = pixels per segment) on operands of
+// the caller's, with create's weight preparation (pw_gemm_rows, w16_planes), through the launchers a forward pass calls.
+int bh_debug_layer_gemm(int device, const float *A, const float *W, const float *bias, const float *R, float *C, size_t M, size_t K,
+                        size_t N, size_t pool_rows, int act, int terms, char *kernel, size_t kernel_cap) try {
+    if (!A || !W || !bias || !C || !M || !K || !N || (terms != 0 && terms != 1 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
+        return fail(BH_ERR_INVALID, "debug_layer_gemm: bad arguments");
+    if (M * K > (size_t)INT32_MAX || M * N > (size_t)INT32_MAX || K * N > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_layer_gemm: operands past 2^31 elements");
+    if (pool_rows) {
+        if (R || !terms || M % pool_rows)
+            return fail(BH_ERR_INVALID, "debug_layer_gemm: the head pool takes no residual, split-f16 terms and whole segments");
+        if (!bh::head_gap16_supports((int)pool_rows, (int)K, (int)N, act))
+            return fail(BH_ERR_UNSUPPORTED, "debug_layer_gemm: head pool of %zu pixels, K %zu, N %zu, %s not built", pool_rows, K, N, act_name(act));
+    } else if (terms ? !bh::pw_gemm16_supports((int)K, act) : K % 4 != 0) {
+        return fail(BH_ERR_UNSUPPORTED, "debug_layer_gemm: K %zu, %s not built for terms %d", K, act_name(act), terms);
+    }
+    HIPCHK(hipSetDevice(device));
+    const size_t ld = align_up(N, 4), out_rows = pool_rows ? M / pool_rows : M;
+    float unscale = 1.0f;
+    std::vector<uint16_t> planes;
+    std::vector<float> w;
+    if (terms) planes = w16_planes(W, (int)K, (int)N, &unscale);
+    else w = pw_gemm_rows(W, K, N, ld);
+    Guarded dA, dW, dB, dR, dC;
+    if (!dA.put(A, M * K * 4, kGuardNaN) ||
+        !(terms ? dW.put(planes.data(), planes.size() * 2, kGuardNaN) : dW.put(w.data(), w.size() * 4, kGuardNaN)) ||
+        !dB.put(bias, N * 4, kGuardNaN) || (R && !dR.put(R, M * N * 4, kGuardNaN)) || !dC.put(nullptr, out_rows * N * 4, kUnwrittenNaN))
+        return fail(BH_ERR_HIP, "debug_layer_gemm: device memory");
+    const float *da = (const float *)dA.p(), *db = (const float *)dB.p(), *dr = R ? (const float *)dR.p() : nullptr;
+    float *dc = (float *)dC.p();
+    const char *name = pool_rows ? bh::launch_head_gap16(da, dW.p(), db, dc, (int)out_rows, (int)pool_rows, (int)K, (int)N, act, terms, unscale, nullptr)
+                       : terms   ? bh::launch_pw_gemm16(da, dW.p(), db, dr, dc, (int)M, (int)K, (int)N, act, terms, unscale, nullptr)
+                                 : bh::launch_pw_gemm(da, (const float *)dW.p(), db, dr, dc, (int)M, (int)K, (int)N, (int)ld, act, nullptr);
+    return finish_debug_launch("debug_layer_gemm", name, dC, C, out_rows * N, kernel, kernel_cap);
 } catch (...) { return on_exception(); }
 
 int bh_debug_mb_stamps(bh_classifier *c, uint64_t *out, size_t cap) {

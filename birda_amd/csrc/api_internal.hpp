@@ -28,6 +28,7 @@
 #include "../../include/birda_hip.h"
 #include "../../include/birda_hip_debug.h"
 #include "../../include/birda_hip_audit.h"
+#include "../../include/birda_hip_layer_debug.h"
 #include "kernels.hpp"
 #include "trace.hpp"
 #include "model.hpp"

@@ -366,16 +366,19 @@ void launch_conv_direct(const float *in, const float *w, const float *b, float *
 // the split-f16 planes of launch_pw_gemm16 over that K.  kh, kw 1 .. 7, strides 1 / 2, cin and cout multiples of 4, NHWC input.
 bool conv_gemm_supports(const ConvParams &p);
 bool conv_gemm16_supports(const ConvParams &p);   // ... and an activation the f16 epilogue is instantiated for
-void launch_conv_gemm(const float *in, const float *W, const float *b, const float *R, float *out, const ConvParams &p, int n_seg,
-                      int ldw, hipStream_t s);
-void launch_conv_gemm16(const float *in, const void *Wf, const float *b, const float *R, float *out, const ConvParams &p, int n_seg,
-                        int terms, float w_unscale, hipStream_t s);
+// (these launchers, launch_pw_gemm, launch_pw_gemm16 and launch_head_gap16 return the instantiation they launched as a static
+//  string with its template arguments, e.g. "conv_gemm_kernel<BM=64,NT=5>", for the diagnostic entry points; the forward pass
+//  ignores it)
+const char *launch_conv_gemm(const float *in, const float *W, const float *b, const float *R, float *out, const ConvParams &p, int n_seg,
+                             int ldw, hipStream_t s);
+const char *launch_conv_gemm16(const float *in, const void *Wf, const float *b, const float *R, float *out, const ConvParams &p, int n_seg,
+                               int terms, float w_unscale, hipStream_t s);
 // depthwise conv NHWC; w [kh][kw][c]
 void launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
                    int n_seg, hipStream_t s);
 // C[M][N] = act(A[M][K] . W[K][ldw] + bias) (+ R); W rows padded to ldw (multiple of 4)
-void launch_pw_gemm(const float *A, const float *W, const float *bias, const float *R, float *C, int M, int K,
-                    int N, int ldw, int act, hipStream_t s);
+const char *launch_pw_gemm(const float *A, const float *W, const float *bias, const float *R, float *C, int M, int K,
+                          int N, int ldw, int act, hipStream_t s);
 // the same product on the f16 MFMA (terms = 3: hi / lo split operands, f32-grade; 1: plain f16); K % 32 == 0;
 // Wf: fragment-major planes [K / 32][ceil(N / 16)]{hi, lo}[64 lanes][8 halves]
 // The planes hold W * w_scale, w_scale = 1 / w_unscale an exact power of two chosen on the host (f16_weight_scale, api.hip)
@@ -383,11 +386,11 @@ void launch_pw_gemm(const float *A, const float *W, const float *bias, const flo
 // He-normal weight at Cin 1152 is ~2^-5, its lo half a subnormal with 2^-24 absolute resolution); the epilogue computes
 // acc * w_unscale + bias in one FMA.
 bool pw_gemm16_supports(int K, int act);
-void launch_pw_gemm16(const float *A, const void *Wf, const float *bias, const float *R, float *C, int M, int K, int N,
-                      int act, int terms, float w_unscale, hipStream_t s);
+const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, const float *R, float *C, int M, int K, int N,
+                             int act, int terms, float w_unscale, hipStream_t s);
 // squeeze-excite blocks (round 5): the project convolution with A = D x gate (gate [M / rows_per_seg][K]; nullptr: plain) ...
-void launch_pw_gemm_gated(const float *A, const float *gate, int rows_per_seg, const float *W, const float *bias, const float *R,
-                          float *C, int M, int K, int N, int ldw, int act, hipStream_t s);
+const char *launch_pw_gemm_gated(const float *A, const float *gate, int rows_per_seg, const float *W, const float *bias, const float *R,
+                                 float *C, int M, int K, int N, int ldw, int act, hipStream_t s);
 // ... on the f16 MFMA (no activation; K % 4 == 0, planes [ceil(K / 32)][ceil(N / 16)]{hi, lo}[64][8] zero-padded in K) ...
 // (a_blocked: A in MbDesc::dblk's layout -- every kernel behind this entry reads either; pw_gemm16_gated_wants_blocked: the
 //  shapes whose kernel is the faster for it, a property of the BLOCK, never of the launch)
@@ -412,8 +415,8 @@ void launch_gap(const float *in, float *out, int n_seg, int P, int C, hipStream_
 void launch_scale(const float *in, const float *gate, float *out, int n_seg, int P, int C, hipStream_t s);
 // head 1x1 conv + activation (GELU / swish / ReLU6) + global average pool fused (f16 hi / lo weight planes as for launch_pw_gemm16)
 bool head_gap16_supports(int P, int K, int N, int act);
-void launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,
-                       int act, int terms, float w_unscale, hipStream_t s);
+const char *launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,
+                              int act, int terms, float w_unscale, hipStream_t s);
 // activation + top-k over logits [n][n_classes] -> idx/conf [n][top_k]
 // Post-filter of the kept top-k (reference apply_range_filter, classifier.rs:587-645): class_score (NaN = species without
 // geomodel entry) selects geomodel_filter.rs:46-82, else species_keep the species-list retain (:617-640); both null = off.

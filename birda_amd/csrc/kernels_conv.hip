@@ -172,27 +172,31 @@ static int pick_nt(int N) {
     return best;
 }
 
-void launch_pw_gemm(const float *A, const float *W, const float *bias, const float *R, float *C, int M, int K,
-                    int N, int ldw, int act, hipStream_t s) {
-    launch_pw_gemm_gated(A, nullptr, 1, W, bias, R, C, M, K, N, ldw, act, s);
+const char *launch_pw_gemm(const float *A, const float *W, const float *bias, const float *R, float *C, int M, int K,
+                          int N, int ldw, int act, hipStream_t s) {
+    return launch_pw_gemm_gated(A, nullptr, 1, W, bias, R, C, M, K, N, ldw, act, s);
 }
 
 // the same GEMM with A = D x gate (gate [M / rows_per_seg][K], nullptr: plain): the project convolution of a squeeze-excite block
-void launch_pw_gemm_gated(const float *A, const float *gate, int rows_per_seg, const float *W, const float *bias, const float *R,
-                          float *C, int M, int K, int N, int ldw, int act, hipStream_t s) {
+const char *launch_pw_gemm_gated(const float *A, const float *gate, int rows_per_seg, const float *W, const float *bias, const float *R,
+                                 float *C, int M, int K, int N, int ldw, int act, hipStream_t s) {
     const int nt = pick_nt(N);
     const long blocks128 = (long)((M + 127) / 128) * ((N + nt * 16 - 1) / (nt * 16));
     const bool small = blocks128 < 512;  // keep >= 2 blocks per CU in flight when M is short
+    const char *name = nullptr;
 #define BH_PW_CASE(NTV)                                                                    \
     case NTV:                                                                              \
         if (small) pw_launch<64, NTV>(A, W, bias, R, C, M, K, N, ldw, act, s, gate, rows_per_seg);             \
         else pw_launch<128, NTV>(A, W, bias, R, C, M, K, N, ldw, act, s, gate, rows_per_seg);                  \
+        name = gate ? (small ? "pw_gemm_kernel<BM=64,NT=" #NTV ",GATE>" : "pw_gemm_kernel<BM=128,NT=" #NTV ",GATE>")   \
+                    : (small ? "pw_gemm_kernel<BM=64,NT=" #NTV ">" : "pw_gemm_kernel<BM=128,NT=" #NTV ">");            \
         break;
     switch (nt) {
         BH_PW_CASE(1) BH_PW_CASE(2) BH_PW_CASE(3) BH_PW_CASE(4)
         BH_PW_CASE(5) BH_PW_CASE(6) BH_PW_CASE(7) BH_PW_CASE(8)
     }
 #undef BH_PW_CASE
+    return name;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1000,8 +1004,8 @@ void launch_pw_gemm16_gated(const float *A, const float *gate, int rows_per_seg,
 #undef BH_GS
 }
 
-void launch_pw_gemm16(const float *A, const void *Wf, const float *bias, const float *R, float *C, int M, int K, int N,
-                      int act, int terms, float w_unscale, hipStream_t s) {
+const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, const float *R, float *C, int M, int K, int N,
+                             int act, int terms, float w_unscale, hipStream_t s) {
     const int n_tiles = (N + 15) / 16;
     const int n_xb = (n_tiles + 7) / 8, n_yb = (M + 127) / 128;
     dim3 grid((unsigned)(8 * ((n_xb + 7) / 8) * n_yb)), block(256);   // (one-dimensional: the kernel deals the blocks XCD by XCD)
@@ -1014,36 +1018,41 @@ void launch_pw_gemm16(const float *A, const void *Wf, const float *bias, const f
     const int ntb = !staged ? 8 : n_xb * n_yb >= 384 ? 8 : ((n_tiles + 3) / 4) * n_yb >= 384 ? 4 : 2;
     const int n_xb_s = (n_tiles + ntb - 1) / ntb;
     const dim3 grid_s((unsigned)(8 * ((n_xb_s + 7) / 8) * n_yb));
-#define BH_G16S(T, ACTV, NTBV)                                                                                                    \
+    const char *name = nullptr;
+#define BH_G16S(T, ACTV, AN, NTBV)                                                                                                \
     do {                                                                                                                          \
         constexpr size_t lds = 2 * ((8 + NTBV) * 2 * 256) * sizeof(float);                                                        \
         static DeviceOnce attr;                                                                                                   \
         attr.run([] { (void)hipFuncSetAttribute((const void *)pw_gemm16s_kernel<T, ACTV, false, NTBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }); \
         hipLaunchKernelGGL((pw_gemm16s_kernel<T, ACTV, false, NTBV>), grid_s, block, lds, s, A, (const f16x8 *)Wf, bias, R, C, M, K, N, n_tiles, w_unscale); \
+        name = "pw_gemm16s_kernel<" #T "," AN ",NTB=" #NTBV ">";                                                                 \
     } while (0)
-#define BH_G16(T, ACTV)                                                                                                           \
+#define BH_G16(T, ACTV, AN)                                                                                                       \
     do {                                                                                                                          \
         if (staged) {                                                                                                             \
-            if (ntb == 8) BH_G16S(T, ACTV, 8); else if (ntb == 4) BH_G16S(T, ACTV, 4); else BH_G16S(T, ACTV, 2);                  \
+            if (ntb == 8) BH_G16S(T, ACTV, AN, 8); else if (ntb == 4) BH_G16S(T, ACTV, AN, 4); else BH_G16S(T, ACTV, AN, 2);      \
         } else if (M <= 32) {    /* one or two row tiles: the skinny kernel per row tile, eight steps in flight (the same bits) */ \
             for (int m0 = 0; m0 < M; m0 += 16)                                                                                    \
                 hipLaunchKernelGGL((pw_gemm16_skinny_kernel<T, ACTV>), dim3((unsigned)((n_tiles + 7) / 8)), block, 0, s, A + (size_t)m0 * K, (const f16x8 *)Wf, bias, \
                                    R ? R + (size_t)m0 * N : nullptr, C + (size_t)m0 * N, std::min(16, M - m0), K, N, n_tiles, w_unscale); \
+            name = "pw_gemm16_skinny_kernel<" #T "," AN ">";                                                                     \
         } else {                                                                                                                  \
             hipLaunchKernelGGL((pw_gemm16_kernel<T, ACTV>), grid, block, 0, s, A, (const f16x8 *)Wf, bias, R, C, M, K, N, n_tiles, w_unscale); \
+            name = "pw_gemm16_kernel<" #T "," AN ">";                                                                            \
         }                                                                                                                         \
     } while (0)
 #define BH_G16A(T)                                                   \
     switch (act) {                                                   \
-    case ACT_GELU_ERF: BH_G16(T, ACT_GELU_ERF); break;               \
-    case ACT_SWISH: BH_G16(T, ACT_SWISH); break;                     \
-    case ACT_RELU6: BH_G16(T, ACT_RELU6); break;                     \
-    default: BH_G16(T, ACT_NONE); break;                             \
+    case ACT_GELU_ERF: BH_G16(T, ACT_GELU_ERF, "GELU"); break;       \
+    case ACT_SWISH: BH_G16(T, ACT_SWISH, "SWISH"); break;            \
+    case ACT_RELU6: BH_G16(T, ACT_RELU6, "RELU6"); break;            \
+    default: BH_G16(T, ACT_NONE, "NONE"); break;                     \
     }
     if (terms == 3) { BH_G16A(3) } else { BH_G16A(1) }
 #undef BH_G16A
 #undef BH_G16
 #undef BH_G16S
+    return name;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1186,27 +1195,30 @@ bool head_gap16_supports(int P, int K, int N, int act) {
     return act_is_templated(act) && K % 32 == 0 && N % 128 == 0 && P >= 1 && P <= 80;
 }
 
-void launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,
-                       int act, int terms, float w_unscale, hipStream_t s) {
+const char *launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,
+                              int act, int terms, float w_unscale, hipStream_t s) {
     const bool few = n_seg <= 32;      // (a launch that leaves most of the chip idle: two column tiles a workgroup, four times the workgroups)
     const int n_tiles = N / 16, n_cb = few ? N / 32 : N / 128;
     const int pt = (P + 15) / 16, sw = pt <= 3 ? 2 : 1;
     const int n_mb = (n_seg + 4 * sw - 1) / (4 * sw);
     dim3 grid((unsigned)(((n_mb + 7) / 8) * n_cb * 8)), block(256);
-#define BH_HG(PTV, SWV, T, ACTV) do { if (few) hipLaunchKernelGGL((head_gap16_kernel<PTV, SWV, T, ACTV, 2>), grid, block, 0, s, A, (const f16x8 *)Wf, bias, out, \
+    const char *name = nullptr;
+#define BH_HG(PTV, SWV, T, ACTV, AN) do { if (few) hipLaunchKernelGGL((head_gap16_kernel<PTV, SWV, T, ACTV, 2>), grid, block, 0, s, A, (const f16x8 *)Wf, bias, out, \
                                                     n_seg, P, K, N, n_tiles, n_cb, w_unscale); \
     else hipLaunchKernelGGL((head_gap16_kernel<PTV, SWV, T, ACTV, 8>), grid, block, 0, s, A, (const f16x8 *)Wf, bias, out, \
-                                                    n_seg, P, K, N, n_tiles, n_cb, w_unscale); } while (0)
+                                                    n_seg, P, K, N, n_tiles, n_cb, w_unscale); \
+    name = few ? "head_gap16_kernel<PT=" #PTV ",SW=" #SWV ",T=" #T "," AN ",CT=2>" : "head_gap16_kernel<PT=" #PTV ",SW=" #SWV ",T=" #T "," AN ",CT=8>"; } while (0)
 #define BH_HGA(PTV, SWV, T)                                          \
     switch (act) {                                                   \
-    case ACT_SWISH: BH_HG(PTV, SWV, T, ACT_SWISH); break;            \
-    case ACT_RELU6: BH_HG(PTV, SWV, T, ACT_RELU6); break;            \
-    default: BH_HG(PTV, SWV, T, ACT_GELU_ERF); break;                \
+    case ACT_SWISH: BH_HG(PTV, SWV, T, ACT_SWISH, "SWISH"); break;   \
+    case ACT_RELU6: BH_HG(PTV, SWV, T, ACT_RELU6, "RELU6"); break;   \
+    default: BH_HG(PTV, SWV, T, ACT_GELU_ERF, "GELU"); break;        \
     }
     if (pt <= 3) { if (terms == 3) { BH_HGA(3, 2, 3) } else { BH_HGA(3, 2, 1) } }
     else { if (terms == 3) { BH_HGA(5, 1, 3) } else { BH_HGA(5, 1, 1) } }
 #undef BH_HGA
 #undef BH_HG
+    return name;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1584,42 +1596,48 @@ static void conv_launch(const float *X, const float *W, const float *bias, const
     hipLaunchKernelGGL((conv_gemm_kernel<BM, NT>), grid, block, 0, s, X, W, bias, R, C, p, M, ldw);
 }
 
-void launch_conv_gemm(const float *X, const float *W, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
-                      int ldw, hipStream_t s) {
+const char *launch_conv_gemm(const float *X, const float *W, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
+                             int ldw, hipStream_t s) {
     const int M = n_seg * p.out_h * p.out_w;
-    if (M <= 0) return;
+    if (M <= 0) return nullptr;
     const int nt = pick_nt(p.cout);
     const long blocks128 = (long)((M + 127) / 128) * ((p.cout + nt * 16 - 1) / (nt * 16));
     const bool small = blocks128 < 512;   // the tile is the layer's shape alone: the same bits at any launch size either way
+    const char *name = nullptr;
 #define BH_CG_CASE(NTV)                                                                       \
     case NTV:                                                                                 \
         if (small) conv_launch<64, NTV>(X, W, bias, R, C, p, M, ldw, s);                     \
         else conv_launch<128, NTV>(X, W, bias, R, C, p, M, ldw, s);                          \
+        name = small ? "conv_gemm_kernel<BM=64,NT=" #NTV ">" : "conv_gemm_kernel<BM=128,NT=" #NTV ">"; \
         break;
     switch (nt) {
         BH_CG_CASE(1) BH_CG_CASE(2) BH_CG_CASE(3) BH_CG_CASE(4)
         BH_CG_CASE(5) BH_CG_CASE(6) BH_CG_CASE(7) BH_CG_CASE(8)
     }
 #undef BH_CG_CASE
+    return name;
 }
 
-void launch_conv_gemm16(const float *X, const void *Wf, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
-                        int terms, float w_unscale, hipStream_t s) {
+const char *launch_conv_gemm16(const float *X, const void *Wf, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
+                               int terms, float w_unscale, hipStream_t s) {
     const int M = n_seg * p.out_h * p.out_w;
-    if (M <= 0) return;
+    if (M <= 0) return nullptr;
     const int n_tiles = (p.cout + 15) / 16;
     const dim3 grid((unsigned)(((n_tiles + 7) / 8) * ((M + 127) / 128))), block(256);
-#define BH_CG16(T, ACTV) hipLaunchKernelGGL((conv_gemm16_kernel<T, ACTV>), grid, block, 0, s, X, (const f16x8 *)Wf, bias, R, C, p, M, n_tiles, w_unscale)
+    const char *name = nullptr;
+#define BH_CG16(T, ACTV, AN) do { hipLaunchKernelGGL((conv_gemm16_kernel<T, ACTV>), grid, block, 0, s, X, (const f16x8 *)Wf, bias, R, C, p, M, n_tiles, w_unscale); \
+                                  name = "conv_gemm16_kernel<" #T "," AN ">"; } while (0)
 #define BH_CG16A(T)                                                  \
     switch (p.act) {                                                 \
-    case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF); break;              \
-    case ACT_SWISH: BH_CG16(T, ACT_SWISH); break;                    \
-    case ACT_RELU6: BH_CG16(T, ACT_RELU6); break;                    \
-    default: BH_CG16(T, ACT_NONE); break;                            \
+    case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF, "GELU"); break;      \
+    case ACT_SWISH: BH_CG16(T, ACT_SWISH, "SWISH"); break;           \
+    case ACT_RELU6: BH_CG16(T, ACT_RELU6, "RELU6"); break;           \
+    default: BH_CG16(T, ACT_NONE, "NONE"); break;                    \
     }
     if (terms == 3) { BH_CG16A(3) } else { BH_CG16A(1) }
 #undef BH_CG16A
 #undef BH_CG16
+    return name;
 }
 
 // ---------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ bench.py's cpu_baseline leg -- never from birda_amd/.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import subprocess
 from typing import List, Optional, Tuple
@@ -304,3 +305,72 @@ def bsg_postprocess(index: np.ndarray, confidence: np.ndarray, intercept: np.nda
         out.append((c, q))
     order = sorted(range(len(out)), key=lambda i: -out[i][1])     # sorted() is stable: ties keep their order
     return [out[i][0] for i in order], [out[i][1] for i in order]
+
+
+# --------------------------------------------------------------------------------------------------------
+# The layer GEMMs and full convolutions (kernels_conv.hip) in float64, numpy restatements for tests/test_layer_gemm*.py.
+# Activation codes as in the model file (kernels.hpp Act).
+# --------------------------------------------------------------------------------------------------------
+ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SIGMOID = range(7)
+ACT_NAMES = {ACT_NONE: "none", ACT_RELU: "relu", ACT_RELU6: "relu6", ACT_SWISH: "swish", ACT_GELU_ERF: "gelu",
+             ACT_GELU_TANH: "gelu_tanh", ACT_SIGMOID: "sigmoid"}
+_erf = np.frompyfunc(math.erf, 1, 1)
+
+
+def _sigmoid64(v: np.ndarray) -> np.ndarray:
+    e = np.exp(-np.abs(v))                  # never overflows
+    return np.where(v >= 0, 1.0 / (1.0 + e), e / (1.0 + e))
+
+
+def act64(v, act: int) -> np.ndarray:
+    """The activation `act` in float64: GELU through math.erf, the tanh form of GELU as ONNX / PyTorch state it."""
+    v = np.asarray(v, np.float64)
+    if act == ACT_NONE:
+        return v.copy()
+    if act == ACT_RELU:
+        return np.maximum(v, 0.0)
+    if act == ACT_RELU6:
+        return np.minimum(np.maximum(v, 0.0), 6.0)
+    if act == ACT_SWISH:
+        return v * _sigmoid64(v)
+    if act == ACT_SIGMOID:
+        return _sigmoid64(v)
+    if act == ACT_GELU_ERF:
+        return 0.5 * v * (1.0 + np.asarray(_erf(v / math.sqrt(2.0)), np.float64))
+    if act == ACT_GELU_TANH:
+        with np.errstate(over="ignore"):    # (v^3 past 1e308 for |v| > 5e102: tanh(+-inf) is +-1, the right limit)
+            return 0.5 * v * (1.0 + np.tanh(math.sqrt(2.0 / math.pi) * (v + 0.044715 * v * v * v)))
+    raise ValueError(f"activation {act} not restated")
+
+
+def im2col_nhwc(X: np.ndarray, kh: int, kw: int, sh: int, sw: int, pad_t: int, pad_l: int, out_h: int, out_w: int) -> np.ndarray:
+    """X [n][in_h][in_w][cin] -> rows [n * out_h * out_w][kh * kw * cin] in float64, k = (dy, dx, channel), taps outside the image
+    zero.  The bottom / right padding is what out_h / out_w imply: (out_h - 1) sh + kh - in_h - pad_t rows, negative = a crop."""
+    X = np.asarray(X, np.float64)
+    n, in_h, in_w, cin = X.shape
+    need_h, need_w = (out_h - 1) * sh + kh, (out_w - 1) * sw + kw
+    Xp = np.zeros((n, max(need_h, pad_t + in_h), max(need_w, pad_l + in_w), cin))
+    Xp[:, pad_t:pad_t + in_h, pad_l:pad_l + in_w] = X
+    cols = np.empty((n, out_h, out_w, kh, kw, cin))
+    for dy in range(kh):
+        for dx in range(kw):
+            cols[:, :, :, dy, dx] = Xp[:, dy:dy + (out_h - 1) * sh + 1:sh, dx:dx + (out_w - 1) * sw + 1:sw]
+    return cols.reshape(n * out_h * out_w, kh * kw * cin)
+
+
+def conv_nhwc64(X, W, bias, sh: int, sw: int, pad_t: int, pad_l: int, out_h: int, out_w: int):
+    """conv(X, W) + bias in float64, X NHWC, W [kh][kw][cin][cout]: (pre [n * out_h * out_w][cout], the im2col rows)."""
+    kh, kw, cin, cout = W.shape
+    A = im2col_nhwc(X, kh, kw, sh, sw, pad_t, pad_l, out_h, out_w)
+    return gemm64(A, np.asarray(W).reshape(kh * kw * cin, cout), bias), A
+
+
+def gemm64(A, W, bias) -> np.ndarray:
+    """A W + bias in float64."""
+    return np.asarray(A, np.float64) @ np.asarray(W, np.float64) + np.asarray(bias, np.float64)
+
+
+def head_pool64(v, P: int) -> np.ndarray:
+    """The mean over each run of P rows: [n * P][N] -> [n][N] (the head convolution's global average pool)."""
+    v = np.asarray(v, np.float64)
+    return v.reshape(-1, P, v.shape[-1]).mean(axis=1)

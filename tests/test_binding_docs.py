@@ -172,3 +172,21 @@ def test_audit_table_matches_its_header():
     import test_arena_plan_gpu as T
     for k in ("LAYER", "FUSED", "FUSED_SE", "HEAD_GAP", "SE_GATE", "INNER"):
         assert getattr(T, "PATH_" + k) == defines["BH_PATH_" + k], k
+
+
+def test_layer_debug_table_matches_its_header():
+    """include/birda_hip_layer_debug.h (the layer kernels alone, for tests/test_layer_gemm_gpu.py) against its ctypes table and the
+    library's exports."""
+    from birda_amd import _lib
+    _, functions, _ = A.parse_c_header(os.path.join(ROOT, "include", "birda_hip_layer_debug.h"))
+    assert {n for n, _, _ in _lib.LAYER_DEBUG_SYMBOLS} == set(functions) == {"bh_debug_conv_gemm", "bh_debug_layer_gemm"}
+    for name, res, args in _lib.LAYER_DEBUG_SYMBOLS:
+        want_ret, want_args = functions[name]
+        assert _eq_ctypes(A.ctypes_class(res), want_ret), name
+        assert len(args) == len(want_args), name
+        for i, (a, b) in enumerate(zip(args, want_args)):
+            assert _eq_ctypes(A.ctypes_class(a), b), (name, i, a, b)
+        assert hasattr(_lib.load(), name), f"{name} declared in include/birda_hip_layer_debug.h but not exported"
+    # (the boundary birda binds, and the Rust text generated from it, hold none of them)
+    assert not set(functions) & set(A.parse_c_header(HIP_H)[1])
+    assert "bh_debug_conv_gemm" not in open(os.path.join(ROOT, "include", "birda_hip_sys.rs")).read()
