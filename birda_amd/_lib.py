@@ -253,6 +253,14 @@ LAYER_DEBUG_SYMBOLS = [
     ("bh_debug_layer_gemm", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ, _SZ, _SZ, _SZ, C.c_int, C.c_int, _VP, _SZ]),
 ]
 
+# include/birda_hip_block_debug.h: one fused MBConv block alone (and its plan, host only), for the tests that hold every
+# instantiation of the fused kernel to float64
+BLOCK_DEBUG_SYMBOLS = [
+    ("bh_debug_mbconv_plan", C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, _SZ]),
+    ("bh_debug_mbconv_block", C.c_int, [C.c_int, _VP, _SZ, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,
+                                        _VP, _VP, _VP, _VP, _VP, _SZ]),
+]
+
 _lib = None
 
 
@@ -265,7 +273,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

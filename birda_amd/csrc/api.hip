@@ -1893,6 +1893,136 @@ int bh_debug_layer_gemm(int device, const float *A, const float *W, const float 
     return finish_debug_launch("debug_layer_gemm", name, dC, C, out_rows * N, kernel, kernel_cap);
 } catch (...) { return on_exception(); }
 
+namespace {
+
+// The block a shape array describes (birda_hip_block_debug.h), not yet planned; false: arguments no block can have.
+bool mb_desc_of_shape(const int32_t *sh, bh::MbDesc &d) {
+    d = bh::MbDesc{};
+    d.H = sh[0]; d.W = sh[1]; d.Cin = sh[2]; d.Cexp = sh[3]; d.Cout = sh[4]; d.Ho = sh[5]; d.Wo = sh[6]; d.pad_t = sh[7]; d.pad_l = sh[8];
+    d.KS = sh[9]; d.ST = sh[10];
+    d.act_e = d.act_d = sh[11]; d.act_p = bh::ACT_NONE;
+    d.prec = sh[12]; d.noexp = sh[13] != 0; d.se = sh[14] != 0; d.dblk = sh[15] != 0;
+    d.stem_c = sh[16]; d.stem_h = sh[17]; d.stem_w = sh[18]; d.stem_k = sh[19]; d.stem_s = sh[20]; d.stem_pt = sh[21]; d.stem_pl = sh[22];
+    d.stem = d.stem_c > 0;
+    if (d.H < 1 || d.W < 1 || d.Cin < 1 || d.Cexp < 1 || d.Cout < 1 || d.Ho < 1 || d.Wo < 1 || d.pad_t < 0 || d.pad_l < 0 || d.KS < 1 || d.ST < 1) return false;
+    if (d.H > 32767 || d.W > 32767 || d.Cin > 65536 || d.Cexp > 65536 || d.Cout > 65536 || d.Ho > d.H + d.pad_t || d.Wo > d.W + d.pad_l) return false;
+    if (d.prec != 0 && d.prec != 1 && d.prec != 3) return false;
+    if (d.noexp && (d.stem || d.Cexp != d.Cin)) return false;
+    if (d.stem && (d.stem_c < 0 || d.stem_h < 1 || d.stem_w < 3 || d.stem_k < 1 || d.stem_s < 1 || d.stem_pt < 0 || d.stem_pl < 0 ||
+                   d.stem_h > 32767 || d.stem_w > 32767 || d.Cin != d.stem_k * d.stem_k * d.stem_c)) return false;
+    if (d.dblk && (!d.se || d.Cexp % 16 || (d.Ho * d.Wo) % 16)) return false;
+    return true;
+}
+
+// mb_plan for the shape, then the variant a forward pass would swap in (0: the planned entry, 1: its one-segment twin, 2: its
+// narrow-tile twin), and the record of what that is.  BH_ERR_UNSUPPORTED with the planner's words when there is none.
+int mb_debug_plan(const int32_t *shape, int force_cfg, int variant, bh::MbDesc &d, int32_t *rec, char *name, size_t name_cap) {
+    if (rec) std::fill(rec, rec + 24, 0);
+    if (rec) rec[0] = -1;
+    if (name && name_cap) name[0] = 0;
+    if (!shape || variant < 0 || variant > 2) return fail(BH_ERR_INVALID, "debug_mbconv: bad arguments");
+    const int nbase = bh::mb_config_count() / 3;   // (three activation copies of one list: kernels_mbconv.hip)
+    for (int k = 0; rec && force_cfg >= 0 && force_cfg < nbase && k < 3; k++) {   // the row's own facts, whatever becomes of the shape
+        int th = 0, has_se = 0, act = -1;
+        if (bh::mb_config_row(force_cfg + k * nbase, &th, &has_se, nullptr, &act) && act == shape[11]) { rec[6] = has_se; rec[7] = th; }
+    }
+    if (!mb_desc_of_shape(shape, d)) return fail(BH_ERR_INVALID, "debug_mbconv: not a block's shape");
+    bh::MbDesc planned = d;
+    if (!bh::mb_plan(planned, force_cfg)) {
+        char why[512];
+        bh::mb_plan_refusal(d, force_cfg, why, sizeof why);
+        return fail(BH_ERR_UNSUPPORTED, "debug_mbconv: %s", why);
+    }
+    bh::MbDesc tw{}, nw{};
+    const bool has_twin = bh::mb_plan_twin(planned, tw), has_narrow = bh::mb_plan_narrow(planned, nw);
+    const bool sums = has_twin && bh::mb_twin_sums_match(planned, tw);
+    if (variant == 1 && !has_twin) return fail(BH_ERR_UNSUPPORTED, "debug_mbconv: the planned entry has no one-segment twin");
+    if (variant == 2 && !has_narrow) return fail(BH_ERR_UNSUPPORTED, "debug_mbconv: the planned entry has no narrow-tile twin");
+    d = variant == 1 ? tw : variant == 2 ? nw : planned;
+    if (rec) {
+        int th = 0, has_se = 0, persist = 0;
+        bh::mb_config_row(d.cfg, &th, &has_se, &persist, nullptr);
+        rec[20] = persist;
+        rec[0] = d.cfg; rec[1] = d.TH; rec[2] = d.tiles_y; rec[3] = d.tiles_x; rec[4] = d.nchunks; rec[5] = d.KG; rec[6] = has_se; rec[7] = th;
+        rec[8] = d.S; rec[9] = d.CE; rec[10] = d.NTOP; rec[11] = (int32_t)d.lds_bytes; rec[12] = mb_ksplit_of(d); rec[13] = has_twin;
+        rec[14] = has_narrow; rec[15] = sums; rec[16] = d.IH; rec[17] = d.IW; rec[18] = d.mpad_max;
+        rec[19] = d.prec != 0 && bh::pw_gemm16_gated_wants_blocked(d.Cexp, d.Cout, d.Ho * d.Wo);
+    }
+    if (name && name_cap) {
+        char nm[128];
+        bh::mb_config_name(d.cfg, nm, sizeof nm);
+        snprintf(name, name_cap, "mbconv<%s,%d>", nm, d.se ? 1 : 0);
+    }
+    return BH_OK;
+}
+
+}  // namespace
+
+int bh_debug_mbconv_plan(const int32_t *shape, int force_cfg, int variant, int32_t *record, char *name, size_t name_cap) try {
+    bh::MbDesc d{};
+    return mb_debug_plan(shape, force_cfg, variant, d, record, name, name_cap);
+} catch (...) { return on_exception(); }
+
+// One fused block alone on operands of the caller's: mb_plan's choice (or the forced entry), plan_fusion's weight preparation
+// (mb_prepare_weights), the launch a forward pass makes -- tests hold every output element of every instantiation to float64.
+int bh_debug_mbconv_block(int device, const int32_t *shape, size_t n_seg, const float *X, const float *We, const float *be, const float *Wd,
+                          const float *bd, const float *Wp, const float *bp, const float *R, const float *gate, int force_cfg, int variant,
+                          int ksplit, float *Y, float *D, float *pool_part, int32_t *record, char *name, size_t name_cap) try {
+    bh::MbDesc d{};
+    int rc = mb_debug_plan(shape, force_cfg, variant, d, record, name, name_cap);
+    if (rc != BH_OK) return rc;
+    if (!n_seg || !X || !Wd || !bd || !Wp || !bp || (!d.noexp && (!We || !be)) || (d.se ? !pool_part : !Y))
+        return fail(BH_ERR_INVALID, "debug_mbconv_block: null operand");
+    if (d.se && (R || gate || ksplit)) return fail(BH_ERR_INVALID, "debug_mbconv_block: pass A takes no residual, gate or channel split");
+    if (gate && !d.noexp && !d.stem) return fail(BH_ERR_INVALID, "debug_mbconv_block: the gated one-launch form is the no-expand and stem blocks'");
+    if (gate && ksplit) return fail(BH_ERR_INVALID, "debug_mbconv_block: no channel split with a gate");
+    const size_t P = (size_t)d.Ho * d.Wo, tiles = (size_t)d.tiles_x * d.tiles_y;
+    const size_t x_fl = n_seg * (d.stem ? (size_t)d.stem_c * d.stem_h * d.stem_w : (size_t)d.H * d.W * d.Cin);
+    const size_t y_fl = n_seg * P * d.Cout, d_fl = n_seg * P * d.Cexp, pp_fl = n_seg * tiles * d.Cexp;
+    if (x_fl > (size_t)INT32_MAX || y_fl > (size_t)INT32_MAX || d_fl > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_mbconv_block: tensors past 2^31 elements");
+    if (d.dblk && (n_seg * P) % 16) return fail(BH_ERR_INVALID, "debug_mbconv_block: blocked D needs whole row tiles");
+    int persist = 0;
+    bh::mb_config_row(d.cfg, nullptr, nullptr, &persist, nullptr);
+    const int ksp = (ksplit && !persist) ? mb_ksplit_of(d) : 1;   // (the persistent instantiations have no channel split: mbconv_kernel.hpp)
+    if (record) record[12] = ksp;
+    HIPCHK(hipSetDevice(device));
+    bhi::MbHostWeights hw;
+    bhi::mb_prepare_weights(d, We, be, Wd, bd, Wp, bp, hw);
+    Guarded dX, dWe, dWp, dWd, dBp, dR, dG, dOut, dPP, dPart;
+    const bool se_store = d.se && D;
+    if (!dX.put(X, x_fl * 4, kGuardNaN) || !dWe.put(hw.we.data(), hw.we.size() * 4, kGuardNaN) || !dWp.put(hw.wp.data(), hw.wp.size() * 4, kGuardNaN) ||
+        !dWd.put(hw.wd.data(), hw.wd.size() * 4, kGuardNaN) || !dBp.put(hw.spa ? hw.bp.data() : bp, (size_t)d.Cout * 4, kGuardNaN) ||
+        (R && !dR.put(R, y_fl * 4, kGuardNaN)) || (gate && !dG.put(gate, n_seg * d.Cexp * 4, kGuardNaN)) ||
+        ((!d.se || se_store) && !dOut.put(nullptr, (d.se ? d_fl : y_fl) * 4, kUnwrittenNaN)) || (d.se && !dPP.put(nullptr, pp_fl * 4, kUnwrittenNaN)) ||
+        (ksp > 1 && !dPart.put(nullptr, (size_t)ksp * y_fl * 4, kUnwrittenNaN)))
+        return fail(BH_ERR_HIP, "debug_mbconv_block: device memory");
+    d.X = (const float *)dX.p(); d.We = (const float *)dWe.p(); d.Wp = (const float *)dWp.p(); d.Wd = (const float *)dWd.p(); d.bp = (const float *)dBp.p();
+    d.R = R ? (const float *)dR.p() : nullptr;
+    d.gate = gate ? (const float *)dG.p() : nullptr;
+    d.Y = d.se ? nullptr : (float *)dOut.p();
+    d.Dout = se_store ? (float *)dOut.p() : nullptr;
+    d.pool_part = d.se ? (float *)dPP.p() : nullptr;
+    d.stamps = nullptr; d.dbg = 0;
+    d.ksplit = ksp > 1 ? ksp : 0; d.partial = ksp > 1 ? (float *)dPart.p() : nullptr;
+    bh::launch_mbconv(d, (int)n_seg, nullptr);
+    if (ksp > 1) bh::launch_mb_reduce_partials(d.partial, d.Y, ksp, y_fl, d.prec != 0 ? d.p_unscale : 1.0f, nullptr);
+    const char *nm = name && name_cap ? name : "mbconv";
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    for (const Guarded *g : {&dOut, &dPP, &dPart}) {
+        if (!g->base) continue;
+        bool intact = false;
+        rc = g->guards_intact(kUnwrittenNaN, &intact);
+        if (rc != BH_OK) return rc;
+        if (!intact) return fail(BH_ERR_INTERNAL, "debug_mbconv_block: %s wrote outside %s", nm, g == &dOut ? (d.se ? "D" : "Y") : g == &dPP ? "pool_part" : "partial");
+    }
+    if (!d.se) HIPCHK(hipMemcpy(Y, dOut.p(), y_fl * 4, hipMemcpyDeviceToHost));
+    if (se_store) HIPCHK(hipMemcpy(D, dOut.p(), d_fl * 4, hipMemcpyDeviceToHost));
+    if (d.se) HIPCHK(hipMemcpy(pool_part, dPP.p(), pp_fl * 4, hipMemcpyDeviceToHost));
+    return BH_OK;
+} catch (...) { return on_exception(); }
+
 int bh_debug_mb_stamps(bh_classifier *c, uint64_t *out, size_t cap) {
     if (!c || !c->d_stamps) return 0;
     const size_t n = std::min(cap, c->mb.size() * 8);

@@ -29,6 +29,7 @@
 #include "../../include/birda_hip_debug.h"
 #include "../../include/birda_hip_audit.h"
 #include "../../include/birda_hip_layer_debug.h"
+#include "../../include/birda_hip_block_debug.h"
 #include "kernels.hpp"
 #include "trace.hpp"
 #include "model.hpp"
@@ -266,6 +267,10 @@ void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std:
 bool gap_gate_chain(const bh::Model &m, size_t i);
 bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, size_t i, int precision, int force_cfg, bh::MbDesc &d);
 std::vector<int> tensor_readers(const bh::Model &m);
+// a planned fused block's weights in the kernel's layouts (host vectors; bp empty when spa == 0: the layer's own biases serve)
+struct MbHostWeights { std::vector<float> we, wp, wd, bp; int spa = 0; };
+void mb_prepare_weights(bh::MbDesc &d, const float *We, const float *be, const float *Wd, const float *bd, const float *Wp, const float *bp,
+                        MbHostWeights &out);
 int plan_fusion(bh_classifier *c);
 // api.hip
 int upload(const void *src, size_t bytes, float **dst);

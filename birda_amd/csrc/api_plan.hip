@@ -345,6 +345,132 @@ std::vector<int> tensor_readers(const bh::Model &m) {
     return readers;
 }
 
+// The weights of one planned fused block as the kernel reads them (kernels.hpp MbDesc): the per-chunk fragment blocks of the picked
+// tile configuration, and everything the f16 modes hang on them -- the plane exponents se / sp, e_fold with the scaled GELU
+// coefficients, the 2x GELU factors, the hi / lo planes, the stem's run-packed im2col order, the folded depthwise taps, bp scaled to
+// the project accumulators' exponent.  Fills d.e_unscale / p_scale / p_unscale / e_fold / gelu.  We, be, Wd, bd, Wp, bp in the
+// loaders' layouts ([Cin][Cexp], [tap][Cexp], [Cexp][Cout]); We / be are not read for a no-expand block.  Host only: plan_fusion
+// uploads the result at create, bh_debug_mbconv_block for one block alone.
+void mb_prepare_weights(bh::MbDesc &d, const float *We, const float *be, const float *Wd, const float *bd, const float *Wp, const float *bp,
+                        MbHostWeights &out) {
+    // per-chunk weight blocks (kernels.hpp MbDesc)
+    const int CE = d.CE, NTE = CE / 16, KG = d.KG, NTOP = d.NTOP, nch = d.nchunks, KK = d.KS * d.KS;
+    const bool h16 = d.prec != 0;
+    // f16 operand planes hold We * 2^se and Wp * 2^sp (kernels.hpp f16_scale_exponent); be / bp are multiplied alike
+    int se = 0, sp = 0;
+    if (h16) {
+        float me = 0.0f, mp = 0.0f;
+        for (size_t q = 0; !d.noexp && q < (size_t)d.Cin * d.Cexp; q++) me = std::max(me, std::fabs(We[q]));
+        for (size_t q = 0; q < (size_t)d.Cexp * d.Cout; q++) mp = std::max(mp, std::fabs(Wp[q]));
+        se = bh::f16_scale_exponent(me);
+        sp = bh::f16_scale_exponent(mp);
+    }
+    // GELU blocks of the f16 modes: the expand GELU runs on the SCALED accumulator with coefficients c_k 2^(-k se) and the 2^-se
+    // moves into the depthwise taps (kernels.hpp gelu_erf_fast4_scaled).  c_5 2^(-5 se) must stay a normal f32 on both sides:
+    // |se| <= 21 (weights 2^7 away from the usual He-normal sizes still land within 2^-8 of the top of the f16 range).
+    d.e_fold = 0;
+    d.gelu = bh::GeluScaled{0.f, 0.f, 0.f, 0.f, 0.f};
+#if BH_GELU_DEGREE == 5
+    if (d.noexp) se = 0;
+    if (h16 && d.act_e == bh::ACT_GELU_ERF && !d.noexp) {
+        se = std::max(-21, std::min(21, se));
+        d.e_fold = 1;
+        float gc[5];
+        for (int k = 1; k <= 5; k++) gc[k - 1] = std::ldexp(bh::kGeluCoef[k - 1], -k * se);
+        d.gelu = bh::GeluScaled{gc[0], gc[1], gc[2], gc[3], gc[4]};
+    }
+#endif
+    // ... and both GELUs of such a block leave TWICE their value (gelu2x_fast4, kernels.hpp): the expand one's factor joins the
+    // 2^-se in the depthwise taps (x2e), the depthwise one's raises the exponent the project accumulators live at (x2d).
+    int x2e = 0, x2d = 0;
+#if BH_GELU_DEGREE == 5 && BH_GELU_2X
+    if (h16 && d.act_d == bh::ACT_GELU_ERF) x2d = 1;
+    x2e = d.e_fold;
+#endif
+    const int spa = sp + x2d;   // the project accumulators hold 2^spa times the output
+    d.e_unscale = std::ldexp(1.0f, -se); d.p_scale = std::ldexp(1.0f, spa); d.p_unscale = std::ldexp(1.0f, -spa);
+    const size_t frag = h16 ? 512 : 256, psteps = h16 ? (CE + 31) / 32 : NTE;
+    const bool p16 = h16 && CE == 16;   // project GEMM as one 16-deep step: [column tile]{hi, lo}[64 lanes][4 halves]
+    const size_t we_fl = (size_t)KG * NTE * frag + CE, wp_fl = p16 ? (size_t)NTOP * 256 : psteps * NTOP * frag, wd_fl = (size_t)KK * CE + CE;
+    std::vector<float> &wef = out.we, &wpf = out.wp, &wdf = out.wd;
+    wef.assign(nch * we_fl, 0.0f); wpf.assign(nch * wp_fl, 0.0f); wdf.assign(nch * wd_fl, 0.0f);
+    // (stem block in the f16 modes: the kernel gathers its im2col columns by memory runs, kernels_mbconv.hip -- position
+    //  8 kq + 3 q + dx of the one 32-deep step is tap (dy, dx) of channel ch with run 2 kq + q = 3 ch + dy)
+    auto we_at = [&](int k, int n) {
+        if (d.stem && h16) {
+            const int g = k >> 5, kq = (k & 31) >> 3, jj = k & 7, r = 8 * g + 2 * kq + jj / 3, dx = jj % 3;
+            if (jj >= 6 || r >= 3 * d.stem_c) return 0.0f;
+            const int ch = r / 3, dy = r - 3 * ch;
+            k = (dy * 3 + dx) * d.stem_c + ch;
+        }
+        return (!d.noexp && k < d.Cin && n < d.Cexp) ? std::ldexp(We[(size_t)k * d.Cexp + n], se) : 0.0f;
+    };
+    auto wp_at = [&](int k, int n) { return (k < d.Cexp && n < d.Cout) ? std::ldexp(Wp[(size_t)k * d.Cout + n], sp) : 0.0f; };
+    // f16: element jj of lane's 8-half fragment = k = 32 g + 8 (lane >> 4) + jj; hi plane then lo plane
+    auto put16 = [&](std::vector<float> &dst, size_t base_fl, int plane, int lane, int jj, float v) {
+        uint16_t *h = reinterpret_cast<uint16_t *>(dst.data() + base_fl) + ((size_t)plane * 64 + lane) * 8 + jj;
+        const uint16_t hi = f32_to_f16(v);
+        *h = plane == 0 ? hi : f32_to_f16(v - f16_to_f32(hi));
+    };
+    for (int ch = 0; ch < nch; ch++) {
+        for (int g = 0; g < KG; g++)
+            for (int j = 0; j < NTE; j++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int n = ch * CE + 16 * j + (lane & 15);
+                    if (h16) {
+                        for (int jj = 0; jj < 8; jj++) {
+                            const float v = we_at(32 * g + 8 * (lane >> 4) + jj, n);
+                            const size_t base = ch * we_fl + ((size_t)g * NTE + j) * 512;
+                            put16(wef, base, 0, lane, jj, v);
+                            put16(wef, base, 1, lane, jj, v);
+                        }
+                    } else {
+                        for (int cc = 0; cc < 4; cc++)
+                            wef[ch * we_fl + (((size_t)g * NTE + j) * 64 + lane) * 4 + cc] = we_at(16 * g + 4 * (lane >> 4) + cc, n);
+                    }
+                }
+        for (int n = 0; n < CE; n++) wef[ch * we_fl + (size_t)KG * NTE * frag + n] = (!d.noexp && ch * CE + n < d.Cexp) ? std::ldexp(be[ch * CE + n], se) : 0.0f;
+        if (p16) {
+            for (int j = 0; j < NTOP; j++)
+                for (int lane = 0; lane < 64; lane++)
+                    for (int jj = 0; jj < 4; jj++) {
+                        const float v = wp_at(ch * CE + 4 * (lane >> 4) + jj, 16 * j + (lane & 15));
+                        uint16_t *h = reinterpret_cast<uint16_t *>(wpf.data() + ch * wp_fl + (size_t)j * 256);
+                        const uint16_t hi = f32_to_f16(v);
+                        h[(size_t)lane * 4 + jj] = hi;
+                        h[(size_t)(64 + lane) * 4 + jj] = f32_to_f16(v - f16_to_f32(hi));
+                    }
+        }
+        for (int g = 0; g < (int)psteps && !p16; g++)
+            for (int j = 0; j < NTOP; j++)
+                for (int lane = 0; lane < 64; lane++) {
+                    const int n = 16 * j + (lane & 15);
+                    if (h16) {
+                        for (int jj = 0; jj < 8; jj++) {
+                            const int kk = 32 * g + 8 * (lane >> 4) + jj;          // k inside the chunk (zero padding past CE)
+                            const float v = kk < CE ? wp_at(ch * CE + kk, n) : 0.0f;
+                            const size_t base = ch * wp_fl + ((size_t)g * NTOP + j) * 512;
+                            put16(wpf, base, 0, lane, jj, v);
+                            put16(wpf, base, 1, lane, jj, v);
+                        }
+                    } else {
+                        for (int cc = 0; cc < 4; cc++)
+                            wpf[ch * wp_fl + (((size_t)g * NTOP + j) * 64 + lane) * 4 + cc] = wp_at(ch * CE + 16 * g + 4 * (lane >> 4) + cc, n);
+                    }
+                }
+        for (int tap = 0; tap < KK; tap++)
+            for (int n = 0; n < CE; n++)
+                wdf[ch * wd_fl + (size_t)tap * CE + n] = ch * CE + n < d.Cexp ? std::ldexp(Wd[(size_t)tap * d.Cexp + ch * CE + n], d.e_fold ? -se - x2e : 0) : 0.0f;
+        for (int n = 0; n < CE; n++) wdf[ch * wd_fl + (size_t)KK * CE + n] = ch * CE + n < d.Cexp ? bd[ch * CE + n] : 0.0f;
+    }
+    out.spa = spa;
+    out.bp.clear();
+    if (spa != 0) {   // bp * 2^spa: the project accumulators start there
+        out.bp.resize(d.Cout);
+        for (int n = 0; n < d.Cout; n++) out.bp[n] = std::ldexp(bp[n], spa);
+    }
+}
+
 // Prepares a fused launch for every block describe_fused_block accepts (weights re-laid fragment-major for the picked tile config).
 int plan_fusion(bh_classifier *c) {
     const auto &m = c->model;
@@ -362,117 +488,10 @@ int plan_fusion(bh_classifier *c) {
         bh_classifier::SeInfo S;
         if (d.se) { bool ne = false; if (!match_se_block(m, readers, i, S, ne)) continue; }
         const auto &E = m.layers[i], &D = m.layers[d.noexp ? i : i + 1], &P = m.layers[d.se ? S.iP : d.noexp ? i + 1 : i + 2];
-        // per-chunk weight blocks (kernels.hpp MbDesc)
-        const int CE = d.CE, NTE = CE / 16, KG = d.KG, NTOP = d.NTOP, nch = d.nchunks, KK = d.KS * d.KS;
-        const float *We = m.blob.data() + E.w_off, *Wp = m.blob.data() + P.w_off, *Wd = m.blob.data() + D.w_off;
-        const float *be = m.blob.data() + E.b_off, *bd = m.blob.data() + D.b_off;
-        const bool h16 = d.prec != 0;
-        // f16 operand planes hold We * 2^se and Wp * 2^sp (kernels.hpp f16_scale_exponent); be / bp are multiplied alike
-        int se = 0, sp = 0;
-        if (h16) {
-            float me = 0.0f, mp = 0.0f;
-            for (size_t q = 0; !d.noexp && q < (size_t)d.Cin * d.Cexp; q++) me = std::max(me, std::fabs(We[q]));
-            for (size_t q = 0; q < (size_t)d.Cexp * d.Cout; q++) mp = std::max(mp, std::fabs(Wp[q]));
-            se = bh::f16_scale_exponent(me);
-            sp = bh::f16_scale_exponent(mp);
-        }
-        // GELU blocks of the f16 modes: the expand GELU runs on the SCALED accumulator with coefficients c_k 2^(-k se) and the 2^-se
-        // moves into the depthwise taps (kernels.hpp gelu_erf_fast4_scaled).  c_5 2^(-5 se) must stay a normal f32 on both sides:
-        // |se| <= 21 (weights 2^7 away from the usual He-normal sizes still land within 2^-8 of the top of the f16 range).
-        d.e_fold = 0;
-        d.gelu = bh::GeluScaled{0.f, 0.f, 0.f, 0.f, 0.f};
-#if BH_GELU_DEGREE == 5
-        if (d.noexp) se = 0;
-        if (h16 && d.act_e == bh::ACT_GELU_ERF && !d.noexp) {
-            se = std::max(-21, std::min(21, se));
-            d.e_fold = 1;
-            float gc[5];
-            for (int k = 1; k <= 5; k++) gc[k - 1] = std::ldexp(bh::kGeluCoef[k - 1], -k * se);
-            d.gelu = bh::GeluScaled{gc[0], gc[1], gc[2], gc[3], gc[4]};
-        }
-#endif
-        // ... and both GELUs of such a block leave TWICE their value (gelu2x_fast4, kernels.hpp): the expand one's factor joins the
-        // 2^-se in the depthwise taps (x2e), the depthwise one's raises the exponent the project accumulators live at (x2d).
-        int x2e = 0, x2d = 0;
-#if BH_GELU_DEGREE == 5 && BH_GELU_2X
-        if (h16 && d.act_d == bh::ACT_GELU_ERF) x2d = 1;
-        x2e = d.e_fold;
-#endif
-        const int spa = sp + x2d;   // the project accumulators hold 2^spa times the output
-        d.e_unscale = std::ldexp(1.0f, -se); d.p_scale = std::ldexp(1.0f, spa); d.p_unscale = std::ldexp(1.0f, -spa);
-        const size_t frag = h16 ? 512 : 256, psteps = h16 ? (CE + 31) / 32 : NTE;
-        const bool p16 = h16 && CE == 16;   // project GEMM as one 16-deep step: [column tile]{hi, lo}[64 lanes][4 halves]
-        const size_t we_fl = (size_t)KG * NTE * frag + CE, wp_fl = p16 ? (size_t)NTOP * 256 : psteps * NTOP * frag, wd_fl = (size_t)KK * CE + CE;
-        std::vector<float> wef(nch * we_fl, 0.0f), wpf(nch * wp_fl, 0.0f), wdf(nch * wd_fl, 0.0f);
-        // (stem block in the f16 modes: the kernel gathers its im2col columns by memory runs, kernels_mbconv.hip -- position
-        //  8 kq + 3 q + dx of the one 32-deep step is tap (dy, dx) of channel ch with run 2 kq + q = 3 ch + dy)
-        auto we_at = [&](int k, int n) {
-            if (d.stem && h16) {
-                const int g = k >> 5, kq = (k & 31) >> 3, jj = k & 7, r = 8 * g + 2 * kq + jj / 3, dx = jj % 3;
-                if (jj >= 6 || r >= 3 * d.stem_c) return 0.0f;
-                const int ch = r / 3, dy = r - 3 * ch;
-                k = (dy * 3 + dx) * d.stem_c + ch;
-            }
-            return (!d.noexp && k < d.Cin && n < d.Cexp) ? std::ldexp(We[(size_t)k * d.Cexp + n], se) : 0.0f;
-        };
-        auto wp_at = [&](int k, int n) { return (k < d.Cexp && n < d.Cout) ? std::ldexp(Wp[(size_t)k * d.Cout + n], sp) : 0.0f; };
-        // f16: element jj of lane's 8-half fragment = k = 32 g + 8 (lane >> 4) + jj; hi plane then lo plane
-        auto put16 = [&](std::vector<float> &dst, size_t base_fl, int plane, int lane, int jj, float v) {
-            uint16_t *h = reinterpret_cast<uint16_t *>(dst.data() + base_fl) + ((size_t)plane * 64 + lane) * 8 + jj;
-            const uint16_t hi = f32_to_f16(v);
-            *h = plane == 0 ? hi : f32_to_f16(v - f16_to_f32(hi));
-        };
-        for (int ch = 0; ch < nch; ch++) {
-            for (int g = 0; g < KG; g++)
-                for (int j = 0; j < NTE; j++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int n = ch * CE + 16 * j + (lane & 15);
-                        if (h16) {
-                            for (int jj = 0; jj < 8; jj++) {
-                                const float v = we_at(32 * g + 8 * (lane >> 4) + jj, n);
-                                const size_t base = ch * we_fl + ((size_t)g * NTE + j) * 512;
-                                put16(wef, base, 0, lane, jj, v);
-                                put16(wef, base, 1, lane, jj, v);
-                            }
-                        } else {
-                            for (int cc = 0; cc < 4; cc++)
-                                wef[ch * we_fl + (((size_t)g * NTE + j) * 64 + lane) * 4 + cc] = we_at(16 * g + 4 * (lane >> 4) + cc, n);
-                        }
-                    }
-            for (int n = 0; n < CE; n++) wef[ch * we_fl + (size_t)KG * NTE * frag + n] = (!d.noexp && ch * CE + n < d.Cexp) ? std::ldexp(be[ch * CE + n], se) : 0.0f;
-            if (p16) {
-                for (int j = 0; j < NTOP; j++)
-                    for (int lane = 0; lane < 64; lane++)
-                        for (int jj = 0; jj < 4; jj++) {
-                            const float v = wp_at(ch * CE + 4 * (lane >> 4) + jj, 16 * j + (lane & 15));
-                            uint16_t *h = reinterpret_cast<uint16_t *>(wpf.data() + ch * wp_fl + (size_t)j * 256);
-                            const uint16_t hi = f32_to_f16(v);
-                            h[(size_t)lane * 4 + jj] = hi;
-                            h[(size_t)(64 + lane) * 4 + jj] = f32_to_f16(v - f16_to_f32(hi));
-                        }
-            }
-            for (int g = 0; g < (int)psteps && !p16; g++)
-                for (int j = 0; j < NTOP; j++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int n = 16 * j + (lane & 15);
-                        if (h16) {
-                            for (int jj = 0; jj < 8; jj++) {
-                                const int kk = 32 * g + 8 * (lane >> 4) + jj;          // k inside the chunk (zero padding past CE)
-                                const float v = kk < CE ? wp_at(ch * CE + kk, n) : 0.0f;
-                                const size_t base = ch * wp_fl + ((size_t)g * NTOP + j) * 512;
-                                put16(wpf, base, 0, lane, jj, v);
-                                put16(wpf, base, 1, lane, jj, v);
-                            }
-                        } else {
-                            for (int cc = 0; cc < 4; cc++)
-                                wpf[ch * wp_fl + (((size_t)g * NTOP + j) * 64 + lane) * 4 + cc] = wp_at(ch * CE + 16 * g + 4 * (lane >> 4) + cc, n);
-                        }
-                    }
-            for (int tap = 0; tap < KK; tap++)
-                for (int n = 0; n < CE; n++)
-                    wdf[ch * wd_fl + (size_t)tap * CE + n] = ch * CE + n < d.Cexp ? std::ldexp(Wd[(size_t)tap * d.Cexp + ch * CE + n], d.e_fold ? -se - x2e : 0) : 0.0f;
-            for (int n = 0; n < CE; n++) wdf[ch * wd_fl + (size_t)KK * CE + n] = ch * CE + n < d.Cexp ? bd[ch * CE + n] : 0.0f;
-        }
+        MbHostWeights hw;
+        mb_prepare_weights(d, m.blob.data() + E.w_off, m.blob.data() + E.b_off, m.blob.data() + D.w_off, m.blob.data() + D.b_off,
+                           m.blob.data() + P.w_off, m.blob.data() + P.b_off, hw);
+        const std::vector<float> &wef = hw.we, &wpf = hw.wp, &wdf = hw.wd;
         float *dwe = nullptr, *dwp = nullptr, *dwd = nullptr;
         int rc = upload(wef.data(), wef.size() * sizeof(float), &dwe);
         if (rc != BH_OK) return rc;
@@ -485,11 +504,9 @@ int plan_fusion(bh_classifier *c) {
         c->d_owned.push_back(dwd);
         d.We = dwe; d.Wp = dwp; d.Wd = dwd;
         d.bp = c->d_blob + P.b_off;
-        if (spa != 0) {   // bp * 2^spa: the project accumulators start there
-            std::vector<float> bps(d.Cout);
-            for (int n = 0; n < d.Cout; n++) bps[n] = std::ldexp(m.blob[P.b_off + n], spa);
+        if (hw.spa != 0) {   // bp * 2^spa (mb_prepare_weights)
             float *dbp = nullptr;
-            rc = upload(bps.data(), bps.size() * sizeof(float), &dbp);
+            rc = upload(hw.bp.data(), hw.bp.size() * sizeof(float), &dbp);
             if (rc != BH_OK) return rc;
             c->d_owned.push_back(dbp);
             d.bp = dbp;

@@ -526,6 +526,8 @@ int mb_config_count();
 int mb_config_name(int ci, char *out, size_t cap);
 // picks the instantiation (force_cfg >= 0: that entry or fail) and fills the derived fields
 bool mb_plan(MbDesc &d, int force_cfg);
+bool mb_config_row(int ci, int *th, int *has_se, int *persist, int *act);   // the row's own tile height; pass A instantiated and reachable (mb_try_th); PERSIST; ACT
+int mb_plan_refusal(const MbDesc &d, int force_cfg, char *out, size_t cap);   // the planner's reason in words
 bool mb_plan_twin(const MbDesc &d, MbDesc &twin);
 bool mb_twin_sums_match(const MbDesc &d, const MbDesc &twin);   // squeeze-excite pass A: the twin's pooled sums are the block's, bit for bit   // one-segment-per-workgroup twin of a two-segment configuration (small launches)
 bool mb_plan_narrow(const MbDesc &d, MbDesc &narrow);   // narrow-tile twin of a whole-image configuration (launches of a few segments)

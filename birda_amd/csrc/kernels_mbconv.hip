@@ -165,6 +165,33 @@ int mb_config_name(int ci, char *out, size_t cap) {
                     c.WN, c.MT_W, c.NT_W, c.TWL, c.XBL, c.S, c.OCC, c.STEM, c.PREC, c.PERSIST, c.ACT, c.COLTH);
 }
 
+// the row's tile height and whether pass A of a squeeze-excite block is instantiated for it (the block diagnostics' plan record)
+bool mb_config_row(int ci, int *th, int *has_se, int *persist, int *act) {
+    if (ci < 0 || ci >= kNCfgs) return false;
+    if (th) *th = kCfgs[ci].TH;
+    if (has_se) *has_se = kCfgs[ci].KS != 0 && kCfgs[ci].launch_se != nullptr && !kCfgs[ci].PERSIST;
+    if (persist) *persist = kCfgs[ci].PERSIST;
+    if (act) *act = kCfgs[ci].ACT;
+    return true;
+}
+
+// Why mb_plan(d, force_cfg) refuses: the reasons mb_try_th counted while the plan ran again on a copy (BIRDA_HIP_MB_WHY's words).
+int mb_plan_refusal(const MbDesc &d, int force_cfg, char *out, size_t cap) {
+    static const char *const names[16] = {nullptr, "activation", "stem channels", "stem kernel", "no pass-A instantiation", "k steps", "column tasks",
+                                          "project tiles", "tile pixels", "rows of X per wave", "LDS over 160 KB"};
+    std::fill(g_why, g_why + 16, 0);
+    MbDesc t = d;
+    if (mb_plan(t, force_cfg)) return snprintf(out, cap, "accepted");
+    int n = snprintf(out, cap, "no entry for %s%d -> %d -> %d k%d s%d %dx%d -> %dx%d act %d prec %d se %d; refused by", d.stem ? "stem " : d.noexp ? "noexp " : "",
+                     d.Cin, d.Cexp, d.Cout, d.KS, d.ST, d.H, d.W, d.Ho, d.Wo, d.act_e, d.prec, d.se);
+    bool any = false;
+    for (int r = 1; r <= 10; r++)
+        if (g_why[r] && n >= 0 && (size_t)n < cap) { n += snprintf(out + n, cap - n, " %s (%d)", names[r], g_why[r]); any = true; }
+    if (!any && n >= 0 && (size_t)n < cap)
+        n += snprintf(out + n, cap - n, " the entry's kernel size / stride / precision, Cin %% 4, Cexp %% 4, the 2^24 offset range or a no-expand mismatch");
+    return n;
+}
+
 bool mb_plan(MbDesc &d, int force_cfg) {
     d.cfg = -1;
     if (force_cfg >= 0) {   // (a base index: the block's own activation selects the copy)

@@ -374,3 +374,58 @@ def head_pool64(v, P: int) -> np.ndarray:
     """The mean over each run of P rows: [n * P][N] -> [n][N] (the head convolution's global average pool)."""
     v = np.asarray(v, np.float64)
     return v.reshape(-1, P, v.shape[-1]).mean(axis=1)
+
+
+# --------------------------------------------------------------------------------------------------------
+# The fused MBConv block (mbconv_kernel.hpp: expand 1x1 or stem conv -> depthwise -> project 1x1 (+ residual)) in float64,
+# for tests/test_mbconv_block*.py.  Weights in the loaders' layouts: We [Cin][Cexp] (stem: rows in [kh][kw][channel] order),
+# Wd [KS * KS][Cexp] (tap = dy * KS + dx), Wp [Cexp][Cout].
+# --------------------------------------------------------------------------------------------------------
+def depthwise64(E, Wd, ks: int, st: int, pad_t: int, pad_l: int, out_h: int, out_w: int) -> np.ndarray:
+    """sum over taps of E [n][H][W][C] (zero outside the image) times Wd [ks * ks][C], stride st: [n][out_h][out_w][C], no bias."""
+    E = np.asarray(E, np.float64)
+    Wd = np.asarray(Wd, np.float64)
+    n, H, W, Cc = E.shape
+    need_h, need_w = (out_h - 1) * st + ks, (out_w - 1) * st + ks
+    Ep = np.zeros((n, max(need_h, pad_t + H), max(need_w, pad_l + W), Cc))
+    Ep[:, pad_t:pad_t + H, pad_l:pad_l + W] = E
+    out = np.zeros((n, out_h, out_w, Cc))
+    for dy in range(ks):
+        for dx in range(ks):
+            out += Ep[:, dy:dy + (out_h - 1) * st + 1:st, dx:dx + (out_w - 1) * st + 1:st] * Wd[dy * ks + dx]
+    return out
+
+
+def stem_rows64(Xp, k: int, s: int, pad_t: int, pad_l: int, out_h: int, out_w: int) -> np.ndarray:
+    """The stem convolution's im2col rows of a planar spectrogram [n][c][h][w]: [n][out_h][out_w][k * k * c], columns in
+    (dy, dx, channel) order, taps outside the image zero."""
+    X = np.transpose(np.asarray(Xp, np.float64), (0, 2, 3, 1))
+    n = X.shape[0]
+    return im2col_nhwc(X, k, k, s, s, pad_t, pad_l, out_h, out_w).reshape(n, out_h, out_w, -1)
+
+
+def mbconv64(X, We, be, Wd, bd, Wp, bp, R, ks: int, st: int, pad_t: int, pad_l: int, out_h: int, out_w: int, act: int,
+             noexp: bool = False, gate=None, stem=None):
+    """One MBConv block in float64.  X is NHWC [n][H][W][Cin]; with stem = (k, s, pad_t, pad_l, H, W) it is the planar spectrogram
+    [n][c][h][w] and the expand convolution is the k x k stride-s stem convolution leaving H x W pixels.  noexp: no expand
+    convolution, E = X.  gate [n][Cexp] (or None) multiplies the depthwise output in front of the project convolution.
+    Returns a dict: A (the expand GEMM's rows [n][H][W][K]), preE, E, preD, D (ungated), Dg (gated: what the project reads), Y,
+    and Dsum [n][Cexp], the per-channel sums of D over the image (pass A of a squeeze-excite block)."""
+    f = np.float64
+    if stem is not None:
+        k, s, spt, spl, H, W = stem
+        A = stem_rows64(X, k, s, spt, spl, H, W)
+    else:
+        A = np.asarray(X, f)
+    if noexp:
+        preE = E = A
+    else:
+        preE = A @ np.asarray(We, f) + np.asarray(be, f)
+        E = act64(preE, act)
+    preD = depthwise64(E, Wd, ks, st, pad_t, pad_l, out_h, out_w) + np.asarray(bd, f)
+    D = act64(preD, act)
+    Dg = D if gate is None else D * np.asarray(gate, f)[:, None, None, :]
+    Y = Dg @ np.asarray(Wp, f) + np.asarray(bp, f)
+    if R is not None:
+        Y = Y + np.asarray(R, f)
+    return {"A": A, "preE": preE, "E": E, "preD": preD, "D": D, "Dg": Dg, "Y": Y, "Dsum": D.sum(axis=(1, 2))}

@@ -190,3 +190,21 @@ def test_layer_debug_table_matches_its_header():
     # (the boundary birda binds, and the Rust text generated from it, hold none of them)
     assert not set(functions) & set(A.parse_c_header(HIP_H)[1])
     assert "bh_debug_conv_gemm" not in open(os.path.join(ROOT, "include", "birda_hip_sys.rs")).read()
+
+
+def test_block_debug_header_matches_ctypes_table():
+    """The fused block's diagnostics (include/birda_hip_block_debug.h) are bound in _lib.BLOCK_DEBUG_SYMBOLS, type for type, and are
+    among the library's exports; the other debug headers and the boundary birda binds hold none of them."""
+    from birda_amd import _lib
+    _, functions, _ = A.parse_c_header(os.path.join(ROOT, "include", "birda_hip_block_debug.h"))
+    assert {n for n, _, _ in _lib.BLOCK_DEBUG_SYMBOLS} == set(functions) == {"bh_debug_mbconv_plan", "bh_debug_mbconv_block"}
+    for name, res, args in _lib.BLOCK_DEBUG_SYMBOLS:
+        want_ret, want_args = functions[name]
+        assert _eq_ctypes(A.ctypes_class(res), want_ret), name
+        assert len(args) == len(want_args), name
+        for i, (a, b) in enumerate(zip(args, want_args)):
+            assert _eq_ctypes(A.ctypes_class(a), b), (name, i, a, b)
+        assert hasattr(_lib.load(), name), f"{name} declared in include/birda_hip_block_debug.h but not exported"
+    for other in ("birda_hip.h", "birda_hip_debug.h", "birda_hip_audit.h", "birda_hip_layer_debug.h"):
+        assert not set(functions) & set(A.parse_c_header(os.path.join(ROOT, "include", other))[1]), other
+    assert "bh_debug_mbconv" not in open(os.path.join(ROOT, "include", "birda_hip_sys.rs")).read()

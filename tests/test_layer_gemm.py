@@ -111,3 +111,92 @@ def test_gelu_reference_points():
     assert abs(O.act64(-1.0, O.ACT_GELU_ERF) + 0.15865525393145707) < 1e-15
     assert abs(O.act64(1.0, O.ACT_SWISH) - 1.0 / (1.0 + math.exp(-1.0))) < 1e-16
     assert O.act64(-1e30, O.ACT_SWISH) == 0.0 and O.act64(1e30, O.ACT_GELU_TANH) == 1e30
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the fused MBConv block's reference (O.mbconv64: tests/test_mbconv_block_gpu.py holds mbconv_kernel to it)
+# ---------------------------------------------------------------------------------------------------------------------------
+def _torch_act(v, act):
+    if act == O.ACT_RELU6:
+        return torch.clamp(v, 0.0, 6.0)
+    if act == O.ACT_SWISH:
+        return v * torch.sigmoid(v)
+    assert act == O.ACT_GELU_ERF
+    return F.gelu(v)
+
+
+def _torch_mbconv(X, We, be, Wd, bd, Wp, bp, R, ks, st, pad_t, pad_l, out_h, out_w, act, noexp, gate, stem):
+    t = torch.from_numpy
+    if stem is not None:
+        k, s, spt, spl, H, W = stem
+        c = X.shape[1]
+        pad_b, pad_r = (H - 1) * s + k - X.shape[2] - spt, (W - 1) * s + k - X.shape[3] - spl
+        w = t(We).reshape(k, k, c, -1).permute(3, 2, 0, 1)
+        e = _torch_act(F.conv2d(F.pad(t(X), (spl, pad_r, spt, pad_b)), w, t(be), stride=s), act)
+    elif noexp:
+        e = t(X).permute(0, 3, 1, 2)
+    else:
+        e = _torch_act(F.conv2d(t(X).permute(0, 3, 1, 2), t(We).T[:, :, None, None], t(be)), act)
+    cexp = e.shape[1]
+    pad_b, pad_r = (out_h - 1) * st + ks - e.shape[2] - pad_t, (out_w - 1) * st + ks - e.shape[3] - pad_l
+    wd = t(Wd).reshape(ks, ks, cexp).permute(2, 0, 1)[:, None]
+    d = _torch_act(F.conv2d(F.pad(e, (pad_l, pad_r, pad_t, pad_b)), wd, t(bd), stride=st, groups=cexp), act)
+    dsum = d.sum(dim=(2, 3))
+    dg = d if gate is None else d * t(gate)[:, :, None, None]
+    y = F.conv2d(dg, t(Wp).T[:, :, None, None], t(bp)).permute(0, 2, 3, 1)
+    if R is not None:
+        y = y + t(R)
+    return e.permute(0, 2, 3, 1).numpy(), d.permute(0, 2, 3, 1).numpy(), y.numpy(), dsum.numpy()
+
+
+MB_REF_CASES = [  # (form, n, H, W, Cin, Cexp, Cout, ks, st, pad_t, pad_l, Ho, Wo, residual)
+    ("plain", 2, 7, 9, 8, 24, 12, 3, 1, 1, 1, 7, 9, True),
+    ("plain", 1, 8, 10, 4, 12, 20, 3, 2, 0, 0, 4, 5, False),        # stride-2 SAME on an even image: pad_t 0, pad_b 1
+    ("plain", 3, 9, 11, 12, 20, 8, 5, 2, 2, 2, 5, 6, False),        # 5x5 stride 2 on an odd image
+    ("plain", 1, 5, 6, 4, 8, 8, 5, 1, 2, 2, 5, 6, True),
+    ("noexp", 2, 6, 7, 16, 16, 8, 3, 1, 1, 1, 6, 7, True),
+    ("gated", 2, 6, 7, 16, 16, 12, 3, 1, 1, 1, 6, 7, False),
+    ("gated", 3, 7, 7, 8, 8, 8, 5, 2, 1, 1, 3, 3, True),            # stride 2, pad_b = 0 by TF's SAME rule on 7 rows of 5x5 taps
+    ("stem1", 2, 0, 0, 1, 16, 8, 3, 1, 1, 1, 0, 0, False),
+    ("stem2", 2, 0, 0, 2, 12, 8, 3, 1, 1, 1, 0, 0, False),
+    ("stem3", 1, 0, 0, 3, 8, 4, 3, 2, 0, 0, 0, 0, False),
+]
+
+
+@pytest.mark.parametrize("act", [O.ACT_GELU_ERF, O.ACT_SWISH, O.ACT_RELU6], ids=lambda a: O.ACT_NAMES[a])
+@pytest.mark.parametrize("case", MB_REF_CASES, ids=lambda c: "%s_n%d_%dx%d_%d-%d-%d_k%ds%d_p%d,%d_o%dx%d_r%d" % c)
+def test_mbconv_reference_matches_torch(case, act):
+    form, n, H, W, Cin, Cexp, Cout, ks, st, pad_t, pad_l, Ho, Wo, residual = case
+    rng = np.random.default_rng(1000 * MB_REF_CASES.index(case) + act)
+    stem = None
+    if form.startswith("stem"):
+        c, sh, sw, ss = Cin, 11, 14, 2                    # an 11x14 spectrogram, stem stride 2 with TF's SAME padding (pad_t 1)
+        H, W = -(-sh // ss), -(-sw // ss)
+        spt, spl = max((H - 1) * ss + 3 - sh, 0) // 2, max((W - 1) * ss + 3 - sw, 0) // 2
+        stem = (3, ss, spt, spl, H, W)
+        X = rng.standard_normal((n, c, sh, sw))
+        Cin = 9 * c
+        Ho, Wo = -(-H // st), -(-W // st)
+    else:
+        X = rng.standard_normal((n, H, W, Cin))
+    noexp = form in ("noexp", "gated")
+    We, be = rng.standard_normal((Cin, Cexp)) * 0.3, rng.standard_normal(Cexp)
+    Wd, bd = rng.standard_normal((ks * ks, Cexp)) * 0.4, rng.standard_normal(Cexp) * 3
+    Wp, bp = rng.standard_normal((Cexp, Cout)) * 0.3, rng.standard_normal(Cout)
+    R = rng.standard_normal((n, Ho, Wo, Cout)) if residual else None
+    gate = rng.uniform(0.0, 1.0, (n, Cexp)) if form == "gated" else None
+    got = O.mbconv64(X, We, be, Wd, bd, Wp, bp, R, ks, st, pad_t, pad_l, Ho, Wo, act, noexp=noexp, gate=gate, stem=stem)
+    e, d, y, dsum = _torch_mbconv(X, We, be, Wd, bd, Wp, bp, R, ks, st, pad_t, pad_l, Ho, Wo, act, noexp, gate, stem)
+    for name, a, b in (("E", got["E"], e), ("D", got["D"], d), ("Y", got["Y"], y), ("Dsum", got["Dsum"], dsum)):
+        assert a.shape == b.shape, name
+        np.testing.assert_allclose(a, b, rtol=1e-12, atol=1e-12, err_msg=name)
+
+
+def test_depthwise_reference_by_hand():
+    """A 3x3 stride-2 depthwise output worked out by hand, SAME on 4x4 (pad_t 0, pad_b 1): taps past the image are zero, and tap
+    (dy, dx) is row dy * 3 + dx of Wd."""
+    E = np.arange(1, 17, dtype=np.float64).reshape(1, 4, 4, 1)
+    Wd = np.arange(1, 10, dtype=np.float64).reshape(9, 1)
+    out = O.depthwise64(E, Wd, 3, 2, 0, 0, 2, 2)
+    assert out[0, 0, 0, 0] == sum(E[0, dy, dx, 0] * Wd[dy * 3 + dx, 0] for dy in range(3) for dx in range(3))
+    assert out[0, 1, 1, 0] == sum(E[0, 2 + dy, 2 + dx, 0] * Wd[dy * 3 + dx, 0] for dy in range(2) for dx in range(2))
