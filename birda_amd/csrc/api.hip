@@ -238,7 +238,10 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
         bh::TraceRange tr("front_end: minmax + mel");
         bh::launch_minmax(d_seg, d_minmax, d_inbad, (int)n, (int)m.h.sample_count, s);
         ctx_mark(ctx, ST_MINMAX);
-        bh::launch_mel(d_seg, d_minmax, T(0), c->fe, c->d_fe, (int)n, s);
+        const char *mel_name = bh::launch_mel(d_seg, d_minmax, T(0), c->fe, c->d_fe, (int)n, s);
+        if (!mel_name)   // (create refuses what launch_mel has no instantiation for: a missing kernel is an error, never a silent skip)
+            return fail(BH_ERR_UNSUPPORTED, "front-end: no kernel instantiation for %d mels at precision %d", c->fe.br[0].n_mels, c->fe.prec);
+        c->fe_kernel.store(mel_name, std::memory_order_relaxed);
         ctx_mark(ctx, ST_MEL);
     }
     for (uint32_t i = 0; i < nl; i++) {
@@ -1046,7 +1049,8 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
         if (b > 0 && nm_pad != c->fe.br[0].nm_pad) return fail(BH_ERR_UNSUPPORTED, "front-end: branches differ in n_mels");
         if (br.frame_length % 128 || br.fft_length != br.frame_length)
             return fail(BH_ERR_UNSUPPORTED, "front-end: frame_length %u must be a multiple of 128 and equal fft_length", br.frame_length);
-        if ((64 * br.frame_step) % 4) return fail(BH_ERR_UNSUPPORTED, "front-end: hop %u unsupported", br.frame_step);
+        // (no condition on the hop: a tile's span starts at sample tile * 48 (or 32) * hop, a multiple of 4 for any hop, so the
+        //  16-byte span loads stay aligned; what bounds the hop is the span's size, checked against the LDS below)
         int gf_s = 0;
         std::vector<float> gf = build_gf(br, m.blob.data() + br.mel_w_off, nm_pad, fe_prec, &gf_s);
         float *d = nullptr;
@@ -1730,7 +1734,9 @@ int bh_classifier_frontend_kernel(const bh_classifier *c, char *out, size_t cap)
     if (!c) return 0;
     char buf[64];
     const int nmp = c->fe.br[0].nm_pad;
-    if (c->fe.prec == 32) snprintf(buf, sizeof buf, "bh::mel32_kernel<%d>", nmp / 32);
+    // what the last forward launched (launch_mel's own answer); before any forward, the dispatch restated from the plan
+    if (const char *ran = c->fe_kernel.load(std::memory_order_relaxed)) snprintf(buf, sizeof buf, "%s", ran);
+    else if (c->fe.prec == 32) snprintf(buf, sizeof buf, "bh::mel32_kernel<%d>", nmp / 32);
     else snprintf(buf, sizeof buf, "bh::mel_kernel<%d, %d, 1>", nmp / 16, c->fe.prec);   // (third argument: HALVES, kernels_frontend.hip)
     const int n = (int)strlen(buf);
     if (out && cap > (size_t)n) memcpy(out, buf, (size_t)n + 1);

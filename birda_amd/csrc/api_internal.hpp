@@ -83,6 +83,7 @@ struct bh_classifier {
     std::vector<float *> d_owned;            // re-laid buffers to free
     bh::FrontendParams fe{};
     bh::FrontendParams *d_fe = nullptr;      // device copy read by the mel kernel
+    std::atomic<const char *> fe_kernel{nullptr};   // what launch_mel launched last (a string literal); nullptr before any forward
     std::vector<int> fused_at;               // per layer: index into mb (expand layer of a fused block) or -1
     std::vector<bh::MbDesc> mb;              // fused MBConv blocks (kernels_mbconv.hip)
     int twin_max_segments = 256;             // launches up to this size take the twins (one workgroup per CU at most either way)

@@ -878,8 +878,9 @@ size_t mel_lds_bytes(const FrontendParams &p) {
     return std::max((size_t)((max_span + 3) & ~3) * sizeof(float), (size_t)4 * 3 * (nmp / 16) * 64 * sizeof(float4));
 }
 
-void launch_mel(const float *x, const float *minmax, float *spec, const FrontendParams &p,
-                const FrontendParams *d_p, int n_seg, hipStream_t s) {
+// Returns the instantiation it launched, spelled as a profiler prints it; nullptr when none takes the front end (nothing launched).
+const char *launch_mel(const float *x, const float *minmax, float *spec, const FrontendParams &p,
+                       const FrontendParams *d_p, int n_seg, hipStream_t s) {
     int max_span = 0, max_frames = 0, nmp = p.br[0].nm_pad;
     for (int b = 0; b < p.n_branches; b++) {
         int span = (MEL_TN - 1) * p.br[b].H + p.br[b].L;
@@ -901,7 +902,8 @@ void launch_mel(const float *x, const float *minmax, float *spec, const Frontend
         static DeviceOnce set32;                                                                                               \
         set32.run([] { (void)hipFuncSetAttribute((const void *)mel32_kernel<MTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
         hipLaunchKernelGGL((mel32_kernel<MTV>), g32, b32, smem32, s, x, minmax, spec, d_p, p.br[0].gf, p.br[1].gf, p.br[2].gf, p.br[3].gf, dbg, ybuf_off, nt32, ni32); \
-    } break;
+        return "bh::mel32_kernel<" #MTV ">";                                                                                   \
+    }
         switch (mt32) {
             BH_MEL32(1)
             BH_MEL32(2)
@@ -910,7 +912,7 @@ void launch_mel(const float *x, const float *minmax, float *spec, const Frontend
         default: break;
         }
 #undef BH_MEL32
-        return;
+        return nullptr;
     }
     const int mt = nmp / 16;
     // 8-wave workgroups on 96-frame items (HALVES = 2 above) for the split-f16 96-mel front-ends: built, parity-green, measured and
@@ -941,7 +943,7 @@ void launch_mel(const float *x, const float *minmax, float *spec, const Frontend
         attr2.run([] { (void)hipFuncSetAttribute((const void *)mel_kernel<6, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
         hipLaunchKernelGGL((mel_kernel<6, 3, 2>), grid, dim3(512), smem, s, x, minmax, spec, d_p, p.br[0].gf, p.br[1].gf, p.br[2].gf, p.br[3].gf,
                            dbg, n_tiles, n_items, paired);
-        return;
+        return "bh::mel_kernel<6, 3, 2>";
     }
 #endif
 #define BH_MEL_CASE(MTV)                                                                                   \
@@ -953,13 +955,15 @@ void launch_mel(const float *x, const float *minmax, float *spec, const Frontend
             (void)hipFuncSetAttribute((const void *)mel_kernel<MTV, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, \
                                 160 * 1024);                                                              \
         });                                                                                                \
-        if (p.prec == 3)                                                                                   \
+        if (p.prec == 3) {                                                                                 \
             hipLaunchKernelGGL((mel_kernel<MTV, 3>), grid, block, smem, s, x, minmax, spec, d_p, p.br[0].gf,   \
                                p.br[1].gf, p.br[2].gf, p.br[3].gf, dbg, n_tiles, n_items, paired);                 \
-        else                                                                                               \
-            hipLaunchKernelGGL((mel_kernel<MTV, 0>), grid, block, smem, s, x, minmax, spec, d_p, p.br[0].gf,   \
-                               p.br[1].gf, p.br[2].gf, p.br[3].gf, dbg, n_tiles, n_items, paired);                 \
-    } break;
+            return "bh::mel_kernel<" #MTV ", 3, 1>";                                                       \
+        }                                                                                                  \
+        hipLaunchKernelGGL((mel_kernel<MTV, 0>), grid, block, smem, s, x, minmax, spec, d_p, p.br[0].gf,       \
+                           p.br[1].gf, p.br[2].gf, p.br[3].gf, dbg, n_tiles, n_items, paired);                     \
+        return "bh::mel_kernel<" #MTV ", 0, 1>";                                                           \
+    }
     switch (mt) {      // (32, 96 and 128 mels are the published families'; 48 / 64 / 80 / 112 -- round 6 -- whatever else a model file holds)
         BH_MEL_CASE(2)
         BH_MEL_CASE(3)
@@ -971,6 +975,7 @@ void launch_mel(const float *x, const float *minmax, float *spec, const Frontend
     default: break;
     }
 #undef BH_MEL_CASE
+    return nullptr;
 }
 
 }  // namespace bh

@@ -342,8 +342,9 @@ BH_API int bh_classifier_fused_blocks(const bh_classifier *c, int32_t *cfgs, siz
 BH_API int bh_plan_fused_blocks(const char *model_path, uint32_t flags, int32_t *cfgs, int32_t *layers, size_t cap);
 
 /* Name of the front-end (STFT x mel) kernel instantiation this classifier launches, as a profiler prints it
- * (e.g. "bh::mel_kernel<6, 3>"): lets the bench match its HIP-event timings and the committed PMC counters to the exact
- * kernel.  Returns the string length. */
+ * (e.g. "bh::mel_kernel<6, 3, 1>"): lets the bench match its HIP-event timings and the committed PMC counters to the exact
+ * kernel.  After a forward pass it is what the launcher reported for the last launch; before any, the one create planned.
+ * Returns the string length. */
 BH_API int bh_classifier_frontend_kernel(const bh_classifier *c, char *out, size_t cap);
 
 /* Template arguments of tile configuration `cfg` as a profiler prints them after

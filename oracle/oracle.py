@@ -429,3 +429,52 @@ def mbconv64(X, We, be, Wd, bd, Wp, bp, R, ks: int, st: int, pad_t: int, pad_l: 
     if R is not None:
         Y = Y + np.asarray(R, f)
     return {"A": A, "preE": preE, "E": E, "preD": preD, "D": D, "Dg": Dg, "Y": Y, "Dsum": D.sum(axis=(1, 2))}
+
+
+# --------------------------------------------------------------------------------------------------------
+# The spectrogram front end (kernels_frontend.hip, api_plan.hip build_gf) in float64, from the DEFINITION
+# and not from the folded operator the device builds, for tests/test_frontend*.py.
+# --------------------------------------------------------------------------------------------------------
+def frontend_operator64(L: int, W) -> np.ndarray:
+    """G[n][m] = hann_periodic[n] sum_k cos(2 pi k n / L) W[k][m], k = 0 .. L/2: window x Re(rFFT) x mel as one dense float64
+    operator (frame . G = Re(rfft(frame * hann)) . W).  Used for the magnitude sums the rounding errors scale with; the
+    spectrogram itself goes through the FFT."""
+    W = np.asarray(W, np.float64)
+    n = np.arange(L)
+    k = np.arange(W.shape[0])
+    cos = np.cos(2.0 * np.pi * ((n[:, None] * k[None, :]) % L) / L)
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * n / L))[:, None] * (cos @ W)
+
+
+def frontend64(m, segs):
+    """The front end of model `m` (birda_amd.modelfile.Model) on segs [n][sample_count] float32, in float64:
+    x <- 2((x - min) / (max - min + eps) - 0.5) per segment (float32 samples and float32 norm_eps, float64 arithmetic); frames of
+    L at hop H; periodic Hann; real part of the rFFT; . mel_W; square; ^ expo, expo = 1 / (1 + exp(mag_scale)); mel flip;
+    [branch][mel][frame]; out_scale, out_shift.
+
+    Returns (spec [n][n_branches][n_mels][n_frames], detail): detail[b] holds, for branch b and in the mel order of the FILE
+    (before the flip), v [n][n_frames][n_mels] (the value the power law is applied to), B [n][n_frames][n_mels] =
+    sum_j |x_j| |G[j][m]| over the frame's samples, G (frontend_operator64), expo, and xn [n][sample_count], the normalised
+    samples."""
+    segs = np.ascontiguousarray(segs, np.float32).reshape(-1, m.sample_count)
+    x = segs.astype(np.float64)
+    mn, mx = x.min(axis=1, keepdims=True), x.max(axis=1, keepdims=True)
+    xn = 2.0 * ((x - mn) / (mx - mn + float(np.float32(m.norm_eps))) - 0.5)
+    n = segs.shape[0]
+    spec = np.empty((n, len(m.branches), m.spec_h, m.spec_w))
+    detail = []
+    for b, br in enumerate(m.branches):
+        L, H, nf, nm = br.frame_length, br.frame_step, br.n_frames, br.n_mels
+        W = np.asarray(m.blob[br.mel_w_off:br.mel_w_off + br.n_bins * nm], np.float64).reshape(br.n_bins, nm)
+        G = frontend_operator64(L, W)
+        hann = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(L) / L)
+        fr = np.lib.stride_tricks.sliding_window_view(xn, L, axis=1)[:, ::H][:, :nf]          # [n][nf][L]
+        v = np.fft.rfft(fr * hann, axis=2).real @ W
+        B = np.abs(fr) @ np.abs(G)
+        expo = 1.0 / (1.0 + math.exp(float(np.float32(br.mag_scale))))
+        out = np.power(v * v, expo) * float(np.float32(br.out_scale)) + float(np.float32(br.out_shift))
+        if br.flags & 1:
+            out = out[:, :, ::-1]
+        spec[:, b] = np.transpose(out, (0, 2, 1))
+        detail.append({"v": v, "B": B, "G": G, "expo": expo, "xn": xn})
+    return spec, detail
