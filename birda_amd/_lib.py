@@ -99,6 +99,7 @@ SYMBOLS = [
     ("bh_batch_context_stage_ms", C.c_int, [_VP, _VP, _VP]),
     ("bh_batch_context_layer_ms", C.c_int, [_VP, _VP, _VP, _SZ]),
     ("bh_classifier_fused_blocks", C.c_int, [_VP, _VP, _SZ]),
+    ("bh_classifier_weight_summary", C.c_int, [_VP, _VP, _SZ]),
     ("bh_plan_fused_blocks", C.c_int, [C.c_char_p, C.c_uint32, _VP, _VP, _SZ]),
     ("bh_mb_config_name", C.c_int, [C.c_int32, C.c_char_p, _SZ]),
     ("bh_classifier_frontend_kernel", C.c_int, [_VP, C.c_char_p, _SZ]),
@@ -253,6 +254,14 @@ LAYER_DEBUG_SYMBOLS = [
     ("bh_debug_layer_gemm", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ, _SZ, _SZ, _SZ, C.c_int, C.c_int, _VP, _SZ]),
 ]
 
+# include/birda_hip_terms_debug.h: which layers run two-term products
+TERMS_DEBUG_SYMBOLS = [
+    ("bh_debug_w16_two_terms", C.c_int, [_VP, _SZ, _SZ]),
+    ("bh_debug_layer_terms", C.c_int, [_VP, _VP, _SZ]),
+    ("bh_debug_layer_kernel", C.c_int, [_VP, C.c_uint32, _VP, _SZ]),
+    ("bh_debug_last_gated_kernel", C.c_int, [_VP, _SZ]),
+]
+
 # include/birda_hip_block_debug.h: one fused MBConv block alone (and its plan, host only), for the tests that hold every
 # instantiation of the fused kernel to float64
 BLOCK_DEBUG_SYMBOLS = [
@@ -273,7 +282,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

@@ -133,10 +133,12 @@ PRECISION_FLAGS = {"auto": 0, "f16x3": 1, "f16": 2, "f32": 3}
 
 class BirdClassifier:
     def __init__(self, model_path: str, labels_path: Optional[str] = None, top_k: int = DEFAULT_TOP_K,
-                 min_confidence: float = DEFAULT_MIN_CONFIDENCE, device: int = 0, precision: str = "auto", low_latency: bool = False):
+                 min_confidence: float = DEFAULT_MIN_CONFIDENCE, device: int = 0, precision: str = "auto", low_latency: bool = False,
+                 full_planes: bool = False):
         self._L = _lib.load()
         self._keep = (model_path.encode(), labels_path.encode() if labels_path else None)
-        flags = PRECISION_FLAGS[precision] | (0x10 if low_latency else 0)   # BH_FLAG_* (include/birda_hip.h); 0x10 = BH_FLAG_LOW_LATENCY
+        # BH_FLAG_* (include/birda_hip.h); 0x10 = BH_FLAG_LOW_LATENCY, 0x20 = BH_FLAG_FULL_PLANES
+        flags = PRECISION_FLAGS[precision] | (0x10 if low_latency else 0) | (0x20 if full_planes else 0)
         cfg = BhConfig(self._keep[0], self._keep[1], top_k, min_confidence, device, flags)
         h = C.c_void_p()
         check(self._L.bh_classifier_create(C.byref(cfg), C.byref(h)))
@@ -170,6 +172,28 @@ class BirdClassifier:
         buf = (C.c_int32 * 256)()
         n = int(self._L.bh_classifier_fused_blocks(self._h, buf, 256))
         return [int(buf[i]) for i in range(min(n, 256))]
+
+    def weight_summary(self) -> dict:
+        """bh_classifier_weight_summary: how the GEMM layers outside the fused blocks hold their weights (BH_WS_* of birda_hip.h)."""
+        buf = (C.c_uint64 * 8)()
+        n = int(self._L.bh_classifier_weight_summary(self._h, buf, 8))
+        if n < 0:
+            check(n)
+        keys = ("float16_file", "gemm_layers", "two_term_layers", "plane_bytes", "two_term_plane_bytes")
+        return {k: int(buf[i]) for i, k in enumerate(keys[:n])}
+
+    def layer_terms(self) -> List[int]:
+        """bh_debug_layer_terms: per model layer 1 / 2 / 3 (the terms of its split-f16 GEMM) or 0 (no f16 operand planes)."""
+        n = int(self._L.bh_debug_layer_terms(self._h, None, 0))
+        buf = (C.c_int32 * max(n, 1))()
+        self._L.bh_debug_layer_terms(self._h, buf, n)
+        return [int(buf[i]) for i in range(n)]
+
+    def layer_kernel(self, layer: int) -> str:
+        """bh_debug_layer_kernel: the split-f16 GEMM instantiation model layer `layer` launched in the last forward ('' if none)."""
+        buf = C.create_string_buffer(160)
+        self._L.bh_debug_layer_kernel(self._h, layer, buf, 160)
+        return buf.value.decode()
 
     def fused_kernel_name(self, cfg: int, se: bool = False) -> str:
         """The block's instantiation as rocprofv3 prints it: the 19 tile arguments of bh_mb_config_name and the twentieth, SE (1 for

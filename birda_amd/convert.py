@@ -31,6 +31,9 @@ from . import modelfile as mf
 from . import onnx_io as ox
 
 SQRT2 = math.sqrt(2.0)
+# the float16 roundings of sqrt 2 and 1 / sqrt 2: what the erf-GELU spelling of a float16 file carries
+SQRT2_F16, RSQRT2_F16 = float(np.float16(SQRT2)), float(np.float16(1.0 / SQRT2))
+FLOAT_CASTS = (ox.FLOAT, ox.FLOAT16, ox.DOUBLE)
 
 
 class ConvertError(ValueError):
@@ -261,6 +264,35 @@ def _scalar(g: ox.Graph, name: str) -> Optional[float]:
     return float(a.reshape(-1)[0]) if a is not None and a.size == 1 else None
 
 
+def _scalar_is_f16(g: ox.Graph, name: str) -> bool:
+    a = g.initializers.get(name)
+    return a is not None and a.dtype == np.float16
+
+
+def _see_through_casts(g: ox.Graph, front_nodes: set) -> ox.Graph:
+    """Cast between floating types is the identity (a float16 constant is the exact real number it encodes; the graph is evaluated
+    in the library's own arithmetic): behind the front-end every such node is dropped and its output renamed to its input everywhere
+    -- consumers and graph outputs -- so the sole-consumer / pattern logic sees through it.  Any other target is refused by name.
+    The csrc/onnx_conv.hpp walk does the same.  Returns a new graph (nodes copied, initializers shared); front-end nodes untouched."""
+    alias: Dict[str, str] = {}
+    nodes = []
+    for i, n in enumerate(g.nodes):
+        if i in front_nodes:
+            nodes.append(n)
+            continue
+        ins = [alias.get(x, x) for x in n.inputs]
+        if n.op_type == "Cast":
+            to = int(n.attrs.get("to", 0))
+            if to not in FLOAT_CASTS:
+                raise ConvertError(f"Cast {n.name!r} to {ox._TYPE_NAMES.get(to, 'element type ' + str(to))} (to = {to}): only casts between "
+                                   "float32, float16 and float64 are read, as the identity")
+            alias[n.outputs[0]] = ins[0]
+            continue
+        nodes.append(ox.Node(n.op_type, ins, list(n.outputs), n.attrs, n.name))
+    outs = [ox.ValueInfo(alias.get(o.name, o.name), o.elem_type, o.shape) for o in g.outputs]
+    return ox.Graph(nodes, g.initializers, g.inputs, outs, g.name, g.opset, g.producer)
+
+
 def _collapse_activations(g: ox.Graph):
     """Find the multi-node activation spellings.  Returns (skip: set of node indices,
     act_of: {final output name: (input name, ACT)})."""
@@ -282,12 +314,15 @@ def _collapse_activations(g: ox.Graph):
             if j is None or g.nodes[j].op_type not in ("Div", "Mul"):
                 continue
             pre = g.nodes[j]
-            cst = [(_scalar(g, a), b) for a, b in ((pre.inputs[1], pre.inputs[0]), (pre.inputs[0], pre.inputs[1]))]
+            cst = [(_scalar(g, a), _scalar_is_f16(g, a), b, side) for side, (a, b) in enumerate(((pre.inputs[1], pre.inputs[0]), (pre.inputs[0], pre.inputs[1])))]
             x = None
-            for c, other in cst:
+            for c, c16, other, _ in cst:
                 if c is None:
                     continue
-                if (pre.op_type == "Div" and abs(c - SQRT2) < 1e-4) or (pre.op_type == "Mul" and abs(c - 1 / SQRT2) < 1e-4):
+                # a float32 constant is held to sqrt 2 at 1e-4; a float16 one must BE the float16 rounding of the expected value
+                is_sqrt2 = c == SQRT2_F16 if c16 else abs(c - SQRT2) < 1e-4
+                is_rsqrt2 = c == RSQRT2_F16 if c16 else abs(c - 1 / SQRT2) < 1e-4
+                if (pre.op_type == "Div" and is_sqrt2) or (pre.op_type == "Mul" and is_rsqrt2):
                     x = other
             k = sole_consumer(n.outputs[0], "Add")
             if x is None or k is None:
@@ -322,6 +357,10 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
     the start of the new blob, so `mel_w_off` stays valid).  Without one, the graph must start at the AUDIO input and the
     front-end is read off it by probing (`frontend_recover.recover_frontend`; `sample_rate` is then required: the graph does
     not state it, the reference takes it from the model type's config, src/inference/classifier.rs:360-377)."""
+    for vi in list(g.inputs) + list(g.outputs):
+        if vi.elem_type == ox.FLOAT16:
+            raise ConvertError(f"graph {'input' if vi in g.inputs else 'output'} {vi.name!r} is float16: only float32 inputs are fed and "
+                               "float32 outputs returned (a float16 file keeps float32 at both ends, behind / in front of a Cast)")
     if frontend is None:
         from .frontend_recover import RecoverError, recover_frontend
         if sample_rate is None:
@@ -335,15 +374,18 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
     if spec is None:
         raise ConvertError("graph has no input")
     # nodes that produce the spectrogram (a graph that starts at the audio input) are the front-end, not layers
-    prod = {o: i for i, n in enumerate(g.nodes) for o in n.outputs}
-    front_nodes, stack = set(), [spec]
-    while stack:
-        t = stack.pop()
-        i = prod.get(t)
-        if i is None or i in front_nodes:
-            continue
-        front_nodes.add(i)
-        stack.extend(g.nodes[i].inputs)
+    def producers_of(gr: ox.Graph, tensor: str) -> set:
+        prod = {o: i for i, n in enumerate(gr.nodes) for o in n.outputs}
+        found, stack = set(), [tensor]
+        while stack:
+            i = prod.get(stack.pop())
+            if i is None or i in found:
+                continue
+            found.add(i)
+            stack.extend(gr.nodes[i].inputs)
+        return found
+    g = _see_through_casts(g, producers_of(g, spec))
+    front_nodes = producers_of(g, spec)
     blob = _Blob(frontend.blob[: max((b.mel_w_off + b.n_bins * b.n_mels for b in frontend.branches), default=0)])
     layers: List[mf.Layer] = []
     # name -> (tensor index, C, H, W) ; H = W = 0 for flattened [N, C]
@@ -545,6 +587,65 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
                     [mf.Branch(**{k: getattr(b, k) for k in ("frame_length", "frame_step", "n_mels", "n_frames", "fmin", "fmax",
                                                              "mag_scale", "out_scale", "out_shift", "flags", "mel_w_off")})
                      for b in frontend.branches], layers, blob.array())
+
+
+def graph_to_float16(g: ox.Graph, frontend: str = "f16", spectrogram: str = "spectrogram") -> ox.Graph:
+    """`g` (a graph from `graph_from_model`) rewritten the way the published float16 export is described: the float32 graph input
+    and outputs kept, a Cast(to=float16) behind the input, a Cast(to=float32) in front of each output, every float32 initializer
+    converted to float16 (round to nearest even; a magnitude above 65 504 becomes inf, as numpy does it).  frontend='f32': the nodes
+    that produce `spectrogram` and the constants only they read stay float32, between a pair of Casts (float16 -> float32 in front
+    of them, float32 -> float16 behind the spectrogram).  Test and tool infrastructure: nothing in the product path calls it."""
+    if frontend not in ("f16", "f32"):
+        raise ConvertError(f"frontend {frontend!r}: 'f16' or 'f32'")
+    nodes = [ox.Node(n.op_type, list(n.inputs), list(n.outputs), dict(n.attrs), n.name) for n in g.nodes]
+    prod = {o: i for i, n in enumerate(nodes) for o in n.outputs}
+    front, stack = set(), [spectrogram]
+    while stack:
+        i = prod.get(stack.pop())
+        if i is None or i in front:
+            continue
+        front.add(i)
+        stack.extend(nodes[i].inputs)
+    keep32 = set()
+    if frontend == "f32" and front:
+        read_elsewhere = {x for i, n in enumerate(nodes) if i not in front for x in n.inputs}
+        keep32 = {x for i in front for x in nodes[i].inputs if x in g.initializers and x not in read_elsewhere}
+    init = {k: (a.astype(np.float16) if a.dtype == np.float32 and k not in keep32 else a) for k, a in g.initializers.items()}
+
+    def cast(src: str, dst: str, to: int) -> ox.Node:
+        return ox.Node("Cast", [src], [dst], {"to": to}, name=dst)
+
+    def rename_readers(old: str, new: str, among) -> None:
+        for i in among:
+            nodes[i].inputs = [new if x == old else x for x in nodes[i].inputs]
+
+    head, everyone = [], range(len(nodes))
+    for vi in g.inputs:
+        if vi.elem_type != ox.FLOAT:
+            continue
+        h16 = vi.name + "_f16"
+        head.append(cast(vi.name, h16, ox.FLOAT16))
+        if keep32:
+            head.append(cast(h16, vi.name + "_f32", ox.FLOAT))
+            rename_readers(vi.name, vi.name + "_f32", everyone)
+        else:
+            rename_readers(vi.name, h16, everyone)
+    body = []
+    for i, n in enumerate(nodes):
+        body.append(n)
+        if keep32 and spectrogram in n.outputs:
+            body.append(cast(spectrogram, spectrogram + "_f16", ox.FLOAT16))
+            rename_readers(spectrogram, spectrogram + "_f16", [j for j in everyone if j not in front])
+    tail = []
+    for vo in g.outputs:
+        if vo.elem_type != ox.FLOAT:
+            continue
+        inner = vo.name + "_f16"
+        for n in nodes:
+            n.outputs = [inner if x == vo.name else x for x in n.outputs]
+        rename_readers(vo.name, inner, everyone)
+        tail.append(cast(inner, vo.name, ox.FLOAT))
+    return ox.Graph(head + body + tail, init, list(g.inputs), list(g.outputs), g.name, g.opset, g.producer)
 
 
 def convert_file(onnx_path: str, frontend_bhm: Optional[str], out_path: str, spectrogram_input: Optional[str] = None,

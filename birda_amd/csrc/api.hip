@@ -46,13 +46,18 @@ namespace bhi {
 // f16 operand planes of a [K][N] weight matrix for the split-f16 GEMMs: [ceil(K / 32)][ceil(N / 16)]{hi, lo}[64 lanes][8 halves],
 // lane (n & 15, k group) holding k = 32 step + 8 (lane >> 4) + 0..7 of column n, scaled by a power of two (1 / *unscale) that puts
 // the largest weight in the f16 range, zero beyond K and N
-std::vector<uint16_t> w16_planes(const float *W, int K, int N, float *unscale) {
+// *lo_zero (may be null): every weight IS an f16 value after the power-of-two pre-scale -- its hi half holds it exactly, so every lo
+// entry is zero and nothing was lost below the f16 subnormal grid either (a residual under half a subnormal step also rounds to a
+// zero lo entry: such a matrix does NOT qualify; inf / NaN weights neither).  The layer may then run two-term products
+// (kernels_conv.hip TERMS == 2) on the compact form of these planes (w16_compact)
+std::vector<uint16_t> w16_planes(const float *W, int K, int N, float *unscale, bool *lo_zero = nullptr) {
     const int nt = (N + 15) / 16, ksteps = (K + 31) / 32;
     std::vector<uint16_t> planes((size_t)ksteps * nt * 2 * 64 * 8, 0);
     float wmax = 0.0f;
     for (size_t q = 0; q < (size_t)K * N; q++) wmax = std::max(wmax, std::fabs(W[q]));
     const int ws = bh::f16_scale_exponent(wmax);
     *unscale = std::ldexp(1.0f, -ws);
+    bool exact = true;
     for (int st = 0; st < ksteps; st++)
         for (int t = 0; t < nt; t++)
             for (int lane = 0; lane < 64; lane++)
@@ -61,10 +66,32 @@ std::vector<uint16_t> w16_planes(const float *W, int K, int N, float *unscale) {
                     const float v = (n < N && k < K) ? std::ldexp(W[(size_t)k * N + n], ws) : 0.0f;
                     const uint16_t hi = f32_to_f16(v);
                     const size_t base = (((size_t)st * nt + t) * 2) * 64 * 8;
+                    const float rest = v - f16_to_f32(hi);
+                    if (!(rest == 0.0f)) exact = false;
                     planes[base + (size_t)lane * 8 + jj] = hi;
-                    planes[base + 64 * 8 + (size_t)lane * 8 + jj] = f32_to_f16(v - f16_to_f32(hi));
+                    planes[base + 64 * 8 + (size_t)lane * 8 + jj] = f32_to_f16(rest);
                 }
+    if (lo_zero) *lo_zero = exact;
     return planes;
+}
+
+// the compact planes of two-term products: [k step][column tile][64 lanes][8 halves], w16_planes' layout without the lo half
+std::vector<uint16_t> w16_compact(const std::vector<uint16_t> &planes) {
+    std::vector<uint16_t> out(planes.size() / 2);
+    for (size_t blk = 0; blk < planes.size() / (2 * 64 * 8); blk++)
+        memcpy(&out[blk * 64 * 8], &planes[blk * 2 * 64 * 8], 64 * 8 * sizeof(uint16_t));
+    return out;
+}
+
+// the planes a debug entry point uploads for `terms`: full for 1 and 3; compact for 2, which is refused (false) when W is not made
+// of f16 values
+static bool debug_planes(const float *W, int K, int N, int terms, float *unscale, std::vector<uint16_t> &planes) {
+    bool lo_zero = false;
+    planes = w16_planes(W, K, N, unscale, &lo_zero);
+    if (terms != 2) return true;
+    if (!lo_zero) return false;
+    planes = w16_compact(planes);
+    return true;
 }
 
 bh::ConvParams conv_params(const bh::LayerRec &L) {
@@ -321,8 +348,8 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
                             float *yg = y + s0 * P * d.Cout;
                             const float *rg = r ? r + s0 * P * d.Cout : nullptr;
                             if (c->d_w16[S.iP])
-                                bh::launch_pw_gemm16_gated(g.Dout, gg, (int)P, c->d_w16[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
-                                                           c->precision == 3 ? 3 : 1, c->w16_unscale[S.iP], g.dblk, s);
+                                c->w16_kernel[S.iP].store(bh::launch_pw_gemm16_gated(g.Dout, gg, (int)P, c->d_w16[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
+                                                           c->w16_terms[S.iP], c->w16_unscale[S.iP], g.dblk, s), std::memory_order_relaxed);
                             else
                                 bh::launch_pw_gemm_gated(g.Dout, gg, (int)P, c->d_w[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
                                                          c->ldw[S.iP], (int)LP.act, s);
@@ -360,8 +387,8 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
                     bh::launch_mbconv(g, (int)n, s);
                 } else
                 if (c->d_w16[S.iP])
-                    bh::launch_pw_gemm16_gated(d.Dout, gate, P, c->d_w16[S.iP], c->d_blob + LP.b_off, r, y, (int)(n * (size_t)P), d.Cexp, d.Cout,
-                                               c->precision == 3 ? 3 : 1, c->w16_unscale[S.iP], d.dblk, s);
+                    c->w16_kernel[S.iP].store(bh::launch_pw_gemm16_gated(d.Dout, gate, P, c->d_w16[S.iP], c->d_blob + LP.b_off, r, y, (int)(n * (size_t)P), d.Cexp, d.Cout,
+                                               c->w16_terms[S.iP], c->w16_unscale[S.iP], d.dblk, s), std::memory_order_relaxed);
                 else
                     bh::launch_pw_gemm_gated(d.Dout, gate, P, c->d_w[S.iP], c->d_blob + LP.b_off, r, y, (int)(n * (size_t)P), d.Cexp, d.Cout,
                                              c->ldw[S.iP], (int)LP.act, s);
@@ -402,7 +429,7 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
             if (L.in_layout == 1)
                 bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
             else if (!ctx->keep_tensors && c->d_w16[i])
-                bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->precision == 3 ? 3 : 1, c->w16_unscale[i], s);
+                c->w16_kernel[i].store(bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
             else
                 bh::launch_conv_gemm(in, c->d_w[i], bias, res, out, p, (int)n, c->ldw[i], s);
             ctx_mark(ctx, ST_STEM, (int)i);
@@ -414,15 +441,15 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
         case bh::OP_PWCONV:
             if (!ctx->keep_tensors && c->head_gap[i]) {
                 float *pooled = (i + 1 == nl - 1) ? d_logits : T(i + 2);
-                bh::launch_head_gap16(in, c->d_w16[i], bias, pooled, (int)n, (int)(L.out_h * L.out_w), (int)L.cin, (int)L.cout,
-                                      (int)L.act, c->precision == 3 ? 3 : 1, c->w16_unscale[i], s);
+                c->w16_kernel[i].store(bh::launch_head_gap16(in, c->d_w16[i], bias, pooled, (int)n, (int)(L.out_h * L.out_w), (int)L.cin, (int)L.cout,
+                                                             (int)L.act, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
                 ctx_mark(ctx, ST_PW, (int)i);
                 i += 1;   // the pool layer is done
                 break;
             }
             if (!ctx->keep_tensors && c->d_w16[i])
-                bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin, (int)L.cout,
-                                     (int)L.act, c->precision == 3 ? 3 : 1, c->w16_unscale[i], s);
+                c->w16_kernel[i].store(bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin, (int)L.cout,
+                                                            (int)L.act, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
             else
             bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin,
                                (int)L.cout, c->ldw[i], (int)L.act, s);
@@ -430,8 +457,8 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
             break;
         case bh::OP_DENSE:
             if (!ctx->keep_tensors && c->d_w16[i])
-                bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, (int)L.act,
-                                     c->precision == 3 ? 3 : 1, c->w16_unscale[i], s);
+                c->w16_kernel[i].store(bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, (int)L.act,
+                                                            c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
             else
             bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, c->ldw[i],
                                (int)L.act, s);
@@ -1009,6 +1036,7 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
         c->precision = pf == BH_FLAG_F32 ? 0 : pf == BH_FLAG_F16 ? 1 : 3;
         c->auto_fallback = pf == BH_FLAG_AUTO;
         c->low_latency = (cfg->flags & BH_FLAG_LOW_LATENCY) != 0;
+        c->full_planes = (cfg->flags & BH_FLAG_FULL_PLANES) != 0;
         c->model_path = cfg->model_path;
     }
     if (const char *pe = (cfg->flags & FLAG_INTERNAL_NO_ENV) ? nullptr : getenv("BIRDA_HIP_PRECISION")) {
@@ -1133,6 +1161,23 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
     // f16 operand planes for the GEMM layers that stay outside the fused blocks (head conv, dense)
     c->d_w16.assign(m.layers.size(), nullptr);
     c->w16_unscale.assign(m.layers.size(), 1.0f);
+    c->w16_terms.assign(m.layers.size(), c->precision == 3 ? 3 : 1);
+    c->w16_bytes.assign(m.layers.size(), 0);
+    c->w16_kernel.reset(new std::atomic<const char *>[m.layers.size()]);
+    for (size_t i = 0; i < m.layers.size(); i++) c->w16_kernel[i].store(nullptr, std::memory_order_relaxed);
+    // Two-term products: decided by the data, per layer -- a layer whose lo plane is all zero AFTER BatchNormalization folding and
+    // the power-of-two pre-scale (a float16 model file's weights, or f16 values in any container) runs TERMS == 2 on compact planes,
+    // half the bytes; every other layer, and every layer under BH_FLAG_FULL_PLANES, BH_FLAG_F16 or BH_FLAG_F32, is what it was.
+    auto upload_planes = [&](size_t i, std::vector<uint16_t> planes, bool lo_zero) {
+        if (c->precision == 3 && lo_zero && !c->full_planes) { planes = w16_compact(planes); c->w16_terms[i] = 2; }
+        float *d = nullptr;
+        const int urc = upload(planes.data(), planes.size() * sizeof(uint16_t), &d);
+        if (urc != BH_OK) return urc;
+        c->d_owned.push_back(d);
+        c->d_w16[i] = d;
+        c->w16_bytes[i] = planes.size() * sizeof(uint16_t);
+        return (int)BH_OK;
+    };
     if (c->precision != 0) {
         std::vector<char> in_block(m.layers.size(), 0), se_project(m.layers.size(), 0);
         for (size_t i = 0; i < m.layers.size(); i++)
@@ -1156,22 +1201,18 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
                 if (!bh::conv_gemm16_supports(conv_params(L)) || L.cout <= 64) continue;
                 const uint32_t cpad = (uint32_t)align_up(L.cin, 32);
                 const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, conv_params(L), (int)L.cout);
-                const std::vector<uint16_t> planes = w16_planes(w.data(), (int)(L.kh * L.kw * cpad), (int)L.cout, &c->w16_unscale[i]);
-                float *d = nullptr;
-                rc = upload(planes.data(), planes.size() * sizeof(uint16_t), &d);
+                bool lo_zero = false;
+                std::vector<uint16_t> planes = w16_planes(w.data(), (int)(L.kh * L.kw * cpad), (int)L.cout, &c->w16_unscale[i], &lo_zero);
+                rc = upload_planes(i, std::move(planes), lo_zero);
                 if (rc != BH_OK) return rc;
-                c->d_owned.push_back(d);
-                c->d_w16[i] = d;
                 continue;
             }
             if (in_block[i] || (L.op != bh::OP_PWCONV && L.op != bh::OP_DENSE)) continue;
             if (!(se_project[i] ? (L.cin % 4 == 0 && L.act == bh::ACT_NONE) : bh::pw_gemm16_supports((int)L.cin, (int)L.act))) continue;
-            const std::vector<uint16_t> planes = w16_planes(m.blob.data() + L.w_off, (int)L.cin, (int)L.cout, &c->w16_unscale[i]);
-            float *d = nullptr;
-            rc = upload(planes.data(), planes.size() * sizeof(uint16_t), &d);
+            bool lo_zero = false;
+            std::vector<uint16_t> planes = w16_planes(m.blob.data() + L.w_off, (int)L.cin, (int)L.cout, &c->w16_unscale[i], &lo_zero);
+            rc = upload_planes(i, std::move(planes), lo_zero);
             if (rc != BH_OK) return rc;
-            c->d_owned.push_back(d);
-            c->d_w16[i] = d;
         }
     }
     // head conv + GELU followed by the global average pool (and read by nothing else): one launch
@@ -1698,6 +1739,48 @@ int bh_onnx_eval(const char *onnx_path, const char *feed_name, const double *fee
     return BH_OK;
 } catch (...) { return on_exception(); }
 
+int bh_classifier_weight_summary(const bh_classifier *c, uint64_t *out, size_t cap) {
+    if (!c) return fail(BH_ERR_INVALID, "weight_summary: null classifier");
+    uint64_t v[BH_WS_COUNT] = {0};
+    v[BH_WS_FLOAT16_FILE] = c->model.file_f16 ? 1 : 0;
+    for (size_t i = 0; i < c->d_w16.size(); i++) {
+        if (!c->d_w16[i]) continue;
+        v[BH_WS_GEMM_LAYERS]++;
+        v[BH_WS_PLANE_BYTES] += c->w16_bytes[i];
+        if (c->w16_terms[i] == 2) { v[BH_WS_TWO_TERM_LAYERS]++; v[BH_WS_TWO_TERM_PLANE_BYTES] += c->w16_bytes[i]; }
+    }
+    for (size_t i = 0; i < cap && i < (size_t)BH_WS_COUNT; i++)
+        if (out) out[i] = v[i];
+    return BH_WS_COUNT;
+}
+
+// per layer: the terms its split-f16 GEMM runs (1, 2 or 3), 0 for a layer without operand planes (inside a fused block, f32, ...)
+int bh_debug_layer_terms(const bh_classifier *c, int32_t *terms, size_t cap) {
+    if (!c) return fail(BH_ERR_INVALID, "debug_layer_terms: null classifier");
+    for (size_t i = 0; i < c->d_w16.size() && i < cap; i++)
+        if (terms) terms[i] = c->d_w16[i] ? c->w16_terms[i] : 0;
+    return (int)c->d_w16.size();
+}
+
+// the instantiation the split-f16 GEMM of `layer` launched last (a launcher's name string), "" before any forward / for a layer
+// that takes none of those launchers; returns its length
+int bh_debug_layer_kernel(const bh_classifier *c, uint32_t layer, char *out, size_t cap) {
+    if (!c || layer >= c->d_w16.size()) return fail(BH_ERR_INVALID, "debug_layer_kernel: bad arguments");
+    const char *name = c->w16_kernel[layer].load(std::memory_order_relaxed);
+    const size_t n = name ? strlen(name) : 0;
+    if (out && cap > n) { if (n) memcpy(out, name, n); out[n] = 0; }
+    return (int)n;
+}
+
+// host only: would create run a [K][N] weight matrix on two terms?  (w16_planes' own answer: the lo plane after the pre-scale)
+int bh_debug_w16_two_terms(const float *W, size_t K, size_t N) try {
+    if (!W || !K || !N || K > (1u << 24) || N > (1u << 24)) return fail(BH_ERR_INVALID, "debug_w16_two_terms: bad arguments");
+    float unscale = 1.0f;
+    bool lo_zero = false;
+    (void)w16_planes(W, (int)K, (int)N, &unscale, &lo_zero);
+    return lo_zero ? 1 : 0;
+} catch (...) { return on_exception(); }
+
 int bh_plan_fused_blocks(const char *model_path, uint32_t flags, int32_t *cfgs, int32_t *layers, size_t cap) try {
     if (!model_path) return fail(BH_ERR_INVALID, "plan_fused_blocks: null model path");
     bh::Model m;
@@ -1743,16 +1826,27 @@ int bh_classifier_frontend_kernel(const bh_classifier *c, char *out, size_t cap)
     return n;
 }
 
+// what the last bh_debug_gated_gemm launched (its signature is the debug header's and carries no name buffer)
+static std::atomic<const char *> g_last_gated_kernel{nullptr};
+int bh_debug_last_gated_kernel(char *out, size_t cap) {
+    const char *name = g_last_gated_kernel.load(std::memory_order_relaxed);
+    const size_t n = name ? strlen(name) : 0;
+    if (out && cap > n) { if (n) memcpy(out, name, n); out[n] = 0; }
+    return (int)n;
+}
+
 // The gated project GEMM of a squeeze-excite block on operands of the caller's (tests: any shape, both layouts of D, every kernel
 // behind launch_pw_gemm16_gated, without a model around it): C = (A x gate[row / rows_per_seg]) W + bias (+ R).
 int bh_debug_gated_gemm(int device, const float *A, const float *gate, const float *W, const float *bias, const float *R, float *C,
                         size_t M, size_t K, size_t N, size_t rows_per_seg, int terms, int blocked) try {
-    if (!A || !gate || !W || !bias || !C || !M || !K || !N || !rows_per_seg || M % rows_per_seg || K % 4 || (terms != 1 && terms != 3))
+    if (!A || !gate || !W || !bias || !C || !M || !K || !N || !rows_per_seg || M % rows_per_seg || K % 4 || (terms != 1 && terms != 2 && terms != 3))
         return fail(BH_ERR_INVALID, "debug_gated_gemm: bad arguments");
     if (blocked && (K % 16 || M % 16)) return fail(BH_ERR_INVALID, "debug_gated_gemm: blocked rows need K % 16 == 0 and M % 16 == 0");
     HIPCHK(hipSetDevice(device));
     float unscale = 1.0f;
-    const std::vector<uint16_t> planes = w16_planes(W, (int)K, (int)N, &unscale);
+    std::vector<uint16_t> planes;
+    if (!debug_planes(W, (int)K, (int)N, terms, &unscale, planes))
+        return fail(BH_ERR_UNSUPPORTED, "debug_gated_gemm: terms 2 needs a W made of f16 values (after the power-of-two pre-scale)");
     std::vector<float> Ab;
     if (blocked) {     // kernels.hpp MbDesc::dblk: [row tile of 16][K / 16][16 rows][16 channels]
         Ab.resize(M * K);
@@ -1767,8 +1861,9 @@ int bh_debug_gated_gemm(int device, const float *A, const float *gate, const flo
     if (!put(dA, blocked ? Ab.data() : A, M * K * 4) || !put(dG, gate, M / rows_per_seg * K * 4) || !put(dW, planes.data(), planes.size() * 2) ||
         !put(dB, bias, N * 4) || (R && !put(dR, R, M * N * 4)) || !put(dC, nullptr, M * N * 4))
         return fail(BH_ERR_HIP, "debug_gated_gemm: device memory");
-    bh::launch_pw_gemm16_gated((const float *)dA.p, (const float *)dG.p, (int)rows_per_seg, dW.p, (const float *)dB.p, (const float *)dR.p,
-                               (float *)dC.p, (int)M, (int)K, (int)N, terms, unscale, blocked, nullptr);
+    g_last_gated_kernel.store(bh::launch_pw_gemm16_gated((const float *)dA.p, (const float *)dG.p, (int)rows_per_seg, dW.p, (const float *)dB.p,
+                                                         (const float *)dR.p, (float *)dC.p, (int)M, (int)K, (int)N, terms, unscale, blocked, nullptr),
+                              std::memory_order_relaxed);
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(C, dC.p, M * N * 4, hipMemcpyDeviceToHost));
     return BH_OK;
@@ -1830,7 +1925,7 @@ int finish_debug_launch(const char *who, const char *name, const Guarded &dC, fl
 // (conv_gemm_rows, w16_planes) -- tests drive every shape, precision and epilogue instantiation without a model around it.
 int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
                        const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap) try {
-    if (!X || !W || !bias || !C || !shape || !n_seg || (terms != 0 && terms != 1 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
+    if (!X || !W || !bias || !C || !shape || !n_seg || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
         return fail(BH_ERR_INVALID, "debug_conv_gemm: bad arguments");
     const bh::ConvParams p{shape[0], shape[1], shape[2], shape[3], shape[4], shape[5], shape[6], shape[7], shape[8], shape[9],
                            shape[10], shape[11], 0, act};
@@ -1848,7 +1943,8 @@ int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *
     const std::vector<float> w = conv_gemm_rows(W, p, ld);
     float unscale = 1.0f;
     std::vector<uint16_t> planes;
-    if (terms) planes = w16_planes(w.data(), (int)K, p.cout, &unscale);
+    if (terms && !debug_planes(w.data(), (int)K, p.cout, terms, &unscale, planes))
+        return fail(BH_ERR_UNSUPPORTED, "debug_conv_gemm: terms 2 needs a W made of f16 values (after the power-of-two pre-scale)");
     Guarded dX, dW, dB, dR, dC;
     if (!dX.put(X, x_floats * 4, kGuardNaN) ||
         !(terms ? dW.put(planes.data(), planes.size() * 2, kGuardNaN) : dW.put(w.data(), w.size() * 4, kGuardNaN)) ||
@@ -1867,7 +1963,7 @@ int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *
 // the caller's, with create's weight preparation (pw_gemm_rows, w16_planes), through the launchers a forward pass calls.
 int bh_debug_layer_gemm(int device, const float *A, const float *W, const float *bias, const float *R, float *C, size_t M, size_t K,
                         size_t N, size_t pool_rows, int act, int terms, char *kernel, size_t kernel_cap) try {
-    if (!A || !W || !bias || !C || !M || !K || !N || (terms != 0 && terms != 1 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
+    if (!A || !W || !bias || !C || !M || !K || !N || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
         return fail(BH_ERR_INVALID, "debug_layer_gemm: bad arguments");
     if (M * K > (size_t)INT32_MAX || M * N > (size_t)INT32_MAX || K * N > (size_t)INT32_MAX)
         return fail(BH_ERR_INVALID, "debug_layer_gemm: operands past 2^31 elements");
@@ -1884,8 +1980,10 @@ int bh_debug_layer_gemm(int device, const float *A, const float *W, const float 
     float unscale = 1.0f;
     std::vector<uint16_t> planes;
     std::vector<float> w;
-    if (terms) planes = w16_planes(W, (int)K, (int)N, &unscale);
-    else w = pw_gemm_rows(W, K, N, ld);
+    if (terms) {
+        if (!debug_planes(W, (int)K, (int)N, terms, &unscale, planes))
+            return fail(BH_ERR_UNSUPPORTED, "debug_layer_gemm: terms 2 needs a W made of f16 values (after the power-of-two pre-scale)");
+    } else w = pw_gemm_rows(W, K, N, ld);
     Guarded dA, dW, dB, dR, dC;
     if (!dA.put(A, M * K * 4, kGuardNaN) ||
         !(terms ? dW.put(planes.data(), planes.size() * 2, kGuardNaN) : dW.put(w.data(), w.size() * 4, kGuardNaN)) ||

@@ -30,6 +30,7 @@
 #include "../../include/birda_hip_audit.h"
 #include "../../include/birda_hip_layer_debug.h"
 #include "../../include/birda_hip_block_debug.h"
+#include "../../include/birda_hip_terms_debug.h"
 #include "kernels.hpp"
 #include "trace.hpp"
 #include "model.hpp"
@@ -75,6 +76,10 @@ struct bh_classifier {
     std::vector<int> ldw;                    // per layer: padded row length of d_w (pw / dense)
     std::vector<void *> d_w16;               // per layer: f16 hi / lo fragment planes (pw / dense outside fused blocks), or null
     std::vector<float> w16_unscale;          // per layer: 2^-s of those planes (they hold W * 2^s, kernels.hpp f16_scale_exponent)
+    std::vector<int> w16_terms;              // per layer: the terms its planes are run with -- 3 (1 under BH_FLAG_F16), or 2 on compact planes
+    std::vector<size_t> w16_bytes;           // per layer: device bytes of those planes
+    bool full_planes = false;                // BH_FLAG_FULL_PLANES: no layer takes two terms
+    std::unique_ptr<std::atomic<const char *>[]> w16_kernel;   // per layer: what its split-f16 launcher launched last (a string literal), or null
     std::vector<char> head_gap;              // per layer: 1 = this 1x1 conv + GELU and the global average pool after it run as one launch
     // per layer: 1 = this pool layer and the two 1x1 layers after it (a squeeze-excite gate of a block that runs layer by layer) run as
     // the two gate launches (launch_se_gate16): the pool layer's tensor holds the hidden partial sums until the gate is written.  Decided

@@ -397,8 +397,10 @@ const char *launch_pw_gemm_gated(const float *A, const float *gate, int rows_per
 // (a_blocked: A in MbDesc::dblk's layout -- every kernel behind this entry reads either; pw_gemm16_gated_wants_blocked: the
 //  shapes whose kernel is the faster for it, a property of the BLOCK, never of the launch)
 bool pw_gemm16_gated_wants_blocked(int K, int N, int rows_per_seg);
-void launch_pw_gemm16_gated(const float *A, const float *gate, int rows_per_seg, const void *Wf, const float *bias, const float *R,
-                            float *C, int M, int K, int N, int terms, float w_unscale, int a_blocked, hipStream_t s);
+// (returns the instantiation it launched, like launch_pw_gemm16: "pw_gemm16_thin_kernel<2,NT=1,SHALLOW=true>",
+//  "pw_gemm16_wide_kernel<3,NT=9,RB=2,PF=4>", "pw_gemm16s_kernel<2,NONE,GATE,NTB=6,BLK=false>")
+const char *launch_pw_gemm16_gated(const float *A, const float *gate, int rows_per_seg, const void *Wf, const float *bias, const float *R,
+                                   float *C, int M, int K, int N, int terms, float w_unscale, int a_blocked, hipStream_t s);
 // ... and the gate itself: pool (from the per-tile channel sums of mbconv pass A, part [n][tiles][C]) -> 1x1 (C -> Cr, act1) -> 1x1
 // (Cr -> C, act2), one launch, fixed summation order
 // the gate beyond 576 channels in two launches of sixteen-segment workgroups (hpart: scratch of n_seg x C floats)

@@ -209,6 +209,13 @@ const char *launch_pw_gemm_gated(const float *A, const float *gate, int rows_per
 // ---------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
+// Two-term products (TERMS == 2): a weight matrix whose every entry IS an f16 value (after the power-of-two pre-scale) has an all-zero
+// lo plane, so of the three products hi hi, hi lo, lo hi the middle one multiplies by zero.  TERMS == 2 runs hi hi, lo hi -- the order
+// the three-term kernel leaves when its middle MFMA is removed: the same sums, element for element -- on COMPACT planes
+// [k step][column tile][64 lanes][8 halves], the layout above without the lo half: half the weight bytes, no zero block fetched or
+// skipped.  BH_PL is the number of planes a (k step, column tile) pair holds in the global layout; TERMS 1 and 3 keep theirs.
+#define BH_PL(T) ((T) == 2 ? 1 : 2)
+
 template <int TERMS, int ACT>
 __global__ __launch_bounds__(256) void pw_gemm16_kernel(const float *__restrict__ A, const f16x8 *__restrict__ Wf,
                                                          const float *__restrict__ bias, const float *__restrict__ R,
@@ -248,7 +255,7 @@ __global__ __launch_bounds__(256) void pw_gemm16_kernel(const float *__restrict_
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int t = min(t0 + j, n_tiles - 1);
-            bh[j] = Wf[(((size_t)st * n_tiles + t) * 2 + 0) * 64 + lane];
+            bh[j] = Wf[(((size_t)st * n_tiles + t) * BH_PL(TERMS) + 0) * 64 + lane];
             if (TERMS == 3) bl[j] = Wf[(((size_t)st * n_tiles + t) * 2 + 1) * 64 + lane];
         }
     };
@@ -265,10 +272,8 @@ __global__ __launch_bounds__(256) void pw_gemm16_kernel(const float *__restrict_
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                if (TERMS == 3) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                }
+                if (TERMS == 3) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                if (TERMS >= 2) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
             }
     };
     load(0, ra0, bh0, bl0);
@@ -334,7 +339,7 @@ __global__ __launch_bounds__(256) void pw_gemm16_skinny_kernel(const float *__re
 #pragma unroll
         for (int j = 0; j < NT; j++) {
             const int t = min(t0 + j, n_tiles - 1);
-            h[j] = Wf[(((size_t)st * n_tiles + t) * 2 + 0) * 64 + lane];
+            h[j] = Wf[(((size_t)st * n_tiles + t) * BH_PL(TERMS) + 0) * 64 + lane];
             if (TERMS == 3) l[j] = Wf[(((size_t)st * n_tiles + t) * 2 + 1) * 64 + lane];
         }
     };
@@ -352,10 +357,8 @@ __global__ __launch_bounds__(256) void pw_gemm16_skinny_kernel(const float *__re
 #pragma unroll
                 for (int j = 0; j < NT; j++) {
                     acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh[u][j], acc[j], 0, 0, 0);
-                    if (TERMS == 3) {
-                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[u][j], acc[j], 0, 0, 0);
-                        acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[u][j], acc[j], 0, 0, 0);
-                    }
+                    if (TERMS == 3) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl[u][j], acc[j], 0, 0, 0);
+                    if (TERMS >= 2) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[u][j], acc[j], 0, 0, 0);
                 }
                 if (st + PF < steps) load(st + PF, ra[u], bh[u], bl[u]);   // (the slot's registers have been read)
             }
@@ -470,7 +473,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm16s_kernel(const float *__restr
             f16x8 h, l;
             bh_split8(v, h, l);
             *reinterpret_cast<f16x8 *>(as + adst[q]) = h;
-            if (TERMS == 3) *reinterpret_cast<f16x8 *>(as + adst[q] + 256) = l;
+            if (TERMS >= 2) *reinterpret_cast<f16x8 *>(as + adst[q] + 256) = l;
         }
     };
     auto dma_b = [&](int st, int buf) {   // 2 NTB (NTB) pieces of 1 KiB: wave w takes column tiles w, w + 4, ...
@@ -480,7 +483,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm16s_kernel(const float *__restr
             if (j >= NTB) continue;     // (wave-uniform)
 #pragma unroll
             for (int pl = 0; pl < (TERMS == 3 ? 2 : 1); pl++) {
-                const f16x8 *src = Wf + (((size_t)st * n_tiles + t) * 2 + pl) * 64;
+                const f16x8 *src = Wf + (((size_t)st * n_tiles + t) * BH_PL(TERMS) + pl) * 64;
                 const unsigned dst = lds0 + 4u * (unsigned)(buf * STAGE + 8 * 2 * 256 + (j * 2 + pl) * 256);
                 asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
                              :: "v"((unsigned)lane * 16u), "s"(src), "s"(dst) : "memory", "m0");
@@ -508,7 +511,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm16s_kernel(const float *__restr
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             ah[i] = *reinterpret_cast<const f16x8 *>(as + (((wm * 4 + i) * 2) * 64 + lane) * 4);
-            if (TERMS == 3) al[i] = *reinterpret_cast<const f16x8 *>(as + (((wm * 4 + i) * 2 + 1) * 64 + lane) * 4);
+            if (TERMS >= 2) al[i] = *reinterpret_cast<const f16x8 *>(as + (((wm * 4 + i) * 2 + 1) * 64 + lane) * 4);
         }
 #pragma unroll
         for (int j = 0; j < NJ; j++) {
@@ -520,10 +523,8 @@ __global__ __launch_bounds__(256, 2) void pw_gemm16s_kernel(const float *__restr
 #pragma unroll
             for (int j = 0; j < NJ; j++) {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                if (TERMS == 3) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                }
+                if (TERMS == 3) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                if (TERMS >= 2) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
             }
         if (more) store_a(cur ^ 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(512, SHALLOW ? 4 : 2) void pw_gemm16_thin_kernel(co
     {   // all of W, once per workgroup
         const float4 *src = reinterpret_cast<const float4 *>(Wf);
         float4 *dst = reinterpret_cast<float4 *>(tsm);
-        const int n4 = steps * NT * 2 * 64;            // float4s: [step][tile]{hi, lo}[64 lanes] x 16 B (8 halves)
+        const int n4 = steps * NT * BH_PL(TERMS) * 64;  // float4s: [step][tile]{hi, lo}[64 lanes] x 16 B (8 halves); TERMS == 2: hi alone
         for (int i = tid; i < n4; i += 512) dst[i] = src[i];
     }
     __syncthreads();
@@ -633,16 +634,14 @@ __global__ __launch_bounds__(512, SHALLOW ? 4 : 2) void pw_gemm16_thin_kernel(co
             }
 #pragma unroll
             for (int j = 0; j < NT; j++) {
-                const f16x8 bh = wf[((st * NT + j) * 2 + 0) * 64 + lane];
+                const f16x8 bh = wf[((st * NT + j) * BH_PL(TERMS) + 0) * 64 + lane];
                 f16x8 bl;
                 if (TERMS == 3) bl = wf[((st * NT + j) * 2 + 1) * 64 + lane];
 #pragma unroll
                 for (int r = 0; r < RB; r++) {
                     acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], bh, acc[r][j], 0, 0, 0);
-                    if (TERMS == 3) {
-                        acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], bl, acc[r][j], 0, 0, 0);
-                        acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[r], bh, acc[r][j], 0, 0, 0);
-                    }
+                    if (TERMS == 3) acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], bl, acc[r][j], 0, 0, 0);
+                    if (TERMS >= 2) acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[r], bh, acc[r][j], 0, 0, 0);
                 }
             }
         }
@@ -659,7 +658,7 @@ __global__ __launch_bounds__(512, SHALLOW ? 4 : 2) void pw_gemm16_thin_kernel(co
             if (t == 12345.678f) C[0] = t;
             continue;
         }
-        float *ep = tsm + (size_t)steps * NT * 2 * 256 + (size_t)wave * (RB * 16 * NT * 16);
+        float *ep = tsm + (size_t)steps * NT * BH_PL(TERMS) * 256 + (size_t)wave * (RB * 16 * NT * 16);
 #pragma unroll
         for (int r = 0; r < RB; r++)
 #pragma unroll
@@ -717,8 +716,9 @@ __global__ __launch_bounds__(512, 1) void pw_gemm16_wide_kernel(const float *__r
     // LDS: PF W step buffers [NT]{hi, lo}[64][8 halves] | the gate rows of the pass's segments [gs_max][32 steps], zero beyond K;
     // the epilogue's per-wave tiles [16][N] lie over both
     extern __shared__ __attribute__((aligned(16))) float wsm[];
-    constexpr int STEP_FL = NT * 2 * 256;                         // floats per W step buffer
-    constexpr int PIECES = (NT * 2 + 7) / 8;                      // 1-KiB pieces per wave and step
+    constexpr int PL = BH_PL(TERMS);
+    constexpr int STEP_FL = NT * PL * 256;                        // floats per W step buffer
+    constexpr int PIECES = (NT * PL + 7) / 8;                     // 1-KiB pieces per wave and step
     constexpr int ND = RB * 2;                                    // row loads per lane and step
     constexpr int INFLIGHT = ND + (PF - 2) * (PIECES + ND);       // what may stay in flight at the top of a step (see above)
     static_assert(PF >= 2 && PF <= 4 && INFLIGHT <= 63, "prefetch depth");
@@ -735,8 +735,8 @@ __global__ __launch_bounds__(512, 1) void pw_gemm16_wide_kernel(const float *__r
         const int buf = st % PF;
 #pragma unroll
         for (int i = 0; i < PIECES; i++) {
-            const int p = min(ws + 8 * i, NT * 2 - 1);
-            const f16x8 *src = Wf + ((size_t)st * NT * 2 + p) * 64;
+            const int p = min(ws + 8 * i, NT * PL - 1);
+            const f16x8 *src = Wf + ((size_t)st * NT * PL + p) * 64;
             const unsigned dst = lds0 + 4u * (unsigned)(buf * STEP_FL + p * 256);
             asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
                          :: "v"((unsigned)lane * 16u), "s"(src), "s"(dst) : "memory", "m0");
@@ -822,7 +822,7 @@ __global__ __launch_bounds__(512, 1) void pw_gemm16_wide_kernel(const float *__r
             for (int j = 0; j < NT; j++) {
                 f16x8 nh = bh, nl = bl;
                 if (j + 1 < NT) {
-                    nh = wf[((j + 1) * 2 + 0) * 64 + lane];
+                    nh = wf[((j + 1) * PL + 0) * 64 + lane];
                     if (TERMS == 3) nl = wf[((j + 1) * 2 + 1) * 64 + lane];
                 }
 #pragma unroll
@@ -830,6 +830,8 @@ __global__ __launch_bounds__(512, 1) void pw_gemm16_wide_kernel(const float *__r
                 if (TERMS == 3) {
 #pragma unroll
                     for (int r = 0; r < RB; r++) acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[r], bl, acc[r][j], 0, 0, 0);
+                }
+                if (TERMS >= 2) {
 #pragma unroll
                     for (int r = 0; r < RB; r++) acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[r], bh, acc[r][j], 0, 0, 0);
                 }
@@ -928,14 +930,16 @@ bool pw_gemm16_gated_wants_blocked(int K, int N, int rows_per_seg) {
     return K % 16 == 0 && rows_per_seg % 16 == 0 && N % 4 == 0 && n_tiles >= 6 && n_tiles <= 15;
 }
 
-void launch_pw_gemm16_gated(const float *A, const float *gate, int rows_per_seg, const void *Wf, const float *bias, const float *R,
-                            float *C, int M, int K, int N, int terms, float w_unscale, int a_blocked, hipStream_t s) {
+const char *launch_pw_gemm16_gated(const float *A, const float *gate, int rows_per_seg, const void *Wf, const float *bias, const float *R,
+                                   float *C, int M, int K, int N, int terms, float w_unscale, int a_blocked, hipStream_t s) {
+    const char *name = nullptr;
     const int n_tiles = (N + 15) / 16;
     // few columns, all of W in LDS (<= 64 KB), many rows: the streaming kernel above
+    // (the kernel is chosen by the full planes' size whatever the terms: a layer takes the same kernel family on two terms as on three)
     const size_t w_bytes = (size_t)((K + 31) / 32) * n_tiles * 2 * 1024;
     if (n_tiles <= 3 && w_bytes <= 64 * 1024 && M >= 4096 && N % 4 == 0 && !a_blocked) {      // (blocked rows: N >= 64 only, pw_gemm16_gated_wants_blocked)
         const bool shallow = K <= 32;
-        const size_t thin_lds = w_bytes + (size_t)8 * (shallow ? (n_tiles <= 2 ? 3 : 2) : (n_tiles <= 2 ? 4 : 3)) * 16 * n_tiles * 16 * sizeof(float);   // + the waves' epilogue tiles
+        const size_t thin_lds = w_bytes / 2 * BH_PL(terms) + (size_t)8 * (shallow ? (n_tiles <= 2 ? 3 : 2) : (n_tiles <= 2 ? 4 : 3)) * 16 * n_tiles * 16 * sizeof(float);   // + the waves' epilogue tiles
         const int n_rt = (M + 15) / 16;
         const int wgs = std::min((n_rt + 31) / 32, 2 * device_cu_count());   // 8-wave workgroups walking the row tiles, 2-4 per wave and pass (one or two resident per CU)
 #define BH_THIN(T, NTV, SH)                                                                                                        \
@@ -943,13 +947,15 @@ void launch_pw_gemm16_gated(const float *A, const float *gate, int rows_per_seg,
             static DeviceOnce attr;                                                                                                \
             attr.run([] { (void)hipFuncSetAttribute((const void *)pw_gemm16_thin_kernel<T, NTV, SH>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); }); \
             hipLaunchKernelGGL((pw_gemm16_thin_kernel<T, NTV, SH>), dim3(wgs), dim3(512), thin_lds, s, A, gate, rows_per_seg, (const f16x8 *)Wf, bias, R, C, M, K, N, w_unscale); \
+            name = "pw_gemm16_thin_kernel<" #T ",NT=" #NTV ",SHALLOW=" #SH ">";                                                   \
         } while (0)
 #define BH_THIN_S(T, NTV) do { if (shallow) BH_THIN(T, NTV, true); else BH_THIN(T, NTV, false); } while (0)
         if (terms == 3) { if (n_tiles == 1) BH_THIN_S(3, 1); else if (n_tiles == 2) BH_THIN_S(3, 2); else BH_THIN_S(3, 3); }
+        else if (terms == 2) { if (n_tiles == 1) BH_THIN_S(2, 1); else if (n_tiles == 2) BH_THIN_S(2, 2); else BH_THIN_S(2, 3); }
         else { if (n_tiles == 1) BH_THIN_S(1, 1); else if (n_tiles == 2) BH_THIN_S(1, 2); else BH_THIN_S(1, 3); }
 #undef BH_THIN_S
 #undef BH_THIN
-        return;
+        return name;
     }
     // N = 64 .. 240 with many rows: the row-streaming kernel with one workgroup per CU, rows and W pieces several steps ahead
     // (N > 144: two row tiles a wave, 256 rows a pass, and a pass lasts ~125 us however few there are -- below ~40 000 rows, fewer
@@ -961,21 +967,21 @@ void launch_pw_gemm16_gated(const float *A, const float *gate, int rows_per_seg,
 #define BH_WIDE(T, NTV, RBV, PFV)                                                                                                  \
         do {                                                                                                                       \
             const int gs_max = (8 * RBV * 16 + rows_per_seg - 2) / rows_per_seg + 1;                                              \
-            const size_t lds = std::max((size_t)PFV * NTV * 2048 + (size_t)gs_max * ((K + 31) / 32 * 32) * sizeof(float),         \
+            const size_t lds = std::max((size_t)PFV * NTV * BH_PL(T) * 1024 + (size_t)gs_max * ((K + 31) / 32 * 32) * sizeof(float),         \
                                         (size_t)8 * 16 * NTV * 16 * sizeof(float));                                              \
             if (lds > 160 * 1024) break;     /* (very many segments a pass: the staged kernel below) */                           \
             const int wgs = std::min((n_rt + 8 * RBV - 1) / (8 * RBV), device_cu_count());                                       \
             static DeviceOnce attr;                                                                                                \
             attr.run([] { (void)hipFuncSetAttribute((const void *)pw_gemm16_wide_kernel<T, NTV, RBV, PFV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
             hipLaunchKernelGGL((pw_gemm16_wide_kernel<T, NTV, RBV, PFV>), dim3(wgs), dim3(512), lds, s, A, gate, rows_per_seg, (const f16x8 *)Wf, bias, R, C, M, K, N, w_unscale, gs_max, a_blocked); \
-            return;                                                                                                                \
+            return "pw_gemm16_wide_kernel<" #T ",NT=" #NTV ",RB=" #RBV ",PF=" #PFV ">";                                          \
         } while (0)
 #define BH_WIDE_T(T)                                                                             \
         switch (n_tiles) {                                                                      \
         case 4: BH_WIDE(T, 4, 3, 3); break; case 5: BH_WIDE(T, 5, 3, 3); break; case 6: BH_WIDE(T, 6, 3, 3); break; case 7: BH_WIDE(T, 7, 3, 3); break; case 8: BH_WIDE(T, 8, 2, 4); break; case 9: BH_WIDE(T, 9, 2, 4); break;  \
         case 10: BH_WIDE(T, 10, 2, 3); break; case 11: BH_WIDE(T, 11, 2, 3); break; case 12: BH_WIDE(T, 12, 2, 3); break; case 13: BH_WIDE(T, 13, 2, 3); break; \
         case 14: BH_WIDE(T, 14, 2, 3); break; default: BH_WIDE(T, 15, 2, 3); break; }
-        if (terms == 3) { BH_WIDE_T(3) } else { BH_WIDE_T(1) }
+        if (terms == 3) { BH_WIDE_T(3) } else if (terms == 2) { BH_WIDE_T(2) } else { BH_WIDE_T(1) }
 #undef BH_WIDE_T
 #undef BH_WIDE
     }
@@ -996,12 +1002,15 @@ void launch_pw_gemm16_gated(const float *A, const float *gate, int rows_per_seg,
         static DeviceOnce attr;                                                                                                   \
         attr.run([] { (void)hipFuncSetAttribute((const void *)pw_gemm16s_kernel<T, ACT_NONE, true, NTBV, BLKV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }); \
         hipLaunchKernelGGL((pw_gemm16s_kernel<T, ACT_NONE, true, NTBV, BLKV>), grid, block, lds, s, A, (const f16x8 *)Wf, bias, R, C, M, K, N, n_tiles, w_unscale, gate, rows_per_seg); \
+        name = "pw_gemm16s_kernel<" #T ",NONE,GATE,NTB=" #NTBV ",BLK=" #BLKV ">";                                                 \
     } while (0)
 #define BH_GS_B(T, NTBV) do { if (a_blocked) BH_GS(T, NTBV, true); else BH_GS(T, NTBV, false); } while (0)
     if (terms == 3) { if (ntb == 6) BH_GS_B(3, 6); else if (ntb == 10) BH_GS_B(3, 10); else BH_GS_B(3, 8); }
+    else if (terms == 2) { if (ntb == 6) BH_GS_B(2, 6); else if (ntb == 10) BH_GS_B(2, 10); else BH_GS_B(2, 8); }
     else { if (ntb == 6) BH_GS_B(1, 6); else if (ntb == 10) BH_GS_B(1, 10); else BH_GS_B(1, 8); }
 #undef BH_GS_B
 #undef BH_GS
+    return name;
 }
 
 const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, const float *R, float *C, int M, int K, int N,
@@ -1048,7 +1057,7 @@ const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, 
     case ACT_RELU6: BH_G16(T, ACT_RELU6, "RELU6"); break;            \
     default: BH_G16(T, ACT_NONE, "NONE"); break;                     \
     }
-    if (terms == 3) { BH_G16A(3) } else { BH_G16A(1) }
+    if (terms == 3) { BH_G16A(3) } else if (terms == 2) { BH_G16A(2) } else { BH_G16A(1) }
 #undef BH_G16A
 #undef BH_G16
 #undef BH_G16S
@@ -1079,7 +1088,8 @@ __global__ __launch_bounds__(256, 1) void head_gap16_kernel(const float *__restr
                                                              const float *__restrict__ bias, float *__restrict__ out,
                                                              int n_seg, int P, int K, int N, int n_tiles, int n_cb, float w_unscale) {
     constexpr int RT = PT * SW;
-    __shared__ __attribute__((aligned(16))) f16x8 Bs[2][CT * 2 * 64];
+    constexpr int PL = BH_PL(TERMS);
+    __shared__ __attribute__((aligned(16))) f16x8 Bs[2][CT * PL * 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
     const int xcd = blockIdx.x & 7, bi = blockIdx.x >> 3;
@@ -1090,11 +1100,11 @@ __global__ __launch_bounds__(256, 1) void head_gap16_kernel(const float *__restr
 
     // B slice of step st -> Bs[buf]: 16 pieces of 1 KiB, four per wave (M0 = LDS address of the piece)
     auto dma = [&](int st, int buf) {
-        const f16x8 *src = Wf + ((size_t)st * n_tiles + cb * CT) * 2 * 64;
+        const f16x8 *src = Wf + ((size_t)st * n_tiles + cb * CT) * PL * 64;
 #pragma unroll
-        for (int q = 0; q < (CT * 2 + 3) / 4; q++) {
+        for (int q = 0; q < (CT * PL + 3) / 4; q++) {
             const int piece = q * 4 + wave;
-            if (piece >= CT * 2) continue;     // (CT = 2: one piece a wave)
+            if (piece >= CT * PL) continue;    // (CT = 2: one piece a wave; with compact planes two of the four waves)
             const unsigned la = (unsigned)(size_t)(&Bs[buf][piece * 64]);
             asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
                          :: "v"(src + piece * 64 + lane), "s"(__builtin_amdgcn_readfirstlane(la)) : "memory", "m0");
@@ -1133,16 +1143,14 @@ __global__ __launch_bounds__(256, 1) void head_gap16_kernel(const float *__restr
     auto compute = [&](int buf) {
 #pragma unroll
         for (int j = 0; j < CT; j++) {
-            const f16x8 bh = Bs[buf][(j * 2 + 0) * 64 + lane];
+            const f16x8 bh = Bs[buf][(j * PL + 0) * 64 + lane];
             f16x8 bl;
             if (TERMS == 3) bl = Bs[buf][(j * 2 + 1) * 64 + lane];
 #pragma unroll
             for (int i = 0; i < RT; i++) {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh, acc[i][j], 0, 0, 0);
-                if (TERMS == 3) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh, acc[i][j], 0, 0, 0);
-                }
+                if (TERMS == 3) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl, acc[i][j], 0, 0, 0);
+                if (TERMS >= 2) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh, acc[i][j], 0, 0, 0);
             }
         }
     };
@@ -1214,8 +1222,8 @@ const char *launch_head_gap16(const float *A, const void *Wf, const float *bias,
     case ACT_RELU6: BH_HG(PTV, SWV, T, ACT_RELU6, "RELU6"); break;   \
     default: BH_HG(PTV, SWV, T, ACT_GELU_ERF, "GELU"); break;        \
     }
-    if (pt <= 3) { if (terms == 3) { BH_HGA(3, 2, 3) } else { BH_HGA(3, 2, 1) } }
-    else { if (terms == 3) { BH_HGA(5, 1, 3) } else { BH_HGA(5, 1, 1) } }
+    if (pt <= 3) { if (terms == 3) { BH_HGA(3, 2, 3) } else if (terms == 2) { BH_HGA(3, 2, 2) } else { BH_HGA(3, 2, 1) } }
+    else { if (terms == 3) { BH_HGA(5, 1, 3) } else if (terms == 2) { BH_HGA(5, 1, 2) } else { BH_HGA(5, 1, 1) } }
 #undef BH_HGA
 #undef BH_HG
     return name;
@@ -1529,7 +1537,7 @@ __global__ __launch_bounds__(256) void conv_gemm16_kernel(const float *__restric
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int t = min(t0 + j, n_tiles - 1);
-            bh[j] = Wf[(((size_t)st * n_tiles + t) * 2 + 0) * 64 + lane];
+            bh[j] = Wf[(((size_t)st * n_tiles + t) * BH_PL(TERMS) + 0) * 64 + lane];
             if (TERMS == 3) bl[j] = Wf[(((size_t)st * n_tiles + t) * 2 + 1) * 64 + lane];
         }
     };
@@ -1546,10 +1554,8 @@ __global__ __launch_bounds__(256) void conv_gemm16_kernel(const float *__restric
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-                if (TERMS == 3) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
-                }
+                if (TERMS == 3) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+                if (TERMS >= 2) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[i], bh[j], acc[i][j], 0, 0, 0);
             }
     };
     load(0, ra0, bh0, bl0);
@@ -1634,7 +1640,7 @@ const char *launch_conv_gemm16(const float *X, const void *Wf, const float *bias
     case ACT_RELU6: BH_CG16(T, ACT_RELU6, "RELU6"); break;           \
     default: BH_CG16(T, ACT_NONE, "NONE"); break;                    \
     }
-    if (terms == 3) { BH_CG16A(3) } else { BH_CG16A(1) }
+    if (terms == 3) { BH_CG16A(3) } else if (terms == 2) { BH_CG16A(2) } else { BH_CG16A(1) }
 #undef BH_CG16A
 #undef BH_CG16
     return name;

@@ -41,6 +41,7 @@ struct Model {
     std::vector<LayerRec> layers;
     std::vector<float> blob;
     std::vector<uint64_t> tensor_floats;  // per-segment floats of tensor i (0 = spectrogram)
+    bool file_f16 = false;                // the file's convolution / dense weights were float16 tensors (an .onnx file; not in the container)
 
     uint64_t macs_per_segment() const {
         uint64_t t = 0;

@@ -21,6 +21,13 @@
 //     the whole published front-end ([EXT] SURVEY.md Appendix B) for a graph that STARTS at the spectrogram, where there is
 //     nothing to read.
 //
+// FLOAT16 FILES (the `fp16` variant the reference's installer picks for a GPU provider): a float16 constant is the exact real
+// number it encodes, Cast between floating types is the identity, and the graph is evaluated in the library's own (f32-grade)
+// arithmetic -- at least as exact as a float16 runtime, without its intermediate rounding or its overflow at 65 504.  Weights,
+// biases, BatchNormalization parameters, Gemm / MatMul operands and the activation spellings' scalars are read through ONE
+// accessor (`finit`: float32 or float16); a graph input / output of element type float16 is refused by name (the C ABI feeds and
+// returns f32).
+//
 // Hand-written protobuf wire-format walk on onnx_dense.hpp's Reader (no protobuf / onnx dependency).  Untrusted input: every
 // length is checked against the buffer, every dimension product against the tensor's payload, and the finished model goes
 // through the same validation as a BHM1 file (model.hpp validate_model); fuzzed under ASan with the other loaders
@@ -121,20 +128,35 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         if (!g.init.count(vi.name)) { if (gin) return fail("the graph has more than one data input"); gin = &vi; }
     if (!gin) return fail("the graph has no data input");
     if (g.outputs.empty()) return fail("the graph has no output");
+    // the C ABI feeds float32 audio and returns float32 scores: a float16 graph input would mean rounding the audio to 11 bits,
+    // which is not done silently (the published float16 files keep float32 at both ends, behind / in front of a Cast)
+    if (gin->elem_type == 10) return fail("graph input '" + gin->name + "' is float16: only float32 inputs are fed (a float16 file keeps its float32 input in front of a Cast)");
+    for (const auto &vo : g.outputs)
+        if (vo.elem_type == 10) return fail("graph output '" + vo.name + "' is float16: only float32 outputs are returned (a float16 file casts its outputs back to float32)");
+    // the node list the conv-stack walk reads: the graph's, with the tensor names behind floating-point Casts replaced by the
+    // Cast's input (below, once the front-end's nodes are known); `outputs` likewise.  Indices are the graph's own.
+    std::vector<Node> nodes = g.nodes;
+    std::vector<std::string> outputs;
+    for (const auto &vo : g.outputs) outputs.push_back(vo.name);
     std::map<std::string, size_t> prod;
-    for (size_t i = 0; i < g.nodes.size(); i++)
-        for (const auto &o : g.nodes[i].out) prod[o] = i;
+    for (size_t i = 0; i < nodes.size(); i++)
+        for (const auto &o : nodes[i].out) prod[o] = i;
     std::map<std::string, std::vector<size_t>> cons;
-    for (size_t i = 0; i < g.nodes.size(); i++)
-        for (const auto &x : g.nodes[i].in) cons[x].push_back(i);
-    auto f32init = [&](const std::string &name) -> const Tensor * {
+    // "a float initializer": float32 or float16 (read as the exact value it encodes).  `role` names the operand in the refusal of
+    // an element type that is present but not read (bfloat16, float64, int8, ...).
+    std::string init_refusal;
+    auto type_name = [](int64_t t) { return t == 16 ? std::string("bfloat16") : t == 11 ? std::string("float64") : t == 3 ? std::string("int8") : t == 2 ? std::string("uint8") : "element type " + std::to_string(t); };
+    auto finit = [&](const std::string &name) -> const Tensor * {
         auto it = g.init.find(name);
-        return it != g.init.end() && it->second.is_f32() ? &it->second : nullptr;
+        if (it == g.init.end()) return nullptr;
+        if (!it->second.is_float()) { init_refusal = " ('" + name + "' is " + type_name(it->second.dtype) + ": not supported)"; return nullptr; }
+        return &it->second;
     };
-    auto scalar = [&](const std::string &name, float &out) {
-        const Tensor *t = f32init(name);
+    auto scalar = [&](const std::string &name, float &out, bool *from_f16 = nullptr) {
+        const Tensor *t = finit(name);
         if (!t || t->count != 1) return false;
         out = t->at(0);
+        if (from_f16) *from_f16 = t->is_f16();
         return true;
     };
 
@@ -177,11 +199,41 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             auto it = prod.find(t);
             if (it == prod.end() || front.count(it->second)) continue;
             front.insert(it->second);
-            for (const auto &x : g.nodes[it->second].in) stack.push_back(x);
+            for (const auto &x : nodes[it->second].in) stack.push_back(x);
         }
     }
 
+    // ---- Cast between floating types is the identity: behind the front-end every such node is taken out of the walk and its
+    // output renamed to its input everywhere (consumers, graph outputs), so the sole-consumer and pattern logic below sees
+    // through it (a Cast between a Conv and its Sigmoid * x does not break the swish fold).  Any other target is refused by name.
+    std::set<size_t> skip;
+    {
+        std::map<std::string, std::string> alias;
+        auto resolve = [&](const std::string &x) { auto it = alias.find(x); return it == alias.end() ? x : it->second; };
+        for (size_t i = 0; i < nodes.size(); i++) {
+            if (front.count(i)) continue;
+            Node &n = nodes[i];
+            for (auto &x : n.in) x = resolve(x);
+            if (n.op != "Cast") continue;
+            if (n.in.empty() || n.out.empty()) return fail("node '" + n.name + "' (Cast) without inputs or outputs");
+            const int64_t to = n.geti("to", 0);
+            if (to != 1 && to != 10 && to != 11)
+                return fail("Cast '" + n.name + "' to " + type_name(to) + " (to = " + std::to_string(to) + "): only casts between float32, float16 and float64 are read, as the identity");
+            alias[n.out[0]] = n.in[0];           // (already resolved: chains of Casts collapse)
+            skip.insert(i);
+        }
+        for (auto &o : outputs) o = resolve(o);
+    }
+    for (size_t i = 0; i < nodes.size(); i++)
+        if (!skip.count(i))
+            for (const auto &x : nodes[i].in) cons[x].push_back(i);
+
     m = Model{};
+    for (const Node &n : nodes)
+        if ((n.op == "Conv" || n.op == "Gemm" || n.op == "MatMul") && n.in.size() > 1) {
+            auto it = g.init.find(n.in[1]);
+            if (it != g.init.end() && it->second.is_f16()) m.file_f16 = true;
+        }
     memcpy(m.h.magic, "BHM1", 4);
     m.h.version = 1;
     m.h.sample_rate = fam->sample_rate; m.h.sample_count = fam->sample_count; m.h.segment_duration = fam->segment_duration;
@@ -217,51 +269,56 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     }
 
     // ---- multi-node activation spellings (convert.py _collapse_activations) ----
-    std::set<size_t> skip;
     std::map<std::string, std::vector<std::pair<std::string, uint32_t>>> first_of_pattern;   // pattern input -> (pattern output, act)
     auto sole_consumer = [&](const std::string &name, const char *op, size_t &k) {
         auto it = cons.find(name);
-        if (it == cons.end() || it->second.size() != 1 || g.nodes[it->second[0]].op != op) return false;
+        if (it == cons.end() || it->second.size() != 1 || nodes[it->second[0]].op != op) return false;
         k = it->second[0];
         return true;
     };
+    // From a float32 tensor the constant is held to sqrt 2 at 1e-4.  From a float16 tensor it must BE the float16 rounding of the
+    // expected value (sqrt 2 -> 1.4140625, 1 / sqrt 2 -> 0.70703125; no wider window), and the exact GELU runs: DESIGN section 5.
     const double SQRT2 = 1.4142135623730951;
-    for (size_t i = 0; i < g.nodes.size(); i++) {
-        const Node &n = g.nodes[i];
+    const float SQRT2_F16 = 1.4140625f, RSQRT2_F16 = 0.70703125f;
+    for (size_t i = 0; i < nodes.size(); i++) {
+        const Node &n = nodes[i];
         if (n.op == "Erf" && !n.in.empty() && !n.out.empty()) {
             auto pj = prod.find(n.in[0]);
             if (pj == prod.end()) continue;
             const size_t j = pj->second;
-            const Node &pre = g.nodes[j];
+            const Node &pre = nodes[j];
             if ((pre.op != "Div" && pre.op != "Mul") || pre.in.size() != 2) continue;
             std::string x;
             for (int side = 0; side < 2; side++) {
                 float c;
-                if (!scalar(pre.in[side ? 0 : 1], c)) continue;
-                if ((pre.op == "Div" && side == 0 && std::fabs((double)c - SQRT2) < 1e-4) || (pre.op == "Mul" && std::fabs((double)c - 1.0 / SQRT2) < 1e-4))
+                bool c16 = false;
+                if (!scalar(pre.in[side ? 0 : 1], c, &c16)) continue;
+                const bool is_sqrt2 = c16 ? c == SQRT2_F16 : std::fabs((double)c - SQRT2) < 1e-4;
+                const bool is_rsqrt2 = c16 ? c == RSQRT2_F16 : std::fabs((double)c - 1.0 / SQRT2) < 1e-4;
+                if ((pre.op == "Div" && side == 0 && is_sqrt2) || (pre.op == "Mul" && is_rsqrt2))
                     x = pre.in[side ? 1 : 0];
             }
             size_t k, m1, m2;
             if (x.empty() || !sole_consumer(n.out[0], "Add", k)) continue;
             bool one = false;
-            for (const auto &a : g.nodes[k].in) { float c; if (scalar(a, c) && std::fabs(c - 1.0f) < 1e-6f) one = true; }
-            if (!one || g.nodes[k].out.empty() || !sole_consumer(g.nodes[k].out[0], "Mul", m1) || g.nodes[m1].out.empty() ||
-                !sole_consumer(g.nodes[m1].out[0], "Mul", m2) || g.nodes[m2].out.empty()) continue;
+            for (const auto &a : nodes[k].in) { float c; if (scalar(a, c) && std::fabs(c - 1.0f) < 1e-6f) one = true; }
+            if (!one || nodes[k].out.empty() || !sole_consumer(nodes[k].out[0], "Mul", m1) || nodes[m1].out.empty() ||
+                !sole_consumer(nodes[m1].out[0], "Mul", m2) || nodes[m2].out.empty()) continue;
             bool has_x = false, has_half = false;
-            for (const auto &a : g.nodes[m1].in) if (a != g.nodes[k].out[0]) { float c; if (a == x) has_x = true; if (scalar(a, c) && std::fabs(c - 0.5f) < 1e-6f) has_half = true; }
-            for (const auto &a : g.nodes[m2].in) if (a != g.nodes[m1].out[0]) { float c; if (a == x) has_x = true; if (scalar(a, c) && std::fabs(c - 0.5f) < 1e-6f) has_half = true; }
+            for (const auto &a : nodes[m1].in) if (a != nodes[k].out[0]) { float c; if (a == x) has_x = true; if (scalar(a, c) && std::fabs(c - 0.5f) < 1e-6f) has_half = true; }
+            for (const auto &a : nodes[m2].in) if (a != nodes[m1].out[0]) { float c; if (a == x) has_x = true; if (scalar(a, c) && std::fabs(c - 0.5f) < 1e-6f) has_half = true; }
             if (has_x && has_half) {
                 skip.insert({j, i, k, m1, m2});
-                first_of_pattern[x].push_back({g.nodes[m2].out[0], A_GELU_ERF});
+                first_of_pattern[x].push_back({nodes[m2].out[0], A_GELU_ERF});
             }
         } else if (n.op == "Sigmoid" && !n.in.empty() && !n.out.empty()) {
             size_t k;
             if (sole_consumer(n.out[0], "Mul", k)) {
                 bool takes_x = false;
-                for (const auto &a : g.nodes[k].in) if (a == n.in[0]) takes_x = true;
-                if (takes_x && !g.nodes[k].out.empty()) {
+                for (const auto &a : nodes[k].in) if (a == n.in[0]) takes_x = true;
+                if (takes_x && !nodes[k].out.empty()) {
                     skip.insert({i, k});
-                    first_of_pattern[n.in[0]].push_back({g.nodes[k].out[0], A_SWISH});
+                    first_of_pattern[n.in[0]].push_back({nodes[k].out[0], A_SWISH});
                 }
             }
         }
@@ -274,7 +331,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     std::vector<LayerRec> &layers = m.layers;
     uint32_t out_act = O_NONE, emb_tensor = 0, emb_dim = 0;
     std::set<std::string> graph_out;
-    for (const auto &o : g.outputs) graph_out.insert(o.name);
+    for (const auto &o : outputs) graph_out.insert(o);
     auto find = [&](const std::string &name, T &t) { auto it = tmap.find(name); if (it == tmap.end()) return false; t = it->second; return true; };
     auto set_act = [&](const std::string &name_in, const std::string &name_out, uint32_t act) {
         T t;
@@ -304,22 +361,23 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     };
     constexpr int64_t DIM_MAX = 1 << 16;
     std::vector<float> tmp, tmpb;
-    for (size_t i = 0; i < g.nodes.size(); i++) {
+    for (size_t i = 0; i < nodes.size(); i++) {
         if (skip.count(i) || front.count(i)) continue;
-        const Node &n = g.nodes[i];
+        const Node &n = nodes[i];
         const std::string &op = n.op;
         if (n.out.empty() || n.in.empty()) return fail("node '" + n.name + "' (" + op + ") without inputs or outputs");
         if (layers.size() > 4000) return fail("more than 4 000 layers");
         if (op == "Conv") {
             T x;
             if (!find(n.in[0], x)) return fail("Conv '" + n.name + "': input '" + n.in[0] + "' is not on the path from '" + spec + "'");
-            const Tensor *W = n.in.size() > 1 ? f32init(n.in[1]) : nullptr;
-            if (!W || W->dims.size() != 4) return fail("Conv '" + n.name + "': weights must be a 4-d float32 initializer");
+            init_refusal.clear();
+            const Tensor *W = n.in.size() > 1 ? finit(n.in[1]) : nullptr;
+            if (!W || W->dims.size() != 4) return fail("Conv '" + n.name + "': weights must be a 4-d float32 or float16 initializer" + init_refusal);
             const int64_t cout = W->dims[0], cin_g = W->dims[1], kh = W->dims[2], kw = W->dims[3], group = n.geti("group", 1);
             if (cout <= 0 || cin_g <= 0 || kh <= 0 || kw <= 0 || group <= 0 || cout > DIM_MAX || cin_g > DIM_MAX || kh > 64 || kw > 64 || group > DIM_MAX)
                 return fail("Conv '" + n.name + "': bad weight shape");
-            const Tensor *B = n.in.size() > 2 && !n.in[2].empty() ? f32init(n.in[2]) : nullptr;
-            if (n.in.size() > 2 && !n.in[2].empty() && (!B || B->count != (uint64_t)cout)) return fail("Conv '" + n.name + "': bias must be a float32 initializer of the output width");
+            const Tensor *B = n.in.size() > 2 && !n.in[2].empty() ? finit(n.in[2]) : nullptr;
+            if (n.in.size() > 2 && !n.in[2].empty() && (!B || B->count != (uint64_t)cout)) return fail("Conv '" + n.name + "': bias must be a float32 or float16 initializer of the output width" + init_refusal);
             int64_t sh = 1, sw = 1;
             if (const auto *st = n.ints("strides")) { if (st->size() != 2) return fail("Conv '" + n.name + "': strides"); sh = (*st)[0]; sw = (*st)[1]; }
             if (sh <= 0 || sw <= 0 || sh > 16 || sw > 16) return fail("Conv '" + n.name + "': strides");
@@ -383,7 +441,8 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             if (L.res_tensor != NO_TENSOR) return fail("BatchNormalization after a residual Add (BN(conv + x)) cannot be folded into the convolution");
             { auto cit = cons.find(n.in[0]); if ((cit != cons.end() && cit->second.size() != 1) || graph_out.count(n.in[0])) return fail("BatchNormalization of a convolution output that has other readers cannot be folded"); }
             const Tensor *p[4];
-            for (int q = 0; q < 4; q++) { p[q] = f32init(n.in[1 + q]); if (!p[q] || p[q]->count != L.cout) return fail("BatchNormalization: parameters must be float32 initializers of the channel count"); }
+            init_refusal.clear();
+            for (int q = 0; q < 4; q++) { p[q] = finit(n.in[1 + q]); if (!p[q] || p[q]->count != L.cout) return fail("BatchNormalization: parameters must be float32 or float16 initializers of the channel count" + init_refusal); }
             const double eps = (double)n.getf("epsilon", 1e-5f);
             const uint64_t nw = L.op == OP_CONV ? (uint64_t)L.kh * L.kw * L.cin * L.cout : L.op == OP_DWCONV ? (uint64_t)L.kh * L.kw * L.cout : (uint64_t)L.cin * L.cout;
             for (uint32_t c = 0; c < L.cout; c++) {
@@ -443,21 +502,22 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             tmap[n.out[0]] = t;
         } else if (op == "Gemm" || op == "MatMul") {
             T t;
-            const Tensor *W = n.in.size() > 1 ? f32init(n.in[1]) : nullptr;
-            if (!find(n.in[0], t) || !W || W->dims.size() != 2) return fail(op + ": needs an activation on the path and a 2-d float32 weight initializer");
+            init_refusal.clear();
+            const Tensor *W = n.in.size() > 1 ? finit(n.in[1]) : nullptr;
+            if (!find(n.in[0], t) || !W || W->dims.size() != 2) return fail(op + ": needs an activation on the path and a 2-d float32 or float16 weight initializer" + init_refusal);
             const bool gemm = op == "Gemm", tb = gemm && n.geti("transB", 0) != 0;
             if (gemm && (n.getf("alpha", 1.0f) != 1.0f || n.getf("beta", 1.0f) != 1.0f || n.geti("transA", 0) != 0)) return fail("Gemm with alpha / beta / transA");
             const int64_t cin = tb ? W->dims[1] : W->dims[0], cout = tb ? W->dims[0] : W->dims[1];
             if (cin <= 0 || cout <= 0 || cin > (1 << 20) || cout > (1 << 24)) return fail(op + ": bad weight shape");
             if ((uint64_t)cin != (uint64_t)t.c * t.h * t.w || (uint64_t)t.h * t.w != 1) return fail(op + ": " + std::to_string(cin) + " input features, activation has " + std::to_string(t.c));
-            const Tensor *B = gemm && n.in.size() > 2 && !n.in[2].empty() ? f32init(n.in[2]) : nullptr;
+            const Tensor *B = gemm && n.in.size() > 2 && !n.in[2].empty() ? finit(n.in[2]) : nullptr;
             std::string out = n.out[0];
             if (!B) {   // MatMul followed by Add(bias)
                 size_t k;
-                if (sole_consumer(out, "Add", k) && g.nodes[k].in.size() == 2 && !g.nodes[k].out.empty()) {
-                    const std::string &other = g.nodes[k].in[0] == out ? g.nodes[k].in[1] : g.nodes[k].in[0];
-                    const Tensor *ob = f32init(other);
-                    if (ob && ob->count == (uint64_t)cout) { B = ob; out = g.nodes[k].out[0]; skip.insert(k); }
+                if (sole_consumer(out, "Add", k) && nodes[k].in.size() == 2 && !nodes[k].out.empty()) {
+                    const std::string &other = nodes[k].in[0] == out ? nodes[k].in[1] : nodes[k].in[0];
+                    const Tensor *ob = finit(other);
+                    if (ob && ob->count == (uint64_t)cout) { B = ob; out = nodes[k].out[0]; skip.insert(k); }
                 }
             }
             if (B && B->count != (uint64_t)cout) return fail(op + ": bias width");
@@ -501,7 +561,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     if (!first_of_pattern.empty()) return fail("activation pattern on a tensor that was never produced: '" + first_of_pattern.begin()->first + "'");
     if (layers.empty() || layers.back().op != OP_DENSE) return fail("the graph does not end in a dense layer");
     T fin;
-    if (!find(g.outputs[0].name, fin) || fin.idx != layers.size()) return fail("the graph output is not the last layer's output");
+    if (!find(outputs[0], fin) || fin.idx != layers.size()) return fail("the graph output is not the last layer's output");
     m.h.n_layers = (uint32_t)layers.size();
     m.h.n_classes = layers.back().cout;
     m.h.embedding_dim = emb_dim;

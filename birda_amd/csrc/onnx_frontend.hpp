@@ -296,9 +296,14 @@ inline Arr arr_of_tensor(const Tensor &t, const std::string &name) {
         a.v.resize(n);
         for (size_t i = 0; i < n; i++) a.v[i] = (double)t.at(i);
     }
+    else if (t.dtype == 10) {                    // float16: the exact value each element encodes (onnx_graph.hpp decodes it into `fl`)
+        if (t.fl.size() != n) throw EvalError("constant '" + name + "' without data");
+        a.v.resize(n);
+        for (size_t i = 0; i < n; i++) a.v[i] = (double)t.fl[i];
+    }
     else if (t.dtype == 11) { if (t.dl.size() != n) throw EvalError("constant '" + name + "' without data"); a.v = t.dl; }
     else if (t.dtype == 7 || t.dtype == 6 || t.dtype == 9) { if (t.il.size() != n) throw EvalError("constant '" + name + "' without data"); a.is_int = true; a.iv = t.il; }
-    else throw EvalError("constant '" + name + "' of element type " + std::to_string(t.dtype) + " (float32, float64, int64, int32 and bool are read)");
+    else throw EvalError("constant '" + name + "' of element type " + std::to_string(t.dtype) + " (float32, float16, float64, int64, int32 and bool are read)");
     return a;
 }
 

@@ -1,5 +1,5 @@
 // onnx_graph.hpp -- the ONNX wire format as far as the classifier's model files need it: ModelProto.graph -> nodes (with their
-// attributes), initializers (float32 / float64 / int64 / int32 payloads; raw_data or the typed repeated fields), Constant nodes
+// attributes), initializers (float32 / float16 / float64 / int64 / int32 payloads; raw_data or the typed repeated fields), Constant nodes
 // as initializers by another spelling, graph inputs / outputs with their static shapes.  Hand-written protobuf walk on
 // onnx_dense.hpp's Reader (no protobuf / onnx dependency).  Untrusted input: every length is checked against the buffer, every
 // dimension product against the tensor's payload.  Used by onnx_conv.hpp (the conv-stack walk) and onnx_frontend.hpp (the
@@ -46,7 +46,25 @@ struct Node {
     const std::vector<int64_t> *ints(const char *k) const { auto it = a.find(k); return it != a.end() && !it->second.ints.empty() ? &it->second.ints : nullptr; }
     std::string gets(const char *k, const char *dflt) const { auto it = a.find(k); return it != a.end() && !it->second.s.empty() ? it->second.s : std::string(dflt); }
 };
-// an initializer: float32 data stays in the file buffer (raw_data) or in `fl` (float_data); int64 / int32 values in `il`
+// IEEE binary16 bit pattern -> the float32 that holds the same real number (every f16 value is an f32 value: exact, subnormals,
+// +-0, inf and NaN -- payload kept -- included)
+inline float f16_bits_to_float(uint16_t h) {
+    const uint32_t sign = (uint32_t)(h & 0x8000u) << 16, e = (h >> 10) & 0x1Fu, m = h & 0x3FFu;
+    uint32_t u;
+    if (e == 0x1Fu) u = sign | 0x7F800000u | (m << 13);
+    else if (e) u = sign | ((e + 112u) << 23) | (m << 13);
+    else if (!m) u = sign;
+    else {                                     // subnormal: m * 2^-24, normalised
+        uint32_t mm = m, sh = 0;
+        while (!(mm & 0x400u)) { mm <<= 1; sh++; }
+        u = sign | ((113u - sh) << 23) | ((mm & 0x3FFu) << 13);
+    }
+    float f; memcpy(&f, &u, 4); return f;
+}
+
+// an initializer: float32 data stays in the file buffer (raw_data) or in `fl` (float_data); int64 / int32 values in `il`.
+// A float16 tensor (element type 10) is decoded into `fl` at parse time -- the exact real number each element encodes -- and keeps
+// its dtype, so a reader can tell where a constant came from (onnx_conv.hpp: the erf-GELU constants).
 struct Tensor {
     std::vector<int64_t> dims;
     int64_t dtype = 1;
@@ -57,13 +75,16 @@ struct Tensor {
     uint64_t count = 0;
     bool has_raw = false;
     bool is_f32() const { return dtype == 1; }
-    // (parse_tensor leaves exactly one payload of `count` elements: raw_data when present -- float_data beside it is dropped -- else float_data)
+    bool is_f16() const { return dtype == 10; }
+    bool is_float() const { return dtype == 1 || dtype == 10; }          // what at() reads
+    // (parse_tensor leaves exactly one payload of `count` elements: raw_data when present -- float_data beside it is dropped -- else float_data;
+    // float16: always `fl`)
     float at(uint64_t i) const {
-        if (!has_raw) return fl[i];
+        if (!has_raw || dtype == 10) return fl[i];
         float v; memcpy(&v, raw.p + 4 * i, 4); return v;
     }
 };
-struct ValueInfo { std::string name; std::vector<int64_t> dims; };   // symbolic dimension: -1
+struct ValueInfo { std::string name; std::vector<int64_t> dims; int64_t elem_type = 0; };   // symbolic dimension: -1; element type 0: not stated
 struct Graph {
     std::vector<Node> nodes;
     std::map<std::string, Tensor> init;
@@ -130,7 +151,22 @@ inline bool parse_tensor(Span s, std::string &name, Tensor &t, std::string &err)
             t.il.resize(t.count);
             for (uint64_t i = 0; i < t.count; i++) t.il[i] = t.raw.p[i] != 0;
         } else if (t.il.size() != t.count) { err = "tensor '" + name + "': integer data size does not match its dims"; return false; }
-    }   // (other element types are carried without data: nothing reads them, and the front-end evaluator refuses them by name)
+    } else if (t.dtype == 10) {                  // float16: raw_data (2 bytes an element) or int32_data (one bit pattern per entry)
+        t.fl.clear();
+        if (has_raw) {
+            if (t.raw.n != t.count * 2) { err = "tensor '" + name + "': float16 raw_data size does not match its dims"; return false; }
+            t.fl.resize(t.count);
+            for (uint64_t i = 0; i < t.count; i++) { uint16_t h; memcpy(&h, t.raw.p + 2 * i, 2); t.fl[i] = f16_bits_to_float(h); }
+        } else {
+            if (t.il.size() != t.count) { err = "tensor '" + name + "': float16 int32_data size does not match its dims"; return false; }
+            t.fl.resize(t.count);
+            for (uint64_t i = 0; i < t.count; i++) {
+                if (t.il[i] < 0 || t.il[i] > 0xFFFF) { err = "malformed tensor '" + name + "': float16 int32_data entry above 0xFFFF"; return false; }
+                t.fl[i] = f16_bits_to_float((uint16_t)t.il[i]);
+            }
+        }
+        t.il.clear();
+    }   // (other element types -- bfloat16, int8, ... -- are carried without data: every reader refuses them by name)
     return true;
 }
 
@@ -209,6 +245,7 @@ inline ValueInfo parse_value_info(Span s) {
                 Reader tt(sp);
                 while (tt.more()) {
                     if (!tt.field(no, wt, v, sp)) break;
+                    if (no == 1 && wt == 0) { vi.elem_type = (int64_t)v; continue; }
                     if (no != 2 || wt != 2) continue;
                     Reader sh(sp);
                     while (sh.more()) {

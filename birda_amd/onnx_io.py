@@ -17,7 +17,8 @@ from typing import Dict, Iterator, List, Optional, Tuple, Union
 import numpy as np
 
 # TensorProto.DataType
-FLOAT, INT64, INT32 = 1, 7, 6
+FLOAT, INT64, INT32, FLOAT16, DOUBLE, BFLOAT16 = 1, 7, 6, 10, 11, 16
+_TYPE_NAMES = {2: "uint8", 3: "int8", 9: "bool", DOUBLE: "float64", BFLOAT16: "bfloat16"}
 # AttributeProto.AttributeType
 A_FLOAT, A_INT, A_STRING, A_TENSOR, A_FLOATS, A_INTS = 1, 2, 3, 4, 6, 7
 
@@ -147,15 +148,23 @@ def _parse_tensor(buf: bytes) -> Tuple[str, np.ndarray]:
             name = v.decode("utf-8")
         elif no == 9:
             raw = v
-    np_t = {FLOAT: "<f4", INT64: "<i8", INT32: "<i4"}.get(dtype)
+    np_t = {FLOAT: "<f4", INT64: "<i8", INT32: "<i4", FLOAT16: "<f2"}.get(dtype)
     if np_t is None:
-        raise ValueError(f"tensor {name!r}: unsupported data type {dtype}")
+        raise ValueError(f"tensor {name!r}: unsupported data type {dtype} ({_TYPE_NAMES.get(dtype, 'not read')})")
     if raw is not None:
+        if len(raw) % np.dtype(np_t).itemsize:
+            raise ValueError(f"tensor {name!r}: raw_data size does not match its dims")
         arr = np.frombuffer(raw, dtype=np_t).copy()
     elif dtype == FLOAT:
         arr = np.asarray(floats, np.float32)
+    elif dtype == FLOAT16:   # int32_data: one IEEE binary16 bit pattern per entry
+        if any(not 0 <= x <= 0xFFFF for x in ints):
+            raise ValueError(f"malformed tensor {name!r}: float16 int32_data entry above 0xFFFF")
+        arr = np.asarray(ints, np.uint16).view(np.float16)
     else:
         arr = np.asarray(ints, np_t)
+    if arr.size != int(np.prod(dims, dtype=np.int64)):
+        raise ValueError(f"tensor {name!r}: data size does not match its dims")
     return name, arr.reshape(dims) if dims else arr.reshape(())
 
 
@@ -266,7 +275,7 @@ def load(data: bytes) -> Graph:
 # ---------------------------------------------------------------------------------------
 def _ser_tensor(name: str, arr: np.ndarray) -> bytes:
     arr = np.asarray(arr)
-    dtype = {np.dtype("float32"): FLOAT, np.dtype("int64"): INT64, np.dtype("int32"): INT32}[arr.dtype]
+    dtype = {np.dtype("float32"): FLOAT, np.dtype("int64"): INT64, np.dtype("int32"): INT32, np.dtype("float16"): FLOAT16}[arr.dtype]
     out = b"".join(_f_varint(1, int(d)) for d in arr.shape)
     out += _f_varint(2, dtype) + _f_str(8, name) + _f_bytes(9, np.ascontiguousarray(arr).astype(arr.dtype.newbyteorder("<")).tobytes())
     return out

@@ -87,6 +87,11 @@ typedef struct {
  *                  they differ from the large-launch path's by the summation order (~1e-7 of the logit scale, inside the fp32
  *                  tolerance).  Off by default: without it every launch size gives the same bits. */
 #define BH_FLAG_LOW_LATENCY 0x10u
+/*   BH_FLAG_FULL_PLANES  (or-ed onto the precision) every split-f16 GEMM layer keeps three terms on full hi / lo weight planes, also
+ *                  where its weights are f16 values and two terms on compact planes give the same numbers (the default under
+ *                  BH_FLAG_AUTO / BH_FLAG_F16X3).  For comparing the two forms on one file in one process; no effect under
+ *                  BH_FLAG_F16 and BH_FLAG_F32. */
+#define BH_FLAG_FULL_PLANES 0x20u
 #define BH_FLAG_PRECISION_MASK 0x3u
 #define BH_FLAG_AUTO 0x0u
 #define BH_FLAG_F16X3 0x1u
@@ -174,7 +179,15 @@ BH_API size_t bh_default_batch_size(uint32_t model_type, const char *provider_ac
 BH_API size_t bh_classifier_default_batch_size(const bh_classifier *c);
 
 /* ClassifierBuilder::build() (classifier.rs:281-283).  Loads the model, uploads weights,
- * precomputes the folded STFT*mel operators, validates the label count. */
+ * precomputes the folded STFT*mel operators, validates the label count.
+ * FLOAT16 MODEL FILES (the `fp16` variant of a published model, which the reference's installer picks for a GPU provider) are
+ * read with this meaning: a float16 constant is the exact real number it encodes; Cast between floating types is the identity;
+ * the graph is evaluated in the library's own (f32-grade) arithmetic.  The result is at least as exact as any float16 runtime's;
+ * it does not imitate that runtime's intermediate rounding or its overflow at 65 504.  The file's input and outputs must be
+ * float32 (as the published files' are, behind / in front of a Cast): a float16 graph input or output is refused by name.
+ * GEMM layers outside the fused blocks whose weights are f16 values -- every layer of such a file whose BatchNormalization was
+ * folded before export -- run two f16 MFMAs per product on half the weight bytes, with the three-term result element for
+ * element (bh_classifier_weight_summary; BH_FLAG_FULL_PLANES keeps three terms). */
 BH_API int bh_classifier_create(const bh_config *cfg, bh_classifier **out);
 /* The conversion bh_classifier_create runs on an .onnx file, as a step of its own (host only, no device): ONNX graph -> BHM1
  * container on disk.  For deployments that convert once and hand the container to every process afterwards (a 437-MB Perch
@@ -334,6 +347,18 @@ BH_API int bh_batch_context_layer_ms(bh_batch_context *ctx, float *ms, uint32_t 
  * tests/test_abi_and_host.py::test_environment_names_in_the_shipped_library_are_the_documented_ones; A/B knobs of earlier
  * rounds -- BIRDA_HIP_STEM_F32, BIRDA_HIP_RESAMPLE_F32, BIRDA_HIP_MB_STAMPS, ... -- exist only in the `make EXPERIMENTS=1` build.) */
 BH_API int bh_classifier_fused_blocks(const bh_classifier *c, int32_t *cfgs, size_t cap);
+
+/* How the weights of the GEMM layers outside the fused blocks (full convolutions, 1x1 convolutions, dense layers: the layers with
+ * f16 operand planes) are held.  Writes min(cap, BH_WS_COUNT) values to out (nullable), indexed by BH_WS_*, and returns
+ * BH_WS_COUNT (or a negative bh_status).  (An array rather than a struct, like bh_classifier_fused_blocks: later values are added
+ * at the end.) */
+#define BH_WS_FLOAT16_FILE 0          /* 1: the model file's convolution / dense weights were float16 tensors (an .onnx file) */
+#define BH_WS_GEMM_LAYERS 1           /* GEMM layers outside fused blocks that run on f16 operand planes (0 under BH_FLAG_F32) */
+#define BH_WS_TWO_TERM_LAYERS 2       /* ... of which run two-term products on compact planes (weights that are f16 values) */
+#define BH_WS_PLANE_BYTES 3           /* device bytes of all those layers' planes */
+#define BH_WS_TWO_TERM_PLANE_BYTES 4  /* device bytes of the two-term layers' planes (half of what BH_FLAG_FULL_PLANES holds for them) */
+#define BH_WS_COUNT 5
+BH_API int bh_classifier_weight_summary(const bh_classifier *c, uint64_t *out, size_t cap);
 
 /* The same plan for a model FILE, without a device (host logic only: which expand -> depthwise -> project triples fuse and the tile
  * configuration the planner picks for each under precision `flags`).  Returns the number of fused blocks (or a negative

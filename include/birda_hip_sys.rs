@@ -5,6 +5,7 @@ use std::ffi::{c_char, c_int, c_void};
 
 pub const BH_MAX_TOP_K: usize = 32;
 pub const BH_FLAG_LOW_LATENCY: u32 = 0x10;
+pub const BH_FLAG_FULL_PLANES: u32 = 0x20;
 pub const BH_FLAG_PRECISION_MASK: u32 = 0x3;
 pub const BH_FLAG_AUTO: u32 = 0x0;
 pub const BH_FLAG_F16X3: u32 = 0x1;
@@ -18,6 +19,12 @@ pub const BH_MODEL_BSG_FINLAND: u32 = 3;
 pub const BH_MIN_BATCH_SIZE: usize = 1;
 pub const BH_MAX_BATCH_SIZE: usize = 512;
 pub const BH_N_STAGES: usize = 9;
+pub const BH_WS_FLOAT16_FILE: usize = 0;
+pub const BH_WS_GEMM_LAYERS: usize = 1;
+pub const BH_WS_TWO_TERM_LAYERS: usize = 2;
+pub const BH_WS_PLANE_BYTES: usize = 3;
+pub const BH_WS_TWO_TERM_PLANE_BYTES: usize = 4;
+pub const BH_WS_COUNT: usize = 5;
 pub const BH_PCM_S16: u32 = 1;
 pub const BH_PCM_S24: u32 = 2;
 pub const BH_PCM_S32: u32 = 3;
@@ -151,6 +158,7 @@ extern "C" {
     pub fn bh_batch_context_stage_ms(ctx: *mut BhBatchContext, ms: *mut f32, launches: *mut u32) -> c_int;
     pub fn bh_batch_context_layer_ms(ctx: *mut BhBatchContext, ms: *mut f32, launches: *mut u32, n_layers: usize) -> c_int;
     pub fn bh_classifier_fused_blocks(c: *const BhClassifier, cfgs: *mut i32, cap: usize) -> c_int;
+    pub fn bh_classifier_weight_summary(c: *const BhClassifier, out: *mut u64, cap: usize) -> c_int;
     pub fn bh_plan_fused_blocks(model_path: *const c_char, flags: u32, cfgs: *mut i32, layers: *mut i32, cap: usize) -> c_int;
     pub fn bh_classifier_frontend_kernel(c: *const BhClassifier, out: *mut c_char, cap: usize) -> c_int;
     pub fn bh_mb_config_name(cfg: i32, out: *mut c_char, cap: usize) -> c_int;
