@@ -159,6 +159,10 @@ void ctx_mark(bh_batch_context *ctx, int stage, int layer = -1) {
     ctx->ev_stage.push_back(stage);
     ctx->ev_layer.push_back(layer);
 }
+// the schedule a context's forwards walk and its arena is planned from
+const std::vector<Step> &schedule_of(const bh_batch_context *ctx) {
+    return !ctx->keep_tensors ? ctx->c->sched : ctx->keep_fused ? ctx->c->sched_keep_fused : ctx->c->sched_layers;
+}
 int ctx_create(bh_classifier *c, size_t max_batch, bool keep, bh_batch_context **out) {
     if (!c || !out || max_batch == 0) return fail(BH_ERR_INVALID, "batch context: bad arguments");
     HIPCHK(hipSetDevice(c->device));
@@ -186,7 +190,7 @@ int ctx_create(bh_classifier *c, size_t max_batch, bool keep, bh_batch_context *
     HIPCHK(hipMalloc((void **)&ctx->d_input, in_bytes));
     HIPCHK(hipMalloc((void **)&ctx->d_minmax, max_batch * 16 * sizeof(float)));
     HIPCHK(hipMalloc((void **)&ctx->d_inbad, max_batch * 8 * sizeof(unsigned)));
-    plan_arena(m, c->fused_at, c->se, c->head_gap, c->gap_gate, max_batch, keep, ctx->t_off, ctx->arena_floats);
+    plan_arena(m, schedule_of(ctx.get()), max_batch, keep, ctx->t_off, ctx->arena_floats);
     // (slack for the lanes: the plans of a slice's sub-slices, side by side, exceed the whole slice's plan by up to 64 floats of
     //  alignment per tensor and sub-plan; the automatic split makes up to 9 sub-slices, bh_batch_context_set_sub_slices more --
     //  16 sub-plans fit, beyond that lanes_begin falls back to one stream and counts it: bh_batch_context_lane_fallbacks)
@@ -236,10 +240,8 @@ void ctx_destroy(bh_batch_context *ctx) {
     delete ctx;
 }
 
-// one slice (n <= max_batch) of the forward pass, enqueued on ctx->stream
-// (lane: where a sub-slice of a host-fed slice runs -- its stream, its own part of the arena with the plan of an n-segment forward,
-//  and its first segment's index within the slice, which places its rows of the per-segment scratch; nullptr: the context's stream
-//  and whole arena)
+// where a sub-slice of a host-fed slice runs: its stream, its own part of the arena with the plan of an n-segment forward, and its
+// first segment's index within the slice, which places its rows of the per-segment scratch
 struct SliceLane { hipStream_t s; float *arena; const size_t *t_off; size_t seg0; };
 // BH_FLAG_LOW_LATENCY: launches of up to this many segments split a late block's expanded channels over workgroups, 2 deep from 6
 // chunks, 4 deep from 12, 8 deep from 32 (fused blocks without a gate: pass A of a squeeze-excite block has no project sums to split)
@@ -249,250 +251,259 @@ static inline int mb_ksplit_of(const bh::MbDesc &d) {
     const int k = (d.se || d.Cout % 4) ? 1 : d.nchunks >= 32 ? 8 : d.nchunks >= 12 ? 4 : d.nchunks >= 6 ? 2 : 1;
     return std::min(k, std::max(cap, 1));
 }
+// What the steps of one slice share.  T(t): where tensor t of a step's lists lives -- its planned bytes of the arena, and for the
+// last layer's output the caller's logits buffer.
+struct SliceRun {
+    bh_classifier *c; bh_batch_context *ctx; size_t n; hipStream_t s; float *arena; const size_t *t_off; float *d_logits; bool in_lane;
+    float *T(uint32_t t) const { return t == c->model.layers.size() ? d_logits : arena + t_off[t]; }
+    const float *in(const Step &st) const { return T(st.reads[0]); }
+    const float *res(const Step &st) const { return st.reads.size() > 1 ? T(st.reads[1]) : nullptr; }
+    float *out(const Step &st) const { return T(st.writes[0]); }
+    int layer(const Step &st) const, fused(const Step &st) const, fused_se(const Step &st) const, head_gap(const Step &st) const,
+        se_gate(const Step &st) const;       // one per path
+};
+// the fused block of a step as this launch runs it
+// (a launch of at most 256 segments: the one-segment-per-workgroup twin where the block has one -- the two-segment tiles would leave
+//  half of the CUs, or more, without a workgroup)
+// (a launch of a few dozen segments: the narrow-tile twin -- two or four workgroups per image -- while those still number no more
+//  than two per CU: what such a launch lasts is one workgroup's walk through the chunks)
+static bh::MbDesc mb_for_launch(const bh_classifier *c, int block, size_t n) {
+    const bh::MbDesc &twin = c->mb_small[block], &narrow = c->mb_narrow[block];
+    return (narrow.cfg >= 0 && n * (size_t)narrow.tiles_x <= (size_t)c->narrow_max_workgroups) ? narrow
+         : (twin.cfg >= 0 && n <= (size_t)c->twin_max_segments) ? twin : c->mb[block];
+}
+
+// one layer, one launch
+int SliceRun::layer(const Step &st) const {
+    const uint32_t i = st.first;
+    const auto &L = c->model.layers[i];
+    const float *in = this->in(st), *res = this->res(st), *bias = c->d_blob + L.b_off;
+    float *out = this->out(st);
+    bh::ConvParams p{(int)L.in_h, (int)L.in_w, (int)L.out_h, (int)L.out_w, (int)L.cin, (int)L.cout,
+                     (int)L.kh, (int)L.kw, (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l,
+                     (int)L.in_layout, (int)L.act};
+    switch (L.op) {
+    case bh::OP_CONV:
+        // the NCHW stem on the direct kernel (when it is not fused into the first block); every NHWC full convolution is an
+        // implicit GEMM on the MFMA (kernels_conv.hip), split-f16 where it has planes
+        if (L.in_layout == 1)
+            bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
+        else if (!ctx->keep_tensors && c->d_w16[i])
+            c->w16_kernel[i].store(bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+        else
+            bh::launch_conv_gemm(in, c->d_w[i], bias, res, out, p, (int)n, c->ldw[i], s);
+        ctx_mark(ctx, ST_STEM, (int)i);
+        break;
+    case bh::OP_DWCONV:
+        bh::launch_dwconv(in, c->d_w[i], bias, out, p, (int)n, s);
+        ctx_mark(ctx, ST_DW, (int)i);
+        break;
+    case bh::OP_PWCONV:
+        if (!ctx->keep_tensors && c->d_w16[i])
+            c->w16_kernel[i].store(bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin, (int)L.cout,
+                                                        (int)L.act, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+        else
+        bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin,
+                           (int)L.cout, c->ldw[i], (int)L.act, s);
+        ctx_mark(ctx, ST_PW, (int)i);
+        break;
+    case bh::OP_DENSE:
+        if (!ctx->keep_tensors && c->d_w16[i])
+            c->w16_kernel[i].store(bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, (int)L.act,
+                                                        c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+        else
+        bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, c->ldw[i],
+                           (int)L.act, s);
+        ctx_mark(ctx, ST_DENSE, (int)i);
+        break;
+    case bh::OP_GAP:
+        bh::launch_gap(in, out, (int)n, (int)(L.in_h * L.in_w), (int)L.cout, s);
+        ctx_mark(ctx, ST_GAP, (int)i);
+        break;
+    case bh::OP_SCALE:   // squeeze-excite: the feature map times its [n][C] gate (res = the gate tensor)
+        bh::launch_scale(in, res, out, (int)n, (int)(L.out_h * L.out_w), (int)L.cout, s);
+        ctx_mark(ctx, ST_DW, (int)i);
+        break;
+    default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
+    }
+    return BH_OK;
+}
+
+// expand -> depthwise -> project (depthwise -> project for a block without an expand convolution) in one launch
+int SliceRun::fused(const Step &st) const {
+    bh::MbDesc d = mb_for_launch(c, st.block, n);
+    d.X = in(st);
+    d.Y = out(st);
+    d.R = res(st);
+    // BH_FLAG_LOW_LATENCY, a launch of at most 32 segments on the context's own stream: a block of many chunks runs 2 or 4
+    // workgroups deep, each walking its share of the expanded channels (kernels.hpp MbDesc::ksplit) -- a handful of
+    // workgroups on the whole chip each streaming ALL of a late block's weights is what such a forward lasts.  The depth is
+    // the block's alone (never the launch's), so within the regime a segment's bits still do not depend on its launch.
+    const int ksp = (c->low_latency && !in_lane && n <= kLowLatencyMaxSegments) ? mb_ksplit_of(d) : 1;
+    if (ksp > 1) {
+        if (!ctx->d_partial) {
+            size_t need = 0;
+            for (const auto &b : c->mb) need = std::max(need, (size_t)mb_ksplit_of(b) * kLowLatencyMaxSegments * b.Ho * b.Wo * b.Cout);
+            HIPCHK(hipMalloc((void **)&ctx->d_partial, std::max<size_t>(need, 4) * sizeof(float)));
+        }
+        d.ksplit = ksp;
+        d.partial = ctx->d_partial;
+        bh::launch_mbconv(d, (int)n, s);
+        bh::launch_mb_reduce_partials(ctx->d_partial, d.Y, ksp, n * (size_t)d.Ho * d.Wo * d.Cout, d.prec != 0 ? d.p_unscale : 1.0f, s);
+    } else
+    bh::launch_mbconv(d, (int)n, s);
+    ctx_mark(ctx, ST_MBCONV, (int)st.first);
+    return BH_OK;
+}
+
+// A squeeze-excite block in three launches: pass A (expand -> depthwise: D and the per-tile channel sums), the gate
+// (pool -> 1x1 -> 1x1), the project GEMM on D x gate (+ residual).  The expanded tensor stays in LDS, the scaled one
+// never exists; D crosses HBM once each way.
+int SliceRun::fused_se(const Step &st) const {
+    const bh::MbDesc d = mb_for_launch(c, st.block, n);
+    const auto &S = c->se[st.block];
+    const auto &G1 = c->model.layers[S.iPw1], &G2 = c->model.layers[S.iPw2], &LP = c->model.layers[S.iP];
+    // (the gate: one launch, a workgroup per segment (se_gate_kernel), or the pool + the two dense layers as GEMMs over all
+    //  segments, through the arena slots of the layers they stand for.  Either way every sum runs in a fixed order.)
+    // (which of the two a BLOCK takes depends on its width alone, never on the launch: up to 576 expanded channels the
+    //  one-launch kernel is the faster one -- three launches cost ~27 us per 1 000 segments whatever their size, measured
+    //  13-36 against 27-50 us; beyond, its per-segment re-read of both weight matrices is: 59-490 against 37-143 us)
+    // (round 6: beyond 576 channels two launches of sixteen-segment workgroups -- the pooled rows x W1 split over channel
+    //  slices, then hidden x W2 -- instead of pool + two GEMMs of a handful of tiles: kernels_conv.hip se_hidden_kernel)
+    // (one selection for whole launches and for the groups below: a segment's bits do not depend on how its launch is cut)
+    static const bool gate1 = [] { const char *e = BH_XENV("BIRDA_HIP_SE_GATE1"); return e && e[0] == '1'; }();
+    auto launch_gate = [&](const float *part, int tiles, int P, float *pooled, float *hidden, float *gate, size_t ns) {
+        if (!gate1 && d.Cexp >= BH_SE_GATE16_MIN && bh::se_gate16_supports(d.Cexp, (int)G1.cout))
+            bh::launch_se_gate16(part, tiles, P, pooled, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
+                                 c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+        else if (!gate1 && d.Cexp > 576)
+            bh::launch_se_gate_gemm(part, tiles, P, pooled, hidden, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
+                                    c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+        else
+            bh::launch_se_gate(part, tiles, P, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
+                               c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+    };
+    // (a block without an expand convolution computes D twice instead of keeping it: pass A leaves only the channel sums,
+    //  the gated one-launch block below does the rest -- kernels.hpp MbDesc::gate)
+    // (round 6: the same for the STEM block -- its input, the planar spectrogram, is a tenth of its D -- was built (the stem
+    //  instantiations take MbDesc::gate) and measured on the Perch-sized plan: 38.75 -> 38.45 k segments/s, three alternations
+    //  on one box at one clock, profiles/r6_n_stem_recompute.txt: the sums-only pass costs more than D's round trip saves.
+    //  Not taken; BIRDA_HIP_SE_STEM_RECOMPUTE=1 in the EXPERIMENTS build.)
+    static const bool stem_recompute = [] { const char *e = BH_XENV("BIRDA_HIP_SE_STEM_RECOMPUTE"); return e && e[0] == '1'; }();
+    const bool recompute = d.noexp != 0 || (d.stem != 0 && stem_recompute);
+    // (D blocked for the f16 gated GEMMs: kernels.hpp MbDesc::dblk)
+    const bool dblk = !recompute && c->d_w16[S.iP] && bh::pw_gemm16_gated_wants_blocked(d.Cexp, d.Cout, d.Ho * d.Wo);
+    // Round 6 (VERDICT r5 next #3a): a block whose D is large -- the early stages: 1.5-2.3 MB a segment -- runs its three
+    // launches per GROUP of segments, so that the D pass A writes is still in the 256 MB Infinity Cache when the gated
+    // project GEMM reads it (at 1 000 segments a launch it crosses HBM both ways).  The tiling -- hence every pooled sum's
+    // order, hence the bits -- is the whole launch's; only the launches are cut.  c->se_group_bytes: the D one group may
+    // hold (0: never); blocks whose whole D fits, and those that compute D twice, run as before.
+    const size_t d_seg_bytes = (size_t)d.Ho * d.Wo * d.Cexp * sizeof(float);
+    size_t grp = (!d.noexp && !d.stem && c->se_group_bytes && d_seg_bytes * n > c->se_group_bytes) ? std::max<size_t>(c->se_group_bytes / d_seg_bytes, 16) : n;
+    if (grp < n) grp -= grp % (size_t)std::max(d.S, 1);     // (whole S-segment workgroups per group)
+    const bool grouped = grp < n;     // (one ST_MBCONV mark for the block; a whole launch marks each of its three)
+    const size_t P = (size_t)d.Ho * d.Wo, tiles = (size_t)d.tiles_x * d.tiles_y;
+    const size_t in_seg = d.stem ? (size_t)d.stem_c * d.stem_h * d.stem_w : (size_t)d.H * d.W * d.Cin;
+    const float *x = in(st), *r = res(st);
+    float *y = out(st), *D = T(st.writes[1]), *sums = T(st.scratch[SE_SUMS].t);
+    float *pooled = T(st.scratch[SE_POOLED].t), *hidden = T(st.scratch[SE_HIDDEN].t), *gate = T(st.scratch[SE_GATE].t);
+    auto run = [&](size_t s0, size_t ng) {      // segments s0 .. s0 + ng - 1
+        bh::MbDesc a = d;
+        a.X = x + s0 * in_seg;
+        a.Dout = recompute ? nullptr : D + s0 * P * d.Cexp;
+        a.pool_part = sums + s0 * tiles * d.Cexp;
+        a.gate = nullptr;
+        a.dblk = dblk;
+        bh::launch_mbconv(a, (int)ng, s);
+        if (!grouped) ctx_mark(ctx, ST_MBCONV, (int)st.first);
+        float *gg = gate + s0 * d.Cexp;
+        launch_gate(a.pool_part, (int)tiles, (int)P, pooled + s0 * d.Cexp, hidden + s0 * G1.cout, gg, ng);
+        if (!grouped) ctx_mark(ctx, ST_GAP, (int)S.iGap);
+        float *yg = y + s0 * P * d.Cout;
+        const float *rg = r ? r + s0 * P * d.Cout : nullptr;
+        if (recompute) {      // depthwise -> x gate -> project (+ residual) in one launch, the block's own weights and tiling
+            bh::MbDesc g = a;
+            g.se = 0; g.gate = gg; g.Y = yg; g.R = rg; g.Dout = nullptr; g.pool_part = nullptr;
+            bh::launch_mbconv(g, (int)ng, s);
+        } else
+        if (c->d_w16[S.iP])
+            c->w16_kernel[S.iP].store(bh::launch_pw_gemm16_gated(a.Dout, gg, (int)P, c->d_w16[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
+                                       c->w16_terms[S.iP], c->w16_unscale[S.iP], a.dblk, s), std::memory_order_relaxed);
+        else
+            bh::launch_pw_gemm_gated(a.Dout, gg, (int)P, c->d_w[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
+                                     c->ldw[S.iP], (int)LP.act, s);
+        if (!grouped) ctx_mark(ctx, ST_PW, (int)S.iP);
+    };
+    if (grouped) {
+        for (size_t s0 = 0; s0 < n; s0 += grp) run(s0, std::min(grp, n - s0));
+        ctx_mark(ctx, ST_MBCONV, (int)st.first);
+    } else
+        run(0, n);
+    return BH_OK;
+}
+
+// head conv + GELU and the global average pool after it in one launch
+int SliceRun::head_gap(const Step &st) const {
+    const uint32_t i = st.first;
+    const auto &L = c->model.layers[i];
+    c->w16_kernel[i].store(bh::launch_head_gap16(in(st), c->d_w16[i], c->d_blob + L.b_off, out(st), (int)n, (int)(L.out_h * L.out_w), (int)L.cin, (int)L.cout,
+                                                 (int)L.act, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+    ctx_mark(ctx, ST_PW, (int)i);
+    return BH_OK;
+}
+
+// The gate of a squeeze-excite block that runs LAYER BY LAYER (wider than the fused entries -- the v3.0-sized model's
+// 640 -> 3 840 -> 640 blocks -- or left there by the f32 planner): pool -> 1x1 -> 1x1 were a pool launch and two GEMMs of
+// M = n rows, the first with a handful of tiles under a K loop of the whole width (171 us per 256 segments for 3 840 ->
+// 160).  On a small image the two gate launches of the fused path take the whole chain: se_hidden_kernel pools the
+// depthwise output itself (its "tiles" are the image's pixels, in order), the pool layer's own tensor holds the partial
+// sums.  Which path a block takes depends on its shapes alone.
+// (the chain's shapes are checked once, at create: gap_gate_chain.  A model that ENDS in such a gate gets it in d_logits.)
+int SliceRun::se_gate(const Step &st) const {
+    const uint32_t i = st.first;
+    const auto &L = c->model.layers[i], &G1 = c->model.layers[i + 1], &G2 = c->model.layers[i + 2];
+    const int P = (int)(L.in_h * L.in_w);
+    bh::launch_se_gate16(in(st), P, P, T(st.scratch[0].t), c->d_w[i + 1], c->d_blob + G1.b_off, c->ldw[i + 1], (int)G1.act, c->d_w[i + 2],
+                         c->d_blob + G2.b_off, c->ldw[i + 2], (int)G2.act, out(st), (int)n, (int)L.cout, (int)G1.cout, s);
+    ctx_mark(ctx, ST_GAP, (int)i);
+    return BH_OK;
+}
+
+// one slice (n <= max_batch) of the forward pass, enqueued on the lane's stream and arena (nullptr: the context's stream and whole
+// arena): the front end, then the context's schedule step by step
 int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, size_t n, float *d_logits,
                   int32_t *d_idx, float *d_conf, const SliceLane *lane = nullptr) {
     const auto &m = c->model;
-    hipStream_t s = lane ? lane->s : ctx->stream;
-    float *const arena = lane ? lane->arena : ctx->d_arena;
-    const size_t *const t_off = lane ? lane->t_off : ctx->t_off.data();
+    const SliceRun r{c, ctx, n, lane ? lane->s : ctx->stream, lane ? lane->arena : ctx->d_arena, lane ? lane->t_off : ctx->t_off.data(),
+                     d_logits, lane != nullptr};
+    hipStream_t s = r.s;
     float *const d_minmax = ctx->d_minmax + (lane ? lane->seg0 * 16 : 0);
     unsigned *const d_inbad = ctx->d_inbad + (lane ? lane->seg0 * 8 : 0);
-    auto T = [&](uint32_t t) { return arena + t_off[t]; };
-    const uint32_t nl = (uint32_t)m.layers.size();
     bh::TraceRange tr_slice("bh_forward_slice");   // ROCTx ranges (BIRDA_HIP_ROCTX=1): the slice, its front end, every layer group
     ctx_mark(ctx, -1);
     {
         bh::TraceRange tr("front_end: minmax + mel");
         bh::launch_minmax(d_seg, d_minmax, d_inbad, (int)n, (int)m.h.sample_count, s);
         ctx_mark(ctx, ST_MINMAX);
-        const char *mel_name = bh::launch_mel(d_seg, d_minmax, T(0), c->fe, c->d_fe, (int)n, s);
+        const char *mel_name = bh::launch_mel(d_seg, d_minmax, r.T(0), c->fe, c->d_fe, (int)n, s);
         if (!mel_name)   // (create refuses what launch_mel has no instantiation for: a missing kernel is an error, never a silent skip)
             return fail(BH_ERR_UNSUPPORTED, "front-end: no kernel instantiation for %d mels at precision %d", c->fe.br[0].n_mels, c->fe.prec);
         c->fe_kernel.store(mel_name, std::memory_order_relaxed);
         ctx_mark(ctx, ST_MEL);
     }
-    for (uint32_t i = 0; i < nl; i++) {
-        const auto &L = m.layers[i];
+    for (const Step &st : schedule_of(ctx)) {
         static const char *const kOpNames[] = {"layer", "conv", "depthwise", "pointwise", "pool", "dense", "scale"};
-        bh::TraceRange tr((!ctx->keep_tensors || ctx->keep_fused) && c->fused_at[i] >= 0 ? "fused_mbconv_block"
-                          : L.op < sizeof(kOpNames) / sizeof(kOpNames[0]) ? kOpNames[L.op] : kOpNames[0]);
-        const float *in = T(L.in_tensor);
-        float *out = (i == nl - 1) ? d_logits : T(i + 1);
-        const float *res = L.res_tensor != bh::NO_TENSOR ? T(L.res_tensor) : nullptr;
-        const float *bias = c->d_blob + L.b_off;
-        bh::ConvParams p{(int)L.in_h, (int)L.in_w, (int)L.out_h, (int)L.out_w, (int)L.cin, (int)L.cout,
-                         (int)L.kh, (int)L.kw, (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l,
-                         (int)L.in_layout, (int)L.act};
-        if ((!ctx->keep_tensors || ctx->keep_fused) && c->fused_at[i] >= 0) {
-            // expand (i) -> depthwise (i+1) -> project (i+2) in one launch
-            // (a launch of at most 256 segments: the one-segment-per-workgroup twin where the block has one -- the two-segment
-            //  tiles would leave half of the CUs, or more, without a workgroup)
-            // (a launch of a few dozen segments: the narrow-tile twin -- two or four workgroups per image -- while those still
-            //  number no more than two per CU: what such a launch lasts is one workgroup's walk through the chunks)
-            const bh::MbDesc &twin = c->mb_small[c->fused_at[i]], &narrow = c->mb_narrow[c->fused_at[i]];
-            bh::MbDesc d = (narrow.cfg >= 0 && n * (size_t)narrow.tiles_x <= (size_t)c->narrow_max_workgroups) ? narrow
-                         : (twin.cfg >= 0 && n <= (size_t)c->twin_max_segments) ? twin : c->mb[c->fused_at[i]];
-            if (d.se) {
-                // A squeeze-excite block in three launches: pass A (expand -> depthwise: D and the per-tile channel sums), the gate
-                // (pool -> 1x1 -> 1x1), the project GEMM on D x gate (+ residual).  The expanded tensor stays in LDS, the scaled one
-                // never exists; D crosses HBM once each way.
-                const auto &S = c->se[c->fused_at[i]];
-                const auto &G1 = m.layers[S.iPw1], &G2 = m.layers[S.iPw2], &LP = m.layers[S.iP];
-                // (the gate: one launch, a workgroup per segment (se_gate_kernel), or the pool + the two dense layers as GEMMs over all
-                //  segments, through the arena slots of the layers they stand for.  Either way every sum runs in a fixed order.)
-                // (which of the two a BLOCK takes depends on its width alone, never on the launch: up to 576 expanded channels the
-                //  one-launch kernel is the faster one -- three launches cost ~27 us per 1 000 segments whatever their size, measured
-                //  13-36 against 27-50 us; beyond, its per-segment re-read of both weight matrices is: 59-490 against 37-143 us)
-                // (round 6: beyond 576 channels two launches of sixteen-segment workgroups -- the pooled rows x W1 split over channel
-                //  slices, then hidden x W2 -- instead of pool + two GEMMs of a handful of tiles: kernels_conv.hip se_hidden_kernel)
-                // (one selection for whole launches and for the groups below: a segment's bits do not depend on how its launch is cut)
-                static const bool gate1 = [] { const char *e = BH_XENV("BIRDA_HIP_SE_GATE1"); return e && e[0] == '1'; }();
-                auto launch_gate = [&](const float *part, int tiles, int P, float *pooled, float *hidden, float *gate, size_t ns) {
-                    if (!gate1 && d.Cexp >= BH_SE_GATE16_MIN && bh::se_gate16_supports(d.Cexp, (int)G1.cout))
-                        bh::launch_se_gate16(part, tiles, P, pooled, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
-                                             c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
-                    else if (!gate1 && d.Cexp > 576)
-                        bh::launch_se_gate_gemm(part, tiles, P, pooled, hidden, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
-                                                c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
-                    else
-                        bh::launch_se_gate(part, tiles, P, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
-                                           c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
-                };
-                // Round 6 (VERDICT r5 next #3a): a block whose D is large -- the early stages: 1.5-2.3 MB a segment -- runs its three
-                // launches per GROUP of segments, so that the D pass A writes is still in the 256 MB Infinity Cache when the gated
-                // project GEMM reads it (at 1 000 segments a launch it crosses HBM both ways).  The tiling -- hence every pooled sum's
-                // order, hence the bits -- is the whole launch's; only the launches are cut.  c->se_group_bytes: the D one group may
-                // hold (0: never); blocks whose whole D fits run as before.
-                {
-                    const size_t d_seg_bytes = (size_t)d.Ho * d.Wo * d.Cexp * sizeof(float);
-                    size_t grp = (!d.noexp && !d.stem && c->se_group_bytes && d_seg_bytes * n > c->se_group_bytes) ? std::max<size_t>(c->se_group_bytes / d_seg_bytes, 16) : n;
-                    if (grp < n) grp -= grp % (size_t)std::max(d.S, 1);     // (whole S-segment workgroups per group)
-                    if (grp < n) {
-                        const size_t P = (size_t)d.Ho * d.Wo, tiles = (size_t)d.tiles_x * d.tiles_y;
-                        const size_t in_seg = d.stem ? (size_t)d.stem_c * d.stem_h * d.stem_w : (size_t)d.H * d.W * d.Cin;
-                        float *gate = T(S.iPw2 + 1);
-                        float *y = (S.iP == nl - 1) ? d_logits : T(S.iP + 1);
-                        const float *r = LP.res_tensor != bh::NO_TENSOR ? T(LP.res_tensor) : nullptr;
-                        const bool blocked = c->d_w16[S.iP] && bh::pw_gemm16_gated_wants_blocked(d.Cexp, d.Cout, d.Ho * d.Wo);
-                        for (size_t s0 = 0; s0 < n; s0 += grp) {
-                            const size_t ng = std::min(grp, n - s0);
-                            bh::MbDesc g = d;
-                            g.X = in + s0 * in_seg;
-                            g.Dout = T(S.iD + 1) + s0 * P * d.Cexp;
-                            g.pool_part = T(S.iScale + 1) + s0 * tiles * d.Cexp;
-                            g.gate = nullptr;
-                            g.dblk = blocked;
-                            bh::launch_mbconv(g, (int)ng, s);
-                            float *gg = gate + s0 * d.Cexp;
-                            launch_gate(g.pool_part, (int)tiles, (int)P, T(S.iGap + 1) + s0 * d.Cexp, T(S.iPw1 + 1) + s0 * G1.cout, gg, ng);
-                            float *yg = y + s0 * P * d.Cout;
-                            const float *rg = r ? r + s0 * P * d.Cout : nullptr;
-                            if (c->d_w16[S.iP])
-                                c->w16_kernel[S.iP].store(bh::launch_pw_gemm16_gated(g.Dout, gg, (int)P, c->d_w16[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
-                                                           c->w16_terms[S.iP], c->w16_unscale[S.iP], g.dblk, s), std::memory_order_relaxed);
-                            else
-                                bh::launch_pw_gemm_gated(g.Dout, gg, (int)P, c->d_w[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
-                                                         c->ldw[S.iP], (int)LP.act, s);
-                        }
-                        ctx_mark(ctx, ST_MBCONV, (int)i);
-                        i = S.iP;
-                        continue;
-                    }
-                }
-                d.X = in;
-                // (a block without an expand convolution computes D twice instead of keeping it: pass A leaves only the channel sums,
-                //  the gated one-launch block below does the rest -- kernels.hpp MbDesc::gate)
-                // (round 6: the same for the STEM block -- its input, the planar spectrogram, is a tenth of its D -- was built (the stem
-                //  instantiations take MbDesc::gate) and measured on the Perch-sized plan: 38.75 -> 38.45 k segments/s, three alternations
-                //  on one box at one clock, profiles/r6_n_stem_recompute.txt: the sums-only pass costs more than D's round trip saves.
-                //  Not taken; BIRDA_HIP_SE_STEM_RECOMPUTE=1 in the EXPERIMENTS build.)
-                static const bool stem_recompute = [] { const char *e = BH_XENV("BIRDA_HIP_SE_STEM_RECOMPUTE"); return e && e[0] == '1'; }();
-                const bool recompute = d.noexp != 0 || (d.stem != 0 && stem_recompute);
-                d.Dout = recompute ? nullptr : T(S.iD + 1);
-                d.pool_part = T(S.iScale + 1);
-                d.gate = nullptr;
-                // (D blocked for the f16 gated GEMMs: kernels.hpp MbDesc::dblk)
-                d.dblk = !recompute && c->d_w16[S.iP] && bh::pw_gemm16_gated_wants_blocked(d.Cexp, d.Cout, d.Ho * d.Wo);
-                bh::launch_mbconv(d, (int)n, s);
-                ctx_mark(ctx, ST_MBCONV, (int)i);
-                float *gate = T(S.iPw2 + 1);
-                const int P = d.Ho * d.Wo;
-                launch_gate(d.pool_part, d.tiles_x * d.tiles_y, P, T(S.iGap + 1), T(S.iPw1 + 1), gate, n);
-                ctx_mark(ctx, ST_GAP, (int)S.iGap);
-                float *y = (S.iP == nl - 1) ? d_logits : T(S.iP + 1);
-                const float *r = LP.res_tensor != bh::NO_TENSOR ? T(LP.res_tensor) : nullptr;
-                if (recompute) {      // depthwise -> x gate -> project (+ residual) in one launch, the block's own weights and tiling
-                    bh::MbDesc g = d;
-                    g.se = 0; g.gate = gate; g.Y = y; g.R = r; g.Dout = nullptr; g.pool_part = nullptr;
-                    bh::launch_mbconv(g, (int)n, s);
-                } else
-                if (c->d_w16[S.iP])
-                    c->w16_kernel[S.iP].store(bh::launch_pw_gemm16_gated(d.Dout, gate, P, c->d_w16[S.iP], c->d_blob + LP.b_off, r, y, (int)(n * (size_t)P), d.Cexp, d.Cout,
-                                               c->w16_terms[S.iP], c->w16_unscale[S.iP], d.dblk, s), std::memory_order_relaxed);
-                else
-                    bh::launch_pw_gemm_gated(d.Dout, gate, P, c->d_w[S.iP], c->d_blob + LP.b_off, r, y, (int)(n * (size_t)P), d.Cexp, d.Cout,
-                                             c->ldw[S.iP], (int)LP.act, s);
-                ctx_mark(ctx, ST_PW, (int)S.iP);
-                i = S.iP;
-                continue;
-            }
-            const size_t ip = d.noexp ? i + 1 : i + 2;   // the project layer
-            const auto &LP = m.layers[ip];
-            d.X = in;
-            d.Y = (ip == nl - 1) ? d_logits : T(ip + 1);
-            d.R = LP.res_tensor != bh::NO_TENSOR ? T(LP.res_tensor) : nullptr;
-            // BH_FLAG_LOW_LATENCY, a launch of at most 32 segments on the context's own stream: a block of many chunks runs 2 or 4
-            // workgroups deep, each walking its share of the expanded channels (kernels.hpp MbDesc::ksplit) -- a handful of
-            // workgroups on the whole chip each streaming ALL of a late block's weights is what such a forward lasts.  The depth is
-            // the block's alone (never the launch's), so within the regime a segment's bits still do not depend on its launch.
-            const int ksp = (c->low_latency && !lane && n <= kLowLatencyMaxSegments) ? mb_ksplit_of(d) : 1;
-            if (ksp > 1) {
-                if (!ctx->d_partial) {
-                    size_t need = 0;
-                    for (const auto &b : c->mb) need = std::max(need, (size_t)mb_ksplit_of(b) * kLowLatencyMaxSegments * b.Ho * b.Wo * b.Cout);
-                    HIPCHK(hipMalloc((void **)&ctx->d_partial, std::max<size_t>(need, 4) * sizeof(float)));
-                }
-                d.ksplit = ksp;
-                d.partial = ctx->d_partial;
-                bh::launch_mbconv(d, (int)n, s);
-                bh::launch_mb_reduce_partials(ctx->d_partial, d.Y, ksp, n * (size_t)d.Ho * d.Wo * d.Cout, d.prec != 0 ? d.p_unscale : 1.0f, s);
-            } else
-            bh::launch_mbconv(d, (int)n, s);
-            ctx_mark(ctx, ST_MBCONV, (int)i);
-            i = ip;
-            continue;
+        const uint32_t op = m.layers[st.first].op;
+        bh::TraceRange tr(st.block >= 0 ? "fused_mbconv_block" : op < sizeof(kOpNames) / sizeof(kOpNames[0]) ? kOpNames[op] : kOpNames[0]);
+        int rc = BH_OK;
+        switch (st.path) {
+        case BH_PATH_LAYER: rc = r.layer(st); break;
+        case BH_PATH_FUSED: rc = r.fused(st); break;
+        case BH_PATH_FUSED_SE: rc = r.fused_se(st); break;
+        case BH_PATH_HEAD_GAP: rc = r.head_gap(st); break;
+        case BH_PATH_SE_GATE: rc = r.se_gate(st); break;
         }
-        switch (L.op) {
-        case bh::OP_CONV:
-            // the NCHW stem on the direct kernel (when it is not fused into the first block); every NHWC full convolution is an
-            // implicit GEMM on the MFMA (kernels_conv.hip), split-f16 where it has planes
-            if (L.in_layout == 1)
-                bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
-            else if (!ctx->keep_tensors && c->d_w16[i])
-                c->w16_kernel[i].store(bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
-            else
-                bh::launch_conv_gemm(in, c->d_w[i], bias, res, out, p, (int)n, c->ldw[i], s);
-            ctx_mark(ctx, ST_STEM, (int)i);
-            break;
-        case bh::OP_DWCONV:
-            bh::launch_dwconv(in, c->d_w[i], bias, out, p, (int)n, s);
-            ctx_mark(ctx, ST_DW, (int)i);
-            break;
-        case bh::OP_PWCONV:
-            if (!ctx->keep_tensors && c->head_gap[i]) {
-                float *pooled = (i + 1 == nl - 1) ? d_logits : T(i + 2);
-                c->w16_kernel[i].store(bh::launch_head_gap16(in, c->d_w16[i], bias, pooled, (int)n, (int)(L.out_h * L.out_w), (int)L.cin, (int)L.cout,
-                                                             (int)L.act, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
-                ctx_mark(ctx, ST_PW, (int)i);
-                i += 1;   // the pool layer is done
-                break;
-            }
-            if (!ctx->keep_tensors && c->d_w16[i])
-                c->w16_kernel[i].store(bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin, (int)L.cout,
-                                                            (int)L.act, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
-            else
-            bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin,
-                               (int)L.cout, c->ldw[i], (int)L.act, s);
-            ctx_mark(ctx, ST_PW, (int)i);
-            break;
-        case bh::OP_DENSE:
-            if (!ctx->keep_tensors && c->d_w16[i])
-                c->w16_kernel[i].store(bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, (int)L.act,
-                                                            c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
-            else
-            bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, c->ldw[i],
-                               (int)L.act, s);
-            ctx_mark(ctx, ST_DENSE, (int)i);
-            break;
-        case bh::OP_GAP: {
-            // The gate of a squeeze-excite block that runs LAYER BY LAYER (wider than the fused entries -- the v3.0-sized model's
-            // 640 -> 3 840 -> 640 blocks -- or left there by the f32 planner): pool -> 1x1 -> 1x1 were a pool launch and two GEMMs of
-            // M = n rows, the first with a handful of tiles under a K loop of the whole width (171 us per 256 segments for 3 840 ->
-            // 160).  On a small image the two gate launches of the fused path take the whole chain: se_hidden_kernel pools the
-            // depthwise output itself (its "tiles" are the image's pixels, in order), the pool layer's own tensor holds the partial
-            // sums.  Which path a block takes depends on its shapes alone.
-            // (the chain's shapes are checked once, at create: gap_gate_chain; the arena plan keeps the pool layer's tensor, which
-            //  holds the partial sums, apart from the gate's.  A model that ENDS in such a gate gets it in d_logits.)
-            if (!ctx->keep_tensors && c->gap_gate[i]) {
-                const auto &G1 = m.layers[i + 1], &G2 = m.layers[i + 2];
-                const int P = (int)(L.in_h * L.in_w);
-                float *gate = (i + 2 == nl - 1) ? d_logits : T(i + 3);
-                bh::launch_se_gate16(in, P, P, out, c->d_w[i + 1], c->d_blob + G1.b_off, c->ldw[i + 1], (int)G1.act, c->d_w[i + 2],
-                                     c->d_blob + G2.b_off, c->ldw[i + 2], (int)G2.act, gate, (int)n, (int)L.cout, (int)G1.cout, s);
-                ctx_mark(ctx, ST_GAP, (int)i);
-                i += 2;          // the two dense layers of the gate are done
-                break;
-            }
-            bh::launch_gap(in, out, (int)n, (int)(L.in_h * L.in_w), (int)L.cout, s);
-            ctx_mark(ctx, ST_GAP, (int)i);
-            break;
-        }
-        case bh::OP_SCALE:   // squeeze-excite: the feature map times its [n][C] gate (res = the gate tensor)
-            bh::launch_scale(in, res, out, (int)n, (int)(L.out_h * L.out_w), (int)L.cout, s);
-            ctx_mark(ctx, ST_DW, (int)i);
-            break;
-        default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
-        }
+        if (rc != BH_OK) return rc;
     }
     if (d_idx && d_conf) {
         bh::TraceRange tr("topk");
@@ -757,7 +768,7 @@ bool lanes_begin(bh_classifier *c, bh_batch_context *ctx, const std::vector<size
         auto it = ctx->plans.find(ns);
         if (it == ctx->plans.end()) {
             bh_batch_context::ArenaPlan p;
-            plan_arena(c->model, c->fused_at, c->se, c->head_gap, c->gap_gate, ns, false, p.t_off, p.total);
+            plan_arena(c->model, c->sched, ns, false, p.t_off, p.total);
             it = ctx->plans.emplace(ns, std::move(p)).first;
         }
         if (base + it->second.total > ctx->arena_cap) { lanes.clear(); ctx->lane_fallbacks++; return false; }
@@ -1179,18 +1190,15 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
         return (int)BH_OK;
     };
     if (c->precision != 0) {
+        // (a squeeze-excite block: its gate layers run in se_gate_kernel (f32 weights as they are), its project convolution on the
+        //  gated GEMM, which takes planes of ANY K % 4 == 0 (zero-padded to whole 32-deep steps))
         std::vector<char> in_block(m.layers.size(), 0), se_project(m.layers.size(), 0);
         for (size_t i = 0; i < m.layers.size(); i++)
-            if (c->fused_at[i] >= 0 && c->se[c->fused_at[i]].iP != 0) {
-                // a squeeze-excite block: its gate layers run in se_gate_kernel (f32 weights as they are), its project convolution
-                // on the gated GEMM, which takes planes of ANY K % 4 == 0 (zero-padded to whole 32-deep steps)
-                const auto &S = c->se[c->fused_at[i]];
-                for (size_t k = i; k < S.iP; k++) in_block[k] = 1;
-                se_project[S.iP] = 1;
-            } else
             if (c->fused_at[i] >= 0) {
-                in_block[i] = in_block[i + 1] = 1;
-                if (!c->mb[c->fused_at[i]].noexp) in_block[i + 2] = 1;
+                const bh::MbDesc &d = c->mb[c->fused_at[i]];
+                const size_t last = fused_block_last(i, d);
+                for (size_t k = i; k <= last; k++) in_block[k] = 1;
+                if (d.se) { in_block[last] = 0; se_project[last] = 1; }
             }
         for (size_t i = 0; i < m.layers.size(); i++) {
             const auto &L = m.layers[i];
@@ -1232,6 +1240,9 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
     }
     c->gap_gate.assign(m.layers.size(), 0);
     for (size_t i = 0; i < m.layers.size(); i++) c->gap_gate[i] = gap_gate_chain(m, i) ? 1 : 0;
+    c->sched = build_schedule(*c, true, true);
+    c->sched_layers = build_schedule(*c, false, false);
+    c->sched_keep_fused = build_schedule(*c, true, false);
     if (const char *e = BH_XENV("BIRDA_HIP_MB_NARROW_MAX")) c->narrow_max_workgroups = atoi(e);   // (A/B aid: 0 = never)
     if (const char *e = getenv("BIRDA_HIP_SE_GROUP_MB")) c->se_group_bytes = (size_t)atol(e) << 20;   // (MB of D per group of segments; 0: whole launches)
     if (const char *st = BH_XENV("BIRDA_HIP_MB_STAMPS"); st && st[0] == '1' && !c->mb.empty()) {
@@ -1656,27 +1667,13 @@ int bh_audit_arena_plan(bh_classifier *c, bh_batch_context *ctx, size_t n, uint6
     std::vector<size_t> off, sz;
     size_t total = 0;
     // n == 0: the context's own plan (what its forwards of max_batch segments use); else the plan a lane of n segments gets
-    plan_arena(m, c->fused_at, c->se, c->head_gap, c->gap_gate, n ? n : ctx->max_batch, keep, off, total, &sz);
+    const std::vector<Step> &sched = schedule_of(ctx);
+    plan_arena(m, sched, n ? n : ctx->max_batch, keep, off, total, &sz);
     if (!n) off = ctx->t_off;
     for (size_t t = 0; t < nt; t++) { off_floats[t] = off[t]; size_floats[t] = sz[t]; }
-    // the path forward_slice takes at each layer (its dispatch, in its order)
+    // the path the forward takes at each layer: its schedule's
     for (size_t i = 0; i < cap; i++) path[i] = BH_PATH_INNER;
-    for (size_t i = 0; i < nl; i++) {
-        const auto &L = m.layers[i];
-        if ((!keep || ctx->keep_fused) && c->fused_at[i] >= 0) {
-            const auto &S = c->se[c->fused_at[i]];
-            const bool se = S.iP != 0;
-            path[i] = se ? BH_PATH_FUSED_SE : BH_PATH_FUSED;
-            i = se ? S.iP : c->mb[c->fused_at[i]].noexp ? i + 1 : i + 2;
-        } else if (!keep && L.op == bh::OP_PWCONV && c->head_gap[i]) {
-            path[i] = BH_PATH_HEAD_GAP;
-            i += 1;
-        } else if (!keep && L.op == bh::OP_GAP && c->gap_gate[i]) {
-            path[i] = BH_PATH_SE_GATE;
-            i += 2;
-        } else
-            path[i] = BH_PATH_LAYER;
-    }
+    for (const Step &st : sched) path[st.first] = st.path;
     return (int)nt;
 } catch (...) { return on_exception(); }
 
@@ -1804,7 +1801,7 @@ int bh_plan_fused_blocks(const char *model_path, uint32_t flags, int32_t *cfgs, 
             if (n < cap) { if (cfgs) cfgs[n] = tw.cfg; if (layers) layers[n] = (int32_t)i; }
             n++;
         }
-        i += d.noexp ? 1 : 2;
+        i = fused_block_last(i, d);
     }
     return (int)n;
 } catch (...) { return on_exception(); }

@@ -62,6 +62,22 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 #define BH_SE_GATE16_MIN 577
 #endif
 
+// One step of the forward, in stream order: the launches that stand for layers first .. last, and every arena tensor they touch
+// (tensor t = the output of layer t - 1; tensor 0 = the spectrogram).  The schedule -- built once, at create (api_plan.hip
+// build_schedule) -- is the one statement of what the forward launches: forward_slice walks it, plan_arena derives every tensor's
+// lifetime and size from it, bh_audit_arena_plan reports its paths.
+struct Step {
+    uint8_t path = BH_PATH_LAYER;          // BH_PATH_* (birda_hip_audit.h)
+    uint32_t first = 0, last = 0;          // the layers it stands for
+    int block = -1;                        // fused paths: index into mb / mb_small / mb_narrow / se
+    std::vector<uint32_t> reads;           // [0] the input of layer `first`, [1] the residual of layer `last` where it has one
+    std::vector<uint32_t> writes;          // [0] the output of layer `last`: the step's result; [1] (SE block) the depthwise output D
+    // tensors whose slot the step borrows; floats != 0: per segment, instead of the tensor's own size
+    struct Scratch { uint32_t t; size_t floats; };
+    std::vector<Scratch> scratch;          // SE block: SE_* below; gate fast path: the pool's and the hidden layer's tensors
+};
+enum { SE_POOLED = 0, SE_HIDDEN, SE_GATE, SE_SUMS };   // Step::scratch of a fused squeeze-excite block
+
 
 }  // namespace bhi
 
@@ -80,16 +96,21 @@ struct bh_classifier {
     std::vector<size_t> w16_bytes;           // per layer: device bytes of those planes
     bool full_planes = false;                // BH_FLAG_FULL_PLANES: no layer takes two terms
     std::unique_ptr<std::atomic<const char *>[]> w16_kernel;   // per layer: what its split-f16 launcher launched last (a string literal), or null
+    // The per-path decisions of create, as made: build_schedule (api_plan.hip) turns them into the schedules below, and nothing
+    // but it and the exported queries reads them afterwards.
     std::vector<char> head_gap;              // per layer: 1 = this 1x1 conv + GELU and the global average pool after it run as one launch
     // per layer: 1 = this pool layer and the two 1x1 layers after it (a squeeze-excite gate of a block that runs layer by layer) run as
-    // the two gate launches (launch_se_gate16): the pool layer's tensor holds the hidden partial sums until the gate is written.  Decided
-    // once, at create (gap_gate_chain), and read by the forward (api.hip forward_slice) and the arena plan (api_plan.hip plan_arena).
+    // the two gate launches (launch_se_gate16): the pool layer's tensor holds the hidden partial sums until the gate is written
+    // (gap_gate_chain)
     std::vector<char> gap_gate;
+    // What a forward launches: the product's schedule (fused blocks, head conv + pool, the gate fast path), the layer-by-layer one of
+    // BIRDA_HIP_KEEP_TENSORS contexts, and the one of debug contexts that still run the fused blocks (BIRDA_HIP_KEEP_FUSED)
+    std::vector<bhi::Step> sched, sched_layers, sched_keep_fused;
     std::vector<float *> d_owned;            // re-laid buffers to free
     bh::FrontendParams fe{};
     bh::FrontendParams *d_fe = nullptr;      // device copy read by the mel kernel
     std::atomic<const char *> fe_kernel{nullptr};   // what launch_mel launched last (a string literal); nullptr before any forward
-    std::vector<int> fused_at;               // per layer: index into mb (expand layer of a fused block) or -1
+    std::vector<int> fused_at;               // per layer: index into mb (expand layer of a fused block) or -1 (plan_fusion's record)
     std::vector<bh::MbDesc> mb;              // fused MBConv blocks (kernels_mbconv.hip)
     int twin_max_segments = 256;             // launches up to this size take the twins (one workgroup per CU at most either way)
     std::vector<bh::MbDesc> mb_small;        // per block: its small-launch twin (cfg < 0: none), same weights (mb_plan_twin)
@@ -98,7 +119,7 @@ struct bh_classifier {
     // channel sums, which live in the arena slot of the (never materialised) OP_SCALE output
     struct SeInfo { uint32_t iD = 0, iGap = 0, iPw1 = 0, iPw2 = 0, iScale = 0, iP = 0; size_t part_floats = 0; };
     std::vector<SeInfo> se;
-    // squeeze-excite blocks: the D one group of segments may hold between pass A and the gated project GEMM (api.hip forward_slice);
+    // squeeze-excite blocks: the D one group of segments may hold between pass A and the gated project GEMM (api.hip SliceRun::fused_se);
     // 0 = whole launches (round 5).  Measured: profiles/r6_i_se_groups.txt
     size_t se_group_bytes = 0;
     bool low_latency = false;                // BH_FLAG_LOW_LATENCY (birda_hip.h)
@@ -267,10 +288,13 @@ namespace bhi {
 uint16_t f32_to_f16(float f);
 float f16_to_f32(uint16_t h);
 std::vector<float> build_gf(const bh::BranchRec &b, const float *W, int nm_pad, int prec, int *scale_exp);
-void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std::vector<bh_classifier::SeInfo> &se, const std::vector<char> &head_gap,
-                const std::vector<char> &gap_gate, size_t max_batch, bool keep, std::vector<size_t> &off, size_t &total,
+std::vector<Step> build_schedule(const bh_classifier &c, bool fused, bool chains);
+void plan_arena(const bh::Model &m, const std::vector<Step> &sched, size_t max_batch, bool keep, std::vector<size_t> &off, size_t &total,
                 std::vector<size_t> *sizes = nullptr);
 bool gap_gate_chain(const bh::Model &m, size_t i);
+// the last layer of the fused block d planned at layer i: its project convolution, which in a squeeze-excite block comes four
+// layers later (pool, 1x1, 1x1, scale: SeInfo::iP)
+inline size_t fused_block_last(size_t i, const bh::MbDesc &d) { return i + (d.noexp ? 1 : 2) + (d.se ? 4 : 0); }
 bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, size_t i, int precision, int force_cfg, bh::MbDesc &d);
 std::vector<int> tensor_readers(const bh::Model &m);
 // a planned fused block's weights in the kernel's layouts (host vectors; bp empty when spa == 0: the layer's own biases serve)

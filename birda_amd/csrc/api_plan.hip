@@ -90,64 +90,72 @@ std::vector<float> build_gf(const bh::BranchRec &b, const float *W, int nm_pad, 
                 }
     return frag;
 }
-// liveness-based arena plan: tensor t is born at step t (tensor 0 = front-end) and dies after
-// the last layer that reads it; the embedding tensor and the logits live to the end.
-void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std::vector<bh_classifier::SeInfo> &se, const std::vector<char> &head_gap,
-                const std::vector<char> &gap_gate, size_t max_batch, bool keep, std::vector<size_t> &off, size_t &total,
+// What a forward launches, from the decisions create has made (plan_fusion: fused_at / mb / se; head_gap; gap_gate): no decision is
+// made here.  fused: the fused blocks run as such; chains: so do head conv + pool and the gate fast path.
+std::vector<Step> build_schedule(const bh_classifier &c, bool fused, bool chains) {
+    const auto &m = c.model;
+    const uint32_t nl = (uint32_t)m.layers.size();
+    std::vector<Step> sched;
+    for (uint32_t i = 0; i < nl; i++) {
+        Step st;
+        st.first = st.last = i;
+        if (fused && c.fused_at[i] >= 0) {
+            // one launch reads the block input while it writes the project's output; the tensors in between stay in LDS
+            st.block = c.fused_at[i];
+            st.path = c.mb[st.block].se ? BH_PATH_FUSED_SE : BH_PATH_FUSED;
+            st.last = (uint32_t)fused_block_last(i, c.mb[st.block]);
+            if (c.mb[st.block].se) {
+                // a squeeze-excite block = pass A (reads the block input; writes the depthwise output D and, into the slot of the
+                // OP_SCALE output -- the scaled tensor never exists --, the per-tile channel sums), the gate launch (sums -> gate
+                // tensor; the pooled sums and the hidden layer in their layers' slots) and the gated project GEMM (D, gate, residual
+                // -> the block output).  The sums are written long before the step their LAYER would have written that slot at.
+                const auto &S = c.se[st.block];
+                st.writes = {S.iD + 1};
+                st.scratch = {{S.iGap + 1, 0}, {S.iPw1 + 1, 0}, {S.iPw2 + 1, 0}, {S.iScale + 1, S.part_floats}};
+            }
+        } else if (chains && c.head_gap[i]) {
+            // head conv + pool in one launch: workgroups still read the conv's input while finished ones store pooled rows; the
+            // conv's output never exists
+            st.path = BH_PATH_HEAD_GAP;
+            st.last = i + 1;
+        } else if (chains && c.gap_gate[i]) {
+            // the gate of a block that runs layer by layer in two launches (gap_gate_chain): se_hidden_kernel reads the pool's input
+            // and writes its partial sums into the pool layer's tensor, se_gate16_kernel reads them while it writes the gate -- the
+            // same n x C floats.  (The hidden layer's slot is kept as well: its values stay in LDS.)
+            st.path = BH_PATH_SE_GATE;
+            st.last = i + 2;
+            st.scratch = {{i + 1, 0}, {i + 2, 0}};
+        }
+        st.reads = {m.layers[i].in_tensor};
+        if (m.layers[st.last].res_tensor != bh::NO_TENSOR) st.reads.push_back(m.layers[st.last].res_tensor);
+        st.writes.insert(st.writes.begin(), st.last + 1);
+        i = st.last;
+        sched.push_back(std::move(st));
+    }
+    return sched;
+}
+
+// liveness-based arena plan over the schedule: tensor t is born at step t (tensor 0 = front-end); a tensor that a step reads, writes
+// or borrows lives through that step's last layer -- a launch that stands for several layers touches tensors earlier, or later,
+// than their layers would --; the output of a layer inside a step that the step does not touch gets no bytes; the embedding
+// tensor and the logits live to the end.  (keep: every tensor at its own size, end to end.)
+void plan_arena(const bh::Model &m, const std::vector<Step> &sched, size_t max_batch, bool keep, std::vector<size_t> &off, size_t &total,
                 std::vector<size_t> *sizes) {
     const size_t nt = m.layers.size() + 1;
     std::vector<size_t> last(nt, 0), sz(nt);
     for (size_t t = 0; t < nt; t++) { last[t] = t; sz[t] = align_up(m.tensor_floats[t] * max_batch, 64); }
-    for (size_t i = 0; i < m.layers.size(); i++) {
-        const auto &L = m.layers[i];
-        last[L.in_tensor] = std::max(last[L.in_tensor], i + 1);
-        if (L.res_tensor != bh::NO_TENSOR) last[L.res_tensor] = std::max(last[L.res_tensor], i + 1);
-    }
     if (!keep)
-        for (size_t i = 0; i < fused_at.size(); i++) {
-            if (fused_at[i] >= 0 && (size_t)fused_at[i] < se.size() && se[fused_at[i]].iP != 0) {
-                // a squeeze-excite block = pass A (reads the block input; writes the depthwise output D and, into the slot of the
-                // OP_SCALE output, the per-tile channel sums), the gate launch (sums -> gate tensor) and the gated project GEMM
-                // (D, gate, residual -> the block output) at the project layer's step.  Everything those launches touch stays
-                // live until that step: the planner gives a tensor its bytes at the step its LAYER would have written it, and the
-                // sums are written earlier than that (with pass A) -- the block input must not have been handed on by then.
-                const auto &S = se[fused_at[i]];
-                const size_t end = (size_t)S.iP + 1;
-                last[m.layers[i].in_tensor] = std::max(last[m.layers[i].in_tensor], end);
-                last[S.iD + 1] = std::max(last[S.iD + 1], end);
-                last[S.iGap + 1] = std::max(last[S.iGap + 1], end);     // (the pooled sums and the hidden layer of the gate launches:
-                last[S.iPw1 + 1] = std::max(last[S.iPw1 + 1], end);     //  written while the per-tile sums -- born "later" -- are read)
-                last[S.iPw2 + 1] = std::max(last[S.iPw2 + 1], end);
-                last[S.iScale + 1] = std::max(last[S.iScale + 1], end);
-                if (S.iD != i) sz[i + 1] = 0;                                  // the expanded tensor stays in LDS
-                sz[S.iScale + 1] = align_up(S.part_floats * max_batch, 64);  // the scaled tensor never exists
-            } else
-            if (fused_at[i] >= 0) {
-                // one launch reads the block input while it writes the block's last tensor (i + 3; i + 2 for a block without an
-                // expand convolution: depthwise -> project); the tensors in between stay in LDS and take no arena space
-                const size_t len = (i + 2 < m.layers.size() && m.layers[i].op != bh::OP_DWCONV) ? 3 : 2;
-                last[m.layers[i].in_tensor] = std::max(last[m.layers[i].in_tensor], i + len);
-                for (size_t k = 1; k < len; k++) sz[i + k] = 0;
+        for (const Step &st : sched) {
+            auto touch = [&](uint32_t t) { last[t] = std::max(last[t], (size_t)st.last + 1); };
+            for (uint32_t t : st.reads) touch(t);
+            for (uint32_t t : st.writes) touch(t);
+            for (const auto &u : st.scratch) {
+                touch(u.t);
+                if (u.floats) sz[u.t] = align_up(u.floats * max_batch, 64);
             }
+            for (size_t t = (size_t)st.first + 1; t <= st.last; t++)
+                if (last[t] <= st.last) sz[t] = 0;       // (an inner tensor nothing above has touched)
         }
-    if (!keep)
-        for (size_t i = 0; i + 1 < head_gap.size(); i++)
-            if (head_gap[i]) {
-                // head conv + pool in one launch: workgroups still read the conv's input while finished ones store
-                // pooled rows (tensor i+2), so the input lives through step i+2; the conv's output never exists
-                last[m.layers[i].in_tensor] = std::max(last[m.layers[i].in_tensor], i + 2);
-                sz[i + 1] = 0;
-            }
-    if (!keep)
-        for (size_t i = 0; i + 2 < gap_gate.size(); i++)
-            if (gap_gate[i]) {
-                // the gate of a block that runs layer by layer in two launches (gap_gate_chain): se_hidden_kernel writes its partial
-                // sums into the pool layer's tensor (i+1), se_gate16_kernel reads them while it writes the gate (tensor i+3, the
-                // same n x C floats): both tensors of the gate's inputs live through the gate's step, or first-fit hands the
-                // gate the partial sums' bytes
-                last[i + 1] = std::max(last[i + 1], i + 3);
-                last[i + 2] = std::max(last[i + 2], i + 3);
-            }
     last[m.h.embedding_tensor] = nt;
     last[nt - 1] = nt;
     if (sizes) *sizes = sz;
@@ -176,8 +184,8 @@ void plan_arena(const bh::Model &m, const std::vector<int> &fused_at, const std:
 }
 // The pool layer i opens a squeeze-excite gate that runs as the two gate launches (se_hidden_kernel, se_gate16_kernel) instead of pool
 // + two GEMMs: an image of at most 64 pixels, at least BH_SE_GATE16_MIN channels, pool -> 1x1 (C -> Cr) -> 1x1 (Cr -> C) with no
-// other reader of the pooled or the hidden tensor, and a shape se_gate16 supports.  Shapes alone decide; the forward
-// (forward_slice) and the arena plan (plan_arena) both read the answer from bh_classifier::gap_gate.
+// other reader of the pooled or the hidden tensor, and a shape se_gate16 supports.  Shapes alone decide; the answer is recorded in
+// bh_classifier::gap_gate, and build_schedule makes a step of it.
 bool gap_gate_chain(const bh::Model &m, size_t i) {
     const size_t nl = m.layers.size();
     if (i + 2 >= nl) return false;
@@ -278,7 +286,7 @@ bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, s
             if (P.act != bh::ACT_NONE) return false;
             d = bh::MbDesc{};
             d.se = 1;
-            d.dblk = 0;      // (set per forward: api.hip forward_slice)
+            d.dblk = 0;      // (set per forward: api.hip SliceRun::fused_se)
             d.noexp = noexp ? 1 : 0;
             d.H = (int)(noexp ? D.in_h : E.in_h); d.W = (int)(noexp ? D.in_w : E.in_w);
             d.Cin = (int)(noexp ? D.cout : E.cin); d.Cexp = (int)D.cout; d.Cout = (int)P.cout;
@@ -533,8 +541,7 @@ int plan_fusion(bh_classifier *c) {
             S.part_floats = d.se ? tiles * (size_t)d.Cexp : 0;
             c->se.push_back(d.se ? S : bh_classifier::SeInfo{});
         }
-        if (d.se) { i = S.iP; continue; }
-        i += d.noexp ? 1 : 2;
+        i = fused_block_last(i, d);
     }
     return BH_OK;
 }

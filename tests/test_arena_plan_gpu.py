@@ -1,16 +1,21 @@
 """The activation arena's plan against what the forward pass actually reads and writes.
 
 plan_arena (birda_amd/csrc/api_plan.hip) gives every tensor bytes of one arena by liveness: a tensor is born at its layer's step
-and its bytes go to the next tensor once its last reader has run.  Several paths of forward_slice (birda_amd/csrc/api.hip) do not
-follow that picture -- a launch that stands for several layers writes tensors earlier, or reads them later, than their layers
-would -- and each of them needs its own liveness patch in the planner.  A missing one is silent: the bytes are shared, a late
-workgroup reads what an early one wrote over its input, and the logits come out wrong and finite.  Whether that shows on the GPU
-depends on how many workgroups are resident at once, so this file does not run a forward at all: it asks the library for its
-plan (bh_audit_arena_plan: offsets, planned sizes, and the path the forward takes at every layer) and replays the launches of
-forward_slice, restated here from reading it, over the planned bytes:
+and its bytes go to the next tensor once its last reader has run.  Several paths of the forward do not follow that picture -- a
+launch that stands for several layers writes tensors earlier, or reads them later, than their layers would.  The library states
+what the forward launches once, as a schedule built at create (build_schedule: per step its path, its layers, and the tensors it
+reads, writes and borrows); forward_slice (birda_amd/csrc/api.hip) walks that schedule and plan_arena derives every lifetime and
+size from it.  A step that names too few tensors is silent: the bytes are shared, a late workgroup reads what an early one wrote
+over its input, and the logits come out wrong and finite.  Whether that shows on the GPU depends on how many workgroups are
+resident at once, so this file does not run a forward at all: it asks the library for its plan (bh_audit_arena_plan: offsets,
+planned sizes, and the path the forward takes at every layer) and replays the launches of the forward, restated here from reading
+the launch code -- on purpose NOT read from the library's schedule: this is the independent witness -- over the planned bytes:
 
   * no launch writes bytes that the same launch reads or writes as another tensor;
   * every read finds its tensor's bytes untouched since the launch that wrote that tensor.
+
+tests/golden/arena_plans.json holds every audited plan as recorded at the commit it names (totals and digests); a change that is
+not meant to move a tensor leaves them equal, one that is records them again (test_arena_plan_is_the_recorded_one).
 
 The restatement per path (tensor t = output of layer t-1, tensor 0 = the spectrogram):
   plain layer        reads its input (+ residual), writes its output;
@@ -25,6 +30,8 @@ The restatement per path (tensor t = output of layer t-1, tensor 0 = the spectro
 and the embedding tensor is read back after the forward.  The last layer's output goes to the caller's logits buffer.
 """
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -46,6 +53,8 @@ WIDE_GATE_PLAN = dict(sr=48000, n=12000, branches=[(512, 100, 32, 0.0, 3000.0)],
 # its gate is se_gate16 on the fused path (more than 576 expanded channels).
 FUSED_WIDE_SE_PLAN = dict(WIDE_GATE_PLAN, stages=[(1, 3, 1, 16, 1), (6, 3, 2, 24, 1), (6, 3, 2, 40, 1), (6, 3, 1, 112, 1), (6, 3, 1, 112, 1)])
 RANDOM_SEEDS = range(12)
+MODEL_NAMES = ["mini", "mini_b0", "mini_hg", "mini_se", "wide_gate", "fused_wide_se", "tail_gate"] + [f"random{s}" for s in RANDOM_SEEDS]
+RECORDED_PLANS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "arena_plans.json")
 BATCHES = (0, 1, 16, 300, 4096)    # 0: the context's own plan (max_batch 16); the others: the plan an n-segment lane gets
 
 
@@ -230,8 +239,7 @@ def _audit_model(path, m, precision):
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
-@pytest.mark.parametrize("name", ["mini", "mini_b0", "mini_hg", "mini_se", "wide_gate", "fused_wide_se", "tail_gate"] +
-                         [f"random{s}" for s in RANDOM_SEEDS])
+@pytest.mark.parametrize("name", MODEL_NAMES)
 def test_arena_plan_keeps_every_launchs_tensors_apart(models, name, precision):
     path, m = models[name]
     tags, failures = _audit_model(path, m, precision)
@@ -251,3 +259,34 @@ def test_arena_plan_of_the_perch_sized_model(perch, precision):
     tags, failures = _audit_model(path, m, precision)
     assert PATH_FUSED_SE in tags, (precision, sorted(set(tags)))
     assert not failures, "\n".join(failures[:20])
+
+
+def plan_digest(off, sz, tags):
+    """What tests/golden/arena_plans.json records of one plan: the arena's floats, and a SHA-256 over the offsets and the planned
+    sizes (little-endian uint64) and the path tags (uint8)."""
+    h = hashlib.sha256(off.astype("<u8").tobytes() + sz.astype("<u8").tobytes() + np.array(tags, np.uint8).tobytes())
+    return {"total": int((off + sz).max()), "sha256": h.hexdigest()}
+
+
+@pytest.fixture(scope="module")
+def recorded_plans():
+    with open(RECORDED_PLANS) as f:
+        return json.load(f)
+
+
+@pytest.mark.parametrize("precision", ["f32", "f16x3"])
+@pytest.mark.parametrize("name", MODEL_NAMES + ["perch_v2"])
+def test_arena_plan_is_the_recorded_one(models, perch, recorded_plans, name, precision):
+    """Every tensor's offset and planned size and every layer's path tag, for every n of BATCHES, are what the library planned at
+    the commit the golden file names: equality, no forward.  (A change that means to move a tensor records the file again.)"""
+    from birda_amd.classifier import BirdClassifier
+    path, _ = perch if name == "perch_v2" else models[name]
+    clf = BirdClassifier(path, None, precision=precision)
+    ctx = clf.create_batch_context(16)
+    try:
+        got = {n: plan_digest(*arena_plan(clf, ctx, n)) for n in BATCHES}
+    finally:
+        ctx.close()
+        clf.close()
+    want = {n: recorded_plans["plans"][f"{name}/{precision}/{n}"] for n in BATCHES}
+    assert got == want, (f"recorded at {recorded_plans['recorded_at']}", got, want)
