@@ -5,7 +5,8 @@
 / 1x1) with BatchNormalization folded, the activation that follows folded into the producing layer
 (Relu, Clip 0..6, Sigmoid*x, the Div-Erf-Add-Mul-Mul spelling of exact GELU, or a fused `Gelu`),
 residual Add folded into the project conv, squeeze-excite blocks (GlobalAveragePool -> 1x1 Conv -> activation -> 1x1 Conv ->
-Sigmoid -> Mul with the feature map) as pool / 1x1 / 1x1 / OP_SCALE layers, GlobalAveragePool / ReduceMean, Flatten, Gemm / MatMul + Add,
+Sigmoid -> Mul with the feature map) as pool / 1x1 / 1x1 / OP_SCALE layers, MaxPool / AveragePool in floor mode (OP_POOL: any
+window, stride and padding; count_include_pad either way), GlobalAveragePool / ReduceMean, Flatten, Gemm / MatMul + Add,
 final Sigmoid / Softmax as the output activation.  Weights move from ONNX's [Cout, Cin/g, kh, kw] to
 the NHWC-friendly layouts of the kernels.
 
@@ -216,6 +217,17 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
         elif L.op == mf.OP_SCALE:
             g.nodes.append(ox.Node("Mul", [x, names[L.res_tensor]], [tag + "_se"]))
             y = tag + "_se"
+        elif L.op == mf.OP_POOL:
+            # explicit pads: the bottom / right ones are the smallest that give out_h, out_w in floor mode
+            pad_b = max((L.out_h - 1) * L.sh + L.kh - L.in_h - L.pad_t, 0)
+            pad_r = max((L.out_w - 1) * L.sw + L.kw - L.in_w - L.pad_l, 0)
+            if ((L.in_h + L.pad_t + pad_b - L.kh) // L.sh + 1, (L.in_w + L.pad_l + pad_r - L.kw) // L.sw + 1) != (L.out_h, L.out_w):
+                raise ConvertError(f"layer {i}: a pool whose output is cropped has no ONNX spelling")
+            attrs = {"kernel_shape": [L.kh, L.kw], "strides": [L.sh, L.sw], "pads": [L.pad_t, L.pad_l, pad_b, pad_r]}
+            if L.reserved != mf.POOL_MAX:
+                attrs["count_include_pad"] = 1 if L.reserved == mf.POOL_AVG_PAD else 0
+            g.nodes.append(ox.Node("MaxPool" if L.reserved == mf.POOL_MAX else "AveragePool", [x], [tag + "_pool"], attrs, name=tag))
+            y = tag + "_pool"
         elif L.op == mf.OP_DENSE:
             w = m.weight(L.w_off, L.cin * L.cout).reshape(L.cin, L.cout)
             g.nodes.append(ox.Node("Gemm", [x, const(tag + "_w", w), const(tag + "_b", m.weight(L.b_off, L.cout))], [tag + "_fc"],
@@ -234,6 +246,11 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
         out = "probabilities"
     g.outputs.append(ox.ValueInfo(out, ox.FLOAT, ["N", m.n_classes]))
     return g
+
+
+def model_to_onnx(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None) -> bytes:
+    """`graph_from_model` serialised: the bytes of the `.onnx` file `bh_classifier_create` opens."""
+    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling))
 
 
 # ---------------------------------------------------------------------------------------
@@ -399,6 +416,9 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         if t is None:
             raise ConvertError(f"activation on unknown tensor {name_in!r}")
         L = layers[t[0] - 1] if t[0] > 0 else None
+        if L is not None and L.op == mf.OP_POOL:
+            raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a MaxPool / AveragePool "
+                               "(a pool layer carries no activation)")
         if L is None or L.act != mf.ACT_NONE or L.res_tensor != mf.NO_TENSOR:
             raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer")
         L.act = act
@@ -517,6 +537,64 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             layers.append(mf.Layer(mf.OP_GAP, mf.ACT_NONE, t[0], mf.NO_TENSOR, t[1], t[1], t[2], t[3], 1, 1, 0, 0, t[2], t[3], 1, 1))
             tmap[n.outputs[0]] = (len(layers), t[1], 1, 1)
             emb_tensor, emb_dim = len(layers), t[1]
+        elif op in ("MaxPool", "AveragePool"):
+            # windowed pooling in floor mode -> OP_POOL (csrc/onnx_conv.hpp has the same branch)
+            who = f"{op} {n.name!r}: "
+            x = tmap.get(n.inputs[0])
+            if x is None:
+                raise ConvertError(who + f"input {n.inputs[0]!r} is not on the path from {spec!r}")
+            t_in, c, h, w = x
+            if t_in == 0:
+                raise ConvertError(who + "pooling on the planar spectrogram (tensor 0) is not supported")
+            if len(n.outputs) > 1 and n.outputs[1]:
+                raise ConvertError(who + "the second output (Indices) is not supported")
+            ks = n.attrs.get("kernel_shape")
+            if ks is None or len(ks) != 2 or not all(1 <= int(k) <= 64 for k in ks):
+                raise ConvertError(who + "kernel_shape must be two values, each 1 .. 64")
+            kh, kw = int(ks[0]), int(ks[1])
+            st = n.attrs.get("strides") or [1, 1]
+            if len(st) != 2 or not all(1 <= int(v) <= 16 for v in st):
+                raise ConvertError(who + "strides must be 1 .. 16")
+            sh, sw = int(st[0]), int(st[1])
+            if any(d != 1 for d in (n.attrs.get("dilations") or [1, 1])):
+                raise ConvertError(who + "a dilation other than 1 is not supported")
+            if int(n.attrs.get("storage_order", 0)) != 0:
+                raise ConvertError(who + "storage_order = 1 (column-major indices) is not supported")
+            cip, ceil_mode = int(n.attrs.get("count_include_pad", 0)), int(n.attrs.get("ceil_mode", 0))
+            if cip not in (0, 1) or ceil_mode not in (0, 1):
+                raise ConvertError(who + "count_include_pad / ceil_mode must be 0 or 1")
+            auto = n.attrs.get("auto_pad", "NOTSET")
+            auto = auto.decode() if isinstance(auto, bytes) else auto
+            if auto in ("SAME_UPPER", "SAME_LOWER"):
+                oh, ow = -(-h // sh), -(-w // sw)
+                th, tw = max((oh - 1) * sh + kh - h, 0), max((ow - 1) * sw + kw - w, 0)
+                pt, pl = (th // 2, tw // 2) if auto == "SAME_UPPER" else (th - th // 2, tw - tw // 2)
+            elif auto in ("NOTSET", "VALID"):
+                pads = [int(p) for p in ((n.attrs.get("pads") if auto == "NOTSET" else None) or [0, 0, 0, 0])]
+                if len(pads) != 4:
+                    raise ConvertError(who + "pads must be four values")
+                if not all(0 <= p <= 64 for p in pads):
+                    raise ConvertError(who + "pads must be 0 .. 64")
+                pt, pl = pads[0], pads[1]
+                eh, ew = h + pads[0] + pads[2] - kh, w + pads[1] + pads[3] - kw
+                if eh < 0 or ew < 0:
+                    raise ConvertError(who + "kernel larger than the padded input")
+                oh, ow = eh // sh + 1, ew // sw + 1
+                if ceil_mode:   # ONNX: round up, but the last window must start inside the image or its top / left padding
+                    ch, cw = -(-eh // sh) + 1, -(-ew // sw) + 1
+                    ch -= (ch - 1) * sh >= h + pads[0]
+                    cw -= (cw - 1) * sw >= w + pads[1]
+                    if (ch, cw) != (oh, ow):
+                        raise ConvertError(who + f"ceil_mode = 1 changes the output size ({oh}x{ow} -> {ch}x{cw}): only floor-mode windows are supported")
+            else:
+                raise ConvertError(who + f"auto_pad {auto!r}")
+            if oh <= 0 or ow <= 0 or oh > 65536 or ow > 65536:
+                raise ConvertError(who + "empty or oversized output")
+            if pt >= kh or pl >= kw or (oh - 1) * sh - pt >= h or (ow - 1) * sw - pl >= w:
+                raise ConvertError(who + "a window without an in-image tap (it lies in the padding alone)")
+            mode = mf.POOL_MAX if op == "MaxPool" else (mf.POOL_AVG_PAD if cip else mf.POOL_AVG)
+            layers.append(mf.Layer(mf.OP_POOL, mf.ACT_NONE, t_in, mf.NO_TENSOR, c, c, kh, kw, sh, sw, pt, pl, h, w, oh, ow, reserved=mode))
+            tmap[n.outputs[0]] = (len(layers), c, oh, ow)
         elif op in ("Flatten", "Reshape", "Squeeze", "Identity", "Dropout"):
             t = tmap.get(n.inputs[0])
             if t is None:

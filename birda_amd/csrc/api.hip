@@ -324,6 +324,10 @@ int SliceRun::layer(const Step &st) const {
         bh::launch_scale(in, res, out, (int)n, (int)(L.out_h * L.out_w), (int)L.cout, s);
         ctx_mark(ctx, ST_DW, (int)i);
         break;
+    case bh::OP_POOL:    // MaxPool / AveragePool: f32 in every precision mode (L.reserved: the pool mode)
+        bh::launch_pool(in, out, p, (int)L.reserved, (int)n, s);
+        ctx_mark(ctx, ST_GAP, (int)i);
+        break;
     default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
     }
     return BH_OK;
@@ -492,7 +496,7 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
         ctx_mark(ctx, ST_MEL);
     }
     for (const Step &st : schedule_of(ctx)) {
-        static const char *const kOpNames[] = {"layer", "conv", "depthwise", "pointwise", "pool", "dense", "scale"};
+        static const char *const kOpNames[] = {"layer", "conv", "depthwise", "pointwise", "pool", "dense", "scale", "window_pool"};
         const uint32_t op = m.layers[st.first].op;
         bh::TraceRange tr(st.block >= 0 ? "fused_mbconv_block" : op < sizeof(kOpNames) / sizeof(kOpNames[0]) ? kOpNames[op] : kOpNames[0]);
         int rc = BH_OK;
@@ -1153,8 +1157,10 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
             if (rc != BH_OK) return rc;
             c->d_owned.push_back(d);
             c->d_w[i] = d;
-        } else if (L.op == bh::OP_GAP || L.op == bh::OP_SCALE) {
+        } else if (L.op == bh::OP_GAP || L.op == bh::OP_SCALE || L.op == bh::OP_POOL) {
             if (L.cout % 4) return fail(BH_ERR_UNSUPPORTED, "layer %zu: channels %u not a multiple of 4", i, L.cout);
+            if (L.op == bh::OP_POOL && !bh::pool_supports(conv_params(L), (int)L.reserved))
+                return fail(BH_ERR_UNSUPPORTED, "layer %zu: pool %ux%u stride %ux%u pad %u,%u mode %u not built", i, L.kh, L.kw, L.sh, L.sw, L.pad_t, L.pad_l, L.reserved);
         }
     }
     if (m.layers.empty() || m.layers.back().cout != m.h.n_classes)
@@ -1163,9 +1169,9 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
     // residual sits on its project convolution; the planner fuses no depthwise layer that carries one) and the NCHW stem
     for (size_t i = 0; i < m.layers.size(); i++) {
         const auto &L = m.layers[i];
-        if (L.res_tensor != bh::NO_TENSOR && (L.op == bh::OP_DWCONV || L.op == bh::OP_GAP || (L.op == bh::OP_CONV && L.in_layout == 1)))
+        if (L.res_tensor != bh::NO_TENSOR && (L.op == bh::OP_DWCONV || L.op == bh::OP_GAP || L.op == bh::OP_POOL || (L.op == bh::OP_CONV && L.in_layout == 1)))
             return fail(BH_ERR_UNSUPPORTED, "layer %zu: a residual on a %s layer is not supported (only convolutions, 1x1 and full NHWC, "
-                        "and dense layers add one)", i, L.op == bh::OP_DWCONV ? "depthwise" : L.op == bh::OP_GAP ? "pool" : "stem convolution");
+                        "and dense layers add one)", i, L.op == bh::OP_DWCONV ? "depthwise" : (L.op == bh::OP_GAP || L.op == bh::OP_POOL) ? "pool" : "stem convolution");
     }
     rc = plan_fusion(c.get());
     if (rc != BH_OK) return rc;
@@ -1904,13 +1910,14 @@ const char *act_name(int act) {
 }
 
 // the launch's end: wait, check C's guards, copy C and the kernel's name out
-int finish_debug_launch(const char *who, const char *name, const Guarded &dC, float *C, size_t c_floats, char *kernel, size_t kernel_cap) {
+int finish_debug_launch(const char *who, const char *name, const Guarded &dC, float *C, size_t c_floats, char *kernel, size_t kernel_cap,
+                        const char *out_name = "C") {
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     bool intact = false;
     int rc = dC.guards_intact(kUnwrittenNaN, &intact);
     if (rc != BH_OK) return rc;
-    if (!intact) return fail(BH_ERR_INTERNAL, "%s: %s wrote outside C", who, name ? name : "the kernel");
+    if (!intact) return fail(BH_ERR_INTERNAL, "%s: %s wrote outside %s", who, name ? name : "the kernel", out_name);
     HIPCHK(hipMemcpy(C, dC.p(), c_floats * 4, hipMemcpyDeviceToHost));
     if (kernel && kernel_cap) snprintf(kernel, kernel_cap, "%s", name ? name : "");
     return BH_OK;
@@ -1992,6 +1999,24 @@ int bh_debug_layer_gemm(int device, const float *A, const float *W, const float 
                        : terms   ? bh::launch_pw_gemm16(da, dW.p(), db, dr, dc, (int)M, (int)K, (int)N, act, terms, unscale, nullptr)
                                  : bh::launch_pw_gemm(da, (const float *)dW.p(), db, dr, dc, (int)M, (int)K, (int)N, (int)ld, act, nullptr);
     return finish_debug_launch("debug_layer_gemm", name, dC, C, out_rows * N, kernel, kernel_cap);
+} catch (...) { return on_exception(); }
+
+// One pool layer alone on operands of the caller's, through the launcher a forward pass takes (include/birda_hip_pool_debug.h).
+int bh_debug_pool(int device, const float *X, float *Y, size_t n_seg, const int32_t *shape, int mode, char *kernel, size_t kernel_cap) try {
+    if (!X || !Y || !shape || !n_seg) return fail(BH_ERR_INVALID, "debug_pool: bad arguments");
+    const bh::ConvParams p{shape[0], shape[1], shape[2], shape[3], shape[4], shape[4], shape[5], shape[6], shape[7], shape[8], shape[9], shape[10], 0, 0};
+    if (!bh::pool_supports(p, mode))
+        return fail(BH_ERR_UNSUPPORTED, "debug_pool: %dx%d -> %dx%d, %d channels, window %dx%d stride %dx%d pad %d,%d, mode %d: not a pool the model "
+                    "validator accepts (channels a multiple of 4, mode 0..2, every window holding a pixel of the image)",
+                    p.in_h, p.in_w, p.out_h, p.out_w, p.cout, p.kh, p.kw, p.sh, p.sw, p.pad_t, p.pad_l, mode);
+    const size_t x_floats = n_seg * (size_t)p.in_h * p.in_w * p.cout, y_floats = n_seg * (size_t)p.out_h * p.out_w * p.cout;
+    if (x_floats > (size_t)INT32_MAX || y_floats > (size_t)INT32_MAX || n_seg > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_pool: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    Guarded dX, dY;
+    if (!dX.put(X, x_floats * 4, kGuardNaN) || !dY.put(nullptr, y_floats * 4, kUnwrittenNaN)) return fail(BH_ERR_HIP, "debug_pool: device memory");
+    const char *name = bh::launch_pool((const float *)dX.p(), (float *)dY.p(), p, mode, (int)n_seg, nullptr);
+    return finish_debug_launch("debug_pool", name, dY, Y, y_floats, kernel, kernel_cap, "Y");
 } catch (...) { return on_exception(); }
 
 namespace {

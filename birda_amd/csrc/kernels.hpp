@@ -417,6 +417,11 @@ void launch_se_gate(const float *part, int tiles, int P, const float *W1, const 
 void launch_gap(const float *in, float *out, int n_seg, int P, int C, hipStream_t s);
 // squeeze-excite gate: out[n][p][c] = in[n][p][c] * gate[n][c]   (C % 4 == 0)
 void launch_scale(const float *in, const float *gate, float *out, int n_seg, int P, int C, hipStream_t s);
+// windowed pooling (ONNX MaxPool / AveragePool, floor mode), NHWC f32 [n][in_h][in_w][c] -> [n][out_h][out_w][c], c % 4 == 0
+// (kernels_pool.hip).  mode 0: max (a NaN tap makes the output NaN); 1: mean over the in-image taps; 2: mean over kh * kw.  Taps
+// outside the image are never read.  p.cout = channels; p.cin / in_layout / act are not read.  Returns the instantiation's name.
+bool pool_supports(const ConvParams &p, int mode);
+const char *launch_pool(const float *in, float *out, const ConvParams &p, int mode, int n_seg, hipStream_t s);
 // head 1x1 conv + activation (GELU / swish / ReLU6) + global average pool fused (f16 hi / lo weight planes as for launch_pw_gemm16)
 bool head_gap16_supports(int P, int K, int N, int act);
 const char *launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,

@@ -9,7 +9,9 @@
 
 namespace bh {
 
-enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
+enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
+// OP_POOL (ONNX MaxPool / AveragePool, floor mode): the record's `reserved` word is the mode.  No weights, no bias, no activation.
+enum PoolMode : uint32_t { POOL_MAX = 0, POOL_AVG = 1, POOL_AVG_PAD = 2 };   // AVG: over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 constexpr uint32_t NO_TENSOR = 0xFFFFFFFFu;
 
 #pragma pack(push, 1)
@@ -90,18 +92,28 @@ inline bool validate_model(Model &m, std::string &err) {
         m.tensor_floats[i + 1] = (uint64_t)L.out_h * L.out_w * L.cout;
         if (L.in_tensor > i || (L.res_tensor != NO_TENSOR && L.res_tensor > i)) { err = "layer reads a later tensor"; return false; }
         // what the layer reads must be what its input tensor holds (a pool reads in_h x in_w x cout, a dense layer cin values)
-        const uint64_t in_floats = L.op == OP_GAP || L.op == OP_DWCONV || L.op == OP_SCALE ? (uint64_t)L.in_h * L.in_w * L.cout
+        const uint64_t in_floats = L.op == OP_GAP || L.op == OP_DWCONV || L.op == OP_SCALE || L.op == OP_POOL ? (uint64_t)L.in_h * L.in_w * L.cout
                                  : L.op == OP_DENSE ? (uint64_t)L.cin : (uint64_t)L.in_h * L.in_w * L.cin;
         if (in_floats != m.tensor_floats[L.in_tensor]) { err = "layer input shape does not match its tensor"; return false; }
         if (L.res_tensor != NO_TENSOR && L.op != OP_SCALE && m.tensor_floats[L.res_tensor] != m.tensor_floats[i + 1]) {
             err = "residual shape does not match the layer output"; return false;
         }
-        if (L.op < OP_CONV || L.op > OP_SCALE) { err = "unknown layer op"; return false; }
+        if (L.op < OP_CONV || L.op > OP_POOL) { err = "unknown layer op"; return false; }
         const uint64_t wn = L.op == OP_CONV ? (uint64_t)L.kh * L.kw * L.cin * L.cout
                           : L.op == OP_DWCONV ? (uint64_t)L.kh * L.kw * L.cout
                           : (L.op == OP_PWCONV || L.op == OP_DENSE) ? (uint64_t)L.cin * L.cout : 0;
         if (L.op == OP_SCALE && (L.res_tensor == NO_TENSOR || m.tensor_floats[L.res_tensor] != L.cout || L.cin != L.cout)) { err = "scale layer without a [C] gate"; return false; }
-        if (L.op != OP_GAP && L.op != OP_SCALE && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
+        if (L.op == OP_POOL) {
+            if (L.reserved > POOL_AVG_PAD) { err = "pool layer with an unknown mode"; return false; }
+            if (L.cin != L.cout) { err = "pool layer that changes the channel count"; return false; }
+            if (L.act != 0) { err = "pool layer with an activation"; return false; }
+            if (L.res_tensor != NO_TENSOR) { err = "pool layer with a residual"; return false; }
+            if (L.in_layout != 0 || L.in_tensor == 0) { err = "pool layer on the planar spectrogram (tensor 0)"; return false; }
+            // every window holds at least one pixel of the image: max never comes from nothing, the in-image mean never divides by zero
+            if (L.pad_t >= L.kh || L.pad_l >= L.kw || (uint64_t)(L.out_h - 1) * L.sh >= (uint64_t)L.in_h + L.pad_t ||
+                (uint64_t)(L.out_w - 1) * L.sw >= (uint64_t)L.in_w + L.pad_l) { err = "pool layer with a window outside the image"; return false; }
+        }
+        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
                                                    L.b_off + L.cout > m.h.blob_floats)) {
             err = "layer weights outside blob"; return false;
         }

@@ -6,7 +6,8 @@
 //     second witness: tests/test_onnx_native.py holds the two to the same layer table and the same weights, bit for bit):
 //     Conv (1x1 -> pointwise, group == channels -> depthwise, else the stem), BatchNormalization folded into the convolution in
 //     front of it, the activation spellings exporters emit (Relu, Clip(0, 6), Sigmoid x Mul = swish, Div / Erf / Add / Mul / Mul
-//     = GELU, the Gelu operator), residual Add folded into its 1x1 convolution, GlobalAveragePool / ReduceMean over H, W,
+//     = GELU, the Gelu operator), residual Add folded into its 1x1 convolution, MaxPool / AveragePool (floor mode; OP_POOL),
+//     GlobalAveragePool / ReduceMean over H, W,
 //     squeeze-excite gates (pool -> 1x1 -> 1x1 -> Sigmoid -> Mul), Flatten / Reshape / Squeeze / Identity / Dropout after the
 //     pool, Gemm / MatMul + Add, a final Sigmoid or Softmax; NCHW weights re-laid for the NHWC kernels.  Anything else is refused
 //     by operator name.
@@ -336,6 +337,8 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     auto set_act = [&](const std::string &name_in, const std::string &name_out, uint32_t act) {
         T t;
         if (!find(name_in, t)) return fail("activation on unknown tensor '" + name_in + "'");
+        if (t.idx != 0 && layers[t.idx - 1].op == OP_POOL)
+            return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a MaxPool / AveragePool (a pool layer carries no activation)");
         if (t.idx == 0 || layers[t.idx - 1].act != A_NONE || layers[t.idx - 1].res_tensor != NO_TENSOR)
             return fail("activation after '" + name_in + "' cannot be folded into its producer");
         layers[t.idx - 1].act = act;
@@ -495,6 +498,53 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             const uint32_t li = new_layer(OP_GAP, t.idx, NO_TENSOR, t.c, t.c, t.h, t.w, 1, 1, 0, 0, t.h, t.w, 1, 1, 0, 0, 0);
             tmap[n.out[0]] = T{li, t.c, 1, 1};
             emb_tensor = li; emb_dim = t.c;
+        } else if (op == "MaxPool" || op == "AveragePool") {
+            // windowed pooling in floor mode -> OP_POOL (convert.py has the same branch; the two are held to the same records)
+            const std::string who = op + " '" + n.name + "': ";
+            T x;
+            if (!find(n.in[0], x)) return fail(who + "input '" + n.in[0] + "' is not on the path from '" + spec + "'");
+            if (x.idx == 0) return fail(who + "pooling on the planar spectrogram (tensor 0) is not supported");
+            if (n.out.size() > 1 && !n.out[1].empty()) return fail(who + "the second output (Indices) is not supported");
+            const auto *ks = n.ints("kernel_shape");
+            if (!ks || ks->size() != 2 || (*ks)[0] < 1 || (*ks)[1] < 1 || (*ks)[0] > 64 || (*ks)[1] > 64) return fail(who + "kernel_shape must be two values, each 1 .. 64");
+            const int64_t kh = (*ks)[0], kw = (*ks)[1];
+            int64_t sh = 1, sw = 1;
+            if (const auto *st = n.ints("strides")) { if (st->size() != 2) return fail(who + "strides"); sh = (*st)[0]; sw = (*st)[1]; }
+            if (sh <= 0 || sw <= 0 || sh > 16 || sw > 16) return fail(who + "strides must be 1 .. 16");
+            if (const auto *dl = n.ints("dilations")) for (int64_t d : *dl) if (d != 1) return fail(who + "a dilation other than 1 is not supported");
+            if (n.geti("storage_order", 0) != 0) return fail(who + "storage_order = 1 (column-major indices) is not supported");
+            const int64_t cip = n.geti("count_include_pad", 0), ceil_mode = n.geti("ceil_mode", 0);
+            if ((cip != 0 && cip != 1) || (ceil_mode != 0 && ceil_mode != 1)) return fail(who + "count_include_pad / ceil_mode must be 0 or 1");
+            const int64_t h = x.h, w = x.w;
+            int64_t oh, ow, pt = 0, pl = 0;
+            const std::string autop = n.gets("auto_pad", "NOTSET");
+            if (autop == "SAME_UPPER" || autop == "SAME_LOWER") {
+                oh = (h + sh - 1) / sh; ow = (w + sw - 1) / sw;
+                const int64_t th = std::max<int64_t>((oh - 1) * sh + kh - h, 0), tw = std::max<int64_t>((ow - 1) * sw + kw - w, 0);
+                if (autop == "SAME_UPPER") { pt = th / 2; pl = tw / 2; } else { pt = th - th / 2; pl = tw - tw / 2; }
+            } else if (autop == "NOTSET" || autop == "VALID") {
+                int64_t pads[4] = {0, 0, 0, 0};
+                if (autop == "NOTSET")
+                    if (const auto *pd = n.ints("pads")) { if (pd->size() != 4) return fail(who + "pads must be four values"); for (int q = 0; q < 4; q++) pads[q] = (*pd)[q]; }
+                for (int64_t p : pads) if (p < 0 || p > 64) return fail(who + "pads must be 0 .. 64");
+                pt = pads[0]; pl = pads[1];
+                const int64_t eh = h + pads[0] + pads[2] - kh, ew = w + pads[1] + pads[3] - kw;
+                if (eh < 0 || ew < 0) return fail(who + "kernel larger than the padded input");
+                oh = eh / sh + 1; ow = ew / sw + 1;
+                if (ceil_mode) {   // ONNX: round up, but the last window must start inside the image or its top / left padding
+                    int64_t ch = (eh + sh - 1) / sh + 1, cw = (ew + sw - 1) / sw + 1;
+                    if ((ch - 1) * sh >= h + pads[0]) ch--;
+                    if ((cw - 1) * sw >= w + pads[1]) cw--;
+                    if (ch != oh || cw != ow)
+                        return fail(who + "ceil_mode = 1 changes the output size (" + std::to_string(oh) + "x" + std::to_string(ow) + " -> " + std::to_string(ch) + "x" + std::to_string(cw) + "): only floor-mode windows are supported");
+                }
+            } else return fail(who + "auto_pad '" + autop + "'");
+            if (oh <= 0 || ow <= 0 || oh > DIM_MAX || ow > DIM_MAX) return fail(who + "empty or oversized output");
+            if (pt >= kh || pl >= kw || (oh - 1) * sh - pt >= h || (ow - 1) * sw - pl >= w) return fail(who + "a window without an in-image tap (it lies in the padding alone)");
+            const uint32_t li = new_layer(OP_POOL, x.idx, NO_TENSOR, x.c, x.c, (uint32_t)kh, (uint32_t)kw, (uint32_t)sh, (uint32_t)sw, (uint32_t)pt, (uint32_t)pl,
+                                          (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, 0, 0, 0);
+            layers[li - 1].reserved = op == "MaxPool" ? POOL_MAX : cip ? POOL_AVG_PAD : POOL_AVG;
+            tmap[n.out[0]] = T{li, x.c, (uint32_t)oh, (uint32_t)ow};
         } else if (op == "Flatten" || op == "Reshape" || op == "Squeeze" || op == "Identity" || op == "Dropout") {
             T t;
             if (!find(n.in[0], t)) return fail(op + ": input not on the path");

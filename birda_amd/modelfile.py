@@ -33,6 +33,8 @@ MAGIC = b"BHM1"
 VERSION = 1
 
 OP_CONV, OP_DWCONV, OP_PWCONV, OP_GAP, OP_DENSE, OP_SCALE = 1, 2, 3, 4, 5, 6   # OP_SCALE: x[n,h,w,c] * gate[n,c] (squeeze-excite), gate = res_tensor
+OP_POOL = 7   # windowed MaxPool / AveragePool (floor mode); Layer.reserved is the mode; no weights, bias, activation or residual
+POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2   # AVG: mean over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SIGMOID = range(7)
 OUT_NONE, OUT_SIGMOID, OUT_SOFTMAX = 0, 1, 2
 NO_TENSOR = 0xFFFFFFFF
@@ -90,6 +92,7 @@ class Layer:
     in_layout: int = 0  # 0 NHWC, 1 planar NCHW (front-end output)
     w_off: int = 0
     b_off: int = 0
+    reserved: int = 0   # OP_POOL: the pool mode (POOL_MAX / POOL_AVG / POOL_AVG_PAD); 0 for every other op
 
 
 @dataclass
@@ -145,7 +148,7 @@ def write_model(path: str, m: Model) -> None:
         for L in m.layers:
             rec = struct.pack(LAYER_FMT, L.op, L.act, L.in_tensor, L.res_tensor, L.cin, L.cout,
                               L.kh, L.kw, L.sh, L.sw, L.pad_t, L.pad_l, L.in_h, L.in_w,
-                              L.out_h, L.out_w, L.in_layout, 0, L.w_off, L.b_off)
+                              L.out_h, L.out_w, L.in_layout, L.reserved, L.w_off, L.b_off)
             f.write(rec.ljust(LAYER_SIZE, b"\0"))
         f.write(b"\0" * (blob_offset - f.tell()))
         f.write(blob.tobytes())
@@ -167,7 +170,7 @@ def read_model(path: str) -> Model:
     for _ in range(n_l):
         r = struct.unpack_from(LAYER_FMT, raw, off)
         m.layers.append(Layer(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10],
-                              r[11], r[12], r[13], r[14], r[15], r[16], r[18], r[19]))
+                              r[11], r[12], r[13], r[14], r[15], r[16], r[18], r[19], r[17]))
         off += LAYER_SIZE
     m.blob = np.frombuffer(raw, dtype="<f4", count=bfl, offset=boff).copy()
     return m

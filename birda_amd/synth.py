@@ -117,6 +117,20 @@ class _Builder:
         L = mf.Layer(mf.OP_GAP, mf.ACT_NONE, tin, mf.NO_TENSOR, c, c, h, w, 1, 1, 0, 0, h, w, 1, 1)
         return self.add(L)
 
+    def pool(self, tin, h, w, c, kh, kw, sh, sw, mode, pad="same"):
+        """MaxPool / AveragePool (mode: mf.POOL_MAX / POOL_AVG / POOL_AVG_PAD) in floor mode.  pad: 'same' (SAME_UPPER: the extra
+        row / column at the bottom / right), 'same_lower', 'valid', or explicit (top, left, bottom, right)."""
+        if pad in ("same", "same_lower"):
+            oh, ow = -(-h // sh), -(-w // sw)
+            th, tw = max((oh - 1) * sh + kh - h, 0), max((ow - 1) * sw + kw - w, 0)
+            pt, pl = (th // 2, tw // 2) if pad == "same" else (th - th // 2, tw - tw // 2)
+        else:
+            pt, pl, pb, pr = (0, 0, 0, 0) if pad == "valid" else pad
+            oh, ow = (h + pt + pb - kh) // sh + 1, (w + pl + pr - kw) // sw + 1
+        assert oh >= 1 and ow >= 1 and pt < kh and pl < kw and (oh - 1) * sh - pt < h and (ow - 1) * sw - pl < w, "a window outside the image"
+        L = mf.Layer(mf.OP_POOL, mf.ACT_NONE, tin, mf.NO_TENSOR, c, c, kh, kw, sh, sw, pt, pl, h, w, oh, ow, reserved=mode)
+        return self.add(L), oh, ow
+
     def dense(self, tin, cin, cout, gain=1.0, act=mf.ACT_NONE, logits=True):
         wt = self.he((cin, cout), cin) * np.float32(gain)
         b = (self.rng.standard_normal(cout) * 0.5 - 2.0).astype(np.float32) if logits else self.bias(cout)
@@ -161,10 +175,16 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     'birdnet_v30' (the v3.0 contract of the reference's manifest: 5 s / 32 kHz, 11 560 classes with the sigmoid inside the model,
     1 280-d embedding; trunk and front-end [EXT]: B0 on the 128-mel front-end),
     'birdnet_v30_sized' (the same contract on a trunk of the published file's size, every stage MBConv),
-    'birdnet_v30_v2l' (the same contract on EfficientNetV2-L's stage plan: three Fused-MBConv stages, 132 M parameters).
+    'birdnet_v30_v2l' (the same contract on EfficientNetV2-L's stage plan: three Fused-MBConv stages, 132 M parameters),
+    'cnn_pool' (a conv + pool backbone in the VGG / PANNs style on the v2.4 front-end, for timing the pool layers: _build_cnn_pool).
+    'pool_plan' (plan = random_pool_plan(seed)) builds that plan's stack of convolutions, MBConv blocks and pools: _build_pool_plan.
     A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
+    if kind == "cnn_pool":
+        return _build_cnn_pool(seed, n_classes)
+    if kind == "pool_plan":
+        return _build_pool_plan(plan, seed)
     rng = np.random.default_rng(seed)
     b = _Builder(rng)
     act_override, act, hidden = act, mf.ACT_GELU_ERF, 0
@@ -357,6 +377,137 @@ def random_plan(seed: int, big: bool = False) -> dict:
     return {"sr": sr, "n": n, "branches": brs, "stem": stem, "stages": stages, "head": ri(8, 40) * 8, "classes": ri(20, 120),
             "act": act, "se": bool(rng.integers(0, 2)), "out_act": int(rng.choice([mf.OUT_SIGMOID, mf.OUT_SOFTMAX, mf.OUT_SIGMOID])),
             "stem_stride": int(rng.choice([1, 2, 2])), "mag_scale": float(rng.uniform(0.8, 1.5)), "se_div": int(rng.choice([4, 2, 6]))}
+
+
+def _finish(b: _Builder, branches, sr: int, n: int, ncls: int, emb_dim: int, emb_t: int, out_act: int, family: int = 0) -> mf.Model:
+    return mf.Model(family, sr, n, n / float(sr), ncls, emb_dim, out_act, emb_t, branches[0].n_mels, branches[0].n_frames, 1e-6,
+                    branches, b.layers, np.concatenate(b.chunks))
+
+
+def _build_cnn_pool(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) -> mf.Model:
+    """The v2.4 front-end (96 mels x 511 frames, two branches), a 3x3 stride-2 NCHW stem to 32 channels, then four stages of two 3x3
+    ReLU convolutions and a 2x2 stride-2 pool -- widths 32 / 64 / 128 / 256, max pools behind stages 1 and 3, average pools behind
+    2 and 4 --, a 1x1 head of 512 channels, the global pool and the dense layer.  Seeded weights: a model for TIMING the pool
+    layers beside the convolutions they sit between, not for accuracy."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 144000
+    branches = [mf.Branch(2048, 278, 96, 511, 0.0, 3000.0, 1.23), mf.Branch(1024, 280, 96, 511, 500.0, 15000.0, 1.23)]
+    for br in branches:
+        br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+        br.out_scale, br.out_shift = 0.8, -0.4
+    t, h, w = b.conv(0, 96, 511, 2, 32, 3, 2, mf.ACT_RELU, in_layout=1)
+    c = 32
+    for si, width in enumerate((32, 64, 128, 256)):
+        t, h, w = b.conv(t, h, w, c, width, 3, 1, mf.ACT_RELU)
+        t, h, w = b.conv(t, h, w, width, width, 3, 1, mf.ACT_RELU)
+        t, h, w = b.pool(t, h, w, width, 2, 2, 2, 2, mf.POOL_MAX if si % 2 == 0 else mf.POOL_AVG, "valid")
+        c = width
+    t = b.pwconv(t, h, w, c, 512, mf.ACT_RELU)
+    t = emb = b.gap(t, h, w, 512)
+    ncls = n_classes or 6522
+    b.dense(t, 512, ncls, gain=1.5)
+    return _finish(b, branches, sr, n, ncls, 512, emb, mf.OUT_SIGMOID)
+
+
+def random_pool_plan(seed: int) -> dict:
+    """A small seeded stack with windowed pools on the mini front-end (one 32-mel branch, 115 frames of a quarter-second segment):
+    a 3x3 stem, then an MBConv block, a pool DIRECTLY behind it, a down-sampling residual block whose shortcut is
+    conv1x1(pool(x)) -- Add(conv3x3 stride 2 (x), conv1x1(pool(x))), the residual folded on either side --, a second MBConv block
+    or a full convolution, and a last pool.  The three pools take the three modes in a drawn order; kernels 2 / 3 / 5 per axis
+    (non-square included), strides 1 / 2 / 3 per axis, SAME_UPPER / SAME_LOWER / VALID / explicit asymmetric pads.
+    Feed to build_model("pool_plan", plan=...).  plan["items"]: ("mb", expand, k, stride, cout) | ("conv", k, stride, cout) |
+    ("pool", mode, kh, kw, sh, sw, pad) | ("shortcut", cout, mode, k, pad, residual_on_shortcut)."""
+    rng = np.random.default_rng(0x9001 + seed)
+    ri = lambda lo, hi: int(rng.integers(lo, hi + 1))
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+    h, w = 32, 115
+    modes = [int(v) for v in rng.permutation(3)]
+
+    def draw_pool(mode, h, w):
+        while True:
+            kh, kw, sh, sw = pick((2, 3, 5)), pick((2, 3, 5)), pick((1, 2, 3)), pick((1, 2, 3))
+            kind = pick(("same", "same_lower", "valid", "explicit", "explicit"))
+            pad = (ri(0, kh - 1), ri(0, kw - 1), ri(0, kh - 1), ri(0, kw - 1)) if kind == "explicit" else kind
+            if kind in ("same", "same_lower"):
+                oh, ow, pt, pl = -(-h // sh), -(-w // sw), 0, 0
+            else:
+                pt, pl, pb, pr = (0, 0, 0, 0) if kind == "valid" else pad
+                if h + pt + pb < kh or w + pl + pr < kw:
+                    continue
+                oh, ow = (h + pt + pb - kh) // sh + 1, (w + pl + pr - kw) // sw + 1
+            if oh >= 2 and ow >= 2 and (oh - 1) * sh - pt < h and (ow - 1) * sw - pl < w:
+                return ("pool", mode, kh, kw, sh, sw, pad), oh, ow
+
+    stem = pick((8, 16, 24))
+    items = []
+    c = pick((8, 16, 24))
+    items.append(("mb", pick((1, 4, 6)) if c == stem else pick((4, 6)), pick((3, 5)), 1, c))
+    it, h, w = draw_pool(modes[0], h, w)
+    items.append(it)
+    c2 = pick((16, 24, 32))
+    items.append(("shortcut", c2, modes[1], pick((2, 3)), pick(("same", "same_lower")), bool(rng.integers(0, 2))))
+    h, w = -(-h // 2), -(-w // 2)
+    if rng.integers(0, 2):
+        st = pick((1, 2)) if min(h, w) >= 6 else 1
+        items.append(("mb", pick((4, 6)), pick((3, 5)), st, pick((16, 24, 40))))
+    else:
+        st = 1
+        items.append(("conv", 3, 1, pick((16, 32, 64))))
+    h, w = -(-h // st), -(-w // st)
+    it, h, w = draw_pool(modes[2], h, w)
+    items.append(it)
+    return {"items": items, "stem": stem, "act": int(pick((mf.ACT_GELU_ERF, mf.ACT_SWISH, mf.ACT_RELU6))), "head": ri(4, 12) * 8,
+            "classes": ri(20, 60), "out_act": int(pick((mf.OUT_SIGMOID, mf.OUT_SOFTMAX)))}
+
+
+def _build_pool_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
+    """random_pool_plan's stack on the mini front-end of one branch (512-sample frames at hop 100: 32 mels x 115 frames)."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 12000
+    br = mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23)
+    br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+    br.out_scale, br.out_shift = 0.8, -0.4
+    act = int(plan["act"])
+    c = int(plan["stem"])
+    t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, c, 3, 1, act, in_layout=1)
+    for it in plan["items"]:
+        if it[0] == "mb":
+            _, e, k, st, cout = it
+            tin, cin = t, c
+            if e != 1:
+                t = b.pwconv(t, h, w, c, c * e, act)
+            t, h, w = b.dwconv(t, h, w, c * e, k, st, act)
+            res = tin if (st == 1 and cin == cout) else mf.NO_TENSOR
+            t = b.pwconv(t, h, w, c * e, cout, mf.ACT_NONE, res, gain=0.5 if res != mf.NO_TENSOR else 1.0)
+            c = cout
+        elif it[0] == "conv":
+            _, k, st, cout = it
+            t, h, w = b.conv(t, h, w, c, cout, k, st, act)
+            c = cout
+        elif it[0] == "pool":
+            _, mode, kh, kw, sh, sw, pad = it
+            t, h, w = b.pool(t, h, w, c, kh, kw, sh, sw, mode, pad)
+        elif it[0] == "shortcut":
+            # Add(act(conv3x3 stride 2 (x)), conv1x1(pool(x))): the residual rides on whichever convolution comes last
+            _, cout, mode, k, pad, on_shortcut = it
+            x = t
+            if on_shortcut:
+                tm, oh, ow = b.conv(x, h, w, c, cout, 3, 2, act, gain=0.5)
+                tp, ph, pw_ = b.pool(x, h, w, c, k, k, 2, 2, mode, pad)
+                t = b.pwconv(tp, ph, pw_, c, cout, mf.ACT_NONE, tm)
+            else:
+                tp, ph, pw_ = b.pool(x, h, w, c, k, k, 2, 2, mode, pad)
+                ts = b.pwconv(tp, ph, pw_, c, cout, mf.ACT_NONE)
+                t, oh, ow = b.conv(x, h, w, c, cout, 3, 2, act, res=ts, gain=0.5)
+            assert (oh, ow) == (ph, pw_)
+            h, w, c = oh, ow, cout
+        else:
+            raise ValueError(it[0])
+    head, ncls = int(plan["head"]), int(plan["classes"])
+    t = b.pwconv(t, h, w, c, head, act)
+    t = emb = b.gap(t, h, w, head)
+    b.dense(t, head, ncls, gain=1.5)
+    return _finish(b, [br], sr, n, ncls, head, emb, int(plan["out_act"]))
 
 
 def random_fused_plan(seed: int, big: bool = False) -> dict:

@@ -23,8 +23,12 @@ for _ in range(5):
 ctx.synchronize()
 st = ctx.stage_ms(); ly = ctx.layer_ms()
 print({k: round(v[0] / 5 * 1e3 / N, 3) for k, v in st.items()}, "us/segment")
-names = {1: "conv", 2: "dw", 3: "pw", 4: "gap", 5: "dense", 6: "scale"}
+names = {1: "conv", 2: "dw", 3: "pw", 4: "gap", 5: "dense", 6: "scale", 7: "pool"}
 for i, (ms, n) in enumerate(ly):
     if n:
         L = m.layers[i]
-        print(f"layer {i:3d} {names[L.op]:5s} {L.cin:5d}->{L.cout:5d} {L.in_h}x{L.in_w} k{L.kh} s{L.sh}  {ms / 5 * 1e3:9.1f} us per {N}")
+        line = f"layer {i:3d} {names[L.op]:5s} {L.cin:5d}->{L.cout:5d} {L.in_h}x{L.in_w} k{L.kh} s{L.sh}  {ms / 5 * 1e3:9.1f} us per {N}"
+        if L.op == mf.OP_POOL:   # HBM-bound: the bytes it moves (input + output) and the rate
+            nbytes = 4 * N * L.cout * (L.in_h * L.in_w + L.out_h * L.out_w)
+            line += f"  {('max', 'avg', 'avg_pad')[L.reserved]} {L.kh}x{L.kw}/{L.sh}x{L.sw}  {nbytes / 1e6:9.1f} MB  {nbytes / (ms / 5 * 1e-3) / 1e12:5.2f} TB/s"
+        print(line)
