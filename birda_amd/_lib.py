@@ -259,6 +259,12 @@ POOL_DEBUG_SYMBOLS = [
     ("bh_debug_pool", C.c_int, [C.c_int, _VP, _VP, _SZ, _VP, C.c_int, _VP, _SZ]),
 ]
 
+# include/birda_hip_resact_debug.h: the layer kernels alone with the activation after the residual add, act(conv + b + R)
+RESACT_DEBUG_SYMBOLS = [
+    ("bh_debug_conv_gemm_after", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, C.c_int, C.c_int, _VP, _SZ]),
+    ("bh_debug_layer_gemm_after", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ, _SZ, _SZ, _SZ, C.c_int, C.c_int, _VP, _SZ]),
+]
+
 # include/birda_hip_terms_debug.h: which layers run two-term products
 TERMS_DEBUG_SYMBOLS = [
     ("bh_debug_w16_two_terms", C.c_int, [_VP, _SZ, _SZ]),
@@ -287,7 +293,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

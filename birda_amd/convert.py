@@ -4,7 +4,8 @@
 [N, C, H, W] to the logits -- into the layer table `modelfile.py` describes: Conv (group 1 / depthwise
 / 1x1) with BatchNormalization folded, the activation that follows folded into the producing layer
 (Relu, Clip 0..6, Sigmoid*x, the Div-Erf-Add-Mul-Mul spelling of exact GELU, or a fused `Gelu`),
-residual Add folded into the project conv, squeeze-excite blocks (GlobalAveragePool -> 1x1 Conv -> activation -> 1x1 Conv ->
+residual Add folded into the project conv -- with the activation that follows the Add, if any, as that layer's (Layer.reserved =
+RES_ACT_AFTER: act(conv + x), the end of a ResNet block) --, squeeze-excite blocks (GlobalAveragePool -> 1x1 Conv -> activation -> 1x1 Conv ->
 Sigmoid -> Mul with the feature map) as pool / 1x1 / 1x1 / OP_SCALE layers, MaxPool / AveragePool in floor mode (OP_POOL: any
 window, stride and padding; count_include_pad either way), GlobalAveragePool / ReduceMean, Flatten, Gemm / MatMul + Add,
 final Sigmoid / Softmax as the output activation.  Weights move from ONNX's [Cout, Cin/g, kh, kw] to
@@ -199,7 +200,11 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
                                    {"group": group, "kernel_shape": [L.kh, L.kw], "strides": [L.sh, L.sw],
                                     "pads": [L.pad_t, L.pad_l, pad_b, pad_r], "dilations": [1, 1]}, name=tag))
             y = tag + "_conv"
-            if L.res_tensor != mf.NO_TENSOR:   # our executor: act(conv) + residual
+            if L.res_tensor != mf.NO_TENSOR and L.reserved == mf.RES_ACT_AFTER and L.op != mf.OP_DWCONV:
+                # act(conv + residual), the end of a ResNet block: Conv -> Add -> activation
+                g.nodes.append(ox.Node("Add", [y, names[L.res_tensor]], [tag + "_res"]))
+                y = activation(tag + "_res", L.act, tag)
+            elif L.res_tensor != mf.NO_TENSOR:   # our executor: act(conv) + residual
                 y = activation(y, L.act, tag)
                 g.nodes.append(ox.Node("Add", [y, names[L.res_tensor]], [tag + "_res"]))
                 y = tag + "_res"
@@ -312,7 +317,7 @@ def _see_through_casts(g: ox.Graph, front_nodes: set) -> ox.Graph:
 
 def _collapse_activations(g: ox.Graph):
     """Find the multi-node activation spellings.  Returns (skip: set of node indices,
-    act_of: {final output name: (input name, ACT)})."""
+    act_of: {final output name: (input name, ACT, the pattern's own node indices)})."""
     prod = {o: i for i, n in enumerate(g.nodes) for o in n.outputs}
     cons: Dict[str, List[int]] = {}
     for i, n in enumerate(g.nodes):
@@ -358,12 +363,12 @@ def _collapse_activations(g: ox.Graph):
             has_half = any(abs((_scalar(g, a) or 0.0) - 0.5) < 1e-6 for a in others)
             if has_x and has_half:
                 skip |= {j, i, k, m1, m2}
-                act_of[g.nodes[m2].outputs[0]] = (x, mf.ACT_GELU_ERF)
+                act_of[g.nodes[m2].outputs[0]] = (x, mf.ACT_GELU_ERF, (j, i, k, m1, m2))
         elif n.op_type == "Sigmoid":
             k = sole_consumer(n.outputs[0], "Mul")
             if k is not None and n.inputs[0] in g.nodes[k].inputs:
                 skip |= {i, k}
-                act_of[g.nodes[k].outputs[0]] = (n.inputs[0], mf.ACT_SWISH)
+                act_of[g.nodes[k].outputs[0]] = (n.inputs[0], mf.ACT_SWISH, (i, k))
     return skip, act_of
 
 
@@ -411,7 +416,10 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
     out_act, emb_tensor, emb_dim = mf.OUT_NONE, 0, 0
     graph_out = {o.name for o in g.outputs}
 
-    def set_act(name_in: str, name_out: str, act: int):
+    sums = set()   # the outputs of the residual Adds folded into a layer
+
+    def set_act(name_in: str, name_out: str, act: int, own):
+        """own: the node indices of the activation itself -- one, or a multi-node spelling's"""
         t = tmap.get(name_in)
         if t is None:
             raise ConvertError(f"activation on unknown tensor {name_in!r}")
@@ -419,20 +427,29 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         if L is not None and L.op == mf.OP_POOL:
             raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a MaxPool / AveragePool "
                                "(a pool layer carries no activation)")
+        if L is not None and name_in in sums and L.res_tensor != mf.NO_TENSOR and L.reserved != mf.RES_ACT_AFTER:
+            # act(conv + x), the end of a ResNet block: the layer keeps its one activation code and records its position
+            if L.act != mf.ACT_NONE:
+                raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: an activation on both sides of a "
+                                   "residual Add (act2(act1(conv) + x))")
+            if name_in in graph_out or any(name_in in q.inputs for k, q in enumerate(g.nodes) if k not in own):
+                raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: the sum has another reader or is "
+                                   "a graph output (it would be handed the activated tensor)")
+            L.act, L.reserved = act, mf.RES_ACT_AFTER
+            tmap[name_out] = t
+            return
         if L is None or L.act != mf.ACT_NONE or L.res_tensor != mf.NO_TENSOR:
             raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer")
         L.act = act
         tmap[name_out] = t
 
-    for out_name, (x, act) in act_of.items():
-        pass   # applied when the walk reaches the pattern's first node (below)
-    first_of_pattern = {}
-    for out_name, (x, act) in act_of.items():
-        first_of_pattern.setdefault(x, []).append((out_name, act))
+    first_of_pattern = {}   # applied when the walk reaches the pattern's input (below)
+    for out_name, (x, act, own) in act_of.items():
+        first_of_pattern.setdefault(x, []).append((out_name, act, own))
 
     def flush_patterns(x: str):
-        for out_name, act in first_of_pattern.pop(x, []):
-            set_act(x, out_name, act)
+        for out_name, act, own in first_of_pattern.pop(x, []):
+            set_act(x, out_name, act, own)
 
     for i, n in enumerate(g.nodes):
         if i in skip or i in front_nodes:
@@ -507,7 +524,7 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
                 act = mf.ACT_GELU_TANH
             else:
                 act = {"Relu": mf.ACT_RELU, "Gelu": mf.ACT_GELU_ERF, "Clip": mf.ACT_RELU6}[op]
-            set_act(n.inputs[0], n.outputs[0], act)
+            set_act(n.inputs[0], n.outputs[0], act, (i,))
         elif op == "Add":
             a, b = (tmap.get(x) for x in n.inputs)
             if a is None or b is None:
@@ -521,9 +538,11 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
                 if conv and L.res_tensor == mf.NO_TENSOR and r[0] < y[0] and r[1:] == y[1:]:
                     L.res_tensor = r[0]
                     tmap[n.outputs[0]] = y
+                    sums.add(n.outputs[0])
                     break
             else:
                 raise ConvertError(f"Add of {n.inputs}: no convolution to fold the residual into")
+            flush_patterns(n.outputs[0])   # (a multi-node activation behind the sum: act(conv + x))
         elif op in ("GlobalAveragePool", "ReduceMean"):
             t = tmap.get(n.inputs[0])
             if t is None:
@@ -634,7 +653,7 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             t = tmap.get(n.inputs[0])
             if t is None or t[2] * t[3] != 1:
                 raise ConvertError("Sigmoid inside the graph that is neither Sigmoid * x nor a squeeze-excite gate")
-            set_act(n.inputs[0], n.outputs[0], mf.ACT_SIGMOID)
+            set_act(n.inputs[0], n.outputs[0], mf.ACT_SIGMOID, (i,))
         elif op == "Mul":
             a, b = (tmap.get(x) for x in n.inputs)
             if a is None or b is None:

@@ -94,9 +94,14 @@ static bool debug_planes(const float *W, int K, int N, int terms, float *unscale
     return true;
 }
 
+// the layer applies its activation AFTER the residual add (model.hpp RES_ACT_AFTER; `reserved` is the pool mode on OP_POOL)
+bool res_act_after(const bh::LayerRec &L) {
+    return (L.op == bh::OP_CONV || L.op == bh::OP_PWCONV || L.op == bh::OP_DENSE) && L.reserved == bh::RES_ACT_AFTER;
+}
+
 bh::ConvParams conv_params(const bh::LayerRec &L) {
     return bh::ConvParams{(int)L.in_h, (int)L.in_w, (int)L.out_h, (int)L.out_w, (int)L.cin, (int)L.cout, (int)L.kh, (int)L.kw,
-                          (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l, (int)L.in_layout, (int)L.act};
+                          (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l, (int)L.in_layout, (int)L.act, res_act_after(L) ? 1 : 0};
 }
 
 // A full convolution's [kh][kw][cin][cout] weights as the implicit GEMM's K x ld rows: the channels of every tap padded to whole
@@ -279,9 +284,12 @@ int SliceRun::layer(const Step &st) const {
     const auto &L = c->model.layers[i];
     const float *in = this->in(st), *res = this->res(st), *bias = c->d_blob + L.b_off;
     float *out = this->out(st);
-    bh::ConvParams p{(int)L.in_h, (int)L.in_w, (int)L.out_h, (int)L.out_w, (int)L.cin, (int)L.cout,
-                     (int)L.kh, (int)L.kw, (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l,
-                     (int)L.in_layout, (int)L.act};
+    // (a layer with its activation after the residual add is a layer like any other: the position rides in p / after, the f32
+    //  kernels branch on it at run time -- BIRDA_HIP_KEEP_TENSORS contexts and the BH_FLAG_AUTO re-run land there -- and the
+    //  split-f16 launchers pick the AFTER instantiations)
+    const bh::ConvParams p = conv_params(L);
+    const int after = p.res_after;
+    const char *launched = "";      // what a GEMM launcher reports; null: it launched nothing (no such instantiation)
     switch (L.op) {
     case bh::OP_CONV:
         // the NCHW stem on the direct kernel (when it is not fused into the first block); every NHWC full convolution is an
@@ -289,9 +297,9 @@ int SliceRun::layer(const Step &st) const {
         if (L.in_layout == 1)
             bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
         else if (!ctx->keep_tensors && c->d_w16[i])
-            c->w16_kernel[i].store(bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+            c->w16_kernel[i].store(launched = bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
         else
-            bh::launch_conv_gemm(in, c->d_w[i], bias, res, out, p, (int)n, c->ldw[i], s);
+            launched = bh::launch_conv_gemm(in, c->d_w[i], bias, res, out, p, (int)n, c->ldw[i], s);
         ctx_mark(ctx, ST_STEM, (int)i);
         break;
     case bh::OP_DWCONV:
@@ -300,20 +308,20 @@ int SliceRun::layer(const Step &st) const {
         break;
     case bh::OP_PWCONV:
         if (!ctx->keep_tensors && c->d_w16[i])
-            c->w16_kernel[i].store(bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin, (int)L.cout,
-                                                        (int)L.act, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+            c->w16_kernel[i].store(launched = bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin, (int)L.cout,
+                                                        (int)L.act, c->w16_terms[i], c->w16_unscale[i], s, after), std::memory_order_relaxed);
         else
-        bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin,
-                           (int)L.cout, c->ldw[i], (int)L.act, s);
+        launched = bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin,
+                           (int)L.cout, c->ldw[i], (int)L.act, s, after);
         ctx_mark(ctx, ST_PW, (int)i);
         break;
     case bh::OP_DENSE:
         if (!ctx->keep_tensors && c->d_w16[i])
-            c->w16_kernel[i].store(bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, (int)L.act,
-                                                        c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+            c->w16_kernel[i].store(launched = bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, (int)L.act,
+                                                        c->w16_terms[i], c->w16_unscale[i], s, after), std::memory_order_relaxed);
         else
-        bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, c->ldw[i],
-                           (int)L.act, s);
+        launched = bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, c->ldw[i],
+                           (int)L.act, s, after);
         ctx_mark(ctx, ST_DENSE, (int)i);
         break;
     case bh::OP_GAP:
@@ -330,6 +338,8 @@ int SliceRun::layer(const Step &st) const {
         break;
     default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
     }
+    // (create's predicates and validate_model keep this from happening; if it does, the output tensor was not written)
+    if (!launched && n) return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for activation %u %s the residual add", i, L.act, after ? "after" : "before");
     return BH_OK;
 }
 
@@ -1212,7 +1222,8 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
                 // (64 output channels or fewer stay on the f32 MFMA: the split-f16 kernel's 128-column tile would idle half or more
                 //  of its MFMAs there, and the f32 kernel is the faster -- 1.08 against 2.22 ms for 3x3 32 -> 32 at 64 x 249 x 256
                 //  segments, profiles/conv_gemm.txt -- and exact; shapes alone decide)
-                if (!bh::conv_gemm16_supports(conv_params(L)) || L.cout <= 64) continue;
+                //  (a layer with its activation after the add: the same rule, over the activations THAT form is instantiated for)
+                if (!(res_act_after(L) ? bh::conv_gemm16_after_supports(conv_params(L)) : bh::conv_gemm16_supports(conv_params(L))) || L.cout <= 64) continue;
                 const uint32_t cpad = (uint32_t)align_up(L.cin, 32);
                 const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, conv_params(L), (int)L.cout);
                 bool lo_zero = false;
@@ -1222,6 +1233,10 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
                 continue;
             }
             if (in_block[i] || (L.op != bh::OP_PWCONV && L.op != bh::OP_DENSE)) continue;
+            // (activation after the add: the AFTER instantiations' activations, and the full convolutions' width rule -- 64 output
+            //  channels or fewer stay on the f32 MFMA -- so that the end of a ResNet block runs where its 3x3 twin would)
+            if (res_act_after(L)) { if (!bh::pw_gemm16_after_supports((int)L.cin, (int)L.act) || L.cout <= 64) continue; }
+            else
             if (!(se_project[i] ? (L.cin % 4 == 0 && L.act == bh::ACT_NONE) : bh::pw_gemm16_supports((int)L.cin, (int)L.act))) continue;
             bool lo_zero = false;
             std::vector<uint16_t> planes = w16_planes(m.blob.data() + L.w_off, (int)L.cin, (int)L.cout, &c->w16_unscale[i], &lo_zero);
@@ -1927,17 +1942,20 @@ int finish_debug_launch(const char *who, const char *name, const Guarded &dC, fl
 
 // One full convolution on the implicit-GEMM kernels, on operands of the caller's, with the weight preparation create does
 // (conv_gemm_rows, w16_planes) -- tests drive every shape, precision and epilogue instantiation without a model around it.
-int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
-                       const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap) try {
+// (after != 0: bh_debug_conv_gemm_after, include/birda_hip_resact_debug.h -- the activation after the residual add)
+static int debug_conv_gemm(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
+                           const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap, int after) {
     if (!X || !W || !bias || !C || !shape || !n_seg || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
         return fail(BH_ERR_INVALID, "debug_conv_gemm: bad arguments");
+    if (after && !R) return fail(BH_ERR_INVALID, "debug_conv_gemm_after: the residual R is required");
     const bh::ConvParams p{shape[0], shape[1], shape[2], shape[3], shape[4], shape[5], shape[6], shape[7], shape[8], shape[9],
-                           shape[10], shape[11], 0, act};
+                           shape[10], shape[11], 0, act, after ? 1 : 0};
     if (p.in_h < 1 || p.in_w < 1 || p.out_h < 1 || p.out_w < 1)
         return fail(BH_ERR_INVALID, "debug_conv_gemm: image %dx%d -> %dx%d", p.in_h, p.in_w, p.out_h, p.out_w);
-    if (terms ? !bh::conv_gemm16_supports(p) : !bh::conv_gemm_supports(p))
-        return fail(BH_ERR_UNSUPPORTED, "debug_conv_gemm: %dx%d stride %dx%d pad %d,%d, %d -> %d channels, %s not built for terms %d",
-                    p.kh, p.kw, p.sh, p.sw, p.pad_t, p.pad_l, p.cin, p.cout, act_name(act), terms);
+    if (after ? (terms ? !bh::conv_gemm16_after_supports(p) : (!bh::conv_gemm_supports(p) || act == bh::ACT_NONE))
+              : (terms ? !bh::conv_gemm16_supports(p) : !bh::conv_gemm_supports(p)))
+        return fail(BH_ERR_UNSUPPORTED, "debug_conv_gemm%s: %dx%d stride %dx%d pad %d,%d, %d -> %d channels, %s not built for terms %d",
+                    after ? "_after" : "", p.kh, p.kw, p.sh, p.sw, p.pad_t, p.pad_l, p.cin, p.cout, act_name(act), terms);
     const size_t M = n_seg * (size_t)p.out_h * p.out_w, x_floats = n_seg * (size_t)p.in_h * p.in_w * p.cin;
     if (M * (size_t)p.cout > (size_t)INT32_MAX || x_floats > (size_t)INT32_MAX)
         return fail(BH_ERR_INVALID, "debug_conv_gemm: tensors past 2^31 elements");
@@ -1961,12 +1979,22 @@ int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *
                              : bh::launch_conv_gemm((const float *)dX.p(), (const float *)dW.p(), (const float *)dB.p(), dr,
                                                     (float *)dC.p(), p, (int)n_seg, ld, nullptr);
     return finish_debug_launch("debug_conv_gemm", name, dC, C, M * p.cout, kernel, kernel_cap);
+}
+int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
+                       const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap) try {
+    return debug_conv_gemm(device, X, W, bias, R, C, n_seg, shape, act, terms, kernel, kernel_cap, 0);
+} catch (...) { return on_exception(); }
+int bh_debug_conv_gemm_after(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
+                             const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap) try {
+    return debug_conv_gemm(device, X, W, bias, R, C, n_seg, shape, act, terms, kernel, kernel_cap, 1);
 } catch (...) { return on_exception(); }
 
 // A pointwise / dense layer (pool_rows == 0) or the fused head convolution + pool (pool_rows = pixels per segment) on operands of
 // the caller's, with create's weight preparation (pw_gemm_rows, w16_planes), through the launchers a forward pass calls.
-int bh_debug_layer_gemm(int device, const float *A, const float *W, const float *bias, const float *R, float *C, size_t M, size_t K,
-                        size_t N, size_t pool_rows, int act, int terms, char *kernel, size_t kernel_cap) try {
+// (after != 0: bh_debug_layer_gemm_after, include/birda_hip_resact_debug.h)
+static int debug_layer_gemm(int device, const float *A, const float *W, const float *bias, const float *R, float *C, size_t M, size_t K,
+                            size_t N, size_t pool_rows, int act, int terms, char *kernel, size_t kernel_cap, int after) {
+    if (after && (!R || pool_rows)) return fail(BH_ERR_INVALID, "debug_layer_gemm_after: the residual R is required, and no head pool");
     if (!A || !W || !bias || !C || !M || !K || !N || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
         return fail(BH_ERR_INVALID, "debug_layer_gemm: bad arguments");
     if (M * K > (size_t)INT32_MAX || M * N > (size_t)INT32_MAX || K * N > (size_t)INT32_MAX)
@@ -1976,8 +2004,9 @@ int bh_debug_layer_gemm(int device, const float *A, const float *W, const float 
             return fail(BH_ERR_INVALID, "debug_layer_gemm: the head pool takes no residual, split-f16 terms and whole segments");
         if (!bh::head_gap16_supports((int)pool_rows, (int)K, (int)N, act))
             return fail(BH_ERR_UNSUPPORTED, "debug_layer_gemm: head pool of %zu pixels, K %zu, N %zu, %s not built", pool_rows, K, N, act_name(act));
-    } else if (terms ? !bh::pw_gemm16_supports((int)K, act) : K % 4 != 0) {
-        return fail(BH_ERR_UNSUPPORTED, "debug_layer_gemm: K %zu, %s not built for terms %d", K, act_name(act), terms);
+    } else if (after ? (terms ? !bh::pw_gemm16_after_supports((int)K, act) : (K % 4 != 0 || act == bh::ACT_NONE))
+                     : (terms ? !bh::pw_gemm16_supports((int)K, act) : K % 4 != 0)) {
+        return fail(BH_ERR_UNSUPPORTED, "debug_layer_gemm%s: K %zu, %s not built for terms %d", after ? "_after" : "", K, act_name(act), terms);
     }
     HIPCHK(hipSetDevice(device));
     const size_t ld = align_up(N, 4), out_rows = pool_rows ? M / pool_rows : M;
@@ -1996,9 +2025,17 @@ int bh_debug_layer_gemm(int device, const float *A, const float *W, const float 
     const float *da = (const float *)dA.p(), *db = (const float *)dB.p(), *dr = R ? (const float *)dR.p() : nullptr;
     float *dc = (float *)dC.p();
     const char *name = pool_rows ? bh::launch_head_gap16(da, dW.p(), db, dc, (int)out_rows, (int)pool_rows, (int)K, (int)N, act, terms, unscale, nullptr)
-                       : terms   ? bh::launch_pw_gemm16(da, dW.p(), db, dr, dc, (int)M, (int)K, (int)N, act, terms, unscale, nullptr)
-                                 : bh::launch_pw_gemm(da, (const float *)dW.p(), db, dr, dc, (int)M, (int)K, (int)N, (int)ld, act, nullptr);
+                       : terms   ? bh::launch_pw_gemm16(da, dW.p(), db, dr, dc, (int)M, (int)K, (int)N, act, terms, unscale, nullptr, after)
+                                 : bh::launch_pw_gemm(da, (const float *)dW.p(), db, dr, dc, (int)M, (int)K, (int)N, (int)ld, act, nullptr, after);
     return finish_debug_launch("debug_layer_gemm", name, dC, C, out_rows * N, kernel, kernel_cap);
+}
+int bh_debug_layer_gemm(int device, const float *A, const float *W, const float *bias, const float *R, float *C, size_t M, size_t K,
+                        size_t N, size_t pool_rows, int act, int terms, char *kernel, size_t kernel_cap) try {
+    return debug_layer_gemm(device, A, W, bias, R, C, M, K, N, pool_rows, act, terms, kernel, kernel_cap, 0);
+} catch (...) { return on_exception(); }
+int bh_debug_layer_gemm_after(int device, const float *A, const float *W, const float *bias, const float *R, float *C, size_t M, size_t K,
+                              size_t N, size_t pool_rows, int act, int terms, char *kernel, size_t kernel_cap) try {
+    return debug_layer_gemm(device, A, W, bias, R, C, M, K, N, pool_rows, act, terms, kernel, kernel_cap, 1);
 } catch (...) { return on_exception(); }
 
 // One pool layer alone on operands of the caller's, through the launcher a forward pass takes (include/birda_hip_pool_debug.h).

@@ -284,6 +284,8 @@ bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, s
             if (D.kh != D.kw || D.sh != D.sw || (!noexp && E.cout != D.cout) || D.in_layout != 0) return false;
             // (the gated project GEMM has no activation on the f16 MFMA; project convolutions of MBConv blocks have none)
             if (P.act != bh::ACT_NONE) return false;
+            // (an activation AFTER the residual add is not in the fused or the gated kernels' epilogues either: layer by layer)
+            if (P.reserved == bh::RES_ACT_AFTER) return false;
             d = bh::MbDesc{};
             d.se = 1;
             d.dblk = 0;      // (set per forward: api.hip SliceRun::fused_se)
@@ -308,6 +310,7 @@ bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, s
         const auto &D = m.layers[i], &P = m.layers[i + 1];
         if (P.in_tensor != i + 1 || readers[i + 1] != 1 || D.res_tensor != bh::NO_TENSOR) return false;
         if (D.kh != D.kw || D.sh != D.sw || D.cout != P.cin || D.in_layout != 0) return false;
+        if (P.reserved == bh::RES_ACT_AFTER) return false;   // act(project + x): never a fused block's project convolution
         d = bh::MbDesc{};
         d.noexp = 1;
         d.H = (int)D.in_h; d.W = (int)D.in_w; d.Cin = (int)D.cout; d.Cexp = (int)D.cout; d.Cout = (int)P.cout;
@@ -325,6 +328,7 @@ bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, s
     if (D.in_tensor != i + 1 || P.in_tensor != i + 2 || readers[i + 1] != 1 || readers[i + 2] != 1) return false;
     if (E.res_tensor != bh::NO_TENSOR || D.res_tensor != bh::NO_TENSOR) return false;
     if (D.kh != D.kw || D.sh != D.sw || E.cout != D.cout || D.cout != P.cin) return false;
+    if (P.reserved == bh::RES_ACT_AFTER) return false;   // act(project + x): never a fused block's project convolution
     d = bh::MbDesc{};
     d.H = (int)E.in_h; d.W = (int)E.in_w; d.Cin = (int)E.cin; d.Cexp = (int)E.cout; d.Cout = (int)P.cout;
     if (stem) {  // the depthwise conv sees the stem's output image; the stem itself is gathered

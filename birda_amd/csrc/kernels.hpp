@@ -321,6 +321,43 @@ __device__ __forceinline__ void bh_act4(bh_f32x2 &v0, bh_f32x2 &v1) {
 // the activations the MFMA epilogues are instantiated for (layers with any other one run on the f32 layer kernels)
 inline bool act_is_templated(int act) { return act == ACT_GELU_ERF || act == ACT_SWISH || act == ACT_RELU6; }
 
+// The activation AFTER the residual add, act(conv + b + R) (model.hpp RES_ACT_AFTER: the end of a ResNet block).  Its argument
+// holds whatever the residual tensor held, so a NaN must come out as NaN and +inf under ReLU as +inf (BH_FLAG_AUTO and
+// BH_ERR_NONFINITE see an f16 operand overflow only if it reaches the logits).  The clamps are therefore comparisons, whose
+// false branch keeps a NaN, not v_med3_f32 / fmaxf, which return the other operand; still no inline asm (see bh_relu1).
+// swish and the GELUs are arithmetic on v all the way through and pass a NaN on as they are; at an INFINITE argument their fast
+// forms end in inf * 0, a NaN the sum never held, so the two limits -- act(+inf) = +inf, act(-inf) = 0 -- are selected by
+// comparison as well (false for a NaN, which stays).
+__device__ __forceinline__ float bh_relu_keep_nan(float v) { return v < 0.0f ? 0.0f : v; }
+__device__ __forceinline__ float bh_relu6_keep_nan(float v) { return v < 0.0f ? 0.0f : (v > 6.0f ? 6.0f : v); }
+__device__ __forceinline__ float bh_act_limits(float v, float r) {
+    r = v == __builtin_inff() ? v : r;
+    return v == -__builtin_inff() ? 0.0f : r;
+}
+template <int ACT>
+__device__ __forceinline__ float bh_act_after(float v) {
+    if constexpr (ACT == ACT_RELU) return bh_relu_keep_nan(v);
+    else if constexpr (ACT == ACT_RELU6) return bh_relu6_keep_nan(v);
+    else return bh_act_limits(v, bh_act<ACT>(v));
+}
+// The run-time activation of the f32 layer kernels in either position: after == false is act_apply_slow, value for value (what
+// every layer without the position flag gets); after == true the forms above.  ONE switch, so that the kernels, which inline it at
+// every accumulator, hold the exp / tanh / GELU code once (a second switch beside the first doubled them: 1.5 MB of code).
+__device__ __forceinline__ float act_apply_pos(float v, int act, bool after) {
+    switch (act) {
+    case ACT_RELU: return after ? bh_relu_keep_nan(v) : fmaxf(v, 0.f);
+    case ACT_RELU6: return after ? bh_relu6_keep_nan(v) : fminf(fmaxf(v, 0.f), 6.f);
+    case ACT_SWISH: { const float r = v / (1.0f + expf(-v)); return after ? bh_act_limits(v, r) : r; }
+    case ACT_GELU_ERF: { const float r = gelu_erf_fast(v); return after ? bh_act_limits(v, r) : r; }
+    case ACT_GELU_TANH: { const float r = 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v))); return after ? bh_act_limits(v, r) : r; }
+    case ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
+    default: return v;
+    }
+}
+// the activations the split-f16 epilogues are instantiated for in the after-the-add form: the templated three and ReLU, which
+// ResNets use (ReLU BEFORE the add is not a templated activation: act_is_templated, and every unflagged layer, stay as they were)
+inline bool act_is_templated_after(int act) { return act == ACT_RELU || act_is_templated(act); }
+
 // One STFT/mel branch of the front-end, with the Hann window, the
 // real-part DFT and the mel projection folded into one operator Gf[K = L/2][n_mels_pad].
 struct BranchParams {
@@ -359,6 +396,7 @@ const char *launch_mel(const float *x, const float *minmax, float *spec, const F
 
 struct ConvParams {
     int in_h, in_w, out_h, out_w, cin, cout, kh, kw, sh, sw, pad_t, pad_l, in_layout, act;
+    int res_after = 0;   // 1: act(conv + b + R) instead of act(conv + b) + R (the GEMM convolutions only; needs R and an activation)
 };
 // direct conv for the small-Cin NCHW stem; w [kh][kw][cin][cout]
 void launch_conv_direct(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
@@ -368,6 +406,7 @@ void launch_conv_direct(const float *in, const float *w, const float *b, float *
 // the split-f16 planes of launch_pw_gemm16 over that K.  kh, kw 1 .. 7, strides 1 / 2, cin and cout multiples of 4, NHWC input.
 bool conv_gemm_supports(const ConvParams &p);
 bool conv_gemm16_supports(const ConvParams &p);   // ... and an activation the f16 epilogue is instantiated for
+bool conv_gemm16_after_supports(const ConvParams &p);   // the same for a layer with p.res_after: ReLU, ReLU6, swish, erf-GELU
 // (these launchers, launch_pw_gemm, launch_pw_gemm16 and launch_head_gap16 return the instantiation they launched as a static
 //  string with its template arguments, e.g. "conv_gemm_kernel<BM=64,NT=5>", for the diagnostic entry points; the forward pass
 //  ignores it)
@@ -379,8 +418,9 @@ const char *launch_conv_gemm16(const float *in, const void *Wf, const float *b, 
 void launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
                    int n_seg, hipStream_t s);
 // C[M][N] = act(A[M][K] . W[K][ldw] + bias) (+ R); W rows padded to ldw (multiple of 4)
+// (res_after != 0, here and in launch_pw_gemm16: C = act(A . W + bias + R); R and an activation are required)
 const char *launch_pw_gemm(const float *A, const float *W, const float *bias, const float *R, float *C, int M, int K,
-                          int N, int ldw, int act, hipStream_t s);
+                          int N, int ldw, int act, hipStream_t s, int res_after = 0);
 // the same product on the f16 MFMA (terms = 3: hi / lo split operands, f32-grade; 1: plain f16); K % 32 == 0;
 // Wf: fragment-major planes [K / 32][ceil(N / 16)]{hi, lo}[64 lanes][8 halves]
 // The planes hold W * w_scale, w_scale = 1 / w_unscale an exact power of two chosen on the host (f16_weight_scale, api.hip)
@@ -388,11 +428,12 @@ const char *launch_pw_gemm(const float *A, const float *W, const float *bias, co
 // He-normal weight at Cin 1152 is ~2^-5, its lo half a subnormal with 2^-24 absolute resolution); the epilogue computes
 // acc * w_unscale + bias in one FMA.
 bool pw_gemm16_supports(int K, int act);
+bool pw_gemm16_after_supports(int K, int act);   // ... in the after-the-add form: ReLU, ReLU6, swish, erf-GELU
 const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, const float *R, float *C, int M, int K, int N,
-                             int act, int terms, float w_unscale, hipStream_t s);
+                             int act, int terms, float w_unscale, hipStream_t s, int res_after = 0);
 // squeeze-excite blocks (round 5): the project convolution with A = D x gate (gate [M / rows_per_seg][K]; nullptr: plain) ...
 const char *launch_pw_gemm_gated(const float *A, const float *gate, int rows_per_seg, const float *W, const float *bias, const float *R,
-                                 float *C, int M, int K, int N, int ldw, int act, hipStream_t s);
+                                 float *C, int M, int K, int N, int ldw, int act, hipStream_t s, int res_after = 0);
 // ... on the f16 MFMA (no activation; K % 4 == 0, planes [ceil(K / 32)][ceil(N / 16)]{hi, lo}[64][8] zero-padded in K) ...
 // (a_blocked: A in MbDesc::dblk's layout -- every kernel behind this entry reads either; pw_gemm16_gated_wants_blocked: the
 //  shapes whose kernel is the faster for it, a property of the BLOCK, never of the launch)

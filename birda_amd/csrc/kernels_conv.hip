@@ -31,7 +31,7 @@ template <int BM, int NT, bool GATE = false>
 __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ A, const float *__restrict__ W,
                                                        const float *__restrict__ bias, const float *__restrict__ R,
                                                        float *__restrict__ C, int M, int K, int N, int ldw, int act,
-                                                       const float *__restrict__ gate = nullptr, int rows_per_seg = 1) {
+                                                       const float *__restrict__ gate = nullptr, int rows_per_seg = 1, int res_after = 0) {
     constexpr int BN = NT * 16;
     constexpr int WM = BM / 4;
     constexpr int MT = WM / 16;
@@ -144,8 +144,12 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ 
             for (int r = 0; r < 4; r++) {
                 const int row = m0 + wave * WM + i * 16 + kq * 4 + r;
                 if (row < M) {
-                    float v = act_apply(acc[i][j][r] + bv, act);
-                    if (R) v += R[(size_t)row * N + col];
+                    // act(conv + b) + R, or (res_after: the host passes R) act(conv + b + R): the residual added on one side of ONE activation call
+                    float v = acc[i][j][r] + bv;
+                    const float rv = R ? R[(size_t)row * N + col] : 0.0f;
+                    if (res_after) v += rv;
+                    v = act_apply_pos(v, act, res_after != 0);
+                    if (R && !res_after) v += rv;
                     C[(size_t)row * N + col] = v;
                 }
             }
@@ -154,10 +158,10 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(const float *__restrict__ 
 
 template <int BM, int NT>
 static void pw_launch(const float *A, const float *W, const float *bias, const float *R, float *C, int M, int K,
-                      int N, int ldw, int act, hipStream_t s, const float *gate = nullptr, int rows_per_seg = 1) {
+                      int N, int ldw, int act, hipStream_t s, const float *gate = nullptr, int rows_per_seg = 1, int res_after = 0) {
     dim3 grid((N + NT * 16 - 1) / (NT * 16), (M + BM - 1) / BM), block(256);
-    if (gate) hipLaunchKernelGGL((pw_gemm_kernel<BM, NT, true>), grid, block, 0, s, A, W, bias, R, C, M, K, N, ldw, act, gate, rows_per_seg);
-    else hipLaunchKernelGGL((pw_gemm_kernel<BM, NT, false>), grid, block, 0, s, A, W, bias, R, C, M, K, N, ldw, act, nullptr, 1);
+    if (gate) hipLaunchKernelGGL((pw_gemm_kernel<BM, NT, true>), grid, block, 0, s, A, W, bias, R, C, M, K, N, ldw, act, gate, rows_per_seg, res_after);
+    else hipLaunchKernelGGL((pw_gemm_kernel<BM, NT, false>), grid, block, 0, s, A, W, bias, R, C, M, K, N, ldw, act, nullptr, 1, res_after);
 }
 
 // pick the widest column tile that wastes the fewest padded columns
@@ -173,21 +177,22 @@ static int pick_nt(int N) {
 }
 
 const char *launch_pw_gemm(const float *A, const float *W, const float *bias, const float *R, float *C, int M, int K,
-                          int N, int ldw, int act, hipStream_t s) {
-    return launch_pw_gemm_gated(A, nullptr, 1, W, bias, R, C, M, K, N, ldw, act, s);
+                          int N, int ldw, int act, hipStream_t s, int res_after) {
+    return launch_pw_gemm_gated(A, nullptr, 1, W, bias, R, C, M, K, N, ldw, act, s, res_after);
 }
 
 // the same GEMM with A = D x gate (gate [M / rows_per_seg][K], nullptr: plain): the project convolution of a squeeze-excite block
 const char *launch_pw_gemm_gated(const float *A, const float *gate, int rows_per_seg, const float *W, const float *bias, const float *R,
-                                 float *C, int M, int K, int N, int ldw, int act, hipStream_t s) {
+                                 float *C, int M, int K, int N, int ldw, int act, hipStream_t s, int res_after) {
+    if (res_after && (!R || act == ACT_NONE)) return nullptr;   // (the position needs a residual and an activation: nothing launched)
     const int nt = pick_nt(N);
     const long blocks128 = (long)((M + 127) / 128) * ((N + nt * 16 - 1) / (nt * 16));
     const bool small = blocks128 < 512;  // keep >= 2 blocks per CU in flight when M is short
     const char *name = nullptr;
 #define BH_PW_CASE(NTV)                                                                    \
     case NTV:                                                                              \
-        if (small) pw_launch<64, NTV>(A, W, bias, R, C, M, K, N, ldw, act, s, gate, rows_per_seg);             \
-        else pw_launch<128, NTV>(A, W, bias, R, C, M, K, N, ldw, act, s, gate, rows_per_seg);                  \
+        if (small) pw_launch<64, NTV>(A, W, bias, R, C, M, K, N, ldw, act, s, gate, rows_per_seg, res_after);  \
+        else pw_launch<128, NTV>(A, W, bias, R, C, M, K, N, ldw, act, s, gate, rows_per_seg, res_after);       \
         name = gate ? (small ? "pw_gemm_kernel<BM=64,NT=" #NTV ",GATE>" : "pw_gemm_kernel<BM=128,NT=" #NTV ",GATE>")   \
                     : (small ? "pw_gemm_kernel<BM=64,NT=" #NTV ">" : "pw_gemm_kernel<BM=128,NT=" #NTV ">");            \
         break;
@@ -216,7 +221,10 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // skipped.  BH_PL is the number of planes a (k step, column tile) pair holds in the global layout; TERMS 1 and 3 keep theirs.
 #define BH_PL(T) ((T) == 2 ? 1 : 2)
 
-template <int TERMS, int ACT>
+// AFTER (here and in the three kernels below that take R ungated): the epilogue is act(acc + bias + R) instead of act(acc + bias) + R
+// -- the end of a ResNet block (model.hpp RES_ACT_AFTER).  Compile time, `if constexpr`: the instantiations without it keep their
+// epilogue, instruction for instruction, and their names.  R is then required (the launchers see to it).
+template <int TERMS, int ACT, bool AFTER = false>
 __global__ __launch_bounds__(256) void pw_gemm16_kernel(const float *__restrict__ A, const f16x8 *__restrict__ Wf,
                                                          const float *__restrict__ bias, const float *__restrict__ R,
                                                          float *__restrict__ C, int M, int K, int N, int n_tiles, float w_unscale) {
@@ -301,8 +309,8 @@ __global__ __launch_bounds__(256) void pw_gemm16_kernel(const float *__restrict_
                     // the activation is a template argument: a run-time switch inlined 64 times bloats
                     // the kernel past the instruction cache
                     float v = __builtin_fmaf(acc[i][j][r], w_unscale, bv);   // the planes hold W / w_unscale
-                    v = bh_act<ACT>(v);
-                    if (R) v += R[(size_t)row * N + col];
+                    if constexpr (AFTER) v = bh_act_after<ACT>(v + R[(size_t)row * N + col]);
+                    else { v = bh_act<ACT>(v); if (R) v += R[(size_t)row * N + col]; }
                     C[(size_t)row * N + col] = v;
                 }
             }
@@ -317,7 +325,7 @@ __global__ __launch_bounds__(256) void pw_gemm16_kernel(const float *__restrict_
 // flight (128 registers), four waves a workgroup, ceil(n_tiles / 8) workgroups.  Per element the same products in the same order
 // as the other two kernels: the same bits.
 // ---------------------------------------------------------------------------------------
-template <int TERMS, int ACT>
+template <int TERMS, int ACT, bool AFTER = false>
 __global__ __launch_bounds__(256) void pw_gemm16_skinny_kernel(const float *__restrict__ A, const f16x8 *__restrict__ Wf,
                                                                 const float *__restrict__ bias, const float *__restrict__ R,
                                                                 float *__restrict__ C, int M, int K, int N, int n_tiles, float w_unscale) {
@@ -374,8 +382,8 @@ __global__ __launch_bounds__(256) void pw_gemm16_skinny_kernel(const float *__re
             const int row = kq * 4 + r;
             if (row < M) {
                 float v = __builtin_fmaf(acc[j][r], w_unscale, bv);
-                v = bh_act<ACT>(v);
-                if (R) v += R[(size_t)row * N + col];
+                if constexpr (AFTER) v = bh_act_after<ACT>(v + R[(size_t)row * N + col]);
+                else { v = bh_act<ACT>(v); if (R) v += R[(size_t)row * N + col]; }
                 C[(size_t)row * N + col] = v;
             }
         }
@@ -399,7 +407,7 @@ __global__ __launch_bounds__(256) void pw_gemm16_skinny_kernel(const float *__re
 // are zero-padded on the host.
 // NTB: column tiles (of 16) per workgroup -- 8 for the dense layers; the gated project convolutions pick 6, 8 or 10 to fit N = 96, 136,
 // 232, 384 with little padding (wave (wm, wn) owns 64 rows x NTB / 2 column tiles)
-template <int TERMS, int ACT, bool GATE = false, int NTB = 8, bool BLK = false>
+template <int TERMS, int ACT, bool GATE = false, int NTB = 8, bool BLK = false, bool AFTER = false>
 __global__ __launch_bounds__(256, 2) void pw_gemm16s_kernel(const float *__restrict__ A, const f16x8 *__restrict__ Wf,
                                                             const float *__restrict__ bias, const float *__restrict__ R,
                                                             float *__restrict__ C, int M, int K, int N, int n_tiles, float w_unscale,
@@ -408,6 +416,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm16s_kernel(const float *__restr
     constexpr int STAGE = (8 + NTB) * 2 * 256;                    // floats per stage (32 KB at NTB = 8)
     constexpr int NJ = NTB / 2;                                   // column tiles per wave
     static_assert(NTB % 2 == 0 && NTB >= 2 && NTB <= 12, "column tiles per workgroup");
+    static_assert(!(AFTER && GATE), "the gated project GEMMs have no after-the-add form");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
     const int wm = wave >> 1, wn = wave & 1;
@@ -543,8 +552,8 @@ __global__ __launch_bounds__(256, 2) void pw_gemm16s_kernel(const float *__restr
                 const int row = m0 + i * 16 + kq * 4 + r;
                 if (row < M) {
                     float v = __builtin_fmaf(acc[i][j][r], w_unscale, bv);   // the planes hold W / w_unscale
-                    v = bh_act<ACT>(v);
-                    if (R) v += R[(size_t)row * N + col];
+                    if constexpr (AFTER) v = bh_act_after<ACT>(v + R[(size_t)row * N + col]);
+                    else { v = bh_act<ACT>(v); if (R) v += R[(size_t)row * N + col]; }
                     C[(size_t)row * N + col] = v;
                 }
             }
@@ -552,6 +561,7 @@ __global__ __launch_bounds__(256, 2) void pw_gemm16s_kernel(const float *__restr
 }
 
 bool pw_gemm16_supports(int K, int act) { return K % 32 == 0 && (act == ACT_NONE || act_is_templated(act)); }
+bool pw_gemm16_after_supports(int K, int act) { return K % 32 == 0 && act_is_templated_after(act); }
 
 // ---------------------------------------------------------------------------------------
 // The gated project convolution of the EARLY squeeze-excite blocks: very many rows (16 000 pixels a segment), few columns
@@ -1014,7 +1024,8 @@ const char *launch_pw_gemm16_gated(const float *A, const float *gate, int rows_p
 }
 
 const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, const float *R, float *C, int M, int K, int N,
-                             int act, int terms, float w_unscale, hipStream_t s) {
+                             int act, int terms, float w_unscale, hipStream_t s, int res_after) {
+    if (res_after && (!R || !act_is_templated_after(act))) return nullptr;   // (no such instantiation: nothing launched)
     const int n_tiles = (N + 15) / 16;
     const int n_xb = (n_tiles + 7) / 8, n_yb = (M + 127) / 128;
     dim3 grid((unsigned)(8 * ((n_xb + 7) / 8) * n_yb)), block(256);   // (one-dimensional: the kernel deals the blocks XCD by XCD)
@@ -1028,36 +1039,46 @@ const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, 
     const int n_xb_s = (n_tiles + ntb - 1) / ntb;
     const dim3 grid_s((unsigned)(8 * ((n_xb_s + 7) / 8) * n_yb));
     const char *name = nullptr;
-#define BH_G16S(T, ACTV, AN, NTBV)                                                                                                \
+    // (AFT, AFN: the after-the-add instantiations and the suffix their names carry, ",AFTER"; the others' names are what they were)
+#define BH_G16S(T, ACTV, AN, NTBV, AFT, AFN)                                                                                      \
     do {                                                                                                                          \
         constexpr size_t lds = 2 * ((8 + NTBV) * 2 * 256) * sizeof(float);                                                        \
         static DeviceOnce attr;                                                                                                   \
-        attr.run([] { (void)hipFuncSetAttribute((const void *)pw_gemm16s_kernel<T, ACTV, false, NTBV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }); \
-        hipLaunchKernelGGL((pw_gemm16s_kernel<T, ACTV, false, NTBV>), grid_s, block, lds, s, A, (const f16x8 *)Wf, bias, R, C, M, K, N, n_tiles, w_unscale); \
-        name = "pw_gemm16s_kernel<" #T "," AN ",NTB=" #NTBV ">";                                                                 \
+        attr.run([] { (void)hipFuncSetAttribute((const void *)pw_gemm16s_kernel<T, ACTV, false, NTBV, false, AFT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); }); \
+        hipLaunchKernelGGL((pw_gemm16s_kernel<T, ACTV, false, NTBV, false, AFT>), grid_s, block, lds, s, A, (const f16x8 *)Wf, bias, R, C, M, K, N, n_tiles, w_unscale); \
+        name = "pw_gemm16s_kernel<" #T "," AN AFN ",NTB=" #NTBV ">";                                                             \
     } while (0)
-#define BH_G16(T, ACTV, AN)                                                                                                       \
+#define BH_G16(T, ACTV, AN, AFT, AFN)                                                                                             \
     do {                                                                                                                          \
         if (staged) {                                                                                                             \
-            if (ntb == 8) BH_G16S(T, ACTV, AN, 8); else if (ntb == 4) BH_G16S(T, ACTV, AN, 4); else BH_G16S(T, ACTV, AN, 2);      \
+            if (ntb == 8) BH_G16S(T, ACTV, AN, 8, AFT, AFN); else if (ntb == 4) BH_G16S(T, ACTV, AN, 4, AFT, AFN); else BH_G16S(T, ACTV, AN, 2, AFT, AFN); \
         } else if (M <= 32) {    /* one or two row tiles: the skinny kernel per row tile, eight steps in flight (the same bits) */ \
             for (int m0 = 0; m0 < M; m0 += 16)                                                                                    \
-                hipLaunchKernelGGL((pw_gemm16_skinny_kernel<T, ACTV>), dim3((unsigned)((n_tiles + 7) / 8)), block, 0, s, A + (size_t)m0 * K, (const f16x8 *)Wf, bias, \
+                hipLaunchKernelGGL((pw_gemm16_skinny_kernel<T, ACTV, AFT>), dim3((unsigned)((n_tiles + 7) / 8)), block, 0, s, A + (size_t)m0 * K, (const f16x8 *)Wf, bias, \
                                    R ? R + (size_t)m0 * N : nullptr, C + (size_t)m0 * N, std::min(16, M - m0), K, N, n_tiles, w_unscale); \
-            name = "pw_gemm16_skinny_kernel<" #T "," AN ">";                                                                     \
+            name = "pw_gemm16_skinny_kernel<" #T "," AN AFN ">";                                                                 \
         } else {                                                                                                                  \
-            hipLaunchKernelGGL((pw_gemm16_kernel<T, ACTV>), grid, block, 0, s, A, (const f16x8 *)Wf, bias, R, C, M, K, N, n_tiles, w_unscale); \
-            name = "pw_gemm16_kernel<" #T "," AN ">";                                                                            \
+            hipLaunchKernelGGL((pw_gemm16_kernel<T, ACTV, AFT>), grid, block, 0, s, A, (const f16x8 *)Wf, bias, R, C, M, K, N, n_tiles, w_unscale); \
+            name = "pw_gemm16_kernel<" #T "," AN AFN ">";                                                                        \
         }                                                                                                                         \
     } while (0)
 #define BH_G16A(T)                                                   \
     switch (act) {                                                   \
-    case ACT_GELU_ERF: BH_G16(T, ACT_GELU_ERF, "GELU"); break;       \
-    case ACT_SWISH: BH_G16(T, ACT_SWISH, "SWISH"); break;            \
-    case ACT_RELU6: BH_G16(T, ACT_RELU6, "RELU6"); break;            \
-    default: BH_G16(T, ACT_NONE, "NONE"); break;                     \
+    case ACT_GELU_ERF: BH_G16(T, ACT_GELU_ERF, "GELU", false, ""); break; \
+    case ACT_SWISH: BH_G16(T, ACT_SWISH, "SWISH", false, ""); break; \
+    case ACT_RELU6: BH_G16(T, ACT_RELU6, "RELU6", false, ""); break; \
+    default: BH_G16(T, ACT_NONE, "NONE", false, ""); break;          \
     }
-    if (terms == 3) { BH_G16A(3) } else if (terms == 2) { BH_G16A(2) } else { BH_G16A(1) }
+#define BH_G16AA(T)                                                  \
+    switch (act) {                                                   \
+    case ACT_GELU_ERF: BH_G16(T, ACT_GELU_ERF, "GELU", true, ",AFTER"); break; \
+    case ACT_SWISH: BH_G16(T, ACT_SWISH, "SWISH", true, ",AFTER"); break; \
+    case ACT_RELU6: BH_G16(T, ACT_RELU6, "RELU6", true, ",AFTER"); break; \
+    default: BH_G16(T, ACT_RELU, "RELU", true, ",AFTER"); break;     \
+    }
+    if (res_after) { if (terms == 3) { BH_G16AA(3) } else if (terms == 2) { BH_G16AA(2) } else { BH_G16AA(1) } }
+    else if (terms == 3) { BH_G16A(3) } else if (terms == 2) { BH_G16A(2) } else { BH_G16A(1) }
+#undef BH_G16AA
 #undef BH_G16A
 #undef BH_G16
 #undef BH_G16S
@@ -1488,8 +1509,11 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const float *__restrict_
             for (int r = 0; r < 4; r++) {
                 const int row = m0 + wave * WM + i * 16 + kq * 4 + r;
                 if (row < M) {
-                    float v = act_apply(acc[i][j][r] + bv, p.act);
-                    if (R) v += R[(size_t)row * N + col];
+                    float v = acc[i][j][r] + bv;          // (the two positions: see pw_gemm_kernel)
+                    const float rv = R ? R[(size_t)row * N + col] : 0.0f;
+                    if (p.res_after) v += rv;
+                    v = act_apply_pos(v, p.act, p.res_after != 0);
+                    if (R && !p.res_after) v += rv;
                     C[(size_t)row * N + col] = v;
                 }
             }
@@ -1500,7 +1524,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const float *__restrict_
 // consecutive channels of its four rows' tap straight into registers one step ahead and splits them there.  Blocks run
 // column block fastest: the blocks that read the same rows of X are adjacent (X is gathered kh kw times per row; those
 // re-reads come from L2), and W -- at most a few MB -- stays in L2 for all of them.
-template <int TERMS, int ACT>
+template <int TERMS, int ACT, bool AFTER = false>
 __global__ __launch_bounds__(256) void conv_gemm16_kernel(const float *__restrict__ X, const f16x8 *__restrict__ Wf,
                                                            const float *__restrict__ bias, const float *__restrict__ R,
                                                            float *__restrict__ C, ConvParams p, int M, int n_tiles, float w_unscale) {
@@ -1581,8 +1605,8 @@ __global__ __launch_bounds__(256) void conv_gemm16_kernel(const float *__restric
                 const int row = m0 + i * 16 + kq * 4 + r;
                 if (row < M) {
                     float v = __builtin_fmaf(acc[i][j][r], w_unscale, bv);   // the planes hold W / w_unscale
-                    v = bh_act<ACT>(v);
-                    if (R) v += R[(size_t)row * N + col];
+                    if constexpr (AFTER) v = bh_act_after<ACT>(v + R[(size_t)row * N + col]);
+                    else { v = bh_act<ACT>(v); if (R) v += R[(size_t)row * N + col]; }
                     C[(size_t)row * N + col] = v;
                 }
             }
@@ -1594,6 +1618,7 @@ bool conv_gemm_supports(const ConvParams &p) {
            p.kw <= 7 && (p.sh == 1 || p.sh == 2) && (p.sw == 1 || p.sw == 2) && p.pad_t >= 0 && p.pad_l >= 0;
 }
 bool conv_gemm16_supports(const ConvParams &p) { return conv_gemm_supports(p) && (p.act == ACT_NONE || act_is_templated(p.act)); }
+bool conv_gemm16_after_supports(const ConvParams &p) { return conv_gemm_supports(p) && act_is_templated_after(p.act); }
 
 template <int BM, int NT>
 static void conv_launch(const float *X, const float *W, const float *bias, const float *R, float *C, const ConvParams &p, int M, int ldw,
@@ -1605,7 +1630,7 @@ static void conv_launch(const float *X, const float *W, const float *bias, const
 const char *launch_conv_gemm(const float *X, const float *W, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
                              int ldw, hipStream_t s) {
     const int M = n_seg * p.out_h * p.out_w;
-    if (M <= 0) return nullptr;
+    if (M <= 0 || (p.res_after && (!R || p.act == ACT_NONE))) return nullptr;
     const int nt = pick_nt(p.cout);
     const long blocks128 = (long)((M + 127) / 128) * ((p.cout + nt * 16 - 1) / (nt * 16));
     const bool small = blocks128 < 512;   // the tile is the layer's shape alone: the same bits at any launch size either way
@@ -1627,20 +1652,29 @@ const char *launch_conv_gemm(const float *X, const float *W, const float *bias, 
 const char *launch_conv_gemm16(const float *X, const void *Wf, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
                                int terms, float w_unscale, hipStream_t s) {
     const int M = n_seg * p.out_h * p.out_w;
-    if (M <= 0) return nullptr;
+    if (M <= 0 || (p.res_after && (!R || !act_is_templated_after(p.act)))) return nullptr;   // (no such instantiation: nothing launched)
     const int n_tiles = (p.cout + 15) / 16;
     const dim3 grid((unsigned)(((n_tiles + 7) / 8) * ((M + 127) / 128))), block(256);
     const char *name = nullptr;
-#define BH_CG16(T, ACTV, AN) do { hipLaunchKernelGGL((conv_gemm16_kernel<T, ACTV>), grid, block, 0, s, X, (const f16x8 *)Wf, bias, R, C, p, M, n_tiles, w_unscale); \
-                                  name = "conv_gemm16_kernel<" #T "," AN ">"; } while (0)
+#define BH_CG16(T, ACTV, AN, AFT, AFN) do { hipLaunchKernelGGL((conv_gemm16_kernel<T, ACTV, AFT>), grid, block, 0, s, X, (const f16x8 *)Wf, bias, R, C, p, M, n_tiles, w_unscale); \
+                                            name = "conv_gemm16_kernel<" #T "," AN AFN ">"; } while (0)
 #define BH_CG16A(T)                                                  \
     switch (p.act) {                                                 \
-    case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF, "GELU"); break;      \
-    case ACT_SWISH: BH_CG16(T, ACT_SWISH, "SWISH"); break;           \
-    case ACT_RELU6: BH_CG16(T, ACT_RELU6, "RELU6"); break;           \
-    default: BH_CG16(T, ACT_NONE, "NONE"); break;                    \
+    case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF, "GELU", false, ""); break; \
+    case ACT_SWISH: BH_CG16(T, ACT_SWISH, "SWISH", false, ""); break; \
+    case ACT_RELU6: BH_CG16(T, ACT_RELU6, "RELU6", false, ""); break; \
+    default: BH_CG16(T, ACT_NONE, "NONE", false, ""); break;         \
     }
-    if (terms == 3) { BH_CG16A(3) } else if (terms == 2) { BH_CG16A(2) } else { BH_CG16A(1) }
+#define BH_CG16AA(T)                                                 \
+    switch (p.act) {                                                 \
+    case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF, "GELU", true, ",AFTER"); break; \
+    case ACT_SWISH: BH_CG16(T, ACT_SWISH, "SWISH", true, ",AFTER"); break; \
+    case ACT_RELU6: BH_CG16(T, ACT_RELU6, "RELU6", true, ",AFTER"); break; \
+    default: BH_CG16(T, ACT_RELU, "RELU", true, ",AFTER"); break;    \
+    }
+    if (p.res_after) { if (terms == 3) { BH_CG16AA(3) } else if (terms == 2) { BH_CG16AA(2) } else { BH_CG16AA(1) } }
+    else if (terms == 3) { BH_CG16A(3) } else if (terms == 2) { BH_CG16A(2) } else { BH_CG16A(1) }
+#undef BH_CG16AA
 #undef BH_CG16A
 #undef BH_CG16
     return name;

@@ -12,6 +12,9 @@ namespace bh {
 enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
 // OP_POOL (ONNX MaxPool / AveragePool, floor mode): the record's `reserved` word is the mode.  No weights, no bias, no activation.
 enum PoolMode : uint32_t { POOL_MAX = 0, POOL_AVG = 1, POOL_AVG_PAD = 2 };   // AVG: over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
+// OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the record's `reserved` word is where `act` stands relative to the residual.  0: act(conv + b) + R
+// (the only meaning of every file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block.
+constexpr uint32_t RES_ACT_AFTER = 1;
 constexpr uint32_t NO_TENSOR = 0xFFFFFFFFu;
 
 #pragma pack(push, 1)
@@ -112,6 +115,13 @@ inline bool validate_model(Model &m, std::string &err) {
             // every window holds at least one pixel of the image: max never comes from nothing, the in-image mean never divides by zero
             if (L.pad_t >= L.kh || L.pad_l >= L.kw || (uint64_t)(L.out_h - 1) * L.sh >= (uint64_t)L.in_h + L.pad_t ||
                 (uint64_t)(L.out_w - 1) * L.sw >= (uint64_t)L.in_w + L.pad_l) { err = "pool layer with a window outside the image"; return false; }
+        }
+        if (L.op == OP_CONV && L.in_layout != 0) {
+            if (L.reserved == RES_ACT_AFTER) { err = "activation after the residual on the NCHW stem convolution"; return false; }
+        } else if (L.op == OP_CONV || L.op == OP_PWCONV || L.op == OP_DENSE) {
+            if (L.reserved > RES_ACT_AFTER) { err = "layer with an unknown activation position"; return false; }
+            if (L.reserved == RES_ACT_AFTER && L.res_tensor == NO_TENSOR) { err = "activation after the residual on a layer without a residual"; return false; }
+            if (L.reserved == RES_ACT_AFTER && L.act == 0) { err = "activation after the residual without an activation (a plain residual is position 0)"; return false; }
         }
         if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
                                                    L.b_off + L.cout > m.h.blob_floats)) {

@@ -35,6 +35,7 @@
 // (tests/test_host_sanitizers.py).
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -270,7 +271,8 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     }
 
     // ---- multi-node activation spellings (convert.py _collapse_activations) ----
-    std::map<std::string, std::vector<std::pair<std::string, uint32_t>>> first_of_pattern;   // pattern input -> (pattern output, act)
+    struct Pattern { std::string out; uint32_t act; std::vector<size_t> nodes; };               // (nodes: the pattern's own, the readers it may have of its input)
+    std::map<std::string, std::vector<Pattern>> first_of_pattern;                            // pattern input -> (pattern output, act)
     auto sole_consumer = [&](const std::string &name, const char *op, size_t &k) {
         auto it = cons.find(name);
         if (it == cons.end() || it->second.size() != 1 || nodes[it->second[0]].op != op) return false;
@@ -310,7 +312,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             for (const auto &a : nodes[m2].in) if (a != nodes[m1].out[0]) { float c; if (a == x) has_x = true; if (scalar(a, c) && std::fabs(c - 0.5f) < 1e-6f) has_half = true; }
             if (has_x && has_half) {
                 skip.insert({j, i, k, m1, m2});
-                first_of_pattern[x].push_back({nodes[m2].out[0], A_GELU_ERF});
+                first_of_pattern[x].push_back(Pattern{nodes[m2].out[0], A_GELU_ERF, {j, i, k, m1, m2}});
             }
         } else if (n.op == "Sigmoid" && !n.in.empty() && !n.out.empty()) {
             size_t k;
@@ -319,7 +321,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 for (const auto &a : nodes[k].in) if (a == n.in[0]) takes_x = true;
                 if (takes_x && !nodes[k].out.empty()) {
                     skip.insert({i, k});
-                    first_of_pattern[n.in[0]].push_back({nodes[k].out[0], A_SWISH});
+                    first_of_pattern[n.in[0]].push_back(Pattern{nodes[k].out[0], A_SWISH, {i, k}});
                 }
             }
         }
@@ -334,11 +336,28 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     std::set<std::string> graph_out;
     for (const auto &o : outputs) graph_out.insert(o);
     auto find = [&](const std::string &name, T &t) { auto it = tmap.find(name); if (it == tmap.end()) return false; t = it->second; return true; };
-    auto set_act = [&](const std::string &name_in, const std::string &name_out, uint32_t act) {
+    std::set<std::string> sums;   // the outputs of the residual Adds folded into a layer
+    // (own: the nodes of the activation itself -- one, or a multi-node spelling's)
+    auto set_act = [&](const std::string &name_in, const std::string &name_out, uint32_t act, const std::vector<size_t> &own) {
         T t;
         if (!find(name_in, t)) return fail("activation on unknown tensor '" + name_in + "'");
         if (t.idx != 0 && layers[t.idx - 1].op == OP_POOL)
             return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a MaxPool / AveragePool (a pool layer carries no activation)");
+        if (t.idx != 0 && sums.count(name_in) && layers[t.idx - 1].res_tensor != NO_TENSOR && layers[t.idx - 1].reserved != RES_ACT_AFTER) {
+            // act(conv + x), the end of a ResNet block: the layer keeps its one activation code and records its position
+            LayerRec &L = layers[t.idx - 1];
+            if (L.act != A_NONE)
+                return fail("activation after '" + name_in + "' cannot be folded into its producer: an activation on both sides of a residual Add (act2(act1(conv) + x))");
+            bool other = graph_out.count(name_in) != 0;
+            auto cit = cons.find(name_in);
+            if (cit != cons.end()) for (size_t k : cit->second) if (std::find(own.begin(), own.end(), k) == own.end()) other = true;
+            if (other)
+                return fail("activation after '" + name_in + "' cannot be folded into its producer: the sum has another reader or is a graph output (it would be handed the activated tensor)");
+            L.act = act;
+            L.reserved = RES_ACT_AFTER;
+            tmap[name_out] = t;
+            return true;
+        }
         if (t.idx == 0 || layers[t.idx - 1].act != A_NONE || layers[t.idx - 1].res_tensor != NO_TENSOR)
             return fail("activation after '" + name_in + "' cannot be folded into its producer");
         layers[t.idx - 1].act = act;
@@ -351,7 +370,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         const auto list = it->second;
         first_of_pattern.erase(it);
         for (const auto &pa : list)
-            if (!set_act(x, pa.first, pa.second)) return false;
+            if (!set_act(x, pa.out, pa.act, pa.nodes)) return false;
         return true;
     };
     auto new_layer = [&](uint32_t op, uint32_t in_t, uint32_t res_t, uint32_t cin, uint32_t cout, uint32_t kh, uint32_t kw, uint32_t sh, uint32_t sw,
@@ -466,7 +485,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 if (!has_lo || !has_hi || lo != 0.0f || hi != 6.0f) return fail("Clip that is not ReLU6 (0, 6)");
             }
             if (op == "Gelu") { const std::string ap = n.gets("approximate", "none"); if (ap != "none") act = A_GELU_TANH; }
-            if (!set_act(n.in[0], n.out[0], act)) return false;
+            if (!set_act(n.in[0], n.out[0], act, {i})) return false;
         } else if (op == "Add") {
             T a, b;
             if (n.in.size() != 2 || !find(n.in[0], a) || !find(n.in[1], b)) return fail("Add of '" + n.in[0] + "': operands are not both activations on the path");
@@ -480,10 +499,12 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 if (conv && L.res_tensor == NO_TENSOR && r.idx < y.idx && r.c == y.c && r.h == y.h && r.w == y.w) {
                     L.res_tensor = r.idx;
                     tmap[n.out[0]] = y;
+                    sums.insert(n.out[0]);
                     done = true;
                 }
             }
             if (!done) return fail("Add of '" + n.in[0] + "', '" + n.in[1] + "': no convolution to fold the residual into");
+            if (!flush_patterns(n.out[0])) return false;   // (a multi-node activation behind the sum: act(conv + x))
         } else if (op == "GlobalAveragePool" || op == "ReduceMean") {
             T t;
             if (!find(n.in[0], t)) return fail(op + ": input not on the path");
@@ -584,7 +605,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             // the gate of a squeeze-excite block: Sigmoid on a pooled [N, C, 1, 1] tensor, consumed by a Mul with the feature map
             T t;
             if (!find(n.in[0], t) || (uint64_t)t.h * t.w != 1) return fail("Sigmoid inside the graph that is neither Sigmoid * x nor a squeeze-excite gate");
-            if (!set_act(n.in[0], n.out[0], A_SIGMOID)) return false;
+            if (!set_act(n.in[0], n.out[0], A_SIGMOID, {i})) return false;
         } else if (op == "Mul") {
             T a, b;
             if (n.in.size() != 2 || !find(n.in[0], a) || !find(n.in[1], b)) return fail("Mul of '" + n.in[0] + "': operands are not both activations on the path");

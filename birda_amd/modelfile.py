@@ -35,6 +35,9 @@ VERSION = 1
 OP_CONV, OP_DWCONV, OP_PWCONV, OP_GAP, OP_DENSE, OP_SCALE = 1, 2, 3, 4, 5, 6   # OP_SCALE: x[n,h,w,c] * gate[n,c] (squeeze-excite), gate = res_tensor
 OP_POOL = 7   # windowed MaxPool / AveragePool (floor mode); Layer.reserved is the mode; no weights, bias, activation or residual
 POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2   # AVG: mean over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
+# OP_CONV (NHWC), OP_PWCONV, OP_DENSE: Layer.reserved is where `act` stands relative to the residual -- 0: act(conv + b) + R (every
+# file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block
+RES_ACT_AFTER = 1
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SIGMOID = range(7)
 OUT_NONE, OUT_SIGMOID, OUT_SOFTMAX = 0, 1, 2
 NO_TENSOR = 0xFFFFFFFF
@@ -92,7 +95,10 @@ class Layer:
     in_layout: int = 0  # 0 NHWC, 1 planar NCHW (front-end output)
     w_off: int = 0
     b_off: int = 0
-    reserved: int = 0   # OP_POOL: the pool mode (POOL_MAX / POOL_AVG / POOL_AVG_PAD); 0 for every other op
+    # OP_POOL: the pool mode (POOL_MAX / POOL_AVG / POOL_AVG_PAD).  OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the position of `act`
+    # relative to the residual -- 0: act(conv + b) + R; RES_ACT_AFTER: act(conv + b + R), which needs a residual and an activation.
+    # 0 for every other op.
+    reserved: int = 0
 
 
 @dataclass

@@ -178,6 +178,9 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     'birdnet_v30_v2l' (the same contract on EfficientNetV2-L's stage plan: three Fused-MBConv stages, 132 M parameters),
     'cnn_pool' (a conv + pool backbone in the VGG / PANNs style on the v2.4 front-end, for timing the pool layers: _build_cnn_pool).
     'pool_plan' (plan = random_pool_plan(seed)) builds that plan's stack of convolutions, MBConv blocks and pools: _build_pool_plan.
+    'resnet_plan' (plan = random_resnet_plan(seed)) builds that plan's ResNet blocks -- act(conv + shortcut), Layer.reserved =
+    RES_ACT_AFTER -- on the same mini front-end: _build_resnet_plan.  'resnet18_audio' (a ResNet-18 on the v2.4 front-end, for timing
+    those layers: _build_resnet18_audio).
     A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
@@ -185,6 +188,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
         return _build_cnn_pool(seed, n_classes)
     if kind == "pool_plan":
         return _build_pool_plan(plan, seed)
+    if kind == "resnet_plan":
+        return _build_resnet_plan(plan, seed)
+    if kind == "resnet18_audio":
+        return _build_resnet18_audio(seed, n_classes)
     rng = np.random.default_rng(seed)
     b = _Builder(rng)
     act_override, act, hidden = act, mf.ACT_GELU_ERF, 0
@@ -508,6 +515,134 @@ def _build_pool_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
     t = emb = b.gap(t, h, w, head)
     b.dense(t, head, ncls, gain=1.5)
     return _finish(b, [br], sr, n, ncls, head, emb, int(plan["out_act"]))
+
+
+def _res_block(b: _Builder, t, h, w, c, kind, shortcut, cout, mid, act, pool_mode=mf.POOL_AVG):
+    """One ResNet block behind tensor t [h][w][c], ending in act(main + shortcut) -- the layer the residual folds into carries `act`
+    and Layer.reserved = RES_ACT_AFTER.  kind 'basic': 3x3 (act) -> 3x3; 'bottleneck': 1x1 (act) -> 3x3 (act) -> 1x1, `mid` channels
+    inside.  shortcut 'identity' (stride 1, cout == c: the main branch's last convolution is the flagged layer), 'proj' (the main
+    branch at stride 2, then a 1x1 stride-2 convolution of the block input, emitted AFTER the main branch as PyTorch exports do: the
+    residual folds into the shortcut convolution, which is the flagged layer) or 'resnetd' (conv1x1(avgpool 2x2 stride 2 (x)), ResNet-D;
+    flagged likewise).  The main branch's last convolution is damped by half, as every residual branch of these synthetic nets is."""
+    x, st = t, 1 if shortcut == "identity" else 2
+    assert shortcut != "identity" or cout == c
+    last_res = x if shortcut == "identity" else mf.NO_TENSOR
+    last_act = act if shortcut == "identity" else mf.ACT_NONE
+    if kind == "basic":
+        t, oh, ow = b.conv(x, h, w, c, cout, 3, st, act)
+        t, oh, ow = b.conv(t, oh, ow, cout, cout, 3, 1, last_act, res=last_res, gain=0.5)
+    else:
+        t = b.pwconv(x, h, w, c, mid, act)
+        t, oh, ow = b.conv(t, h, w, mid, mid, 3, st, act)
+        t = b.pwconv(t, oh, ow, mid, cout, last_act, last_res, gain=0.5)
+    if shortcut == "identity":
+        b.layers[-1].reserved = mf.RES_ACT_AFTER
+    elif shortcut == "proj":
+        t, ph, pw_ = b.conv(x, h, w, c, cout, 1, 2, act, res=t)
+        assert (ph, pw_) == (oh, ow)
+        b.layers[-1].reserved = mf.RES_ACT_AFTER
+    elif shortcut == "resnetd":
+        tp, ph, pw_ = b.pool(x, h, w, c, 2, 2, 2, 2, pool_mode, "same")
+        assert (ph, pw_) == (oh, ow)
+        t = b.pwconv(tp, ph, pw_, c, cout, act, t)
+        b.layers[-1].reserved = mf.RES_ACT_AFTER
+    else:
+        raise ValueError(shortcut)
+    return t, oh, ow
+
+
+def random_resnet_plan(seed: int) -> dict:
+    """A small seeded ResNet on the mini front-end of _build_pool_plan (32 mels x 115 frames): a stem -- 3x3, or 7x7 stride 2
+    followed by MaxPool 3x3 stride 2 pad 1 --, then four blocks drawn from basic / bottleneck x identity / projection /
+    ResNet-D shortcut (_res_block), and one MBConv block whose input is a flagged layer's output.  Every plan opens with an identity
+    block at a narrow width (16 / 24: a flagged layer of 64 output channels or fewer), widens through a down-sampling block (72 /
+    136: one above 64), holds a bottleneck identity block there (its flagged 1x1 has K = 32) and ends in a basic identity block or a
+    second down-sampling block.  The
+    activation is ReLU on the even seeds and ReLU6 / swish / GELU in turn on the odd ones; the MBConv block of a ReLU plan takes ReLU6 (MobileNet's), the fused kernels having no ReLU instantiation.
+    Feed to build_model("resnet_plan", plan=...).  plan["items"]: ("res", kind, shortcut, cout, mid) | ("mb", expand, k, cout)."""
+    rng = np.random.default_rng(0x4E57 + seed)
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+    act = mf.ACT_RELU if seed % 2 == 0 else (mf.ACT_RELU6, mf.ACT_SWISH, mf.ACT_GELU_ERF)[(seed // 2) % 3]
+    narrow, wide = pick((16, 24)), pick((72, 136))
+    kind = lambda: pick(("basic", "bottleneck"))
+    down = lambda: pick(("proj", "resnetd"))
+    # (a wide bottleneck is 32 channels inside: its last 1x1 has K % 32 == 0, what the split-f16 pointwise GEMMs take)
+    res = lambda shortcut, cout: ("res", kind(), shortcut, cout, 32 if cout > 64 else cout)
+    # (the wide identity block is a bottleneck in EVERY plan: a flagged 1x1 layer above 64 channels at K = 32, which the split-f16
+    #  pointwise GEMMs take -- a ResNet-D shortcut from a 16-, 24- or 40-channel tensor has K % 32 != 0 and stays on the f32 kernel)
+    items = [("res", "bottleneck" if seed % 2 else "basic", "identity", narrow, narrow), res(down(), wide), ("res", "bottleneck", "identity", wide, 32)]
+    items.append(res(down(), pick((72, 136))) if rng.integers(0, 2) else ("res", "basic", "identity", wide, wide))
+    # the MBConv block: behind the first block, or behind the wide identity block or a later one (each ends in a flagged layer)
+    items.insert(int(pick([1] + list(range(3, len(items) + 1)))), ("mb", pick((4, 6)), pick((3, 5)), pick((24, 40))))
+    # (behind the MBConv block the next res block's identity shortcut needs its input width: re-thread the widths)
+    fixed, c = [], narrow
+    for it in items:
+        if it[0] == "res" and it[2] == "identity" and it[3] != c:
+            it = ("res", it[1], pick(("proj", "resnetd")), it[3], it[4])
+        fixed.append(it)
+        c = it[3]
+    return {"items": fixed, "stem": pick(("3x3", "7x7")), "stem_c": narrow, "act": act,
+            "mb_act": mf.ACT_RELU6 if act == mf.ACT_RELU else act, "head": int(rng.integers(4, 13)) * 8,
+            "classes": int(rng.integers(20, 61)), "out_act": int(pick((mf.OUT_SIGMOID, mf.OUT_SOFTMAX)))}
+
+
+def _build_resnet_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
+    """random_resnet_plan's stack on the mini front-end of one branch (512-sample frames at hop 100: 32 mels x 115 frames)."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 12000
+    br = mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23)
+    br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+    br.out_scale, br.out_shift = 0.8, -0.4
+    act, mb_act, c = int(plan["act"]), int(plan["mb_act"]), int(plan["stem_c"])
+    if plan["stem"] == "7x7":
+        t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, c, 7, 2, act, in_layout=1)
+        t, h, w = b.pool(t, h, w, c, 3, 3, 2, 2, mf.POOL_MAX, (1, 1, 1, 1))
+    else:
+        t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, c, 3, 1, act, in_layout=1)
+    for it in plan["items"]:
+        if it[0] == "res":
+            _, kind, shortcut, cout, mid = it
+            t, h, w = _res_block(b, t, h, w, c, kind, shortcut, cout, mid, act)
+            c = cout
+        elif it[0] == "mb":
+            _, e, k, cout = it
+            tin, cin = t, c
+            t = b.pwconv(t, h, w, c, c * e, mb_act)
+            t, h, w = b.dwconv(t, h, w, c * e, k, 1, mb_act)
+            res = tin if cin == cout else mf.NO_TENSOR
+            t = b.pwconv(t, h, w, c * e, cout, mf.ACT_NONE, res, gain=0.5 if res != mf.NO_TENSOR else 1.0)
+            c = cout
+        else:
+            raise ValueError(it[0])
+    head, ncls = int(plan["head"]), int(plan["classes"])
+    t = b.pwconv(t, h, w, c, head, act)
+    t = emb = b.gap(t, h, w, head)
+    b.dense(t, head, ncls, gain=1.5)
+    return _finish(b, [br], sr, n, ncls, head, emb, int(plan["out_act"]))
+
+
+def _build_resnet18_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) -> mf.Model:
+    """ResNet-18 on the v2.4 front-end (96 mels x 511 frames, two branches): a 7x7 stride-2 NCHW stem to 64 channels with ReLU,
+    MaxPool 3x3 stride 2 pad 1, four stages of two basic blocks at widths 64 / 128 / 256 / 512 -- relu(conv(relu(conv(x))) + shortcut),
+    projection shortcuts (1x1 stride 2) at the three stride-2 blocks --, the global pool and the dense layer.  Seeded weights: a model
+    for TIMING the after-the-add layers in the manner of cnn_pool, not for accuracy."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 144000
+    branches = [mf.Branch(2048, 278, 96, 511, 0.0, 3000.0, 1.23), mf.Branch(1024, 280, 96, 511, 500.0, 15000.0, 1.23)]
+    for br in branches:
+        br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+        br.out_scale, br.out_shift = 0.8, -0.4
+    t, h, w = b.conv(0, 96, 511, 2, 64, 7, 2, mf.ACT_RELU, in_layout=1)
+    t, h, w = b.pool(t, h, w, 64, 3, 3, 2, 2, mf.POOL_MAX, (1, 1, 1, 1))
+    c = 64
+    for width in (64, 128, 256, 512):
+        t, h, w = _res_block(b, t, h, w, c, "basic", "identity" if width == c else "proj", width, width, mf.ACT_RELU)
+        t, h, w = _res_block(b, t, h, w, width, "basic", "identity", width, width, mf.ACT_RELU)
+        c = width
+    t = emb = b.gap(t, h, w, 512)
+    ncls = n_classes or 6522
+    b.dense(t, 512, ncls, gain=1.5)
+    return _finish(b, branches, sr, n, ncls, 512, emb, mf.OUT_SIGMOID)
 
 
 def random_fused_plan(seed: int, big: bool = False) -> dict:

@@ -28,6 +28,8 @@ for i, (ms, n) in enumerate(ly):
     if n:
         L = m.layers[i]
         line = f"layer {i:3d} {names[L.op]:5s} {L.cin:5d}->{L.cout:5d} {L.in_h}x{L.in_w} k{L.kh} s{L.sh}  {ms / 5 * 1e3:9.1f} us per {N}"
+        if L.op in (mf.OP_CONV, mf.OP_PWCONV, mf.OP_DENSE) and L.reserved == mf.RES_ACT_AFTER:
+            line += "  act after the residual add"
         if L.op == mf.OP_POOL:   # HBM-bound: the bytes it moves (input + output) and the rate
             nbytes = 4 * N * L.cout * (L.in_h * L.in_w + L.out_h * L.out_w)
             line += f"  {('max', 'avg', 'avg_pad')[L.reserved]} {L.kh}x{L.kw}/{L.sh}x{L.sw}  {nbytes / 1e6:9.1f} MB  {nbytes / (ms / 5 * 1e-3) / 1e12:5.2f} TB/s"
