@@ -2,7 +2,7 @@
 
 `model_from_graph` turns the classifier part of an ONNX graph -- from the spectrogram tensor
 [N, C, H, W] to the logits -- into the layer table `modelfile.py` describes: Conv (group 1 / depthwise
-/ 1x1) with BatchNormalization folded, the activation that follows folded into the producing layer
+/ 1x1 / any other group count: OP_GCONV) with BatchNormalization folded, the activation that follows folded into the producing layer
 (Relu, Clip 0..6, Sigmoid*x, the Div-Erf-Add-Mul-Mul spelling of exact GELU, or a fused `Gelu`),
 residual Add folded into the project conv -- with the activation that follows the Add, if any, as that layer's (Layer.reserved =
 RES_ACT_AFTER: act(conv + x), the end of a ResNet block) --, squeeze-excite blocks (GlobalAveragePool -> 1x1 Conv -> activation -> 1x1 Conv ->
@@ -184,8 +184,12 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
 
     for i, L in enumerate(m.layers):
         tag, x = f"l{i}", names[L.in_tensor]
-        if L.op in (mf.OP_CONV, mf.OP_DWCONV, mf.OP_PWCONV):
-            if L.op == mf.OP_CONV:
+        if L.op in (mf.OP_CONV, mf.OP_DWCONV, mf.OP_PWCONV, mf.OP_GCONV):
+            if L.op == mf.OP_GCONV:      # compact [kh][kw][cin / G][cout] -> ONNX [cout][cin / G][kh][kw]
+                gi = L.cin // L.reserved
+                w = m.weight(L.w_off, L.kh * L.kw * gi * L.cout).reshape(L.kh, L.kw, gi, L.cout).transpose(3, 2, 0, 1)
+                group = L.reserved
+            elif L.op == mf.OP_CONV:
                 w = m.weight(L.w_off, L.kh * L.kw * L.cin * L.cout).reshape(L.kh, L.kw, L.cin, L.cout).transpose(3, 2, 0, 1)
                 group = 1
             elif L.op == mf.OP_DWCONV:
@@ -488,14 +492,27 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
                 L = mf.Layer(mf.OP_CONV, mf.ACT_NONE, t_in, mf.NO_TENSOR, cin, cout, kh, kw, sh, sw, pt, pl, h, w, oh, ow,
                              1 if t_in == 0 else 0, blob.put(W.transpose(2, 3, 1, 0)), blob.put(B))
             else:
-                raise ConvertError(f"Conv {n.name!r}: group {group} with {cin} -> {cout} channels")
+                # a grouped convolution -> OP_GCONV (csrc/onnx_conv.hpp has the same branch, refusal for refusal)
+                who = f"Conv {n.name!r}: group {group} with {cin} -> {cout} channels"
+                if t_in == 0:
+                    raise ConvertError(who + ": a grouped convolution on the spectrogram (tensor 0) is not supported")
+                if group < 1 or cin % group or cout % group or cin_g * group != cin:
+                    raise ConvertError(who + f": the group count does not divide them (the weights hold {cin_g} input channels a group)")
+                if cin_g % 4 or (cout // group) % 4:
+                    raise ConvertError(who + f": a group width ({cin_g} -> {cout // group}) that is not a multiple of 4 is not supported")
+                if kh > 7 or kw > 7:
+                    raise ConvertError(who + f": a grouped kernel of {kh}x{kw} (1 .. 7 are supported)")
+                if sh > 2 or sw > 2:
+                    raise ConvertError(who + f": grouped strides of {sh}x{sw} (1 .. 2 are supported)")
+                L = mf.Layer(mf.OP_GCONV, mf.ACT_NONE, t_in, mf.NO_TENSOR, cin, cout, kh, kw, sh, sw, pt, pl, h, w, oh, ow, 0,
+                             blob.put(W.transpose(2, 3, 1, 0)), blob.put(B), reserved=group)
             layers.append(L)
             tmap[n.outputs[0]] = (len(layers), cout, L.out_h, L.out_w)
             flush_patterns(n.outputs[0])
         elif op == "BatchNormalization":
             t = tmap.get(n.inputs[0])
             L = layers[t[0] - 1] if t and t[0] > 0 else None
-            if L is None or L.op not in (mf.OP_CONV, mf.OP_DWCONV, mf.OP_PWCONV) or L.act != mf.ACT_NONE:
+            if L is None or L.op not in (mf.OP_CONV, mf.OP_DWCONV, mf.OP_PWCONV, mf.OP_GCONV) or L.act != mf.ACT_NONE:
                 raise ConvertError("BatchNormalization that does not follow a convolution directly")
             # folding rewrites the convolution's weights: a residual already folded into the layer (BN(conv + x)) or another
             # reader of the convolution's output (a skip taken before the BN) would silently see the wrong values
@@ -505,7 +522,8 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
                 raise ConvertError("BatchNormalization of a convolution output that has other readers cannot be folded")
             gamma, beta, mean, var = (g.initializers[a].astype(np.float64) for a in n.inputs[1:5])
             scale = gamma / np.sqrt(var + float(n.attrs.get("epsilon", 1e-5)))
-            nw = {mf.OP_CONV: L.kh * L.kw * L.cin * L.cout, mf.OP_DWCONV: L.kh * L.kw * L.cout, mf.OP_PWCONV: L.cin * L.cout}[L.op]
+            nw = {mf.OP_CONV: L.kh * L.kw * L.cin * L.cout, mf.OP_DWCONV: L.kh * L.kw * L.cout, mf.OP_PWCONV: L.cin * L.cout,
+                  mf.OP_GCONV: L.kh * L.kw * (L.cin // max(L.reserved, 1)) * L.cout}[L.op]
             arr = blob.array()
             wv = arr[L.w_off: L.w_off + nw].reshape(-1, L.cout) * scale.astype(np.float32)     # cout is the last axis in all three layouts
             bv = ((arr[L.b_off: L.b_off + L.cout] - mean) * scale + beta).astype(np.float32)

@@ -115,6 +115,42 @@ std::vector<float> conv_gemm_rows(const float *W, const bh::ConvParams &p, int l
     return w;
 }
 
+// A grouped convolution's compact [kh][kw][cin / G][cout] weights as the matrix Wt [K][16 n_tiles] of kernels_gconv.hip: column o
+// of column tile t is dense over k = tap * span + (c - c0), [c0, c0 + span) the tile's span of input channels (gconv_tile_span),
+// zero where channel c is not in o's group; K = the largest tile's kh kw span, padded ONCE at the end to whole 32-deep steps
+std::vector<float> gconv_matrix(const float *W, const bh::ConvParams &p, int G, int *K_out) {
+    const int nt = (p.cout + 15) / 16, gi = p.cin / G, go = p.cout / G, taps = p.kh * p.kw;
+    size_t kmax = 0;
+    for (int t = 0; t < nt; t++) {
+        int c0, span;
+        bh::gconv_tile_span(p.cin, p.cout, G, t, c0, span);
+        kmax = std::max(kmax, (size_t)taps * span);
+    }
+    const size_t K = align_up(kmax, 32), ld = (size_t)nt * 16;
+    std::vector<float> wt(K * ld, 0.0f);
+    for (int o = 0; o < p.cout; o++) {
+        int c0, span;
+        bh::gconv_tile_span(p.cin, p.cout, G, o / 16, c0, span);
+        const int first = (o / go) * gi - c0;      // the group's first channel within the span
+        for (int tap = 0; tap < taps; tap++)
+            for (int c = 0; c < gi; c++)
+                wt[((size_t)tap * span + first + c) * ld + o] = W[((size_t)tap * gi + c) * p.cout + o];
+    }
+    *K_out = (int)K;
+    return wt;
+}
+// ... and its f32 MFMA fragments [K / 16][n_tiles][64 lanes][4]: element (g, t, lane, c) = Wt[16g + 4 (lane >> 4) + c][16t + (lane & 15)]
+std::vector<float> gconv_fragments(const std::vector<float> &wt, int K, int nt) {
+    std::vector<float> f((size_t)K * nt * 16);
+    const size_t ld = (size_t)nt * 16;
+    for (int g = 0; g < K / 16; g++)
+        for (int t = 0; t < nt; t++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int c = 0; c < 4; c++)
+                    f[(((size_t)g * nt + t) * 64 + lane) * 4 + c] = wt[((size_t)16 * g + 4 * (lane >> 4) + c) * ld + 16 * t + (lane & 15)];
+    return f;
+}
+
 // A pointwise / dense layer's [K][N] weights with the rows padded to ld = align_up(N, 4) (the f32 GEMM's 16-B loads); zero in the padding
 std::vector<float> pw_gemm_rows(const float *W, size_t K, size_t N, size_t ld) {
     std::vector<float> w(K * ld, 0.0f);
@@ -332,6 +368,13 @@ int SliceRun::layer(const Step &st) const {
         bh::launch_scale(in, res, out, (int)n, (int)(L.out_h * L.out_w), (int)L.cout, s);
         ctx_mark(ctx, ST_DW, (int)i);
         break;
+    case bh::OP_GCONV:   // a grouped convolution (L.reserved: the group count): per-tile weight blocks, split-f16 where it has planes
+        if (!ctx->keep_tensors && c->d_w16[i])
+            c->w16_kernel[i].store(launched = bh::launch_gconv16(in, c->d_w16[i], bias, out, p, (int)L.reserved, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+        else   // (the f32 kernel's name is kept too: bh_debug_layer_kernel tells which of the three instantiations a grouped layer ran)
+            c->w16_kernel[i].store(launched = bh::launch_gconv(in, c->d_w[i], bias, out, p, (int)L.reserved, (int)n, s), std::memory_order_relaxed);
+        ctx_mark(ctx, ST_STEM, (int)i);
+        break;
     case bh::OP_POOL:    // MaxPool / AveragePool: f32 in every precision mode (L.reserved: the pool mode)
         bh::launch_pool(in, out, p, (int)L.reserved, (int)n, s);
         ctx_mark(ctx, ST_GAP, (int)i);
@@ -506,7 +549,7 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
         ctx_mark(ctx, ST_MEL);
     }
     for (const Step &st : schedule_of(ctx)) {
-        static const char *const kOpNames[] = {"layer", "conv", "depthwise", "pointwise", "pool", "dense", "scale", "window_pool"};
+        static const char *const kOpNames[] = {"layer", "conv", "depthwise", "pointwise", "pool", "dense", "scale", "window_pool", "grouped_conv"};
         const uint32_t op = m.layers[st.first].op;
         bh::TraceRange tr(st.block >= 0 ? "fused_mbconv_block" : op < sizeof(kOpNames) / sizeof(kOpNames[0]) ? kOpNames[op] : kOpNames[0]);
         int rc = BH_OK;
@@ -1167,6 +1210,19 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
             if (rc != BH_OK) return rc;
             c->d_owned.push_back(d);
             c->d_w[i] = d;
+        } else if (L.op == bh::OP_GCONV) {   // per-tile weight blocks as f32 MFMA fragments (the f16 planes: below, with the other layers')
+            const bh::ConvParams p = conv_params(L);
+            if (!bh::gconv_supports(p, (int)L.reserved))
+                return fail(BH_ERR_UNSUPPORTED, "layer %zu: grouped convolution %ux%u stride %ux%u, %u -> %u channels in %u groups not built "
+                            "(kernel 1..7, stride 1 / 2, group widths multiples of 4, NHWC, no residual)", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout, L.reserved);
+            int K = 0;
+            const std::vector<float> wt = gconv_matrix(m.blob.data() + L.w_off, p, (int)L.reserved, &K);
+            const std::vector<float> w = gconv_fragments(wt, K, (int)(L.cout + 15) / 16);
+            float *d = nullptr;
+            rc = upload(w.data(), w.size() * sizeof(float), &d);
+            if (rc != BH_OK) return rc;
+            c->d_owned.push_back(d);
+            c->d_w[i] = d;
         } else if (L.op == bh::OP_GAP || L.op == bh::OP_SCALE || L.op == bh::OP_POOL) {
             if (L.cout % 4) return fail(BH_ERR_UNSUPPORTED, "layer %zu: channels %u not a multiple of 4", i, L.cout);
             if (L.op == bh::OP_POOL && !bh::pool_supports(conv_params(L), (int)L.reserved))
@@ -1179,9 +1235,10 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
     // residual sits on its project convolution; the planner fuses no depthwise layer that carries one) and the NCHW stem
     for (size_t i = 0; i < m.layers.size(); i++) {
         const auto &L = m.layers[i];
-        if (L.res_tensor != bh::NO_TENSOR && (L.op == bh::OP_DWCONV || L.op == bh::OP_GAP || L.op == bh::OP_POOL || (L.op == bh::OP_CONV && L.in_layout == 1)))
+        if (L.res_tensor != bh::NO_TENSOR && (L.op == bh::OP_DWCONV || L.op == bh::OP_GAP || L.op == bh::OP_POOL || L.op == bh::OP_GCONV || (L.op == bh::OP_CONV && L.in_layout == 1)))
             return fail(BH_ERR_UNSUPPORTED, "layer %zu: a residual on a %s layer is not supported (only convolutions, 1x1 and full NHWC, "
-                        "and dense layers add one)", i, L.op == bh::OP_DWCONV ? "depthwise" : (L.op == bh::OP_GAP || L.op == bh::OP_POOL) ? "pool" : "stem convolution");
+                        "and dense layers add one)", i, L.op == bh::OP_DWCONV ? "depthwise" : (L.op == bh::OP_GAP || L.op == bh::OP_POOL) ? "pool"
+                                                        : L.op == bh::OP_GCONV ? "grouped convolution" : "stem convolution");
     }
     rc = plan_fusion(c.get());
     if (rc != BH_OK) return rc;
@@ -1230,6 +1287,18 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
                 std::vector<uint16_t> planes = w16_planes(w.data(), (int)(L.kh * L.kw * cpad), (int)L.cout, &c->w16_unscale[i], &lo_zero);
                 rc = upload_planes(i, std::move(planes), lo_zero);
                 if (rc != BH_OK) return rc;
+                continue;
+            }
+            if (L.op == bh::OP_GCONV) {   // planes over the per-tile K: three terms (f16x3 / auto, a float16 file included) or one, never two
+                int K = 0;
+                const std::vector<float> wt = gconv_matrix(m.blob.data() + L.w_off, conv_params(L), (int)L.reserved, &K);
+                std::vector<uint16_t> planes = w16_planes(wt.data(), K, (int)((L.cout + 15) / 16 * 16), &c->w16_unscale[i]);
+                float *d = nullptr;
+                rc = upload(planes.data(), planes.size() * sizeof(uint16_t), &d);
+                if (rc != BH_OK) return rc;
+                c->d_owned.push_back(d);
+                c->d_w16[i] = d;
+                c->w16_bytes[i] = planes.size() * sizeof(uint16_t);
                 continue;
             }
             if (in_block[i] || (L.op != bh::OP_PWCONV && L.op != bh::OP_DENSE)) continue;
@@ -1781,7 +1850,7 @@ int bh_debug_layer_terms(const bh_classifier *c, int32_t *terms, size_t cap) {
 }
 
 // the instantiation the split-f16 GEMM of `layer` launched last (a launcher's name string), "" before any forward / for a layer
-// that takes none of those launchers; returns its length
+// that takes none of those launchers; a grouped convolution names its f32 kernel as well; returns its length
 int bh_debug_layer_kernel(const bh_classifier *c, uint32_t layer, char *out, size_t cap) {
     if (!c || layer >= c->d_w16.size()) return fail(BH_ERR_INVALID, "debug_layer_kernel: bad arguments");
     const char *name = c->w16_kernel[layer].load(std::memory_order_relaxed);
@@ -1987,6 +2056,44 @@ int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *
 int bh_debug_conv_gemm_after(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
                              const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap) try {
     return debug_conv_gemm(device, X, W, bias, R, C, n_seg, shape, act, terms, kernel, kernel_cap, 1);
+} catch (...) { return on_exception(); }
+
+// One grouped convolution alone on operands of the caller's, with create's weight preparation (gconv_matrix, gconv_fragments,
+// w16_planes), through the launchers a forward pass takes (include/birda_hip_gconv_debug.h).
+int bh_debug_gconv(int device, const float *X, const float *W, const float *bias, float *C, size_t n_seg, const int32_t *shape, int act,
+                   int terms, char *kernel, size_t kernel_cap) try {
+    if (!X || !W || !bias || !C || !shape || !n_seg || terms < 0 || terms > 3 || act < 0 || act > bh::ACT_SIGMOID)
+        return fail(BH_ERR_INVALID, "debug_gconv: bad arguments");
+    const bh::ConvParams p{shape[0], shape[1], shape[2], shape[3], shape[4], shape[5], shape[6], shape[7], shape[8], shape[9],
+                           shape[10], shape[11], 0, act, 0};
+    const int G = shape[12];
+    if (p.in_h < 1 || p.in_w < 1 || p.out_h < 1 || p.out_w < 1 || p.in_h > 65536 || p.in_w > 65536 || p.out_h > 65536 || p.out_w > 65536 ||
+        p.cin > 65536 || p.cout > (1 << 24))
+        return fail(BH_ERR_INVALID, "debug_gconv: image %dx%d -> %dx%d, %d -> %d channels", p.in_h, p.in_w, p.out_h, p.out_w, p.cin, p.cout);
+    if (terms == 2 || !bh::gconv_supports(p, G))
+        return fail(BH_ERR_UNSUPPORTED, "debug_gconv: %dx%d stride %dx%d pad %d,%d, %d -> %d channels in %d groups, %s not built for terms %d",
+                    p.kh, p.kw, p.sh, p.sw, p.pad_t, p.pad_l, p.cin, p.cout, G, act_name(act), terms);
+    const size_t M = n_seg * (size_t)p.out_h * p.out_w, x_floats = n_seg * (size_t)p.in_h * p.in_w * p.cin;
+    if (M * (size_t)p.cout > (size_t)INT32_MAX || x_floats > (size_t)INT32_MAX || n_seg > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_gconv: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    int K = 0;
+    const int nt = (p.cout + 15) / 16;
+    const std::vector<float> wt = gconv_matrix(W, p, G, &K);
+    float unscale = 1.0f;
+    std::vector<uint16_t> planes;
+    std::vector<float> frags;
+    if (terms) planes = w16_planes(wt.data(), K, nt * 16, &unscale);
+    else frags = gconv_fragments(wt, K, nt);
+    Guarded dX, dW, dB, dC;
+    if (!dX.put(X, x_floats * 4, kGuardNaN) ||
+        !(terms ? dW.put(planes.data(), planes.size() * 2, kGuardNaN) : dW.put(frags.data(), frags.size() * 4, kGuardNaN)) ||
+        !dB.put(bias, (size_t)p.cout * 4, kGuardNaN) || !dC.put(nullptr, M * p.cout * 4, kUnwrittenNaN))
+        return fail(BH_ERR_HIP, "debug_gconv: device memory");
+    const char *name = terms ? bh::launch_gconv16((const float *)dX.p(), dW.p(), (const float *)dB.p(), (float *)dC.p(), p, G, (int)n_seg, terms, unscale, nullptr)
+                             : bh::launch_gconv((const float *)dX.p(), (const float *)dW.p(), (const float *)dB.p(), (float *)dC.p(), p, G, (int)n_seg, nullptr);
+    if (!name) return fail(BH_ERR_UNSUPPORTED, "debug_gconv: a launch of %zu rows is beyond the grid", M);
+    return finish_debug_launch("debug_gconv", name, dC, C, M * p.cout, kernel, kernel_cap);
 } catch (...) { return on_exception(); }
 
 // A pointwise / dense layer (pool_rows == 0) or the fused head convolution + pool (pool_rows = pixels per segment) on operands of

@@ -31,6 +31,7 @@
 #include "../../include/birda_hip_layer_debug.h"
 #include "../../include/birda_hip_pool_debug.h"
 #include "../../include/birda_hip_resact_debug.h"
+#include "../../include/birda_hip_gconv_debug.h"
 #include "../../include/birda_hip_block_debug.h"
 #include "../../include/birda_hip_terms_debug.h"
 #include "kernels.hpp"

@@ -414,6 +414,23 @@ const char *launch_conv_gemm(const float *in, const float *W, const float *b, co
                              int ldw, hipStream_t s);
 const char *launch_conv_gemm16(const float *in, const void *Wf, const float *b, const float *R, float *out, const ConvParams &p, int n_seg,
                                int terms, float w_unscale, hipStream_t s);
+// grouped convolution NHWC (kernels_gconv.hip; model.hpp OP_GCONV): `groups` G >= 2, cin / G and cout / G multiples of 4, kh, kw 1 .. 7,
+// strides 1 / 2, no residual; p.act is a run-time argument (any code of act_apply_pos).  Every 16-wide column tile t has a K range
+// of its own over its SPAN, the contiguous input channels [c0, c0 + span) of the groups its output channels belong to:
+__host__ __device__ inline void gconv_tile_span(int cin, int cout, int groups, int t, int &c0, int &span) {
+    const int gi = cin / groups, go = cout / groups;
+    const int last = (16 * t + 15 < cout ? 16 * t + 15 : cout - 1) / go, first = 16 * t / go;
+    c0 = first * gi;
+    span = (last - first + 1) * gi;
+}
+// Wf (f32): fragments [K16 / 16][ceil(cout / 16)][64 lanes][4] of the per-tile dense matrix Wt [K][16 ceil(cout / 16)] that api.hip
+// gconv_matrix builds (column o: k = tap * span + (c - c0), zero where c is not in o's group; K padded once at the end);
+// Wf (f16 modes): w16_planes of the same Wt, terms 3 or 1 (there is no two-term form).  The launchers return the instantiation's
+// name ("gconv_kernel", "gconv16_kernel<3>", "gconv16_kernel<1>"); nullptr when nothing was launched.
+bool gconv_supports(const ConvParams &p, int groups);
+const char *launch_gconv(const float *in, const float *Wf, const float *b, float *out, const ConvParams &p, int groups, int n_seg, hipStream_t s);
+const char *launch_gconv16(const float *in, const void *Wf, const float *b, float *out, const ConvParams &p, int groups, int n_seg, int terms,
+                           float w_unscale, hipStream_t s);
 // depthwise conv NHWC; w [kh][kw][c]
 void launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
                    int n_seg, hipStream_t s);

@@ -9,12 +9,15 @@
 
 namespace bh {
 
-enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
+enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
 // OP_POOL (ONNX MaxPool / AveragePool, floor mode): the record's `reserved` word is the mode.  No weights, no bias, no activation.
 enum PoolMode : uint32_t { POOL_MAX = 0, POOL_AVG = 1, POOL_AVG_PAD = 2 };   // AVG: over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 // OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the record's `reserved` word is where `act` stands relative to the residual.  0: act(conv + b) + R
 // (the only meaning of every file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block.
 constexpr uint32_t RES_ACT_AFTER = 1;
+// OP_GCONV (a grouped convolution, NHWC): the record's `reserved` word is the group count G, 1 < G; cin and cout are the totals, the
+// weights compact [kh][kw][cin / G][cout] -- output channel o reads input channels (o / (cout / G)) * (cin / G) + 0 .. cin / G - 1 --,
+// bias [cout].  G = 1 stays OP_CONV and one input channel per group with cout == cin stays OP_DWCONV: one spelling each.  No residual.
 constexpr uint32_t NO_TENSOR = 0xFFFFFFFFu;
 
 #pragma pack(push, 1)
@@ -54,6 +57,7 @@ struct Model {
             const uint64_t px = (uint64_t)L.out_h * L.out_w;
             if (L.op == OP_CONV) t += px * L.kh * L.kw * L.cin * L.cout;
             else if (L.op == OP_DWCONV) t += px * L.kh * L.kw * L.cout;
+            else if (L.op == OP_GCONV && L.reserved) t += px * L.kh * L.kw * (L.cin / L.reserved) * L.cout;
             else if (L.op == OP_PWCONV || L.op == OP_DENSE) t += px * L.cin * L.cout;
         }
         return t;
@@ -101,8 +105,19 @@ inline bool validate_model(Model &m, std::string &err) {
         if (L.res_tensor != NO_TENSOR && L.op != OP_SCALE && m.tensor_floats[L.res_tensor] != m.tensor_floats[i + 1]) {
             err = "residual shape does not match the layer output"; return false;
         }
-        if (L.op < OP_CONV || L.op > OP_POOL) { err = "unknown layer op"; return false; }
+        if (L.op < OP_CONV || L.op > OP_GCONV) { err = "unknown layer op"; return false; }
+        if (L.op == OP_GCONV) {
+            const uint32_t G = L.reserved;
+            if (G < 2) { err = "grouped convolution with fewer than two groups (one group is a full convolution)"; return false; }
+            if (L.cin % G || L.cout % G) { err = "grouped convolution whose group count does not divide its channels"; return false; }
+            if ((L.cin / G) % 4 || (L.cout / G) % 4) { err = "grouped convolution with a group width that is not a multiple of 4"; return false; }
+            if (L.res_tensor != NO_TENSOR) { err = "grouped convolution with a residual"; return false; }
+            if (L.in_layout != 0 || L.in_tensor == 0) { err = "grouped convolution on the planar spectrogram (tensor 0)"; return false; }
+            if (L.kh > 7 || L.kw > 7) { err = "grouped convolution with a kernel outside 1 .. 7"; return false; }
+            if (L.sh > 2 || L.sw > 2) { err = "grouped convolution with a stride outside 1 .. 2"; return false; }
+        }
         const uint64_t wn = L.op == OP_CONV ? (uint64_t)L.kh * L.kw * L.cin * L.cout
+                          : L.op == OP_GCONV ? (uint64_t)L.kh * L.kw * (L.cin / L.reserved) * L.cout
                           : L.op == OP_DWCONV ? (uint64_t)L.kh * L.kw * L.cout
                           : (L.op == OP_PWCONV || L.op == OP_DENSE) ? (uint64_t)L.cin * L.cout : 0;
         if (L.op == OP_SCALE && (L.res_tensor == NO_TENSOR || m.tensor_floats[L.res_tensor] != L.cout || L.cin != L.cout)) { err = "scale layer without a [C] gate"; return false; }

@@ -4,7 +4,7 @@
 //
 //   * the CONV STACK is read off the graph (round 4; a C++ port of birda_amd/convert.py model_from_graph, which stays as the
 //     second witness: tests/test_onnx_native.py holds the two to the same layer table and the same weights, bit for bit):
-//     Conv (1x1 -> pointwise, group == channels -> depthwise, else the stem), BatchNormalization folded into the convolution in
+//     Conv (1x1 -> pointwise, group == channels -> depthwise, any other group count -> OP_GCONV, else full), BatchNormalization folded into the convolution in
 //     front of it, the activation spellings exporters emit (Relu, Clip(0, 6), Sigmoid x Mul = swish, Div / Erf / Add / Mul / Mul
 //     = GELU, the Gelu operator), residual Add folded into its 1x1 convolution, MaxPool / AveragePool (floor mode; OP_POOL),
 //     GlobalAveragePool / ReduceMean over H, W,
@@ -447,7 +447,28 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 const uint64_t wo = blob.put(tmp), bo = blob.put(tmpb);
                 li = new_layer(OP_CONV, x.idx, NO_TENSOR, (uint32_t)cin, (uint32_t)cout, (uint32_t)kh, (uint32_t)kw, (uint32_t)sh, (uint32_t)sw, (uint32_t)pt, (uint32_t)pl,
                                (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, x.idx == 0 ? 1u : 0u, wo, bo);
-            } else return fail("Conv '" + n.name + "': group " + std::to_string(group) + " with " + std::to_string(cin) + " -> " + std::to_string(cout) + " channels");
+            } else {
+                // a grouped convolution -> OP_GCONV (convert.py has the same branch, refusal for refusal): compact weights
+                // W[cout][cin / G][kh][kw] -> [kh][kw][cin / G][cout], the group count in the record's reserved word
+                const std::string who = "Conv '" + n.name + "': group " + std::to_string(group) + " with " + std::to_string(cin) + " -> " + std::to_string(cout) + " channels";
+                if (x.idx == 0) return fail(who + ": a grouped convolution on the spectrogram (tensor 0) is not supported");
+                if (cin % group || cout % group || cin_g * group != cin)
+                    return fail(who + ": the group count does not divide them (the weights hold " + std::to_string(cin_g) + " input channels a group)");
+                if (cin_g % 4 || (cout / group) % 4)
+                    return fail(who + ": a group width (" + std::to_string(cin_g) + " -> " + std::to_string(cout / group) + ") that is not a multiple of 4 is not supported");
+                if (kh > 7 || kw > 7) return fail(who + ": a grouped kernel of " + std::to_string(kh) + "x" + std::to_string(kw) + " (1 .. 7 are supported)");
+                if (sh > 2 || sw > 2) return fail(who + ": grouped strides of " + std::to_string(sh) + "x" + std::to_string(sw) + " (1 .. 2 are supported)");
+                tmp.resize((size_t)kh * kw * cin_g * cout);
+                for (int64_t o = 0; o < cout; o++)
+                    for (int64_t c = 0; c < cin_g; c++)
+                        for (int64_t y = 0; y < kh; y++)
+                            for (int64_t z = 0; z < kw; z++)
+                                tmp[(size_t)(((y * kw + z) * cin_g + c) * cout + o)] = W->at((uint64_t)(((o * cin_g + c) * kh + y) * kw + z));
+                const uint64_t wo = blob.put(tmp), bo = blob.put(tmpb);
+                li = new_layer(OP_GCONV, x.idx, NO_TENSOR, (uint32_t)cin, (uint32_t)cout, (uint32_t)kh, (uint32_t)kw, (uint32_t)sh, (uint32_t)sw, (uint32_t)pt, (uint32_t)pl,
+                               (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, 0, wo, bo);
+                layers[li - 1].reserved = (uint32_t)group;
+            }
             if (oh <= 0 || ow <= 0 || oh > DIM_MAX || ow > DIM_MAX) return fail("Conv '" + n.name + "': empty or oversized output");
             tmap[n.out[0]] = T{li, (uint32_t)cout, layers[li - 1].out_h, layers[li - 1].out_w};
             if (!flush_patterns(n.out[0])) return false;
@@ -455,7 +476,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             T t;
             if (!find(n.in[0], t) || t.idx == 0) return fail("BatchNormalization that does not follow a convolution directly");
             LayerRec &L = layers[t.idx - 1];
-            if ((L.op != OP_CONV && L.op != OP_DWCONV && L.op != OP_PWCONV) || L.act != A_NONE || n.in.size() < 5)
+            if ((L.op != OP_CONV && L.op != OP_DWCONV && L.op != OP_PWCONV && L.op != OP_GCONV) || L.act != A_NONE || n.in.size() < 5)
                 return fail("BatchNormalization that does not follow a convolution directly");
             // folding rewrites the convolution's weights, so the BN must be the ONLY reader of the convolution's
             // output (a skip taken before the BN would see scaled values), and a residual already folded into the layer means the BN
@@ -466,7 +487,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             init_refusal.clear();
             for (int q = 0; q < 4; q++) { p[q] = finit(n.in[1 + q]); if (!p[q] || p[q]->count != L.cout) return fail("BatchNormalization: parameters must be float32 or float16 initializers of the channel count" + init_refusal); }
             const double eps = (double)n.getf("epsilon", 1e-5f);
-            const uint64_t nw = L.op == OP_CONV ? (uint64_t)L.kh * L.kw * L.cin * L.cout : L.op == OP_DWCONV ? (uint64_t)L.kh * L.kw * L.cout : (uint64_t)L.cin * L.cout;
+            const uint64_t nw = L.op == OP_CONV ? (uint64_t)L.kh * L.kw * L.cin * L.cout : L.op == OP_GCONV ? (uint64_t)L.kh * L.kw * (L.cin / L.reserved) * L.cout : L.op == OP_DWCONV ? (uint64_t)L.kh * L.kw * L.cout : (uint64_t)L.cin * L.cout;
             for (uint32_t c = 0; c < L.cout; c++) {
                 const double gamma = p[0]->at(c), beta = p[1]->at(c), mean = p[2]->at(c), var = p[3]->at(c);
                 const double scale = gamma / std::sqrt(var + eps);

@@ -34,6 +34,8 @@ VERSION = 1
 
 OP_CONV, OP_DWCONV, OP_PWCONV, OP_GAP, OP_DENSE, OP_SCALE = 1, 2, 3, 4, 5, 6   # OP_SCALE: x[n,h,w,c] * gate[n,c] (squeeze-excite), gate = res_tensor
 OP_POOL = 7   # windowed MaxPool / AveragePool (floor mode); Layer.reserved is the mode; no weights, bias, activation or residual
+OP_GCONV = 8  # grouped convolution (NHWC, no residual); Layer.reserved is the group count G >= 2; cin / cout are the totals, weights
+              # compact [kh][kw][cin / G][cout] (output channel o reads input channels (o // (cout // G)) * (cin // G) + 0 .. cin // G - 1)
 POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2   # AVG: mean over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 # OP_CONV (NHWC), OP_PWCONV, OP_DENSE: Layer.reserved is where `act` stands relative to the residual -- 0: act(conv + b) + R (every
 # file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block
@@ -97,7 +99,7 @@ class Layer:
     b_off: int = 0
     # OP_POOL: the pool mode (POOL_MAX / POOL_AVG / POOL_AVG_PAD).  OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the position of `act`
     # relative to the residual -- 0: act(conv + b) + R; RES_ACT_AFTER: act(conv + b + R), which needs a residual and an activation.
-    # 0 for every other op.
+    # OP_GCONV: the group count.  0 for every other op.
     reserved: int = 0
 
 
@@ -130,6 +132,8 @@ class Model:
                 total += px * L.kh * L.kw * L.cin * L.cout
             elif L.op == OP_DWCONV:
                 total += px * L.kh * L.kw * L.cout
+            elif L.op == OP_GCONV:
+                total += px * L.kh * L.kw * (L.cin // L.reserved) * L.cout
             elif L.op in (OP_PWCONV, OP_DENSE):
                 total += px * L.cin * L.cout
         return total

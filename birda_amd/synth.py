@@ -103,6 +103,22 @@ class _Builder:
                      0, self.put(wt), self.put(self.bias(c)))
         return self.add(L), oh, ow
 
+    def gconv(self, tin, h, w, cin, cout, k, s, groups, act, gain=1.0, kw=None, pad="same"):
+        """A grouped convolution (mf.OP_GCONV; reserved = groups): k x kw (kw: k), stride s, SAME_UPPER padding or explicit (top, left,
+        bottom, right); compact weights [kh][kw][cin / groups][cout], He-normal over the group's own fan-in."""
+        kw = k if kw is None else kw
+        assert groups >= 2 and cin % groups == 0 and cout % groups == 0 and (cin // groups) % 4 == 0 and (cout // groups) % 4 == 0
+        if pad == "same":
+            (oh, pt), (ow, pl) = _same_pad(h, k, s), _same_pad(w, kw, s)
+        else:
+            pt, pl, pb, pr = pad
+            oh, ow = (h + pt + pb - k) // s + 1, (w + pl + pr - kw) // s + 1
+        gi = cin // groups
+        wt = self.he((k, kw, gi, cout), k * kw * gi) * np.float32(gain)
+        L = mf.Layer(mf.OP_GCONV, act, tin, mf.NO_TENSOR, cin, cout, k, kw, s, s, pt, pl, h, w, oh, ow,
+                     0, self.put(wt), self.put(self.bias(cout)), reserved=groups)
+        return self.add(L), oh, ow
+
     def pwconv(self, tin, h, w, cin, cout, act, res=mf.NO_TENSOR, gain=1.0):
         wt = self.he((cin, cout), cin) * np.float32(gain)
         L = mf.Layer(mf.OP_PWCONV, act, tin, res, cin, cout, 1, 1, 1, 1, 0, 0, h, w, h, w,
@@ -181,6 +197,9 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     'resnet_plan' (plan = random_resnet_plan(seed)) builds that plan's ResNet blocks -- act(conv + shortcut), Layer.reserved =
     RES_ACT_AFTER -- on the same mini front-end: _build_resnet_plan.  'resnet18_audio' (a ResNet-18 on the v2.4 front-end, for timing
     those layers: _build_resnet18_audio).
+    'resnext_plan' (plan = random_resnext_plan(seed)) builds that plan's ResNeXt bottleneck blocks around grouped convolutions
+    (mf.OP_GCONV): _build_resnext_plan.  'resnext_audio' (a ResNeXt-26 32x4d-like trunk on the v2.4 front-end, for timing the grouped
+    layers: _build_resnext_audio).
     A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
@@ -192,6 +211,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
         return _build_resnet_plan(plan, seed)
     if kind == "resnet18_audio":
         return _build_resnet18_audio(seed, n_classes)
+    if kind == "resnext_plan":
+        return _build_resnext_plan(plan, seed)
+    if kind == "resnext_audio":
+        return _build_resnext_audio(seed, n_classes)
     rng = np.random.default_rng(seed)
     b = _Builder(rng)
     act_override, act, hidden = act, mf.ACT_GELU_ERF, 0
@@ -643,6 +666,131 @@ def _build_resnet18_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = No
     ncls = n_classes or 6522
     b.dense(t, 512, ncls, gain=1.5)
     return _finish(b, branches, sr, n, ncls, 512, emb, mf.OUT_SIGMOID)
+
+
+def _resnext_block(b: _Builder, t, h, w, c, shortcut, cout, mid_in, mid_out, groups, act, se=False):
+    """One ResNeXt bottleneck behind tensor t [h][w][c]: 1x1 (c -> mid_in, act) -> grouped 3x3 (mid_in -> mid_out in `groups` groups,
+    stride 1 / 2, act) [-> squeeze-excite gate] -> 1x1 (mid_out -> cout) + shortcut, the activation after the add (Layer.reserved =
+    RES_ACT_AFTER on the layer the residual folds into).  Shortcuts as _res_block's: 'identity', 'proj', 'resnetd'."""
+    x, st = t, 1 if shortcut == "identity" else 2
+    assert shortcut != "identity" or cout == c
+    last_res = x if shortcut == "identity" else mf.NO_TENSOR
+    last_act = act if shortcut == "identity" else mf.ACT_NONE
+    t = b.pwconv(x, h, w, c, mid_in, act)
+    t, oh, ow = b.gconv(t, h, w, mid_in, mid_out, 3, st, groups, act)
+    if se:   # pool -> fc (act) -> fc (sigmoid) -> gate, behind the grouped layer (SE-ResNeXt, RegNetY)
+        cr = max(8, mid_out // 4 // 4 * 4)
+        tg = b.gap(t, oh, ow, mid_out)
+        tg = b.pwconv(tg, 1, 1, mid_out, cr, act)
+        tg = b.pwconv(tg, 1, 1, cr, mid_out, mf.ACT_SIGMOID)
+        t = b.scale(t, tg, oh, ow, mid_out)
+    t = b.pwconv(t, oh, ow, mid_out, cout, last_act, last_res, gain=0.5)
+    if shortcut == "identity":
+        b.layers[-1].reserved = mf.RES_ACT_AFTER
+    elif shortcut == "proj":
+        t, ph, pw_ = b.conv(x, h, w, c, cout, 1, 2, act, res=t)
+        assert (ph, pw_) == (oh, ow)
+        b.layers[-1].reserved = mf.RES_ACT_AFTER
+    elif shortcut == "resnetd":
+        tp, ph, pw_ = b.pool(x, h, w, c, 2, 2, 2, 2, mf.POOL_AVG, "same")
+        assert (ph, pw_) == (oh, ow)
+        t = b.pwconv(tp, ph, pw_, c, cout, act, t)
+        b.layers[-1].reserved = mf.RES_ACT_AFTER
+    else:
+        raise ValueError(shortcut)
+    return t, oh, ow
+
+
+_GROUP_WIDTHS = (4, 8, 16, 24, 32)
+_GROUP_COUNTS = {4: (4, 8), 8: (2, 4, 8), 16: (2, 4), 24: (2, 3), 32: (2, 3)}   # per width, group counts that keep the layer at 96 channels or fewer
+
+
+def random_resnext_plan(seed: int) -> dict:
+    """A small seeded ResNeXt on the mini front-end of _build_pool_plan (32 mels x 115 frames): a 3x3 stride-2 stem, then three
+    bottleneck blocks 1x1 -> grouped 3x3 -> 1x1 + shortcut with the activation after the add (_resnext_block) -- an identity block, a
+    down-sampling block (projection or ResNet-D shortcut) whose grouped layer has UNEQUAL in / out group widths, a second identity
+    block -- and one grouped 1x1 layer in front of the head.  Group widths come from 4 / 8 / 16 / 24 / 32, rotated by the seed so that
+    five consecutive seeds see every width in every position; the activation is ReLU / ReLU6 / swish / GELU in turn; the plans
+    with seed % 3 == 1 put a squeeze-excite gate behind every grouped 3x3.
+    Feed to build_model("resnext_plan", plan=...).  plan["items"]: ("block", shortcut, cout, in_width, out_width, groups, se) |
+    ("g1x1", cout, in_width, out_width, groups)."""
+    rng = np.random.default_rng(0x6C0F + seed)
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+    act = (mf.ACT_RELU, mf.ACT_RELU6, mf.ACT_SWISH, mf.ACT_GELU_ERF)[seed % 4]
+    wd = lambda k: _GROUP_WIDTHS[(seed + k) % 5]
+    se = seed % 3 == 1
+    c0, c1 = pick((32, 48)), pick((64, 80))
+    w0, w1, w2, w3 = wd(0), wd(1), wd(2), wd(3)
+    w1o = pick([x for x in _GROUP_WIDTHS if x != w1 and x <= 16])       # the unequal layer: in width w1, out width w1o
+    items = [("block", "identity", c0, w0, w0, pick(_GROUP_COUNTS[w0]), se),
+             ("block", pick(("proj", "resnetd")), c1, w1, w1o, pick(_GROUP_COUNTS[w1]), se),
+             ("block", "identity", c1, w2, w2, pick(_GROUP_COUNTS[w2]), se)]
+    g3 = pick(_GROUP_COUNTS[w3])
+    items.append(("g1x1", g3 * w3, w3, w3, g3))
+    return {"items": items, "stem_c": c0, "act": act, "head": int(rng.integers(4, 13)) * 8, "classes": int(rng.integers(20, 61)),
+            "out_act": int(pick((mf.OUT_SIGMOID, mf.OUT_SOFTMAX)))}
+
+
+def _build_resnext_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
+    """random_resnext_plan's stack on the mini front-end of one branch (512-sample frames at hop 100: 32 mels x 115 frames)."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 12000
+    br = mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23)
+    br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+    br.out_scale, br.out_shift = 0.8, -0.4
+    act, c = int(plan["act"]), int(plan["stem_c"])
+    t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, c, 3, 2, act, in_layout=1)
+    for it in plan["items"]:
+        if it[0] == "block":
+            _, shortcut, cout, wi, wo, g, se = it
+            t, h, w = _resnext_block(b, t, h, w, c, shortcut, cout, g * wi, g * wo, g, act, se)
+            c = cout
+        elif it[0] == "g1x1":    # a grouped 1x1 layer (ShuffleNet-style) between two ordinary 1x1 layers
+            _, cout, wi, wo, g = it
+            t = b.pwconv(t, h, w, c, g * wi, act)
+            t, h, w = b.gconv(t, h, w, g * wi, g * wo, 1, 1, g, act)
+            c = g * wo
+        else:
+            raise ValueError(it[0])
+    head, ncls = int(plan["head"]), int(plan["classes"])
+    t = b.pwconv(t, h, w, c, head, act)
+    t = emb = b.gap(t, h, w, head)
+    b.dense(t, head, ncls, gain=1.5)
+    return _finish(b, [br], sr, n, ncls, head, emb, int(plan["out_act"]))
+
+
+def _build_resnext_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) -> mf.Model:
+    """A ResNeXt-26 32x4d-like trunk on the v2.4 front-end (96 mels x 511 frames, two branches): a 7x7 stride-2 NCHW stem to 64
+    channels with ReLU, MaxPool 3x3 stride 2 pad 1, four stages of two bottleneck blocks -- 1x1 -> grouped 3x3 in 32 groups (group
+    widths 4 / 8 / 16 / 32 over the stages) -> 1x1, relu(main + shortcut), projection shortcuts at the stage entries -- at widths
+    256 / 512 / 1024 / 2048, the global pool and the dense layer.  Seeded weights: a model for TIMING the grouped layers in the manner
+    of resnet18_audio, not for accuracy."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 144000
+    branches = [mf.Branch(2048, 278, 96, 511, 0.0, 3000.0, 1.23), mf.Branch(1024, 280, 96, 511, 500.0, 15000.0, 1.23)]
+    for br in branches:
+        br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+        br.out_scale, br.out_shift = 0.8, -0.4
+    t, h, w = b.conv(0, 96, 511, 2, 64, 7, 2, mf.ACT_RELU, in_layout=1)
+    t, h, w = b.pool(t, h, w, 64, 3, 3, 2, 2, mf.POOL_MAX, (1, 1, 1, 1))
+    c = 64
+    for stage, width in enumerate((256, 512, 1024, 2048)):
+        mid = width // 2
+        if stage == 0:   # the first stage keeps the image: a stride-1 projection shortcut (1x1 + add, activation after the add)
+            x = t
+            t = b.pwconv(x, h, w, c, mid, mf.ACT_RELU)
+            t, h, w = b.gconv(t, h, w, mid, mid, 3, 1, 32, mf.ACT_RELU)
+            t = b.pwconv(t, h, w, mid, width, mf.ACT_NONE, gain=0.5)
+            t = b.pwconv(x, h, w, c, width, mf.ACT_RELU, t)
+            b.layers[-1].reserved = mf.RES_ACT_AFTER
+        else:
+            t, h, w = _resnext_block(b, t, h, w, c, "proj", width, mid, mid, 32, mf.ACT_RELU)
+        t, h, w = _resnext_block(b, t, h, w, width, "identity", width, mid, mid, 32, mf.ACT_RELU)
+        c = width
+    t = emb = b.gap(t, h, w, 2048)
+    ncls = n_classes or 6522
+    b.dense(t, 2048, ncls, gain=1.5)
+    return _finish(b, branches, sr, n, ncls, 2048, emb, mf.OUT_SIGMOID)
 
 
 def random_fused_plan(seed: int, big: bool = False) -> dict:

@@ -1,4 +1,5 @@
-"""Per-launch times of one forward (HIP events per layer; fused blocks are booked on their first layer): python tools/gpu_layer_times.py [kind] [n] [precision]"""
+"""Per-launch times of one forward (HIP events per layer; fused blocks are booked on their first layer): python tools/gpu_layer_times.py [kind] [n] [precision]
+(kind: any model of synth.build_model -- perch_v2, cnn_pool, resnet18_audio, resnext_audio, ...)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -23,13 +24,16 @@ for _ in range(5):
 ctx.synchronize()
 st = ctx.stage_ms(); ly = ctx.layer_ms()
 print({k: round(v[0] / 5 * 1e3 / N, 3) for k, v in st.items()}, "us/segment")
-names = {1: "conv", 2: "dw", 3: "pw", 4: "gap", 5: "dense", 6: "scale", 7: "pool"}
+names = {1: "conv", 2: "dw", 3: "pw", 4: "gap", 5: "dense", 6: "scale", 7: "pool", 8: "gconv"}
 for i, (ms, n) in enumerate(ly):
     if n:
         L = m.layers[i]
         line = f"layer {i:3d} {names[L.op]:5s} {L.cin:5d}->{L.cout:5d} {L.in_h}x{L.in_w} k{L.kh} s{L.sh}  {ms / 5 * 1e3:9.1f} us per {N}"
         if L.op in (mf.OP_CONV, mf.OP_PWCONV, mf.OP_DENSE) and L.reserved == mf.RES_ACT_AFTER:
             line += "  act after the residual add"
+        if L.op == mf.OP_GCONV:  # near the HBM / MFMA ridge: the kernel it ran, the bytes it moves (input + output) and the rate
+            nbytes = 4 * N * (L.in_h * L.in_w * L.cin + L.out_h * L.out_w * L.cout)
+            line += f"  {L.reserved} groups of {L.cin // L.reserved}->{L.cout // L.reserved}  {clf.layer_kernel(i)}  {nbytes / 1e6:9.1f} MB  {nbytes / (ms / 5 * 1e-3) / 1e12:5.2f} TB/s"
         if L.op == mf.OP_POOL:   # HBM-bound: the bytes it moves (input + output) and the rate
             nbytes = 4 * N * L.cout * (L.in_h * L.in_w + L.out_h * L.out_w)
             line += f"  {('max', 'avg', 'avg_pad')[L.reserved]} {L.kh}x{L.kw}/{L.sh}x{L.sw}  {nbytes / 1e6:9.1f} MB  {nbytes / (ms / 5 * 1e-3) / 1e12:5.2f} TB/s"
