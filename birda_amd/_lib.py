@@ -15,6 +15,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libbirda_hip.so")
 BH_MAX_TOP_K = 32
+BH_MAX_CLASSES = 32768   # the widest model the create entry points accept (include/birda_hip.h)
 BH_N_STAGES = 9
 # ("stem": every full convolution -- the unfused NCHW stem and the k x k group-1 layers past it, e.g. Fused-MBConv expands)
 STAGE_NAMES = ["minmax", "mel", "stem", "depthwise", "pointwise", "pool", "dense", "topk", "mbconv"]

@@ -1080,6 +1080,10 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
     std::string err;
     if (!load_any_model(cfg->model_path, c->model, err)) return fail(model_load_status(err), "%s", err.c_str());
     const auto &m = c->model;
+    static_assert(BH_MAX_CLASSES == bh::TOPK_MAX_CLASSES, "the documented class-count ceiling is the top-k kernel's row");
+    if (m.h.n_classes > BH_MAX_CLASSES)   // (before anything touches a device: the top-k launch would fail with a bare HIP error)
+        return fail(BH_ERR_UNSUPPORTED, "the model has %u classes: the activation / top-k stage holds at most %d (a segment's logits in 128 KB of LDS)",
+                    m.h.n_classes, BH_MAX_CLASSES);
     if (cfg->labels_path) {
         int rc = read_labels(cfg->labels_path, c->labels);
         if (rc != BH_OK) return rc;

@@ -170,6 +170,9 @@ int bh_custom_classifier_create(const char *model_path, const char *labels_path,
     std::unique_ptr<bh_custom_classifier, void (*)(bh_custom_classifier *)> cc(new bh_custom_classifier(), bh_custom_classifier_destroy);
     std::string err;
     if (!bh::load_custom_model(model_path, cc->model, err)) return fail(BH_ERR_IO, "%s", err.c_str());
+    if (cc->model.h.n_classes > BH_MAX_CLASSES)   // (a geomodel's scores are never ranked: bh_range_filter_create is not held to this)
+        return fail(BH_ERR_UNSUPPORTED, "the custom classifier has %u classes: the activation / top-k stage holds at most %d (a segment's logits in 128 KB of LDS)",
+                    cc->model.h.n_classes, BH_MAX_CLASSES);
     int rc = cc_build(cc.get(), labels_path, device, top_k, false);
     if (rc != BH_OK) return rc;
     *out = cc.release();

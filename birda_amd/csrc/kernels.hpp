@@ -499,6 +499,9 @@ struct TopkFilter {
 };
 // in_bad (nullable): launch_minmax's flags [n_seg][8]; nonfinite (nullable): counter that receives +1 for every segment whose
 // logits hold an inf / NaN although its samples were all finite (an operand left the f16 range on the way)
+// The kernel holds a segment's logits in dynamic LDS: TOPK_MAX_CLASSES f32 = 128 KB is the widest row it is launched with (the
+// static arrays next to it take the CU's 160 KB no further).  The create entry points refuse a wider model (BH_MAX_CLASSES).
+constexpr int TOPK_MAX_CLASSES = 32768;
 void launch_topk(const float *logits, int n_seg, int n_classes, int out_act, int top_k, float min_conf,
                  const TopkFilter &filter, int32_t *idx, float *conf, const unsigned *in_bad, unsigned *nonfinite, hipStream_t s);
 

@@ -2172,7 +2172,7 @@ void launch_topk(const float *logits, int n_seg, int n_classes, int out_act, int
     static DeviceOnce once;
     once.run([] {
         // (the kernel also has a few static __shared__ words: ask for less than the full 160 KB)
-        if (hipFuncSetAttribute((const void *)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
+        if (hipFuncSetAttribute((const void *)topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TOPK_MAX_CLASSES * (int)sizeof(float)) != hipSuccess)
             (void)hipGetLastError();
     });
     hipLaunchKernelGGL(topk_kernel, dim3(n_seg), dim3(256), (size_t)n_classes * sizeof(float), s, logits, n_classes, out_act, top_k,

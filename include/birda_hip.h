@@ -41,6 +41,11 @@ typedef enum {
 } bh_status;
 
 #define BH_MAX_TOP_K 32
+/* The widest output a classifier may have: the activation / top-k stage holds one segment's logits in the LDS of its workgroup,
+ * 32 768 f32 = 128 KB of the CU's 160 KB.  bh_classifier_create and bh_custom_classifier_create refuse a model with more classes
+ * (BH_ERR_UNSUPPORTED; the message states this limit and the model's class count) -- a BHM1 / BHC1 container and an .onnx file
+ * alike.  (A geomodel is not ranked and is not held to it.) */
+#define BH_MAX_CLASSES 32768
 
 /* ClassifierBuilder::new().model_path().labels_path().top_k().min_confidence()
  * (classifier.rs:269-273) + execution-provider choice (classifier.rs:662-691 -> device). */
