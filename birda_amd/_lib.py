@@ -260,6 +260,13 @@ POOL_DEBUG_SYMBOLS = [
     ("bh_debug_pool", C.c_int, [C.c_int, _VP, _VP, _SZ, _VP, C.c_int, _VP, _SZ]),
 ]
 
+# include/birda_hip_gate_debug.h: the squeeze-excite gate in its three forms and the plain f32 layer kernels (depthwise, the stem's
+# direct convolution, global average pool, gate multiply) alone, for the tests that hold them to float64
+GATE_DEBUG_SYMBOLS = [
+    ("bh_debug_se_gate", C.c_int, [C.c_int, _VP, _SZ, _SZ, _SZ, _SZ, _SZ, _VP, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _SZ]),
+    ("bh_debug_plain_layer", C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, C.c_int, _VP, _SZ]),
+]
+
 # include/birda_hip_gconv_debug.h: one grouped convolution (OP_GCONV) alone, for the tests that hold it to float64
 GCONV_DEBUG_SYMBOLS = [
     ("bh_debug_gconv", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _SZ, _VP, C.c_int, C.c_int, _VP, _SZ]),
@@ -299,7 +306,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS + GCONV_DEBUG_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS + GCONV_DEBUG_SYMBOLS + GATE_DEBUG_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

@@ -158,6 +158,17 @@ std::vector<float> pw_gemm_rows(const float *W, size_t K, size_t N, size_t ld) {
     return w;
 }
 
+// Which of its three forms the gate of a fused squeeze-excite block of C expanded and Cr hidden channels takes -- its widths alone
+// decide, never the launch: 1 = the two sixteen-segment launches (launch_se_gate16) from BH_SE_GATE16_MIN channels where they
+// support the shape, 2 = the pool and two GEMMs (launch_se_gate_gemm) for the other widths beyond 576, 0 = the one-launch kernel
+// (launch_se_gate).  -1: no form takes it (plan_fusion keeps such a block layer by layer).  SliceRun::fused_se and bh_debug_se_gate
+// both ask here.
+int se_gate_form(int C, int Cr) {
+    if (C >= BH_SE_GATE16_MIN && bh::se_gate16_supports(C, Cr)) return 1;
+    if (C > 576) return 2;
+    return bh::se_gate_supports(C, Cr) ? 0 : -1;
+}
+
 int upload(const void *src, size_t bytes, float **dst) {
     HIPCHK(hipMalloc((void **)dst, bytes ? bytes : 4));
     if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
@@ -331,7 +342,7 @@ int SliceRun::layer(const Step &st) const {
         // the NCHW stem on the direct kernel (when it is not fused into the first block); every NHWC full convolution is an
         // implicit GEMM on the MFMA (kernels_conv.hip), split-f16 where it has planes
         if (L.in_layout == 1)
-            bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
+            launched = bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
         else if (!ctx->keep_tensors && c->d_w16[i])
             c->w16_kernel[i].store(launched = bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
         else
@@ -339,7 +350,7 @@ int SliceRun::layer(const Step &st) const {
         ctx_mark(ctx, ST_STEM, (int)i);
         break;
     case bh::OP_DWCONV:
-        bh::launch_dwconv(in, c->d_w[i], bias, out, p, (int)n, s);
+        launched = bh::launch_dwconv(in, c->d_w[i], bias, out, p, (int)n, s);
         ctx_mark(ctx, ST_DW, (int)i);
         break;
     case bh::OP_PWCONV:
@@ -382,7 +393,11 @@ int SliceRun::layer(const Step &st) const {
     default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
     }
     // (create's predicates and validate_model keep this from happening; if it does, the output tensor was not written)
-    if (!launched && n) return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for activation %u %s the residual add", i, L.act, after ? "after" : "before");
+    if (!launched && n) {
+        if (L.op == bh::OP_DWCONV || (L.op == bh::OP_CONV && L.in_layout == 1))
+            return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for a %ux%u stride %ux%u window, %u -> %u channels", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout);
+        return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for activation %u %s the residual add", i, L.act, after ? "after" : "before");
+    }
     return BH_OK;
 }
 
@@ -430,10 +445,11 @@ int SliceRun::fused_se(const Step &st) const {
     // (one selection for whole launches and for the groups below: a segment's bits do not depend on how its launch is cut)
     static const bool gate1 = [] { const char *e = BH_XENV("BIRDA_HIP_SE_GATE1"); return e && e[0] == '1'; }();
     auto launch_gate = [&](const float *part, int tiles, int P, float *pooled, float *hidden, float *gate, size_t ns) {
-        if (!gate1 && d.Cexp >= BH_SE_GATE16_MIN && bh::se_gate16_supports(d.Cexp, (int)G1.cout))
+        const int form = gate1 ? 0 : se_gate_form(d.Cexp, (int)G1.cout);
+        if (form == 1)
             bh::launch_se_gate16(part, tiles, P, pooled, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
                                  c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
-        else if (!gate1 && d.Cexp > 576)
+        else if (form == 2)
             bh::launch_se_gate_gemm(part, tiles, P, pooled, hidden, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
                                     c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
         else
@@ -1196,10 +1212,10 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
                 c->d_w[i] = d;
             }
         } else if (L.op == bh::OP_DWCONV) {
-            if (L.cout % 4 || L.kh != L.kw || L.sh != L.sw || !((L.kh == 3 || L.kh == 5) && (L.sh == 1 || L.sh == 2)))
+            if (!bh::dwconv_supports(conv_params(L)))
                 return fail(BH_ERR_UNSUPPORTED, "layer %zu: depthwise %ux%u stride %u channels %u not built", i, L.kh, L.kw, L.sh, L.cout);
         } else if (L.op == bh::OP_CONV && L.in_layout == 1) {   // the NCHW stem: the direct kernel, weights in LDS
-            if (L.cout % 4 || (size_t)L.kh * L.kw * L.cin * L.cout * 4 > 64 * 1024)
+            if (!bh::conv_direct_supports(conv_params(L)))
                 return fail(BH_ERR_UNSUPPORTED, "layer %zu: direct conv shape not built", i);
         } else if (L.op == bh::OP_CONV) {   // NHWC: the implicit GEMM, W rows padded per tap to whole 32-deep steps
             const bh::ConvParams p = conv_params(L);
@@ -2165,6 +2181,104 @@ int bh_debug_pool(int device, const float *X, float *Y, size_t n_seg, const int3
     if (!dX.put(X, x_floats * 4, kGuardNaN) || !dY.put(nullptr, y_floats * 4, kUnwrittenNaN)) return fail(BH_ERR_HIP, "debug_pool: device memory");
     const char *name = bh::launch_pool((const float *)dX.p(), (float *)dY.p(), p, mode, (int)n_seg, nullptr);
     return finish_debug_launch("debug_pool", name, dY, Y, y_floats, kernel, kernel_cap, "Y");
+} catch (...) { return on_exception(); }
+
+// The gate of one squeeze-excite block alone on operands of the caller's, in the form a forward pass takes for its widths
+// (se_gate_form) or a forced one, with create's row padding of W1 and W2 and scratch buffers of the forward's sizes
+// (include/birda_hip_gate_debug.h).
+int bh_debug_se_gate(int device, const float *part, size_t n_seg, size_t tiles, size_t P, size_t C, size_t Cr, const float *W1, const float *b1,
+                     int act1, const float *W2, const float *b2, int act2, int form, float *gate, char *kernel, size_t kernel_cap) try {
+    if (!part || !W1 || !b1 || !W2 || !b2 || !gate || !n_seg || !tiles || !P || !C || !Cr || form < -1 || form > 2 || act1 < 0 ||
+        act1 > bh::ACT_SIGMOID || act2 < 0 || act2 > bh::ACT_SIGMOID)
+        return fail(BH_ERR_INVALID, "debug_se_gate: bad arguments");
+    if (C > (1u << 24) || Cr > (1u << 24) || tiles > (1u << 24) || P > (size_t)INT32_MAX || n_seg > (size_t)INT32_MAX ||
+        tiles * C > (size_t)INT32_MAX || n_seg * (tiles * C) > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_se_gate: operands past 2^31 elements");
+    const int c = (int)C, cr = (int)Cr;
+    if (form < 0 && (form = se_gate_form(c, cr)) < 0)
+        return fail(BH_ERR_UNSUPPORTED, "debug_se_gate: no form of the gate takes %d -> %d -> %d channels", c, cr, c);
+    if (form == 0 && !bh::se_gate_supports(c, cr))
+        return fail(BH_ERR_UNSUPPORTED, "debug_se_gate: the one-launch gate keeps C + 256 + Cr floats in 64 KiB of LDS and at most 256 hidden channels: %d, %d", c, cr);
+    if (form == 1 && !bh::se_gate16_supports(c, cr))
+        return fail(BH_ERR_UNSUPPORTED, "debug_se_gate: the partial hidden sums of %d -> %d channels do not fit n_seg x C floats (or Cr > 256)", c, cr);
+    if (form == 2 && (C % 4 || Cr % 4))
+        return fail(BH_ERR_UNSUPPORTED, "debug_se_gate: the GEMM form needs C and Cr multiples of 4: %d, %d", c, cr);
+    HIPCHK(hipSetDevice(device));
+    const size_t ld1 = align_up(Cr, 4), ld2 = align_up(C, 4);
+    const std::vector<float> w1 = pw_gemm_rows(W1, C, Cr, ld1), w2 = pw_gemm_rows(W2, Cr, C, ld2);
+    Guarded dP, dW1, dB1, dW2, dB2, dPooled, dHidden, dG;
+    if (!dP.put(part, n_seg * tiles * C * 4, kGuardNaN) || !dW1.put(w1.data(), w1.size() * 4, kGuardNaN) || !dB1.put(b1, Cr * 4, kGuardNaN) ||
+        !dW2.put(w2.data(), w2.size() * 4, kGuardNaN) || !dB2.put(b2, C * 4, kGuardNaN) ||
+        (form != 0 && !dPooled.put(nullptr, n_seg * C * 4, kUnwrittenNaN)) || (form == 2 && !dHidden.put(nullptr, n_seg * Cr * 4, kUnwrittenNaN)) ||
+        !dG.put(nullptr, n_seg * C * 4, kUnwrittenNaN))
+        return fail(BH_ERR_HIP, "debug_se_gate: device memory");
+    const float *dp = (const float *)dP.p(), *d1 = (const float *)dW1.p(), *db1 = (const float *)dB1.p(), *d2 = (const float *)dW2.p(),
+                *db2 = (const float *)dB2.p();
+    float *dg = (float *)dG.p();
+    const char *name =
+        form == 1 ? bh::launch_se_gate16(dp, (int)tiles, (int)P, (float *)dPooled.p(), d1, db1, (int)ld1, act1, d2, db2, (int)ld2, act2, dg, (int)n_seg, c, cr, nullptr)
+      : form == 2 ? bh::launch_se_gate_gemm(dp, (int)tiles, (int)P, (float *)dPooled.p(), (float *)dHidden.p(), d1, db1, (int)ld1, act1, d2, db2, (int)ld2, act2,
+                                            dg, (int)n_seg, c, cr, nullptr)
+                  : bh::launch_se_gate(dp, (int)tiles, (int)P, d1, db1, (int)ld1, act1, d2, db2, (int)ld2, act2, dg, (int)n_seg, c, cr, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    if (!name) return fail(BH_ERR_INTERNAL, "debug_se_gate: a GEMM of the three-launch form had no instantiation");
+    for (const Guarded *g : {&dPooled, &dHidden}) {
+        if (!g->base) continue;
+        bool intact = false;
+        const int rc = g->guards_intact(kUnwrittenNaN, &intact);
+        if (rc != BH_OK) return rc;
+        if (!intact) return fail(BH_ERR_INTERNAL, "debug_se_gate: %s wrote outside %s", name, g == &dPooled ? "the pooled / partial-sum scratch" : "the hidden scratch");
+    }
+    return finish_debug_launch("debug_se_gate", name, dG, gate, n_seg * C, kernel, kernel_cap, "gate");
+} catch (...) { return on_exception(); }
+
+// One plain f32 layer (depthwise, the NCHW stem's direct convolution, global average pool, gate multiply) alone on operands of the
+// caller's, through the launcher SliceRun::layer takes, refusing what create refuses for the op (include/birda_hip_gate_debug.h).
+int bh_debug_plain_layer(int device, int op, const float *X, const float *W, const float *bias, const float *gate, float *Y, size_t n_seg,
+                         const int32_t *shape, int act, char *kernel, size_t kernel_cap) try {
+    if (!X || !Y || !shape || !n_seg || n_seg > (size_t)INT32_MAX || act < 0 || act > bh::ACT_SIGMOID)
+        return fail(BH_ERR_INVALID, "debug_plain_layer: bad arguments");
+    const bool conv = op == bh::OP_CONV, dw = op == bh::OP_DWCONV, gap = op == bh::OP_GAP, scale = op == bh::OP_SCALE;
+    if (!conv && !dw && !gap && !scale) return fail(BH_ERR_INVALID, "debug_plain_layer: op %d is not one of the plain layers", op);
+    if (((conv || dw) && (!W || !bias)) || (scale && !gate)) return fail(BH_ERR_INVALID, "debug_plain_layer: null operand");
+    const bh::ConvParams p{shape[0], shape[1], shape[2], shape[3], conv ? shape[11] : shape[4], shape[4], shape[5], shape[6], shape[7], shape[8],
+                           shape[9], shape[10], conv ? 1 : 0, act, 0};
+    // (validate_model's ranges)
+    if (p.in_h < 1 || p.in_w < 1 || p.out_h < 1 || p.out_w < 1 || p.in_h > 65536 || p.in_w > 65536 || p.out_h > 65536 || p.out_w > 65536 || p.cin < 1 ||
+        p.cin > 65536 || p.cout < 1 || p.cout > (1 << 24) || p.kh < 1 || p.kw < 1 || p.kh > 64 || p.kw > 64 || p.sh < 1 || p.sw < 1 || p.sh > 16 ||
+        p.sw > 16 || p.pad_t < 0 || p.pad_l < 0 || p.pad_t > 64 || p.pad_l > 64)
+        return fail(BH_ERR_INVALID, "debug_plain_layer: layer dimensions out of range");
+    if (gap && (p.out_h != 1 || p.out_w != 1)) return fail(BH_ERR_INVALID, "debug_plain_layer: a global pool leaves one pixel");
+    if (scale && (p.out_h != p.in_h || p.out_w != p.in_w)) return fail(BH_ERR_INVALID, "debug_plain_layer: a gate multiply keeps the image");
+    if (dw && !bh::dwconv_supports(p))
+        return fail(BH_ERR_UNSUPPORTED, "debug_plain_layer: depthwise %dx%d stride %dx%d channels %d not built (square 3x3 / 5x5 windows, one stride of 1 or 2, "
+                    "channels a multiple of 4)", p.kh, p.kw, p.sh, p.sw, p.cout);
+    if (conv && !bh::conv_direct_supports(p))
+        return fail(BH_ERR_UNSUPPORTED, "debug_plain_layer: direct conv shape not built (output channels a multiple of 4, %dx%dx%dx%d weights within 64 KiB of LDS)",
+                    p.kh, p.kw, p.cin, p.cout);
+    if ((gap || scale) && p.cout % 4) return fail(BH_ERR_UNSUPPORTED, "debug_plain_layer: channels %d not a multiple of 4", p.cout);
+    // (n_seg < 2^31 and a segment <= 2^16 x 2^16 x 2^24 is checked per segment first: none of these products wraps)
+    const size_t x_seg = (size_t)p.in_h * p.in_w, y_seg = (size_t)p.out_h * p.out_w;
+    if (x_seg * (conv ? p.cin : p.cout) > (size_t)INT32_MAX || y_seg * p.cout > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_plain_layer: tensors past 2^31 elements");
+    const size_t x_floats = n_seg * (x_seg * (conv ? p.cin : p.cout)), y_floats = n_seg * (y_seg * p.cout);
+    const size_t w_floats = conv ? (size_t)p.kh * p.kw * p.cin * p.cout : (size_t)p.kh * p.kw * p.cout;
+    if (x_floats > (size_t)INT32_MAX || y_floats > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_plain_layer: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    Guarded dX, dW, dB, dG, dY;
+    if (!dX.put(X, x_floats * 4, kGuardNaN) || ((conv || dw) && (!dW.put(W, w_floats * 4, kGuardNaN) || !dB.put(bias, (size_t)p.cout * 4, kGuardNaN))) ||
+        (scale && !dG.put(gate, n_seg * p.cout * 4, kGuardNaN)) || !dY.put(nullptr, y_floats * 4, kUnwrittenNaN))
+        return fail(BH_ERR_HIP, "debug_plain_layer: device memory");
+    const float *dx = (const float *)dX.p();
+    float *dy = (float *)dY.p();
+    const char *name = dw   ? bh::launch_dwconv(dx, (const float *)dW.p(), (const float *)dB.p(), dy, p, (int)n_seg, nullptr)
+                     : conv ? bh::launch_conv_direct(dx, (const float *)dW.p(), (const float *)dB.p(), dy, p, (int)n_seg, nullptr)
+                     : gap  ? bh::launch_gap(dx, dy, (int)n_seg, p.in_h * p.in_w, p.cout, nullptr)
+                            : bh::launch_scale(dx, (const float *)dG.p(), dy, (int)n_seg, p.out_h * p.out_w, p.cout, nullptr);
+    if (!name) return fail(BH_ERR_INTERNAL, "debug_plain_layer: the launcher has no instantiation for a shape the validator accepts");
+    return finish_debug_launch("debug_plain_layer", name, dY, Y, y_floats, kernel, kernel_cap, "Y");
 } catch (...) { return on_exception(); }
 
 namespace {

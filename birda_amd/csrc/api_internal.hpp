@@ -30,6 +30,7 @@
 #include "../../include/birda_hip_audit.h"
 #include "../../include/birda_hip_layer_debug.h"
 #include "../../include/birda_hip_pool_debug.h"
+#include "../../include/birda_hip_gate_debug.h"
 #include "../../include/birda_hip_resact_debug.h"
 #include "../../include/birda_hip_gconv_debug.h"
 #include "../../include/birda_hip_block_debug.h"

@@ -398,8 +398,10 @@ struct ConvParams {
     int in_h, in_w, out_h, out_w, cin, cout, kh, kw, sh, sw, pad_t, pad_l, in_layout, act;
     int res_after = 0;   // 1: act(conv + b + R) instead of act(conv + b) + R (the GEMM convolutions only; needs R and an activation)
 };
-// direct conv for the small-Cin NCHW stem; w [kh][kw][cin][cout]
-void launch_conv_direct(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
+// direct conv for the small-Cin NCHW stem; w [kh][kw][cin][cout], all of it in LDS: cout % 4 == 0 and at most 64 KB of weights
+// (conv_direct_supports: create's rule).  Returns the instantiation's name ("conv_direct_kernel<NC=8>"); nullptr: nothing launched.
+bool conv_direct_supports(const ConvParams &p);
+const char *launch_conv_direct(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
                         int n_seg, hipStream_t s);
 // full convolution NHWC (group 1) as an implicit GEMM: out = act(im2col(in) . W + b) (+ R).  W is K x N with K = kh kw cpad,
 // cpad = align_up(cin, 32), the channels of every tap zero-padded to whole 32-deep steps: f32 rows [K][ldw] (ldw % 4 == 0), or
@@ -431,8 +433,10 @@ bool gconv_supports(const ConvParams &p, int groups);
 const char *launch_gconv(const float *in, const float *Wf, const float *b, float *out, const ConvParams &p, int groups, int n_seg, hipStream_t s);
 const char *launch_gconv16(const float *in, const void *Wf, const float *b, float *out, const ConvParams &p, int groups, int n_seg, int terms,
                            float w_unscale, hipStream_t s);
-// depthwise conv NHWC; w [kh][kw][c]
-void launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
+// depthwise conv NHWC; w [kh][kw][c]: square 3x3 / 5x5 windows, one stride 1 / 2, c % 4 == 0 (dwconv_supports: create's rule).
+// Returns the instantiation's name ("dwconv_kernel<3,2>"); nullptr when no instantiation matches and nothing was launched.
+bool dwconv_supports(const ConvParams &p);
+const char *launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
                    int n_seg, hipStream_t s);
 // C[M][N] = act(A[M][K] . W[K][ldw] + bias) (+ R); W rows padded to ldw (multiple of 4)
 // (res_after != 0, here and in launch_pw_gemm16: C = act(A . W + bias + R); R and an activation are required)
@@ -462,19 +466,22 @@ const char *launch_pw_gemm16_gated(const float *A, const float *gate, int rows_p
 // ... and the gate itself: pool (from the per-tile channel sums of mbconv pass A, part [n][tiles][C]) -> 1x1 (C -> Cr, act1) -> 1x1
 // (Cr -> C, act2), one launch, fixed summation order
 // the gate beyond 576 channels in two launches of sixteen-segment workgroups (hpart: scratch of n_seg x C floats)
+// (the three gate launchers return their kernels' names joined by '+', e.g. "se_hidden_kernel+se_gate16_kernel"; the GEMMs of the
+//  three-launch form by their family, "se_pool_kernel+pw_gemm_kernel" -- launch_pw_gemm names the instantiations --; nullptr: one
+//  of those GEMMs had no instantiation)
 bool se_gate16_supports(int C, int Cr);
-void launch_se_gate16(const float *part, int tiles, int P, float *hpart, const float *W1, const float *b1, int ld1, int act1, const float *W2,
+const char *launch_se_gate16(const float *part, int tiles, int P, float *hpart, const float *W1, const float *b1, int ld1, int act1, const float *W2,
                       const float *b2, int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s);
 bool se_gate_supports(int C, int Cr);
 // (the same gate as three launches -- the pool, then the two dense layers as GEMMs over all segments: launches of many segments)
-void launch_se_gate_gemm(const float *part, int tiles, int P, float *pooled, float *hidden, const float *W1, const float *b1, int ld1, int act1,
+const char *launch_se_gate_gemm(const float *part, int tiles, int P, float *pooled, float *hidden, const float *W1, const float *b1, int ld1, int act1,
                          const float *W2, const float *b2, int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s);
-void launch_se_gate(const float *part, int tiles, int P, const float *W1, const float *b1, int ld1, int act1, const float *W2, const float *b2,
+const char *launch_se_gate(const float *part, int tiles, int P, const float *W1, const float *b1, int ld1, int act1, const float *W2, const float *b2,
                     int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s);
-// global average pool [n][P][C] -> [n][C]
-void launch_gap(const float *in, float *out, int n_seg, int P, int C, hipStream_t s);
-// squeeze-excite gate: out[n][p][c] = in[n][p][c] * gate[n][c]   (C % 4 == 0)
-void launch_scale(const float *in, const float *gate, float *out, int n_seg, int P, int C, hipStream_t s);
+// global average pool [n][P][C] -> [n][C]   (C % 4 == 0; returns "gap_kernel")
+const char *launch_gap(const float *in, float *out, int n_seg, int P, int C, hipStream_t s);
+// squeeze-excite gate: out[n][p][c] = in[n][p][c] * gate[n][c]   (C % 4 == 0; returns "scale_kernel")
+const char *launch_scale(const float *in, const float *gate, float *out, int n_seg, int P, int C, hipStream_t s);
 // windowed pooling (ONNX MaxPool / AveragePool, floor mode), NHWC f32 [n][in_h][in_w][c] -> [n][out_h][out_w][c], c % 4 == 0
 // (kernels_pool.hip).  mode 0: max (a NaN tap makes the output NaN); 1: mean over the in-image taps; 2: mean over kh * kw.  Taps
 // outside the image are never read.  p.cout = channels; p.cin / in_layout / act are not read.  Returns the instantiation's name.

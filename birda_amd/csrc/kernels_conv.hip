@@ -1290,8 +1290,12 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float *__restrict__ i
     }
 }
 
-void launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p, int n_seg,
-                   hipStream_t s) {
+bool dwconv_supports(const ConvParams &p) {
+    return p.cout % 4 == 0 && p.kh == p.kw && p.sh == p.sw && (p.kh == 3 || p.kh == 5) && (p.sh == 1 || p.sh == 2);
+}
+
+const char *launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p, int n_seg,
+                          hipStream_t s) {
     const long total = (long)n_seg * p.out_h * p.out_w * (p.cout / 4);
     long blocks = (total + 255) / 256;
     if (blocks > 256L * 64) blocks = 256L * 64;
@@ -1299,10 +1303,11 @@ void launch_dwconv(const float *in, const float *w, const float *b, float *out, 
 #define BH_DW_CASE(KSV, STV)                                                                       \
     if (p.kh == KSV && p.sh == STV) {                                                               \
         hipLaunchKernelGGL((dwconv_kernel<KSV, STV>), grid, block, 0, s, in, w, b, out, p, n_seg);  \
-        return;                                                                                     \
+        return "dwconv_kernel<" #KSV "," #STV ">";                                                  \
     }
     BH_DW_CASE(3, 1) BH_DW_CASE(3, 2) BH_DW_CASE(5, 1) BH_DW_CASE(5, 2)
 #undef BH_DW_CASE
+    return nullptr;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1354,8 +1359,13 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(const float *__restric
     }
 }
 
-void launch_conv_direct(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
-                        int n_seg, hipStream_t s) {
+bool conv_direct_supports(const ConvParams &p) {
+    return p.cout % 4 == 0 && (size_t)p.kh * p.kw * p.cin * p.cout * sizeof(float) <= 64 * 1024;
+}
+
+const char *launch_conv_direct(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
+                               int n_seg, hipStream_t s) {
+    if (!conv_direct_supports(p)) return nullptr;
     const int nc = p.cout % 8 ? 4 : 8;
     const long total = (long)n_seg * p.out_h * p.out_w * (p.cout / nc);
     long blocks = (total + 255) / 256;
@@ -1363,6 +1373,7 @@ void launch_conv_direct(const float *in, const float *w, const float *b, float *
     const size_t smem = (size_t)p.kh * p.kw * p.cin * p.cout * sizeof(float);
     if (nc == 8) hipLaunchKernelGGL(conv_direct_kernel<8>, dim3((unsigned)blocks), dim3(256), smem, s, in, w, b, out, p, n_seg);
     else hipLaunchKernelGGL(conv_direct_kernel<4>, dim3((unsigned)blocks), dim3(256), smem, s, in, w, b, out, p, n_seg);
+    return nc == 8 ? "conv_direct_kernel<NC=8>" : "conv_direct_kernel<NC=4>";
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1701,9 +1712,10 @@ __global__ __launch_bounds__(256) void gap_kernel(const float *__restrict__ in, 
     *reinterpret_cast<float4 *>(out + (size_t)seg * C + c) = make_float4(acc.x * inv, acc.y * inv, acc.z * inv, acc.w * inv);
 }
 
-void launch_gap(const float *in, float *out, int n_seg, int P, int C, hipStream_t s) {
+const char *launch_gap(const float *in, float *out, int n_seg, int P, int C, hipStream_t s) {
     const long total = (long)n_seg * (C / 4);
     hipLaunchKernelGGL(gap_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, in, out, n_seg, P, C);
+    return "gap_kernel";
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1938,8 +1950,8 @@ __global__ __launch_bounds__(256) void se_gate16_kernel(const float *__restrict_
 // (the partial hidden sums live in the caller's pooled-tensor scratch, [n][C] floats: KS x Cr <= C is asked of the block)
 bool se_gate16_supports(int C, int Cr) { return C >= 1 && Cr >= 1 && Cr <= 256 && se_hidden_shape(C, Cr).slices * Cr <= C; }
 
-void launch_se_gate16(const float *part, int tiles, int P, float *hpart, const float *W1, const float *b1, int ld1, int act1, const float *W2,
-                      const float *b2, int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s) {
+const char *launch_se_gate16(const float *part, int tiles, int P, float *hpart, const float *W1, const float *b1, int ld1, int act1, const float *W2,
+                             const float *b2, int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s) {
     const SeHiddenShape sh = se_hidden_shape(C, Cr);
     const int groups = (n_seg + SE_SG - 1) / SE_SG;
     const size_t lds = ((size_t)sh.slice * SE_SG + 256 * SE_SG) * sizeof(float);          // 32 KB at most
@@ -1947,6 +1959,7 @@ void launch_se_gate16(const float *part, int tiles, int P, float *hpart, const f
                        sh.slice);
     hipLaunchKernelGGL(se_gate16_kernel, dim3((unsigned)groups, (unsigned)((C + 255) / 256)), dim3(256), 0, s, hpart, sh.slices, b1, act1, W2, b2, ld2, act2,
                        gate, n_seg, C, Cr);
+    return "se_hidden_kernel+se_gate16_kernel";
 }
 
 // (se_gate_kernel keeps pooled [C] + partial sums [256] + hidden [Cr] in LDS and is launched without a raised dynamic-LDS limit: 64 KB)
@@ -1966,20 +1979,22 @@ __global__ __launch_bounds__(256) void se_pool_kernel(const float *__restrict__ 
 // The gate for a LARGE launch: the two dense layers as GEMMs over all segments (the per-segment kernel above re-reads both weight
 // matrices for every segment -- 1.8 MB at C = 2 304 -- and runs their dot products as serial loops: 0.5 us per segment for the last
 // block alone), pooled and hidden in the arena slots of the layers they stand for
-void launch_se_gate_gemm(const float *part, int tiles, int P, float *pooled, float *hidden, const float *W1, const float *b1, int ld1, int act1,
-                         const float *W2, const float *b2, int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s) {
+const char *launch_se_gate_gemm(const float *part, int tiles, int P, float *pooled, float *hidden, const float *W1, const float *b1, int ld1, int act1,
+                                const float *W2, const float *b2, int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s) {
     const size_t n = (size_t)n_seg * C;
     hipLaunchKernelGGL(se_pool_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, tiles, 1.0f / (float)P, pooled, n_seg, C);
-    launch_pw_gemm(pooled, W1, b1, nullptr, hidden, n_seg, C, Cr, ld1, act1, s);
-    launch_pw_gemm(hidden, W2, b2, nullptr, gate, n_seg, Cr, C, ld2, act2, s);
+    const char *g1 = launch_pw_gemm(pooled, W1, b1, nullptr, hidden, n_seg, C, Cr, ld1, act1, s);
+    const char *g2 = launch_pw_gemm(hidden, W2, b2, nullptr, gate, n_seg, Cr, C, ld2, act2, s);
+    return g1 && g2 ? "se_pool_kernel+pw_gemm_kernel" : nullptr;
 }
 
-void launch_se_gate(const float *part, int tiles, int P, const float *W1, const float *b1, int ld1, int act1, const float *W2, const float *b2,
-                    int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s) {
+const char *launch_se_gate(const float *part, int tiles, int P, const float *W1, const float *b1, int ld1, int act1, const float *W2, const float *b2,
+                           int ld2, int act2, float *gate, int n_seg, int C, int Cr, hipStream_t s) {
     int crp = 4;
     while (crp < Cr) crp <<= 1;
     const size_t lds = ((size_t)C + 256 + Cr) * sizeof(float);
     hipLaunchKernelGGL(se_gate_kernel, dim3(n_seg), dim3(256), lds, s, part, tiles, 1.0f / (float)P, W1, b1, ld1, act1, W2, b2, ld2, act2, gate, C, Cr, crp);
+    return "se_gate_kernel";
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1995,11 +2010,12 @@ __global__ __launch_bounds__(256) void scale_kernel(const float4 *__restrict__ i
     }
 }
 
-void launch_scale(const float *in, const float *gate, float *out, int n_seg, int P, int C, hipStream_t s) {
+const char *launch_scale(const float *in, const float *gate, float *out, int n_seg, int P, int C, hipStream_t s) {
     const int c4n = C / 4;
     const long total4 = (long)n_seg * P * c4n;
     const unsigned blocks = (unsigned)std::min<long>((total4 + 255) / 256, 256L * 64);
     hipLaunchKernelGGL(scale_kernel, dim3(blocks), dim3(256), 0, s, (const float4 *)in, (const float4 *)gate, (float4 *)out, total4, P * c4n, c4n);
+    return "scale_kernel";
 }
 
 // ---------------------------------------------------------------------------------------

@@ -370,6 +370,22 @@ def gemm64(A, W, bias) -> np.ndarray:
     return np.asarray(A, np.float64) @ np.asarray(W, np.float64) + np.asarray(bias, np.float64)
 
 
+def se_gate64(part, P: int, W1, b1, act1: int, W2, b2, act2: int):
+    """The gate of a squeeze-excite block in float64: part [n][tiles][C] (per-tile channel sums), W1 [C][Cr], W2 [Cr][C] ->
+    (gate [n][C], pooled [n][C] = sum over tiles / P, preH, H = act1(preH) [n][Cr], preG [n][C]); gate = act2(preG)."""
+    pooled = np.asarray(part, np.float64).sum(axis=1) / float(P)
+    preH = gemm64(pooled, W1, b1)
+    H = act64(preH, act1)
+    preG = gemm64(H, W2, b2)
+    return act64(preG, act2), pooled, preH, H, preG
+
+
+def direct_conv64(Xp, W, bias, sh: int, sw: int, pad_t: int, pad_l: int, out_h: int, out_w: int):
+    """The NCHW stem convolution in float64: Xp planar [n][cin][h][w], W [kh][kw][cin][cout] -> (pre [n * out_h * out_w][cout] NHWC
+    rows, the im2col rows), through conv_nhwc64 on the transposed input."""
+    return conv_nhwc64(np.transpose(np.asarray(Xp, np.float64), (0, 2, 3, 1)), W, bias, sh, sw, pad_t, pad_l, out_h, out_w)
+
+
 def head_pool64(v, P: int) -> np.ndarray:
     """The mean over each run of P rows: [n * P][N] -> [n][N] (the head convolution's global average pool)."""
     v = np.asarray(v, np.float64)
