@@ -294,6 +294,11 @@ BLOCK_DEBUG_SYMBOLS = [
                                         _VP, _VP, _VP, _VP, _VP, _SZ]),
 ]
 
+# include/birda_hip_pcm_debug.h: the segments the device PCM front end cut, read back after a bh_predict_pcm* call
+PCM_DEBUG_SYMBOLS = [
+    ("bh_debug_read_segments", C.c_int, [_VP, _VP, C.c_int, _VP, _SZ, _SZ]),
+]
+
 _lib = None
 
 
@@ -306,7 +311,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS + GCONV_DEBUG_SYMBOLS + GATE_DEBUG_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS + GCONV_DEBUG_SYMBOLS + GATE_DEBUG_SYMBOLS + PCM_DEBUG_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

@@ -129,6 +129,9 @@ class BatchInferenceContext:
 
 # BH_FLAG_* (include/birda_hip.h): "auto" = split-f16 compute with rows that leave the f16 range re-run on the f32 kernels
 PRECISION_FLAGS = {"auto": 0, "f16x3": 1, "f16": 2, "f32": 3}
+# BH_PCM_* (include/birda_hip.h) and the bytes of one sample
+PCM_FORMATS = {"s16": 1, "s24": 2, "s32": 3, "f32": 4}
+PCM_SAMPLE_BYTES = {"s16": 2, "s24": 3, "s32": 4, "f32": 4}
 
 
 class BirdClassifier:
@@ -342,6 +345,72 @@ class BirdClassifier:
                 continue
             check(rc)
             return self._results(res, int(n.value)), [int(starts[i]) for i in range(int(n.value))]
+
+    # ---- the same for every sample format the decoder hands over (bh_predict_pcm_rows / _fd_rows / _at): thin wrappers ----
+    @staticmethod
+    def _pcm_view(raw, fmt: str, channels: int):
+        """-> (uint8 view of the interleaved stream, not a copy where `raw` is contiguous; whole frames it holds)"""
+        a = np.frombuffer(raw, np.uint8) if isinstance(raw, (bytes, bytearray, memoryview)) else np.ascontiguousarray(raw).reshape(-1).view(np.uint8)
+        return a, a.size // (PCM_SAMPLE_BYTES[fmt] * channels)
+
+    def _pcm_rows_call(self, call, n_frames: int, on_rows):
+        """call(res, cap, n, starts, cb) -> rc, retried once with the capacity the library asks for"""
+        cap = max(n_frames // max(1, self.sample_count() // 4) + 8, 8)
+        while True:
+            res = (BhResult * cap)()
+            starts = (C.c_uint64 * cap)()
+            n = C.c_size_t()
+            raised = []   # (as in predict_pcm16: an exception inside the ctypes trampoline is kept and re-raised after the call)
+
+            def _cb(_user, first, count, rows, st):
+                if raised:
+                    return
+                try:
+                    on_rows(int(first), self._results(rows, int(count)), [int(st[i]) for i in range(int(count))])
+                except BaseException as e:   # noqa: BLE001
+                    raised.append(e)
+            cb = _lib.BhRowsFn(_cb) if on_rows is not None else _lib.BhRowsFn()
+            rc = call(res, cap, n, starts, cb)
+            if rc != 0 and int(n.value) > cap:
+                cap = int(n.value)
+                continue
+            if raised:
+                raise raised[0]
+            check(rc)
+            return self._results(res, int(n.value)), [int(starts[i]) for i in range(int(n.value))]
+
+    def predict_pcm(self, ctx: BatchInferenceContext, raw, fmt: str, channels: int, source_rate: int, overlap: int = 0, on_rows=None):
+        """raw: the interleaved stream as the decoder holds it (bytes or a contiguous array), fmt "s16" | "s24" | "s32" | "f32"
+        (s24: three bytes a sample, little endian); overlap in model-rate samples.  Returns (results, start_samples)."""
+        a, n_frames = self._pcm_view(raw, fmt, channels)
+        return self._pcm_rows_call(
+            lambda res, cap, n, starts, cb: self._L.bh_predict_pcm_rows(self._h, ctx._h, a.ctypes.data, PCM_FORMATS[fmt], n_frames, channels,
+                                                                        source_rate, overlap, res, cap, C.byref(n), starts, cb, None),
+            n_frames, on_rows)
+
+    def predict_pcm_fd(self, ctx: BatchInferenceContext, fd: int, file_offset: int, fmt: str, n_frames: int, channels: int,
+                       source_rate: int, overlap: int = 0, on_rows=None):
+        """The stream is bytes [file_offset, file_offset + n_frames x frame bytes) of the open file `fd` (bh_predict_pcm_fd_rows)."""
+        return self._pcm_rows_call(
+            lambda res, cap, n, starts, cb: self._L.bh_predict_pcm_fd_rows(self._h, ctx._h, fd, file_offset, PCM_FORMATS[fmt], n_frames,
+                                                                           channels, source_rate, overlap, res, cap, C.byref(n), starts, cb, None),
+            n_frames, on_rows)
+
+    def predict_pcm_at(self, ctx: BatchInferenceContext, raw, fmt: str, channels: int, source_rate: int, starts: Sequence[int]):
+        """One segment from each of `starts` (source-rate frames, not decreasing, inside the stream): bh_predict_pcm_at."""
+        a, n_frames = self._pcm_view(raw, fmt, channels)
+        n = len(starts)
+        st = (C.c_uint64 * max(n, 1))(*[int(s) for s in starts])
+        res = (BhResult * max(n, 1))()
+        check(self._L.bh_predict_pcm_at(self._h, ctx._h, a.ctypes.data, PCM_FORMATS[fmt], n_frames, channels, source_rate, st, n, res))
+        return self._results(res, n)
+
+    def read_segments(self, ctx: BatchInferenceContext, which: int, rows: int, row_floats: int) -> np.ndarray:
+        """bh_debug_read_segments (include/birda_hip_pcm_debug.h): the last slice's rows of the last predict_pcm* call on ctx --
+        which 0 the model's input, 1 the source-rate rows before the resampler.  Tests only."""
+        out = np.empty((rows, row_floats), np.float32)
+        check(self._L.bh_debug_read_segments(self._h, ctx._h, which, out.ctypes.data, rows, row_floats))
+        return out
 
     # ---- resampler (reference src/audio/resample.rs:10-105) ----
     def resample(self, samples: np.ndarray, from_rate: int, to_rate: int) -> np.ndarray:

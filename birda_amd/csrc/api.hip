@@ -2818,6 +2818,33 @@ static int predict_pcm16_core(bh_classifier *c, bh_batch_context *ctx, const voi
     }
     return BH_OK;
 }
+
+// Diagnostic (include/birda_hip_pcm_debug.h): what the last slice of the last bh_predict_pcm* call left in d_input (which 0) or
+// d_raw (which 1), read back as it lies; nothing of the product path passes through here.
+int bh_debug_read_segments(bh_classifier *c, bh_batch_context *ctx, int which, float *host, size_t rows, size_t row_floats) try {
+    int rc = check_ctx(c, ctx);
+    if (rc != BH_OK) return rc;
+    if (!host) return fail(BH_ERR_INVALID, "read_segments: null host buffer");
+    if (which != 0 && which != 1) return fail(BH_ERR_INVALID, "read_segments: which = %d (0: model-rate input, 1: raw source-rate rows)", which);
+    if (rows == 0 || rows > ctx->max_batch) return fail(BH_ERR_INVALID, "read_segments: %zu rows, the context holds %zu", rows, ctx->max_batch);
+    const float *src;
+    if (which == 0) {
+        if (row_floats != c->model.h.sample_count)
+            return fail(BH_ERR_INVALID, "read_segments: rows of %zu floats, the model's input has %u", row_floats, c->model.h.sample_count);
+        src = ctx->d_input;
+    } else {
+        if (!ctx->d_raw || ctx->raw_len == 0) return fail(BH_ERR_INVALID, "read_segments: no resampling call has run on this context: there are no raw rows");
+        if (row_floats == 0 || row_floats > ctx->raw_len)
+            return fail(BH_ERR_INVALID, "read_segments: raw rows of %zu floats, the raw buffer's rows hold %zu", row_floats, ctx->raw_len);
+        src = ctx->d_raw;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(ctx->copy_stream));
+    lanes_sync(ctx);
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(host, src, rows * row_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return BH_OK;
+} catch (...) { return on_exception(); }
 }  // extern "C"
 
 extern "C" {
