@@ -2864,6 +2864,17 @@ int bh_resample_supported(bh_classifier *c, uint32_t from_rate, uint32_t to_rate
     return BH_OK;
 } catch (...) { return on_exception(); }
 
+// What launch_resample and its kernels take as int: a row's lengths, and the segment count that becomes the grid's z dimension.
+// Looks at the numbers alone -- called before a buffer is allocated, copied or read.
+static int resample_ranges(const char *who, size_t src_len, size_t out_len, size_t n_seg) {
+    if (src_len > (size_t)INT32_MAX || out_len > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "%s: %zu source samples -> %zu outputs a segment: the resampler indexes a row with 32-bit integers (2^31 - 1 at most)",
+                    who, src_len, out_len);
+    if (n_seg > 65535)
+        return fail(BH_ERR_INVALID, "%s: %zu segments in one launch: the grid's z dimension takes 65 535 at most", who, n_seg);
+    return BH_OK;
+}
+
 int bh_resample_device(bh_classifier *c, bh_batch_context *ctx, const float *d_in, size_t in_stride, size_t src_len,
                        uint32_t from_rate, uint32_t to_rate, float *d_out, size_t out_stride, size_t out_len,
                        size_t n_seg) try {
@@ -2871,6 +2882,8 @@ int bh_resample_device(bh_classifier *c, bh_batch_context *ctx, const float *d_i
     if (rc != BH_OK) return rc;
     if (!d_in || !d_out || from_rate == 0 || to_rate == 0 || src_len > in_stride || out_len > out_stride)
         return fail(BH_ERR_INVALID, "resample_device: bad arguments");
+    // (equal rates are a strided copy of any row count; the lengths are refused alike, so that a caller meets one rule)
+    if ((rc = resample_ranges("resample_device", src_len, out_len, from_rate == to_rate ? 0 : n_seg)) != BH_OK) return rc;
     if (n_seg == 0) return BH_OK;
     HIPCHK(hipSetDevice(c->device));
     if (from_rate == to_rate) {  // resample.rs:11-13: identity; then resize(segment_samples, 0.0)
@@ -2897,6 +2910,8 @@ int bh_resample(bh_classifier *c, const float *in, size_t n_in, uint32_t from_ra
     if (from_rate == 0 || to_rate == 0) return fail(BH_ERR_INVALID, "resample: a sample rate of 0");   // (was a division by zero: tools/fuzz_args.py)
     const size_t need = bh::resample_output_len(n_in, from_rate, to_rate);
     if (need > out_cap) return fail(BH_ERR_INVALID, "resample: output buffer too small (%zu < %zu)", out_cap, need);
+    int rrc = resample_ranges("resample", n_in, need, 1);
+    if (rrc != BH_OK) return rrc;
     *n_out = need;
     if (need == 0) return BH_OK;
     HIPCHK(hipSetDevice(c->device));
@@ -2914,6 +2929,46 @@ int bh_resample(bh_classifier *c, const float *in, size_t n_in, uint32_t from_ra
     if (hipStreamSynchronize(ctx->stream) != hipSuccess && rc == BH_OK) rc = fail(BH_ERR_HIP, "resample: stream sync failed");
     (void)hipFree(d_in); (void)hipFree(d_out);
     return rc;
+} catch (...) { return on_exception(); }
+
+// The plan of a rate pair as it lies on the device (include/birda_hip_resample_debug.h): the layouts are not undone here.
+int bh_debug_resample_plan(int device, uint32_t from_rate, uint32_t to_rate, int32_t *params, float *op, size_t op_cap, uint16_t *op16,
+                           size_t op16_cap) try {
+    if (!params || from_rate == 0 || to_rate == 0 || from_rate == to_rate) return fail(BH_ERR_INVALID, "debug_resample_plan: bad arguments");
+    HIPCHK(hipSetDevice(device));
+    const char *err = nullptr;
+    const bh::ResamplePlan *pl = bh::resample_plan(from_rate, to_rate, &err);
+    if (!pl) return fail(BH_ERR_UNSUPPORTED, "%s (%u -> %u Hz)", err ? err : "resampler", from_rate, to_rate);
+    const int32_t p[8] = {pl->hop, pl->N, pl->nblk, pl->K, pl->dmin, pl->block_form, bh::resample_frame_tiles(*pl), pl->op16_exp};
+    memcpy(params, p, sizeof p);
+    const size_t n_op = (size_t)pl->nblk * pl->K * 160, n_op16 = 2 * n_op;
+    if ((op && op_cap < n_op) || (op16 && op16_cap < n_op16))
+        return fail(BH_ERR_INVALID, "debug_resample_plan: the operator is %zu floats and %zu halves", n_op, n_op16);
+    if (op) HIPCHK(hipMemcpy(op, pl->d_op, n_op * sizeof(float), hipMemcpyDeviceToHost));
+    if (op16) HIPCHK(hipMemcpy(op16, pl->d_op16, n_op16 * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return BH_OK;
+} catch (...) { return on_exception(); }
+
+// One launch_resample on operands of the caller's, no classifier (include/birda_hip_resample_debug.h).
+int bh_debug_resample(int device, const float *in, size_t n_seg, size_t in_stride, size_t src_len, uint32_t from_rate, uint32_t to_rate,
+                      float *out, size_t out_stride, size_t out_len, int split_f16, char *kernel, size_t kernel_cap) try {
+    if (!in || !out || !n_seg || !out_len || from_rate == 0 || to_rate == 0 || from_rate == to_rate || src_len > in_stride ||
+        out_len > out_stride || (split_f16 != 0 && split_f16 != 1))
+        return fail(BH_ERR_INVALID, "debug_resample: bad arguments");
+    int rc = resample_ranges("debug_resample", src_len, out_len, n_seg);
+    if (rc != BH_OK) return rc;
+    if (in_stride > (size_t)INT32_MAX / n_seg || out_stride > (size_t)INT32_MAX / n_seg)
+        return fail(BH_ERR_INVALID, "debug_resample: buffers past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    const char *err = nullptr;
+    const bh::ResamplePlan *pl = bh::resample_plan(from_rate, to_rate, &err);
+    if (!pl) return fail(BH_ERR_UNSUPPORTED, "%s (%u -> %u Hz)", err ? err : "resampler", from_rate, to_rate);
+    Guarded dX, dY;
+    if (!dX.put(in, n_seg * in_stride * 4, kGuardNaN) || !dY.put(nullptr, n_seg * out_stride * 4, kUnwrittenNaN))
+        return fail(BH_ERR_HIP, "debug_resample: device memory");
+    const char *name = bh::launch_resample(*pl, (const float *)dX.p(), in_stride, (int)src_len, (float *)dY.p(), out_stride, (int)out_len,
+                                           (int)n_seg, split_f16 != 0, nullptr);
+    return finish_debug_launch("debug_resample", name, dY, out, n_seg * out_stride, kernel, kernel_cap, "out");
 } catch (...) { return on_exception(); }
 
 }  // extern "C"

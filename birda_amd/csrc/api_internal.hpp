@@ -36,6 +36,7 @@
 #include "../../include/birda_hip_block_debug.h"
 #include "../../include/birda_hip_terms_debug.h"
 #include "../../include/birda_hip_pcm_debug.h"
+#include "../../include/birda_hip_resample_debug.h"
 #include "kernels.hpp"
 #include "trace.hpp"
 #include "model.hpp"

@@ -519,6 +519,8 @@ struct ResamplePlan {
     const float *d_op;          // device, fragment-major [nblk][K/16][10][64][4]
     const void *d_op16;         // the same operator as f16 hi / lo planes [2 nblk (80 phases each)][K/32][5]{hi, lo}[64 lanes][8 halves], k = 32 s + 8 (lane >> 4) + j
     float op16_unscale;         // the planes hold G * 2^s (max in [2^13, 2^14)); the kernel's store multiplies by 2^-s
+    int op16_exp;               // that s
+    int block_form;             // 0: polyphase (a frame = lcm(Q, 160) output phases), 1: a frame = one rubato block (resample.hip)
 };
 void resample_sizes(uint32_t from, uint32_t to, int *fft_in, int *fft_out);
 size_t resample_output_len(size_t n, uint32_t from, uint32_t to);  // rubato's output length for n inputs
@@ -527,8 +529,11 @@ const ResamplePlan *resample_plan(uint32_t from, uint32_t to, const char **err);
 // min(out_len, rubato length) samples are the resampled signal, the rest up to out_len zeros
 // (`samples.resize(segment_samples, 0.0)`, reference src/pipeline/processor.rs:87)
 // split_f16: the GEMM on the split-f16 MFMA (three v_mfma_f32_16x16x32_f16 per product, f32-grade sums) instead of the f32 MFMA
-void launch_resample(const ResamplePlan &pl, const float *d_in, size_t in_stride, int src_len, float *d_out,
-                     size_t out_stride, int out_len, int n_seg, bool split_f16, hipStream_t s);
+// -> the name of the instantiation launched, e.g. "resample_kernel<FT=2>", "resample16_kernel<FT=4>" (FT: resample_frame_tiles)
+// src_len, out_len <= INT32_MAX and n_seg <= 65 535 (the grid's z limit) are the callers' to check (api.hip resample_ranges)
+const char *launch_resample(const ResamplePlan &pl, const float *d_in, size_t in_stride, int src_len, float *d_out,
+                            size_t out_stride, int out_len, int n_seg, bool split_f16, hipStream_t s);
+int resample_frame_tiles(const ResamplePlan &pl);   // frame row tiles (of 16) a workgroup of launch_resample owns: 4, 2 or 1
 
 // Fused MBConv block (kernels_mbconv.hip): expand 1x1 -> depthwise -> project 1x1 (+ residual).
 struct MbDesc {

@@ -168,7 +168,7 @@ const ResamplePlan *resample_plan(uint32_t from, uint32_t to, const char **err) 
     }
     if (dmax < dmin) { *err = "resampler: empty operator"; return nullptr; }
     ResamplePlan pl{};
-    pl.from = from; pl.to = to; pl.hop = hop; pl.N = N; pl.nblk = (N + 159) / 160; pl.dmin = dmin;
+    pl.from = from; pl.to = to; pl.hop = hop; pl.N = N; pl.nblk = (N + 159) / 160; pl.dmin = dmin; pl.block_form = block_form ? 1 : 0;
     pl.K = (dmax - dmin + 1 + 127) / 128 * 128;   // 4 waves x an even number of 16-deep groups
     const size_t span_floats = (size_t)15 * hop + pl.K;          // one frame row tile a workgroup at the least (launch_resample picks 4 / 2 / 1)
     if (span_floats * 4 + 32 > kResampleLdsBytes) { *err = "resampler: frame span exceeds LDS"; return nullptr; }
@@ -195,6 +195,7 @@ const ResamplePlan *resample_plan(uint32_t from, uint32_t to, const char **err) 
     for (float v : frag) op_max = std::max(op_max, std::fabs(v));
     const int op_s = f16_scale_exponent(op_max);   // planes hold G * 2^s; the kernel's store multiplies by 2^-s
     pl.op16_unscale = std::ldexp(1.0f, -op_s);
+    pl.op16_exp = op_s;
     for (int cb = 0; cb < 2 * pl.nblk; cb++)   // column blocks of 80 phases (5 tiles) for this kernel
         for (int st = 0; st < pl.K / 32; st++)
             for (int mt = 0; mt < 5; mt++)
@@ -229,6 +230,15 @@ constexpr int RS_MT = 10;
 // the LDS; 2 or 1 for the pairs that decimate by a large factor (round 6: 192 / 256 / 384 kHz recorders against 48 / 32 kHz models have
 // hop 640-1 920 and were refused).  The K reduction stays split over the four waves; waves 0 .. FT - 1 own the frame tiles.  Every
 // output sample is the same sum in the same order whatever FT (the waves' partial sums meet in wave order).
+//
+// Non-finite samples (both kernels; tests/test_resampler_kernel_gpu.py): a NaN or an inf among the samples makes every output
+// whose K-window [hop m + dmin, + K) covers it non-finite -- the window's zero padding taps included, 0 x inf is NaN -- and no
+// other output; outputs at or past the resampled length are 0 whatever the window holds.  Around it resample_kernel gives the bits
+// it gives without the sample.  resample16_kernel's span maximum skips a NaN (fmaxf) and an inf switches the span's scale off
+// (ex = 255): the other outputs of that workgroup stay finite and f32-grade while |x| < 65 504.
+//
+// Accuracy: an output is the f32 chain of its K products (one fused multiply-add each, k ascending within a wave's quarter, then
+// the four partial sums), K + 3 roundings of at most 2^-24 |partial sum|: DESIGN.md section 3, "The resampler, held to its own operator".
 template <int FT>
 __global__ __launch_bounds__(256) void resample_kernel(const float *__restrict__ in, size_t in_stride, int src_len,
                                                        float *__restrict__ out, size_t out_stride, int out_len,
@@ -374,19 +384,25 @@ __global__ __launch_bounds__(256, 2) void resample16_kernel(const float *__restr
     // Block floating point for the f16 operand split: the span is multiplied by the power of two that puts its largest
     // sample in [2^13, 2^14) (quiet recordings -- |x| ~ 1e-4 is ordinary field audio -- would otherwise sit among the f16
     // subnormals and lose their lo halves entirely), and the store multiplies by its inverse.  Exact (powers of two), local
-    // to the workgroup, independent of every other segment.  A span of zeros / denormals, or one holding inf, keeps scale 1.
+    // to the workgroup, independent of every other segment.  A span of zeros, or one holding inf, keeps scale 1.
+    // A span whose largest sample is below 2^-63 (denormals included) takes the factor in two exact steps, 2^64 first: one
+    // float cannot hold 2^(140 - ex) for ex < 13, nor its inverse for ex < 14, and with scale 1 every such sample was an f16
+    // zero -- the kernel returned silence where the f32 kernel resamples (tests/test_resampler_kernel_gpu.py, amplitudes).
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
     float *amax_s = smem + ((span + 3) & ~3);
     if (lane == 0) amax_s[wave] = amax;
     __syncthreads();
     amax = fmaxf(fmaxf(amax_s[0], amax_s[1]), fmaxf(amax_s[2], amax_s[3]));
+    const bool tiny = amax > 0.0f && amax < 0x1p-63f;
+    const float pre = tiny ? 0x1p64f : 1.0f;
+    amax *= pre;                                                       // exact
     const int ex = (int)((__float_as_uint(amax) >> 23) & 255u);        // amax = m 2^(ex - 127), m in [1, 2)
-    const bool rescale = ex >= 14 && ex <= 253 && ex != 140;           // 2^(140 - ex) and its inverse are normal floats
+    const bool rescale = ex >= 14 && ex <= 254 && ex != 140;           // 2^(140 - ex) and its inverse are normal floats (255: inf)
     const float in_scale = rescale ? __uint_as_float((unsigned)(267 - ex) << 23) : 1.0f;     // 2^(140 - ex)
     const float out_unscale = op_unscale * (rescale ? __uint_as_float((unsigned)(ex - 13) << 23) : 1.0f);   // x 2^(ex - 140)
-    if (rescale) {
-        for (int i = tid; i < span; i += 256) smem[i] *= in_scale;
+    if (rescale || tiny) {
+        for (int i = tid; i < span; i += 256) smem[i] = smem[i] * pre * in_scale;
     }
     __syncthreads();
 
@@ -481,7 +497,10 @@ __global__ __launch_bounds__(256, 2) void resample16_kernel(const float *__restr
             v[0] += q.x; v[1] += q.y; v[2] += q.z; v[3] += q.w;
         }
 #pragma unroll
-        for (int r = 0; r < 4; r++) v[r] *= out_unscale;   // the operator planes hold G * 2^s, the span x * 2^(140 - ex)
+        for (int r = 0; r < 4; r++) {   // the operator planes hold G * 2^s, the span x * 2^(140 - ex) [* 2^64]
+            v[r] *= out_unscale;
+            if (tiny) v[r] *= 0x1p-64f;
+        }
         const int pc = cb * 80 + m * 16 + kq * 4;                // 4 consecutive output phases (the block form's N is any number:
         const long o = (long)t * N + pc;                          //  columns past it are padding, and rows may start unaligned)
         if (pc + 3 < N && (N & 3) == 0 && o + 3 < out_len && o + 3 < n_valid) {
@@ -494,14 +513,21 @@ __global__ __launch_bounds__(256, 2) void resample16_kernel(const float *__restr
     }
 }
 
-void launch_resample(const ResamplePlan &pl, const float *d_in, size_t in_stride, int src_len, float *d_out,
-                     size_t out_stride, int out_len, int n_seg, bool split_f16, hipStream_t s) {
+namespace {
+size_t resample_span_bytes(const ResamplePlan &pl, int ft) { return ((size_t)(16 * ft - 1) * pl.hop + pl.K) * sizeof(float) + 32; }   // (+ the f16 kernel's 4 wave maxima)
+}  // namespace
+
+// frame row tiles a workgroup: as many of 4 / 2 / 1 as the input span leaves room for (resample_plan refused what not even one fits)
+int resample_frame_tiles(const ResamplePlan &pl) {
+    return resample_span_bytes(pl, 4) <= kResampleLdsBytes ? 4 : resample_span_bytes(pl, 2) <= kResampleLdsBytes ? 2 : 1;
+}
+
+const char *launch_resample(const ResamplePlan &pl, const float *d_in, size_t in_stride, int src_len, float *d_out,
+                            size_t out_stride, int out_len, int n_seg, bool split_f16, hipStream_t s) {
     const int n_valid = (int)std::min<size_t>((size_t)out_len, resample_output_len((size_t)src_len, pl.from, pl.to));
-    const int frames = (out_len + pl.N - 1) / pl.N;
-    // frame row tiles a workgroup: as many of 4 / 2 / 1 as the input span leaves room for (resample_plan refused what not even one fits)
-    auto span_bytes_of = [&](int ft) { return ((size_t)(16 * ft - 1) * pl.hop + pl.K) * sizeof(float) + 32; };   // (+ the f16 kernel's 4 wave maxima)
-    const int ft = span_bytes_of(4) <= kResampleLdsBytes ? 4 : span_bytes_of(2) <= kResampleLdsBytes ? 2 : 1;
-    const size_t span_bytes = span_bytes_of(ft);
+    const int frames = (int)(((long long)out_len + pl.N - 1) / pl.N);   // (out_len may be INT32_MAX)
+    const int ft = resample_frame_tiles(pl);
+    const size_t span_bytes = resample_span_bytes(pl, ft);
     dim3 block(256);
 #define BH_RS_LAUNCH(FTV)                                                                                                                  \
     do {                                                                                                                                   \
@@ -523,6 +549,9 @@ void launch_resample(const ResamplePlan &pl, const float *d_in, size_t in_stride
     } while (0)
     if (ft == 4) BH_RS_LAUNCH(4); else if (ft == 2) BH_RS_LAUNCH(2); else BH_RS_LAUNCH(1);
 #undef BH_RS_LAUNCH
+    static const char *const names[2][3] = {{"resample_kernel<FT=1>", "resample_kernel<FT=2>", "resample_kernel<FT=4>"},
+                                            {"resample16_kernel<FT=1>", "resample16_kernel<FT=2>", "resample16_kernel<FT=4>"}};
+    return names[split_f16 ? 1 : 0][ft == 4 ? 2 : ft == 2 ? 1 : 0];
 }
 
 }  // namespace bh

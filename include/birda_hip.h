@@ -448,7 +448,13 @@ BH_API int bh_predict_pcm16_at(bh_classifier *c, bh_batch_context *ctx, const in
  * operator as a GEMM (birda_amd/csrc/resample.hip: polyphase with period (from, to) / gcd where the block operator is shift-
  * invariant -- up-sampling, decimation by at most 1.5 --, one rubato block a frame beyond: 88.2 ... 500 kHz recordings); identity when
  * the rates are equal.
- * Tolerance vs the block-FFT restatement in the oracle: 2e-5 absolute on |x| <= 1 inputs. */
+ * Tolerance vs the block-FFT restatement in the oracle: 2e-5 absolute on |x| <= 1 inputs (that number also covers the block
+ * operator's own shift-variance where it decimates in polyphase form).  The kernels themselves are held to their own operator:
+ * every output within 7 x 1.2 tau B of the float64 sum over the device's table, tau = 4e-7 max(1, sqrt(K / 1024)), B = sum |t| |x|
+ * (+ the f16 planes' subnormal floors in the split-f16 kernel), and the table within one f32 rounding of the float64 operator
+ * (tests/test_resampler_kernel_gpu.py, tests/test_resampler.py).
+ * src_len, out_len and n_in above 2^31 - 1, and more than 65 535 segments in one bh_resample_device launch between different rates,
+ * are BH_ERR_INVALID. */
 /* resample(samples, from, to) -> Vec<f32> (resample.rs:10-91): host in, host out */
 BH_API int bh_resample(bh_classifier *c, const float *in, size_t n_in, uint32_t from_rate,
                        uint32_t to_rate, float *out, size_t out_cap, size_t *n_out);
