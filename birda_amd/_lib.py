@@ -267,6 +267,11 @@ GATE_DEBUG_SYMBOLS = [
     ("bh_debug_plain_layer", C.c_int, [C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, _SZ, _VP, C.c_int, _VP, _SZ]),
 ]
 
+# include/birda_hip_concat_debug.h: one channel concat / window / shuffle launch (OP_CONCAT) alone, for the tests that hold it bit for bit
+CONCAT_DEBUG_SYMBOLS = [
+    ("bh_debug_concat", C.c_int, [C.c_int, _VP, C.c_int, _VP, _SZ, _VP, _VP, _SZ]),
+]
+
 # include/birda_hip_gconv_debug.h: one grouped convolution (OP_GCONV) alone, for the tests that hold it to float64
 GCONV_DEBUG_SYMBOLS = [
     ("bh_debug_gconv", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _SZ, _VP, C.c_int, C.c_int, _VP, _SZ]),
@@ -317,7 +322,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS + GCONV_DEBUG_SYMBOLS + GATE_DEBUG_SYMBOLS + PCM_DEBUG_SYMBOLS + RESAMPLE_DEBUG_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS + GCONV_DEBUG_SYMBOLS + GATE_DEBUG_SYMBOLS + PCM_DEBUG_SYMBOLS + RESAMPLE_DEBUG_SYMBOLS + CONCAT_DEBUG_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

@@ -7,7 +7,9 @@
 residual Add folded into the project conv -- with the activation that follows the Add, if any, as that layer's (Layer.reserved =
 RES_ACT_AFTER: act(conv + x), the end of a ResNet block) --, squeeze-excite blocks (GlobalAveragePool -> 1x1 Conv -> activation -> 1x1 Conv ->
 Sigmoid -> Mul with the feature map) as pool / 1x1 / 1x1 / OP_SCALE layers, MaxPool / AveragePool in floor mode (OP_POOL: any
-window, stride and padding; count_include_pad either way), GlobalAveragePool / ReduceMean, Flatten, Gemm / MatMul + Add,
+window, stride and padding; count_include_pad either way), Concat / Split / Slice over the channels and the Reshape -> Transpose ->
+Reshape channel shuffle (OP_CONCAT; a Split / Slice output that only Concat nodes read is a view folded into their windows),
+GlobalAveragePool / ReduceMean, Flatten, Gemm / MatMul + Add,
 final Sigmoid / Softmax as the output activation.  Weights move from ONNX's [Cout, Cin/g, kh, kw] to
 the NHWC-friendly layouts of the kernels.
 
@@ -237,6 +239,36 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
                 attrs["count_include_pad"] = 1 if L.reserved == mf.POOL_AVG_PAD else 0
             g.nodes.append(ox.Node("MaxPool" if L.reserved == mf.POOL_MAX else "AveragePool", [x], [tag + "_pool"], attrs, name=tag))
             y = tag + "_pool"
+        elif L.op == mf.OP_CONCAT:
+            # Slice (a window that is not its whole source) + Concat (two sources, or one that is neither sliced nor shuffled) + the
+            # three nodes of the channel shuffle: what either reader turns back into this record
+            parts = []
+            for side, t_src, off, n_ch in (("a", L.in_tensor, L.w_off, L.cin), ("b", L.res_tensor, L.b_off, L.cout - L.cin)):
+                if t_src == mf.NO_TENSOR:
+                    continue
+                if t_src == 0:
+                    raise ConvertError(f"layer {i}: a concat of the spectrogram has no ONNX spelling here")
+                if off == 0 and n_ch == m.layers[t_src - 1].cout:
+                    parts.append(names[t_src])
+                    continue
+                cut = f"{tag}_{side}"
+                for suffix, v in (("starts", off), ("ends", off + n_ch), ("axes", 1)):
+                    g.initializers[f"{cut}_{suffix}"] = np.asarray([v], np.int64)
+                g.nodes.append(ox.Node("Slice", [names[t_src], cut + "_starts", cut + "_ends", cut + "_axes"], [cut], name=cut))
+                parts.append(cut)
+            y = parts[0]
+            # (a lone Slice that only concats read would be folded into their windows: a one-input Concat keeps it a record)
+            only_concats = all(M.op == mf.OP_CONCAT for M in m.layers if i + 1 in (M.in_tensor, M.res_tensor))
+            if len(parts) == 2 or (L.reserved <= 1 and (y == names[L.in_tensor] or only_concats)):
+                g.nodes.append(ox.Node("Concat", parts, [tag + "_cat"], {"axis": 1}, name=tag))
+                y = tag + "_cat"
+            if L.reserved > 1:
+                g.initializers[tag + "_s5"] = np.asarray([0, L.reserved, L.cout // L.reserved, L.out_h, L.out_w], np.int64)
+                g.initializers[tag + "_s4"] = np.asarray([0, L.cout, L.out_h, L.out_w], np.int64)
+                g.nodes.append(ox.Node("Reshape", [y, tag + "_s5"], [tag + "_r5"], name=tag + "_shuffle"))
+                g.nodes.append(ox.Node("Transpose", [tag + "_r5"], [tag + "_tr"], {"perm": [0, 2, 1, 3, 4]}))
+                g.nodes.append(ox.Node("Reshape", [tag + "_tr", tag + "_s4"], [tag + "_shuffled"]))
+                y = tag + "_shuffled"
         elif L.op == mf.OP_DENSE:
             w = m.weight(L.w_off, L.cin * L.cout).reshape(L.cin, L.cout)
             g.nodes.append(ox.Node("Gemm", [x, const(tag + "_w", w), const(tag + "_b", m.weight(L.b_off, L.cout))], [tag + "_fc"],
@@ -376,6 +408,80 @@ def _collapse_activations(g: ox.Graph):
     return skip, act_of
 
 
+def _const_ints(g: ox.Graph, name: str) -> Optional[List[int]]:
+    """The integer list a node input names -- an initializer or a Constant node's value -- or None (at most 64 entries are read)"""
+    a = g.initializers.get(name)
+    if a is None:
+        for n in g.nodes:
+            if n.op_type == "Constant" and n.outputs and n.outputs[0] == name:
+                v = n.attrs.get("value", n.attrs.get("value_ints", [n.attrs["value_int"]] if "value_int" in n.attrs else None))
+                a = None if v is None else np.asarray(v)
+    if a is None or a.dtype.kind not in "iu" or a.size > 64:
+        return None
+    return [int(v) for v in np.asarray(a).reshape(-1)]
+
+
+def _find_shuffles(g: ox.Graph, skip: set, front_nodes: set):
+    """The channel shuffle: Reshape [N, g, C / g, H, W] -> Transpose (0, 2, 1, 3, 4) -> Reshape [N, C, H, W], each with one reader,
+    the shapes constants (csrc/onnx_conv.hpp finds it the same way).  Returns ({first Reshape's node index: (output name, shape 1,
+    shape 2)}, the first Reshapes of patterns whose shapes are computed); the other two nodes of a found pattern join `skip`."""
+    cons: Dict[str, List[int]] = {}
+    for i, n in enumerate(g.nodes):
+        for x in n.inputs:
+            cons.setdefault(x, []).append(i)
+
+    def sole_consumer(name: str, op: str) -> Optional[int]:
+        c = cons.get(name, [])
+        return c[0] if len(c) == 1 and g.nodes[c[0]].op_type == op else None
+
+    found, computed = {}, set()
+    for i, n in enumerate(g.nodes):
+        if n.op_type != "Reshape" or i in skip or i in front_nodes or len(n.inputs) < 2 or not n.outputs:
+            continue
+        t = sole_consumer(n.outputs[0], "Transpose")
+        if t is None or not g.nodes[t].outputs or t in skip or list(g.nodes[t].attrs.get("perm") or []) != [0, 2, 1, 3, 4]:
+            continue
+        r2 = sole_consumer(g.nodes[t].outputs[0], "Reshape")
+        if r2 is None or len(g.nodes[r2].inputs) < 2 or not g.nodes[r2].outputs or r2 in skip:
+            continue
+        s1, s2 = _const_ints(g, n.inputs[1]), _const_ints(g, g.nodes[r2].inputs[1])
+        if s1 is None or s2 is None:
+            computed.add(i)
+            continue
+        found[i] = (g.nodes[r2].outputs[0], s1, s2)
+        skip |= {t, r2}
+    return found, computed
+
+
+def _resolve_shape(shape: List[int], dims: List[int], total: int) -> Optional[List[int]]:
+    """A Reshape's target with its 0 (copy the input's dimension) and -1 (whatever is left) entries resolved, the batch dimension
+    aside: `dims` and the result hold the dimensions behind it.  None: not a shape of `total` elements."""
+    out, known, infer = [], 1, -1
+    for k in range(1, len(shape)):
+        v = shape[k]
+        if v == 0:
+            if k - 1 >= len(dims):
+                return None
+            v = dims[k - 1]
+        if v == -1:
+            if infer >= 0 or shape[0] == -1:
+                return None
+            infer, v = len(out), 1
+        elif v <= 0 or v > (1 << 24) or known > (1 << 40):
+            return None
+        else:
+            known *= v
+        out.append(v)
+    if infer >= 0:
+        if total % known:
+            return None
+        out[infer], known = total // known, total
+    return out if known == total else None
+
+
+_QUAD = "a channel count or offset that is not a multiple of 4 is not supported (ShuffleNetV2 x1.0's 58-channel halves, for one)"
+
+
 def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogram_input: Optional[str] = None,
                      sample_rate: Optional[int] = None, family: int = 0) -> mf.Model:
     """`frontend` supplies everything the conv stack does not say: family, sample rate / count, segment
@@ -431,6 +537,9 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         if L is not None and L.op == mf.OP_POOL:
             raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a MaxPool / AveragePool "
                                "(a pool layer carries no activation)")
+        if L is not None and L.op == mf.OP_CONCAT:
+            raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a Concat, Split, Slice "
+                               "or channel shuffle (the record carries no activation)")
         if L is not None and name_in in sums and L.res_tensor != mf.NO_TENSOR and L.reserved != mf.RES_ACT_AFTER:
             # act(conv + x), the end of a ResNet block: the layer keeps its one activation code and records its position
             if L.act != mf.ACT_NONE:
@@ -455,11 +564,150 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         for out_name, act, own in first_of_pattern.pop(x, []):
             set_act(x, out_name, act, own)
 
+    shuffle_at, shuffle_computed = _find_shuffles(g, skip, front_nodes)
+    vmap: Dict[str, Tuple[int, int, int, int, int]] = {}   # the views: name -> (tensor, C, H, W, first channel); only Concat looks here
+    readers: Dict[str, List[str]] = {}
+    for q in g.nodes:
+        for x in q.inputs:
+            readers.setdefault(x, []).append(q.op_type)
+
+    def concat_rec(a, b, groups: int):
+        """one OP_CONCAT record: the window a = (tensor, C, H, W, first channel), then b's (None: a alone) -> its output, whole"""
+        cout = a[1] + (b[1] if b else 0)
+        layers.append(mf.Layer(mf.OP_CONCAT, mf.ACT_NONE, a[0], b[0] if b else mf.NO_TENSOR, a[1], cout, 1, 1, 1, 1, 0, 0, a[2], a[3], a[2], a[3],
+                               0, a[4], b[4] if b else 0, reserved=groups))
+        return (len(layers), cout, a[2], a[3])
+
+    def publish_view(name: str, x, off: int, c: int):
+        """an output of a Split / Slice: a view where only Concat nodes read it, else a record of its own that materialises it"""
+        v = (x[0], c, x[2], x[3], off)
+        if name in graph_out or any(o != "Concat" for o in readers.get(name, [])):
+            tmap[name] = concat_rec(v, None, 0)
+        else:
+            vmap[name] = v
+
     for i, n in enumerate(g.nodes):
         if i in skip or i in front_nodes:
             continue
         op = n.op_type
-        if op == "Conv":
+        if op == "Constant":      # (the library's parser turns these into initializers; _const_ints reads them where they are)
+            continue
+        if op == "Concat":
+            who = f"Concat {n.name!r}: "
+            if len(n.inputs) > 64:
+                raise ConvertError(who + f"{len(n.inputs)} inputs (1 .. 64 are read)")
+            axis = int(n.attrs.get("axis", 0))
+            if axis not in (1, -3):
+                raise ConvertError(who + f"axis {axis}: only the channel axis (1, or -3) is concatenated")
+            src = []
+            for name in n.inputs:
+                if name in g.initializers or any(q.op_type == "Constant" and name in q.outputs for q in g.nodes):
+                    raise ConvertError(who + f"input {name!r} is a constant: only activations are concatenated")
+                x = vmap.get(name) or (tmap[name] + (0,) if name in tmap else None)
+                if x is None:
+                    raise ConvertError(who + f"input {name!r} is not on the path from {spec!r}")
+                if x[0] == 0:
+                    raise ConvertError(who + "the spectrogram (tensor 0) as an input is not supported")
+                if src and x[2:4] != src[0][2:4]:
+                    raise ConvertError(who + f"inputs of different images ({src[0][2]}x{src[0][3]} and {x[2]}x{x[3]})")
+                if x[1] % 4 or x[4] % 4:
+                    raise ConvertError(who + f"input {name!r} is {x[1]} channels from channel {x[4]}: " + _QUAD)
+                src.append(x)
+            if sum(x[1] for x in src) > 65536:
+                raise ConvertError(who + "more than 65 536 channels")
+            y = concat_rec(src[0], src[1] if len(src) > 1 else None, 0)
+            for x in src[2:]:
+                y = concat_rec(y + (0,), x, 0)
+            tmap[n.outputs[0]] = y
+            flush_patterns(n.outputs[0])
+        elif op in ("Split", "Slice"):
+            who = f"{op} {n.name!r}: "
+            x = tmap.get(n.inputs[0])
+            if x is None:
+                raise ConvertError(who + f"input {n.inputs[0]!r} is not on the path from {spec!r}")
+            if x[0] == 0:
+                raise ConvertError(who + "the spectrogram (tensor 0) as the input is not supported")
+            C = x[1]
+            if op == "Split":
+                axis = int(n.attrs.get("axis", 0))
+                if axis not in (1, -3):
+                    raise ConvertError(who + f"axis {axis}: only the channel axis (1) is split")
+                parts = len(n.outputs)
+                if parts > 64:
+                    raise ConvertError(who + f"{parts} outputs (1 .. 64 are read)")
+                if n.attrs.get("split"):
+                    sizes = [int(v) for v in n.attrs["split"]]
+                elif len(n.inputs) > 1 and n.inputs[1]:
+                    sizes = _const_ints(g, n.inputs[1])
+                    if sizes is None:
+                        raise ConvertError(who + f"sizes {n.inputs[1]!r} that are not a constant")
+                else:
+                    if int(n.attrs.get("num_outputs", parts)) != parts or C % parts:
+                        raise ConvertError(who + f"{C} channels in {parts} equal parts")
+                    sizes = [C // parts] * parts
+                if len(sizes) != parts:
+                    raise ConvertError(who + f"{len(sizes)} sizes for {parts} outputs")
+                starts, at = [], 0
+                for s in sizes:
+                    if s <= 0 or s > 65536:
+                        raise ConvertError(who + f"a part of {s} channels")
+                    starts.append(at)
+                    at += s
+                if at != C:
+                    raise ConvertError(who + f"sizes that add up to {at}, the input has {C} channels")
+            else:
+                lst = [None] * 4   # starts, ends, axes, steps
+                for q in range(4):
+                    if len(n.inputs) > q + 1 and n.inputs[q + 1]:
+                        lst[q] = _const_ints(g, n.inputs[q + 1])
+                        if lst[q] is None:
+                            raise ConvertError(who + f"{n.inputs[q + 1]!r} is not a constant (starts, ends, axes and steps are read from constant inputs)")
+                if lst[0] is None or lst[1] is None or lst[2] is None or any(v is not None and len(v) != 1 for v in lst):
+                    raise ConvertError(who + "only a slice along one stated axis, the channels, is read")
+                if lst[2][0] not in (1, -3):
+                    raise ConvertError(who + f"axis {lst[2][0]}: only the channel axis (1) is sliced")
+                if lst[3] is not None and lst[3][0] != 1:
+                    raise ConvertError(who + f"step {lst[3][0]}: only step 1 is read")
+                s, e = lst[0][0], lst[1][0]
+                s = (0 if s < -C else s + C) if s < 0 else s
+                e = (0 if e < -C else e + C) if e < 0 else e
+                s, e = min(s, C), min(e, C)
+                if e <= s:
+                    raise ConvertError(who + "an empty slice")
+                starts, sizes = [s], [e - s]
+            for k, (st, sz) in enumerate(zip(starts, sizes)):
+                if sz % 4 or st % 4:
+                    raise ConvertError(who + f"output {k} is {sz} channels from channel {st}: " + _QUAD)
+            for name, st, sz in zip(n.outputs, starts, sizes):
+                if not name:
+                    continue
+                publish_view(name, x, st, sz)
+                flush_patterns(name)
+        elif op == "Reshape" and i in shuffle_at:
+            out_name, s1, s2 = shuffle_at[i]
+            who = f"Reshape {n.name!r} (channel shuffle): "
+            x = tmap.get(n.inputs[0])
+            if x is None:
+                raise ConvertError(who + f"input {n.inputs[0]!r} is not on the path from {spec!r}")
+            if x[0] == 0:
+                raise ConvertError(who + "the spectrogram (tensor 0) as the input is not supported")
+            _, C, h, w = x
+            d5 = _resolve_shape(s1, [C, h, w], C * h * w) if len(s1) == 5 and len(s2) == 4 else None
+            d4 = _resolve_shape(s2, [d5[1], d5[0], h, w], C * h * w) if d5 is not None and (d5[0] * d5[1], d5[2], d5[3]) == (C, h, w) else None
+            if d4 != [C, h, w]:
+                raise ConvertError(who + f"the shapes are not [N, g, C / g, H, W] and [N, C, H, W] of its {C} x {h} x {w} input")
+            if C % 4:
+                raise ConvertError(who + f"{C} channels: " + _QUAD)
+            P = layers[x[0] - 1]
+            if P.op == mf.OP_CONCAT and P.reserved <= 1 and n.inputs[0] not in graph_out and len(readers.get(n.inputs[0], [])) == 1:
+                P.reserved = d5[0]
+                tmap[out_name] = x
+            else:
+                tmap[out_name] = concat_rec(x + (0,), None, d5[0])
+            flush_patterns(out_name)
+        elif op == "Reshape" and i in shuffle_computed:
+            raise ConvertError(f"Reshape {n.name!r}: a channel shuffle whose shape is computed (Shape -> Gather -> Concat) is not read: the shapes must be constants")
+        elif op == "Conv":
             x = tmap.get(n.inputs[0])
             if x is None:
                 raise ConvertError(f"Conv {n.name!r}: input {n.inputs[0]!r} is not on the path from {spec!r}")
@@ -512,6 +760,9 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         elif op == "BatchNormalization":
             t = tmap.get(n.inputs[0])
             L = layers[t[0] - 1] if t and t[0] > 0 else None
+            if L is not None and L.op == mf.OP_CONCAT:
+                raise ConvertError(f"BatchNormalization {n.name!r} directly after a Concat, Split, Slice or channel shuffle cannot be folded "
+                                   "(the record carries neither a scale nor an activation)")
             if L is None or L.op not in (mf.OP_CONV, mf.OP_DWCONV, mf.OP_PWCONV, mf.OP_GCONV) or L.act != mf.ACT_NONE:
                 raise ConvertError("BatchNormalization that does not follow a convolution directly")
             # folding rewrites the convolution's weights: a residual already folded into the layer (BN(conv + x)) or another

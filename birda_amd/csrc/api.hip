@@ -104,6 +104,17 @@ bh::ConvParams conv_params(const bh::LayerRec &L) {
                           (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l, (int)L.in_layout, (int)L.act, res_act_after(L) ? 1 : 0};
 }
 
+// The sources of an OP_CONCAT record as launch_concat takes them (model.hpp: w_off / b_off are channel offsets there, res_tensor a
+// second input).  validate_model has held the windows to their tensors.
+std::array<bh::ConcatSource, 2> concat_sources(const bh::Model &m, const bh::LayerRec &L, const float *a, const float *b) {
+    const uint64_t img = (uint64_t)L.in_h * L.in_w;
+    std::array<bh::ConcatSource, 2> src{};
+    src[0] = bh::ConcatSource{a, (int)(m.tensor_floats[L.in_tensor] / img / 4), (int)L.w_off, (int)L.cin};
+    if (L.res_tensor != bh::NO_TENSOR)
+        src[1] = bh::ConcatSource{b, (int)(m.tensor_floats[L.res_tensor] / img / 4), (int)L.b_off, (int)(L.cout - L.cin)};
+    return src;
+}
+
 // A full convolution's [kh][kw][cin][cout] weights as the implicit GEMM's K x ld rows: the channels of every tap padded to whole
 // 32-deep steps (K = kh kw align_up(cin, 32)), the columns to ld; zero in the padding
 std::vector<float> conv_gemm_rows(const float *W, const bh::ConvParams &p, int ld) {
@@ -312,7 +323,7 @@ struct SliceRun {
     const float *res(const Step &st) const { return st.reads.size() > 1 ? T(st.reads[1]) : nullptr; }
     float *out(const Step &st) const { return T(st.writes[0]); }
     int layer(const Step &st) const, fused(const Step &st) const, fused_se(const Step &st) const, head_gap(const Step &st) const,
-        se_gate(const Step &st) const;       // one per path
+        se_gate(const Step &st) const, concat(const Step &st) const;       // one per path
 };
 // the fused block of a step as this launch runs it
 // (a launch of at most 256 segments: the one-segment-per-workgroup twin where the block has one -- the two-segment tiles would leave
@@ -390,6 +401,13 @@ int SliceRun::layer(const Step &st) const {
         bh::launch_pool(in, out, p, (int)L.reserved, (int)n, s);
         ctx_mark(ctx, ST_GAP, (int)i);
         break;
+    case bh::OP_CONCAT: {   // channel windows of one or two tensors, optionally shuffled: a copy, the same in every precision mode
+        const auto src = concat_sources(c->model, L, in, res);   // (res: the second input, not a residual)
+        c->w16_kernel[i].store(launched = bh::launch_concat(src.data(), L.res_tensor == bh::NO_TENSOR ? 1 : 2, out, (int)L.out_h, (int)L.out_w,
+                                                            (int)L.reserved, (int)n, s), std::memory_order_relaxed);
+        ctx_mark(ctx, ST_GAP, (int)i);
+        break;
+    }
     default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
     }
     // (create's predicates and validate_model keep this from happening; if it does, the output tensor was not written)
@@ -542,6 +560,28 @@ int SliceRun::se_gate(const Step &st) const {
     return BH_OK;
 }
 
+// a chain of concat records (an N-way Concat; concat_chain_len) as one launch: the leaves -- A of the first record, then every
+// record's B, st.reads in that order -- gathered straight into the last record's tensor, with the last record's shuffle
+int SliceRun::concat(const Step &st) const {
+    const auto &m = c->model;
+    const auto &F = m.layers[st.first], &Z = m.layers[st.last];
+    const uint64_t img = (uint64_t)F.in_h * F.in_w;
+    bh::ConcatSource src[4];
+    int n_src = 0;
+    auto leaf = [&](uint32_t t, uint64_t off, uint32_t len) {
+        if (n_src < 4) src[n_src] = bh::ConcatSource{T(t), (int)(m.tensor_floats[t] / img / 4), (int)off, (int)len};
+        n_src++;
+    };
+    leaf(F.in_tensor, F.w_off, F.cin);
+    for (uint32_t j = st.first; j <= st.last; j++)
+        if (m.layers[j].res_tensor != bh::NO_TENSOR) leaf(m.layers[j].res_tensor, m.layers[j].b_off, m.layers[j].cout - m.layers[j].cin);
+    if (n_src > 4 || (size_t)n_src != st.reads.size()) return fail(BH_ERR_INTERNAL, "layer %u: a concat chain of %d leaves", st.first, n_src);
+    const char *name = bh::launch_concat(src, n_src, out(st), (int)Z.out_h, (int)Z.out_w, (int)Z.reserved, (int)n, s);
+    for (uint32_t j = st.first; j <= st.last; j++) c->w16_kernel[j].store(name, std::memory_order_relaxed);
+    ctx_mark(ctx, ST_GAP, (int)st.first);
+    return BH_OK;
+}
+
 // one slice (n <= max_batch) of the forward pass, enqueued on the lane's stream and arena (nullptr: the context's stream and whole
 // arena): the front end, then the context's schedule step by step
 int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, size_t n, float *d_logits,
@@ -565,7 +605,7 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
         ctx_mark(ctx, ST_MEL);
     }
     for (const Step &st : schedule_of(ctx)) {
-        static const char *const kOpNames[] = {"layer", "conv", "depthwise", "pointwise", "pool", "dense", "scale", "window_pool", "grouped_conv"};
+        static const char *const kOpNames[] = {"layer", "conv", "depthwise", "pointwise", "pool", "dense", "scale", "window_pool", "grouped_conv", "layer", "concat"};
         const uint32_t op = m.layers[st.first].op;
         bh::TraceRange tr(st.block >= 0 ? "fused_mbconv_block" : op < sizeof(kOpNames) / sizeof(kOpNames[0]) ? kOpNames[op] : kOpNames[0]);
         int rc = BH_OK;
@@ -575,6 +615,7 @@ int forward_slice(bh_classifier *c, bh_batch_context *ctx, const float *d_seg, s
         case BH_PATH_FUSED_SE: rc = r.fused_se(st); break;
         case BH_PATH_HEAD_GAP: rc = r.head_gap(st); break;
         case BH_PATH_SE_GATE: rc = r.se_gate(st); break;
+        case BH_PATH_CONCAT: rc = r.concat(st); break;
         }
         if (rc != BH_OK) return rc;
     }
@@ -1247,10 +1288,17 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
             if (L.cout % 4) return fail(BH_ERR_UNSUPPORTED, "layer %zu: channels %u not a multiple of 4", i, L.cout);
             if (L.op == bh::OP_POOL && !bh::pool_supports(conv_params(L), (int)L.reserved))
                 return fail(BH_ERR_UNSUPPORTED, "layer %zu: pool %ux%u stride %ux%u pad %u,%u mode %u not built", i, L.kh, L.kw, L.sh, L.sw, L.pad_t, L.pad_l, L.reserved);
+        } else if (L.op == bh::OP_CONCAT) {
+            const auto src = concat_sources(m, L, nullptr, nullptr);
+            if (!bh::concat_supports((int)L.out_h, (int)L.out_w, src.data(), L.res_tensor == bh::NO_TENSOR ? 1 : 2, (int)L.reserved))
+                return fail(BH_ERR_UNSUPPORTED, "layer %zu: concat of channels %llu + %u and %llu + %u into %u (shuffle groups %u) on a %ux%u image not built "
+                            "(offsets and lengths multiples of 4, inside their sources; groups dividing the channels)", i, (unsigned long long)L.w_off, L.cin,
+                            (unsigned long long)L.b_off, L.cout - L.cin, L.cout, L.reserved, L.out_h, L.out_w);
         }
     }
     if (m.layers.empty() || m.layers.back().cout != m.h.n_classes)
         return fail(BH_ERR_IO, "model: last layer width != n_classes");
+    // (an OP_CONCAT record's res_tensor is its second input, not a residual: the check below does not look at it)
     // a residual on a layer whose kernel cannot add one is refused, not dropped: depthwise and pool layers (a fused block's
     // residual sits on its project convolution; the planner fuses no depthwise layer that carries one) and the NCHW stem
     for (size_t i = 0; i < m.layers.size(); i++) {
@@ -1350,6 +1398,8 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
     }
     c->gap_gate.assign(m.layers.size(), 0);
     for (size_t i = 0; i < m.layers.size(); i++) c->gap_gate[i] = gap_gate_chain(m, i) ? 1 : 0;
+    c->concat_chain.assign(m.layers.size(), 0);
+    for (size_t i = 0; i < m.layers.size(); i++) c->concat_chain[i] = (char)concat_chain_len(m, i);
     c->sched = build_schedule(*c, true, true);
     c->sched_layers = build_schedule(*c, false, false);
     c->sched_keep_fused = build_schedule(*c, true, false);
@@ -2279,6 +2329,38 @@ int bh_debug_plain_layer(int device, int op, const float *X, const float *W, con
                             : bh::launch_scale(dx, (const float *)dG.p(), dy, (int)n_seg, p.out_h * p.out_w, p.cout, nullptr);
     if (!name) return fail(BH_ERR_INTERNAL, "debug_plain_layer: the launcher has no instantiation for a shape the validator accepts");
     return finish_debug_launch("debug_plain_layer", name, dY, Y, y_floats, kernel, kernel_cap, "Y");
+} catch (...) { return on_exception(); }
+
+// One concat / window / shuffle launch alone on operands of the caller's, through the launcher a forward pass takes
+// (include/birda_hip_concat_debug.h).
+int bh_debug_concat(int device, const float *const *X, int n_src, float *Y, size_t n_seg, const int32_t *shape, char *kernel, size_t kernel_cap) try {
+    if (!X || !Y || !shape || !n_seg || n_src < 1 || n_src > 4) return fail(BH_ERR_INVALID, "debug_concat: bad arguments");
+    for (int k = 0; k < n_src; k++) if (!X[k]) return fail(BH_ERR_INVALID, "debug_concat: source %d is null", k);
+    const int h = shape[0], w = shape[1], groups = shape[2];
+    bh::ConcatSource src[4] = {};
+    long long C = 0;
+    for (int k = 0; k < n_src; k++) {
+        const int32_t *q = shape + 3 + 3 * k;
+        if (q[0] % 4 || q[0] < 4) return fail(BH_ERR_UNSUPPORTED, "debug_concat: source %d has %d channels (a multiple of 4 is needed)", k, q[0]);
+        src[k] = bh::ConcatSource{nullptr, q[0] / 4, q[1], q[2]};
+        C += q[2];
+    }
+    if (!bh::concat_supports(h, w, src, n_src, groups))
+        return fail(BH_ERR_UNSUPPORTED, "debug_concat: %dx%d image, %d sources, %lld channels, %d groups: not a concat the model validator accepts (offsets and "
+                    "lengths multiples of 4, windows inside their sources, groups dividing the channels)", h, w, n_src, C, groups);
+    const size_t px = n_seg * (size_t)h * w, y_floats = px * (size_t)C;
+    if (y_floats > (size_t)INT32_MAX || n_seg > (size_t)INT32_MAX) return fail(BH_ERR_INVALID, "debug_concat: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    Guarded dX[4], dY;
+    for (int k = 0; k < n_src; k++) {
+        const size_t x_floats = px * 4 * (size_t)src[k].total4;
+        if (x_floats > (size_t)INT32_MAX) return fail(BH_ERR_INVALID, "debug_concat: tensors past 2^31 elements");
+        if (!dX[k].put(X[k], x_floats * 4, kGuardNaN)) return fail(BH_ERR_HIP, "debug_concat: device memory");
+        src[k].p = (const float *)dX[k].p();
+    }
+    if (!dY.put(nullptr, y_floats * 4, kUnwrittenNaN)) return fail(BH_ERR_HIP, "debug_concat: device memory");
+    const char *name = bh::launch_concat(src, n_src, (float *)dY.p(), h, w, groups, (int)n_seg, nullptr);
+    return finish_debug_launch("debug_concat", name, dY, Y, y_floats, kernel, kernel_cap, "Y");
 } catch (...) { return on_exception(); }
 
 namespace {

@@ -30,6 +30,7 @@
 #include "../../include/birda_hip_audit.h"
 #include "../../include/birda_hip_layer_debug.h"
 #include "../../include/birda_hip_pool_debug.h"
+#include "../../include/birda_hip_concat_debug.h"
 #include "../../include/birda_hip_gate_debug.h"
 #include "../../include/birda_hip_resact_debug.h"
 #include "../../include/birda_hip_gconv_debug.h"
@@ -109,6 +110,8 @@ struct bh_classifier {
     // the two gate launches (launch_se_gate16): the pool layer's tensor holds the hidden partial sums until the gate is written
     // (gap_gate_chain)
     std::vector<char> gap_gate;
+    // records of the concat chain that starts at layer i and runs as ONE launch (0: none; concat_chain_len)
+    std::vector<char> concat_chain;
     // What a forward launches: the product's schedule (fused blocks, head conv + pool, the gate fast path), the layer-by-layer one of
     // BIRDA_HIP_KEEP_TENSORS contexts, and the one of debug contexts that still run the fused blocks (BIRDA_HIP_KEEP_FUSED)
     std::vector<bhi::Step> sched, sched_layers, sched_keep_fused;
@@ -298,6 +301,7 @@ std::vector<Step> build_schedule(const bh_classifier &c, bool fused, bool chains
 void plan_arena(const bh::Model &m, const std::vector<Step> &sched, size_t max_batch, bool keep, std::vector<size_t> &off, size_t &total,
                 std::vector<size_t> *sizes = nullptr);
 bool gap_gate_chain(const bh::Model &m, size_t i);
+int concat_chain_len(const bh::Model &m, size_t i);
 // the last layer of the fused block d planned at layer i: its project convolution, which in a squeeze-excite block comes four
 // layers later (pool, 1x1, 1x1, scale: SeInfo::iP)
 inline size_t fused_block_last(size_t i, const bh::MbDesc &d) { return i + (d.noexp ? 1 : 2) + (d.se ? 4 : 0); }

@@ -125,8 +125,17 @@ std::vector<Step> build_schedule(const bh_classifier &c, bool fused, bool chains
             st.path = BH_PATH_SE_GATE;
             st.last = i + 2;
             st.scratch = {{i + 1, 0}, {i + 2, 0}};
+        } else if (chains && c.concat_chain[i]) {
+            // an N-way Concat: one launch gathers the leaves straight into the last record's tensor; the records' own outputs in
+            // between never exist (they get no bytes, as a fused block's inner tensors get none)
+            st.path = BH_PATH_CONCAT;
+            st.last = i + (uint32_t)c.concat_chain[i] - 1;
         }
         st.reads = {m.layers[i].in_tensor};
+        if (st.path == BH_PATH_CONCAT) {          // every leaf: A of the first record, then every record's B
+            for (uint32_t j = i; j <= st.last; j++)
+                if (m.layers[j].res_tensor != bh::NO_TENSOR) st.reads.push_back(m.layers[j].res_tensor);
+        } else
         if (m.layers[st.last].res_tensor != bh::NO_TENSOR) st.reads.push_back(m.layers[st.last].res_tensor);
         st.writes.insert(st.writes.begin(), st.last + 1);
         i = st.last;
@@ -199,6 +208,27 @@ bool gap_gate_chain(const bh::Model &m, size_t i) {
         if ((j > i + 1 && m.layers[j].in_tensor == i + 1) || (j > i + 2 && m.layers[j].in_tensor == i + 2) ||
             m.layers[j].res_tensor == i + 1 || m.layers[j].res_tensor == i + 2) ok = false;
     return ok;
+}
+
+// The OP_CONCAT records from layer i on that run as one launch: each of records 2 .. k reads its predecessor whole as A and brings a B
+// of its own; the predecessor has no other reader, is not the embedding tensor and carries no shuffle (a shuffle is allowed on the
+// last record only); all on one image; at most four leaf sources in total.  -> k (2 .. 4), or 0: the record runs alone.  Shapes
+// alone decide; the answer is recorded in bh_classifier::concat_chain, and build_schedule makes a step of it (a longer chain
+// splits into steps: the next one starts at the record behind this one's last).
+int concat_chain_len(const bh::Model &m, size_t i) {
+    const size_t nl = m.layers.size();
+    if (i >= nl || m.layers[i].op != bh::OP_CONCAT) return 0;
+    int leaves = m.layers[i].res_tensor == bh::NO_TENSOR ? 1 : 2, k = 1;
+    for (size_t j = i + 1; j < nl && leaves < 4; j++) {
+        const auto &P = m.layers[j - 1], &L = m.layers[j];
+        if (L.op != bh::OP_CONCAT || L.in_tensor != j || L.res_tensor == bh::NO_TENSOR || L.res_tensor == j || L.w_off != 0 || L.cin != P.cout ||
+            L.in_h != P.out_h || L.in_w != P.out_w || P.reserved > 1 || m.h.embedding_tensor == j) break;
+        bool other = false;
+        for (size_t q = j + 1; q < nl && !other; q++) other = m.layers[q].in_tensor == j || m.layers[q].res_tensor == j;
+        if (other) break;
+        leaves++; k++;
+    }
+    return k >= 2 ? k : 0;
 }
 
 // IEEE binary16 round-to-nearest-even of a float, and back (host side of the hi/lo operand split)

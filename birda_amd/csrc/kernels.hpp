@@ -487,6 +487,14 @@ const char *launch_scale(const float *in, const float *gate, float *out, int n_s
 // outside the image are never read.  p.cout = channels; p.cin / in_layout / act are not read.  Returns the instantiation's name.
 bool pool_supports(const ConvParams &p, int mode);
 const char *launch_pool(const float *in, float *out, const ConvParams &p, int mode, int n_seg, hipStream_t s);
+// channel concatenation / channel windows / channel shuffle (kernels_concat.hip; model.hpp OP_CONCAT), NHWC f32: out [n][h][w][C]
+// holds the windows [off, off + len) of up to four sources [n][h][w][4 total4] one after the other, C = the sum of the lengths;
+// offsets and lengths multiples of 4.  groups > 1: out[p][c] = cat[p][(c % groups) * (C / groups) + c / groups], groups | C.  A copy:
+// every bit pattern comes out as it went in; channels outside a window are never read.  Returns the instantiation's name.
+struct ConcatSource { const float *p; int total4, off, len; };
+constexpr unsigned kConcatMaxWorkgroups = 256 * 8;   // of 256 threads, one 16-byte output group each a trip of the grid-stride loop
+bool concat_supports(int h, int w, const ConcatSource *src, int n_src, int groups);
+const char *launch_concat(const ConcatSource *src, int n_src, float *out, int h, int w, int groups, int n_seg, hipStream_t s);
 // head 1x1 conv + activation (GELU / swish / ReLU6) + global average pool fused (f16 hi / lo weight planes as for launch_pw_gemm16)
 bool head_gap16_supports(int P, int K, int N, int act);
 const char *launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,

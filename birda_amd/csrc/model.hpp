@@ -9,7 +9,7 @@
 
 namespace bh {
 
-enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
+enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8, OP_CONCAT = 10 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
 // OP_POOL (ONNX MaxPool / AveragePool, floor mode): the record's `reserved` word is the mode.  No weights, no bias, no activation.
 enum PoolMode : uint32_t { POOL_MAX = 0, POOL_AVG = 1, POOL_AVG_PAD = 2 };   // AVG: over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 // OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the record's `reserved` word is where `act` stands relative to the residual.  0: act(conv + b) + R
@@ -18,6 +18,12 @@ constexpr uint32_t RES_ACT_AFTER = 1;
 // OP_GCONV (a grouped convolution, NHWC): the record's `reserved` word is the group count G, 1 < G; cin and cout are the totals, the
 // weights compact [kh][kw][cin / G][cout] -- output channel o reads input channels (o / (cout / G)) * (cin / G) + 0 .. cin / G - 1 --,
 // bias [cout].  G = 1 stays OP_CONV and one input channel per group with cout == cin stays OP_DWCONV: one spelling each.  No residual.
+// OP_CONCAT = 10 (ONNX Concat / Split / Slice over the channels, and the Reshape -> Transpose -> Reshape channel shuffle): a copy, NHWC
+// f32, no weights, bias or activation.  Code 9 is never used: it stays the "unknown layer op" that tests/test_gconv.py demands.
+// in_tensor = source A, w_off = the first channel read from A, cin = how many; res_tensor = source B -- a SECOND INPUT, not a
+// residual -- or NO_TENSOR (a window and / or a shuffle of A alone), b_off = the first channel read from B, which gives cout - cin
+// channels; a source's channel count is its tensor's floats / (in_h in_w).  `reserved` = the shuffle's group count g (0, 1: none):
+// out[p][c] = cat[p][(c % g) * (cout / g) + c / g], cat = A's window then B's.  Offsets and lengths are multiples of 4.
 constexpr uint32_t NO_TENSOR = 0xFFFFFFFFu;
 
 #pragma pack(push, 1)
@@ -90,7 +96,7 @@ inline bool validate_model(Model &m, std::string &err) {
         const auto &L = m.layers[i];
         // (a global pool's "kernel" is its whole input image -- the squeeze of a squeeze-excite gate in an early block pools 64 x 249)
         const uint32_t kmax = L.op == OP_GAP ? (1u << 16) : 64;
-        if (L.cin == 0 || L.cout == 0 || L.cin > (1u << 16) || L.cout > (1u << 24) || L.kh == 0 || L.kw == 0 || L.kh > kmax || L.kw > kmax ||
+        if ((L.cin == 0 && L.op != OP_CONCAT) || L.cout == 0 || L.cin > (1u << 16) || L.cout > (1u << 24) || L.kh == 0 || L.kw == 0 || L.kh > kmax || L.kw > kmax ||
             L.sh == 0 || L.sw == 0 || L.sh > 16 || L.sw > 16 || L.pad_t > 64 || L.pad_l > 64 || L.in_h == 0 || L.in_w == 0 || L.out_h == 0 ||
             L.out_w == 0 || L.in_h > (1u << 16) || L.in_w > (1u << 16) || L.out_h > (1u << 16) || L.out_w > (1u << 16) ||
             (uint64_t)L.out_h * L.out_w * L.cout > (1ull << 31) || (uint64_t)L.in_h * L.in_w * L.cin > (1ull << 31)) {
@@ -100,12 +106,14 @@ inline bool validate_model(Model &m, std::string &err) {
         if (L.in_tensor > i || (L.res_tensor != NO_TENSOR && L.res_tensor > i)) { err = "layer reads a later tensor"; return false; }
         // what the layer reads must be what its input tensor holds (a pool reads in_h x in_w x cout, a dense layer cin values)
         const uint64_t in_floats = L.op == OP_GAP || L.op == OP_DWCONV || L.op == OP_SCALE || L.op == OP_POOL ? (uint64_t)L.in_h * L.in_w * L.cout
-                                 : L.op == OP_DENSE ? (uint64_t)L.cin : (uint64_t)L.in_h * L.in_w * L.cin;
+                                 : L.op == OP_DENSE ? (uint64_t)L.cin
+                                 : L.op == OP_CONCAT ? m.tensor_floats[L.in_tensor]   // (a window of its source: held below)
+                                 : (uint64_t)L.in_h * L.in_w * L.cin;
         if (in_floats != m.tensor_floats[L.in_tensor]) { err = "layer input shape does not match its tensor"; return false; }
-        if (L.res_tensor != NO_TENSOR && L.op != OP_SCALE && m.tensor_floats[L.res_tensor] != m.tensor_floats[i + 1]) {
+        if (L.res_tensor != NO_TENSOR && L.op != OP_SCALE && L.op != OP_CONCAT && m.tensor_floats[L.res_tensor] != m.tensor_floats[i + 1]) {
             err = "residual shape does not match the layer output"; return false;
         }
-        if (L.op < OP_CONV || L.op > OP_GCONV) { err = "unknown layer op"; return false; }
+        if (L.op < OP_CONV || L.op > OP_CONCAT || L.op == 9) { err = "unknown layer op"; return false; }
         if (L.op == OP_GCONV) {
             const uint32_t G = L.reserved;
             if (G < 2) { err = "grouped convolution with fewer than two groups (one group is a full convolution)"; return false; }
@@ -131,6 +139,20 @@ inline bool validate_model(Model &m, std::string &err) {
             if (L.pad_t >= L.kh || L.pad_l >= L.kw || (uint64_t)(L.out_h - 1) * L.sh >= (uint64_t)L.in_h + L.pad_t ||
                 (uint64_t)(L.out_w - 1) * L.sw >= (uint64_t)L.in_w + L.pad_l) { err = "pool layer with a window outside the image"; return false; }
         }
+        if (L.op == OP_CONCAT) {
+            const bool two = L.res_tensor != NO_TENSOR;
+            const uint64_t img = (uint64_t)L.in_h * L.in_w;
+            if (L.act != 0) { err = "concat layer with an activation"; return false; }
+            if (L.kh != 1 || L.kw != 1 || L.sh != 1 || L.sw != 1 || L.pad_t != 0 || L.pad_l != 0) { err = "concat layer with a kernel, stride or padding other than 1 / 1 / 0"; return false; }
+            if (L.in_h != L.out_h || L.in_w != L.out_w) { err = "concat layer whose output image is not its input image"; return false; }
+            if (L.in_layout != 0 || L.in_tensor == 0 || L.res_tensor == 0) { err = "concat layer on the planar spectrogram (tensor 0)"; return false; }
+            if (L.cin == 0 || L.cin > L.cout || (two ? L.cout == L.cin : L.cout != L.cin)) { err = "concat layer whose output channels are not the sum of its windows"; return false; }
+            if (L.w_off % 4 || L.cin % 4 || L.cout % 4 || (two && L.b_off % 4)) { err = "concat layer with an offset or a length that is not a multiple of 4"; return false; }
+            if (m.tensor_floats[L.in_tensor] % img || (two && m.tensor_floats[L.res_tensor] % img)) { err = "concat layer with a source that does not hold whole images of its size"; return false; }
+            const uint64_t ca = m.tensor_floats[L.in_tensor] / img, cb = two ? m.tensor_floats[L.res_tensor] / img : 0;
+            if (L.w_off > ca || L.cin > ca - L.w_off || (two && (L.b_off > cb || L.cout - L.cin > cb - L.b_off))) { err = "concat layer with a window past its source's channels"; return false; }
+            if (L.reserved > 1 && (L.reserved > L.cout || L.cout % L.reserved)) { err = "concat layer with a shuffle group count that does not divide its channels"; return false; }
+        }
         if (L.op == OP_CONV && L.in_layout != 0) {
             if (L.reserved == RES_ACT_AFTER) { err = "activation after the residual on the NCHW stem convolution"; return false; }
         } else if (L.op == OP_CONV || L.op == OP_PWCONV || L.op == OP_DENSE) {
@@ -138,7 +160,7 @@ inline bool validate_model(Model &m, std::string &err) {
             if (L.reserved == RES_ACT_AFTER && L.res_tensor == NO_TENSOR) { err = "activation after the residual on a layer without a residual"; return false; }
             if (L.reserved == RES_ACT_AFTER && L.act == 0) { err = "activation after the residual without an activation (a plain residual is position 0)"; return false; }
         }
-        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
+        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && L.op != OP_CONCAT && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
                                                    L.b_off + L.cout > m.h.blob_floats)) {
             err = "layer weights outside blob"; return false;
         }

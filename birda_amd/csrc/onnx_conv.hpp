@@ -7,7 +7,8 @@
 //     Conv (1x1 -> pointwise, group == channels -> depthwise, any other group count -> OP_GCONV, else full), BatchNormalization folded into the convolution in
 //     front of it, the activation spellings exporters emit (Relu, Clip(0, 6), Sigmoid x Mul = swish, Div / Erf / Add / Mul / Mul
 //     = GELU, the Gelu operator), residual Add folded into its 1x1 convolution, MaxPool / AveragePool (floor mode; OP_POOL),
-//     GlobalAveragePool / ReduceMean over H, W,
+//     GlobalAveragePool / ReduceMean over H, W, Concat / Split / Slice over the channels and the Reshape -> Transpose -> Reshape channel
+//     shuffle (OP_CONCAT: a Split / Slice output that only Concat nodes read is a view folded into their windows),
 //     squeeze-excite gates (pool -> 1x1 -> 1x1 -> Sigmoid -> Mul), Flatten / Reshape / Squeeze / Identity / Dropout after the
 //     pool, Gemm / MatMul + Add, a final Sigmoid or Softmax; NCHW weights re-laid for the NHWC kernels.  Anything else is refused
 //     by operator name.
@@ -328,7 +329,9 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     }
 
     // ---- the walk (convert.py model_from_graph) ----
-    struct T { uint32_t idx, c, h, w; };                       // tensor index, channels, height, width (1 x 1 once pooled)
+    // tensor index, channels, height, width (1 x 1 once pooled).  view: the output of a Split / Slice that only Concat nodes read --
+    // channels off .. off + c - 1 of tensor idx, folded into those records' windows; no other node ever looks one up
+    struct T { uint32_t idx, c, h, w, off = 0; bool view = false; };
     std::map<std::string, T> tmap;
     tmap[spec] = T{0, m.h.n_branches, m.h.spec_h, m.h.spec_w};
     std::vector<LayerRec> &layers = m.layers;
@@ -337,12 +340,62 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     for (const auto &o : outputs) graph_out.insert(o);
     auto find = [&](const std::string &name, T &t) { auto it = tmap.find(name); if (it == tmap.end()) return false; t = it->second; return true; };
     std::set<std::string> sums;   // the outputs of the residual Adds folded into a layer
+    // ---- the channel shuffle (convert.py _find_shuffles): Reshape [N, g, C / g, H, W] -> Transpose (0, 2, 1, 3, 4) -> Reshape
+    // [N, C, H, W], each with one reader, the shapes constants.  Found here, where the activation spellings are; the walk makes an
+    // OP_CONCAT record (or the `reserved` word of the Concat in front) of the first Reshape and skips the other two nodes.
+    auto const_ints = [&](const std::string &name) -> const std::vector<int64_t> * {
+        auto it = g.init.find(name);
+        return it != g.init.end() && (it->second.dtype == 7 || it->second.dtype == 6) && it->second.il.size() <= 64 ? &it->second.il : nullptr;
+    };
+    struct Shuffle { std::string out; std::vector<int64_t> s1, s2; };
+    std::map<size_t, Shuffle> shuffle_at;          // the first Reshape's node -> the pattern
+    std::set<size_t> shuffle_computed;             // ... whose shapes are not constants: refused by name at the walk
+    for (size_t i = 0; i < nodes.size(); i++) {
+        const Node &n = nodes[i];
+        size_t t, r2;
+        if (n.op != "Reshape" || skip.count(i) || front.count(i) || n.in.size() < 2 || n.out.empty() || !sole_consumer(n.out[0], "Transpose", t) ||
+            nodes[t].out.empty() || skip.count(t)) continue;
+        const auto *perm = nodes[t].ints("perm");
+        if (!perm || *perm != std::vector<int64_t>{0, 2, 1, 3, 4}) continue;
+        if (!sole_consumer(nodes[t].out[0], "Reshape", r2) || nodes[r2].in.size() < 2 || nodes[r2].out.empty() || skip.count(r2)) continue;
+        const auto *s1 = const_ints(n.in[1]), *s2 = const_ints(nodes[r2].in[1]);
+        if (!s1 || !s2) { shuffle_computed.insert(i); continue; }
+        shuffle_at[i] = Shuffle{nodes[r2].out[0], *s1, *s2};
+        skip.insert(t); skip.insert(r2);
+    }
+    // a Reshape's target with its 0 (copy the input's dimension) and -1 (whatever is left) entries resolved, the batch dimension
+    // aside: `in` and the result hold the dimensions behind it.  false: not a shape of `total` elements.
+    auto resolve_shape = [](const std::vector<int64_t> &shape, const std::vector<int64_t> &in, int64_t total, std::vector<int64_t> &out) {
+        out.clear();
+        int64_t known = 1;
+        int infer = -1;
+        for (size_t k = 1; k < shape.size(); k++) {
+            int64_t v = shape[k];
+            if (v == 0) { if (k - 1 >= in.size()) return false; v = in[k - 1]; }
+            if (v == -1) { if (infer >= 0 || shape[0] == -1) return false; infer = (int)out.size(); v = 1; }
+            else if (v <= 0 || v > (1 << 24) || known > (1ll << 40)) return false;
+            else known *= v;
+            out.push_back(v);
+        }
+        if (infer >= 0) { if (total % known) return false; out[(size_t)infer] = total / known; known = total; }
+        return known == total;
+    };
+    // one OP_CONCAT record: the window of a (and of b behind it), shuffled in g groups
+    const std::string quad = "a channel count or offset that is not a multiple of 4 is not supported (ShuffleNetV2 x1.0's 58-channel halves, for one)";
+    auto has_other_reader = [&](const std::string &name) {     // than Concat nodes
+        if (graph_out.count(name)) return true;
+        auto it = cons.find(name);
+        if (it != cons.end()) for (size_t k : it->second) if (nodes[k].op != "Concat") return true;
+        return false;
+    };
     // (own: the nodes of the activation itself -- one, or a multi-node spelling's)
     auto set_act = [&](const std::string &name_in, const std::string &name_out, uint32_t act, const std::vector<size_t> &own) {
         T t;
         if (!find(name_in, t)) return fail("activation on unknown tensor '" + name_in + "'");
         if (t.idx != 0 && layers[t.idx - 1].op == OP_POOL)
             return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a MaxPool / AveragePool (a pool layer carries no activation)");
+        if (t.idx != 0 && layers[t.idx - 1].op == OP_CONCAT)
+            return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a Concat, Split, Slice or channel shuffle (the record carries no activation)");
         if (t.idx != 0 && sums.count(name_in) && layers[t.idx - 1].res_tensor != NO_TENSOR && layers[t.idx - 1].reserved != RES_ACT_AFTER) {
             // act(conv + x), the end of a ResNet block: the layer keeps its one activation code and records its position
             LayerRec &L = layers[t.idx - 1];
@@ -382,6 +435,18 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         return (uint32_t)layers.size();
     };
     constexpr int64_t DIM_MAX = 1 << 16;
+    // one OP_CONCAT record: the window of a, then that of b (null: a alone), shuffled in g groups (0: not); -> its output, whole
+    auto concat_rec = [&](const T &a, const T *b, uint32_t g) {
+        const uint32_t cout = a.c + (b ? b->c : 0);
+        const uint32_t li = new_layer(OP_CONCAT, a.idx, b ? b->idx : NO_TENSOR, a.c, cout, 1, 1, 1, 1, 0, 0, a.h, a.w, a.h, a.w, 0, a.off, b ? b->off : 0);
+        layers[li - 1].reserved = g;
+        return T{li, cout, a.h, a.w};
+    };
+    // the outputs of a Split / Slice: a view where only Concat nodes read it, else a record of its own that materialises it
+    auto publish_view = [&](const std::string &name, const T &x, uint32_t off, uint32_t c) {
+        T v{x.idx, c, x.h, x.w, x.off + off, true};
+        tmap[name] = has_other_reader(name) ? concat_rec(v, nullptr, 0) : v;
+    };
     std::vector<float> tmp, tmpb;
     for (size_t i = 0; i < nodes.size(); i++) {
         if (skip.count(i) || front.count(i)) continue;
@@ -476,6 +541,8 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             T t;
             if (!find(n.in[0], t) || t.idx == 0) return fail("BatchNormalization that does not follow a convolution directly");
             LayerRec &L = layers[t.idx - 1];
+            if (L.op == OP_CONCAT)
+                return fail("BatchNormalization '" + n.name + "' directly after a Concat, Split, Slice or channel shuffle cannot be folded (the record carries neither a scale nor an activation)");
             if ((L.op != OP_CONV && L.op != OP_DWCONV && L.op != OP_PWCONV && L.op != OP_GCONV) || L.act != A_NONE || n.in.size() < 5)
                 return fail("BatchNormalization that does not follow a convolution directly");
             // folding rewrites the convolution's weights, so the BN must be the ONLY reader of the convolution's
@@ -587,6 +654,106 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                                           (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, 0, 0, 0);
             layers[li - 1].reserved = op == "MaxPool" ? POOL_MAX : cip ? POOL_AVG_PAD : POOL_AVG;
             tmap[n.out[0]] = T{li, x.c, (uint32_t)oh, (uint32_t)ow};
+        } else if (op == "Concat") {
+            // over the channels -> OP_CONCAT: two inputs one record, more a left-to-right chain, each record reading the one before
+            // as its first source (convert.py has the same branch; the two are held to the same records)
+            const std::string who = "Concat '" + n.name + "': ";
+            if (n.in.size() > 64) return fail(who + std::to_string(n.in.size()) + " inputs (1 .. 64 are read)");
+            const int64_t axis = n.geti("axis", 0);
+            if (axis != 1 && axis != -3) return fail(who + "axis " + std::to_string(axis) + ": only the channel axis (1, or -3) is concatenated");
+            std::vector<T> src;
+            int64_t sum = 0;
+            for (const auto &name : n.in) {
+                T x;
+                if (g.init.count(name)) return fail(who + "input '" + name + "' is a constant: only activations are concatenated");
+                if (!find(name, x)) return fail(who + "input '" + name + "' is not on the path from '" + spec + "'");
+                if (x.idx == 0) return fail(who + "the spectrogram (tensor 0) as an input is not supported");
+                if (!src.empty() && (x.h != src[0].h || x.w != src[0].w))
+                    return fail(who + "inputs of different images (" + std::to_string(src[0].h) + "x" + std::to_string(src[0].w) + " and " + std::to_string(x.h) + "x" + std::to_string(x.w) + ")");
+                if (x.c % 4 || x.off % 4) return fail(who + "input '" + name + "' is " + std::to_string(x.c) + " channels from channel " + std::to_string(x.off) + ": " + quad);
+                sum += x.c;
+                src.push_back(x);
+            }
+            if (sum > DIM_MAX) return fail(who + "more than 65 536 channels");
+            T y = concat_rec(src[0], src.size() > 1 ? &src[1] : nullptr, 0);
+            for (size_t k = 2; k < src.size(); k++) y = concat_rec(y, &src[k], 0);
+            tmap[n.out[0]] = y;
+            if (!flush_patterns(n.out[0])) return false;
+        } else if (op == "Split" || op == "Slice") {
+            // over the channels: every output is a view of the input (publish_view)
+            const std::string who = op + " '" + n.name + "': ";
+            T x;
+            if (!find(n.in[0], x)) return fail(who + "input '" + n.in[0] + "' is not on the path from '" + spec + "'");
+            if (x.idx == 0) return fail(who + "the spectrogram (tensor 0) as the input is not supported");
+            std::vector<int64_t> starts, sizes;
+            if (op == "Split") {
+                const int64_t axis = n.geti("axis", 0);
+                if (axis != 1 && axis != -3) return fail(who + "axis " + std::to_string(axis) + ": only the channel axis (1) is split");
+                const int64_t parts = (int64_t)n.out.size();
+                if (parts > 64) return fail(who + std::to_string(parts) + " outputs (1 .. 64 are read)");
+                if (const auto *sp = n.ints("split")) sizes = *sp;
+                else if (n.in.size() > 1 && !n.in[1].empty()) {
+                    const auto *sp2 = const_ints(n.in[1]);
+                    if (!sp2) return fail(who + "sizes '" + n.in[1] + "' that are not a constant");
+                    sizes = *sp2;
+                } else {
+                    if (n.geti("num_outputs", parts) != parts || x.c % parts) return fail(who + std::to_string(x.c) + " channels in " + std::to_string(parts) + " equal parts");
+                    sizes.assign((size_t)parts, x.c / parts);
+                }
+                int64_t at = 0;
+                if ((int64_t)sizes.size() != parts) return fail(who + std::to_string(sizes.size()) + " sizes for " + std::to_string(parts) + " outputs");
+                for (int64_t s : sizes) { if (s <= 0 || s > DIM_MAX) return fail(who + "a part of " + std::to_string(s) + " channels"); starts.push_back(at); at += s; }
+                if (at != x.c) return fail(who + "sizes that add up to " + std::to_string(at) + ", the input has " + std::to_string(x.c) + " channels");
+            } else {
+                const std::vector<int64_t> *lst[4] = {nullptr, nullptr, nullptr, nullptr};   // starts, ends, axes, steps
+                for (size_t q = 0; q < 4; q++)
+                    if (n.in.size() > q + 1 && !n.in[q + 1].empty()) {
+                        lst[q] = const_ints(n.in[q + 1]);
+                        if (!lst[q]) return fail(who + "'" + n.in[q + 1] + "' is not a constant (starts, ends, axes and steps are read from constant inputs)");
+                    }
+                if (!lst[0] || !lst[1] || !lst[2] || lst[0]->size() != 1 || lst[1]->size() != 1 || lst[2]->size() != 1 || (lst[3] && lst[3]->size() != 1))
+                    return fail(who + "only a slice along one stated axis, the channels, is read");
+                if ((*lst[2])[0] != 1 && (*lst[2])[0] != -3) return fail(who + "axis " + std::to_string((*lst[2])[0]) + ": only the channel axis (1) is sliced");
+                if (lst[3] && (*lst[3])[0] != 1) return fail(who + "step " + std::to_string((*lst[3])[0]) + ": only step 1 is read");
+                const int64_t C = x.c;
+                int64_t s = (*lst[0])[0], e = (*lst[1])[0];
+                if (s < 0) s = s < -C ? 0 : s + C;
+                if (e < 0) e = e < -C ? 0 : e + C;
+                s = std::min(s, C); e = std::min(e, C);
+                if (e <= s) return fail(who + "an empty slice");
+                starts.push_back(s); sizes.push_back(e - s);
+            }
+            for (size_t k = 0; k < sizes.size(); k++)
+                if (sizes[k] % 4 || starts[k] % 4)
+                    return fail(who + "output " + std::to_string(k) + " is " + std::to_string(sizes[k]) + " channels from channel " + std::to_string(starts[k]) + ": " + quad);
+            for (size_t k = 0; k < sizes.size(); k++) {
+                if (n.out[k].empty()) continue;
+                publish_view(n.out[k], x, (uint32_t)starts[k], (uint32_t)sizes[k]);
+                if (!flush_patterns(n.out[k])) return false;
+            }
+        } else if (op == "Reshape" && shuffle_at.count(i)) {
+            // the channel shuffle: the `reserved` word of the Concat record in front when this is its only reader, else a record of its own
+            const Shuffle &sh = shuffle_at[i];
+            const std::string who = "Reshape '" + n.name + "' (channel shuffle): ";
+            T x;
+            if (!find(n.in[0], x)) return fail(who + "input '" + n.in[0] + "' is not on the path from '" + spec + "'");
+            if (x.idx == 0) return fail(who + "the spectrogram (tensor 0) as the input is not supported");
+            std::vector<int64_t> d5, d4;
+            const int64_t total = (int64_t)x.c * x.h * x.w;
+            if (sh.s1.size() != 5 || sh.s2.size() != 4 || !resolve_shape(sh.s1, {x.c, x.h, x.w}, total, d5) || d5[0] * d5[1] != x.c || d5[2] != x.h || d5[3] != x.w ||
+                !resolve_shape(sh.s2, {d5[1], d5[0], x.h, x.w}, total, d4) || d4[0] != x.c || d4[1] != x.h || d4[2] != x.w)
+                return fail(who + "the shapes are not [N, g, C / g, H, W] and [N, C, H, W] of its " + std::to_string(x.c) + " x " + std::to_string(x.h) + " x " + std::to_string(x.w) + " input");
+            if (x.c % 4 || x.off % 4) return fail(who + std::to_string(x.c) + " channels: " + quad);
+            const uint32_t groups = (uint32_t)d5[0];
+            auto cit = cons.find(n.in[0]);
+            LayerRec &P = layers[x.idx - 1];
+            if (!x.view && P.op == OP_CONCAT && P.reserved <= 1 && !graph_out.count(n.in[0]) && cit != cons.end() && cit->second.size() == 1) {
+                P.reserved = groups;
+                tmap[sh.out] = x;
+            } else tmap[sh.out] = concat_rec(x, nullptr, groups);
+            if (!flush_patterns(sh.out)) return false;
+        } else if (op == "Reshape" && shuffle_computed.count(i)) {
+            return fail("Reshape '" + n.name + "': a channel shuffle whose shape is computed (Shape -> Gather -> Concat) is not read: the shapes must be constants");
         } else if (op == "Flatten" || op == "Reshape" || op == "Squeeze" || op == "Identity" || op == "Dropout") {
             T t;
             if (!find(n.in[0], t)) return fail(op + ": input not on the path");

@@ -36,7 +36,11 @@ OP_CONV, OP_DWCONV, OP_PWCONV, OP_GAP, OP_DENSE, OP_SCALE = 1, 2, 3, 4, 5, 6   #
 OP_POOL = 7   # windowed MaxPool / AveragePool (floor mode); Layer.reserved is the mode; no weights, bias, activation or residual
 OP_GCONV = 8  # grouped convolution (NHWC, no residual); Layer.reserved is the group count G >= 2; cin / cout are the totals, weights
               # compact [kh][kw][cin / G][cout] (output channel o reads input channels (o // (cout // G)) * (cin // G) + 0 .. cin // G - 1)
-POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2   # AVG: mean over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
+OP_CONCAT = 10  # channel Concat / Split / Slice / shuffle: a copy, NHWC f32, no weights, bias or activation.  (9 is never used: it stays the
+                # "unknown layer op" tests/test_gconv.py demands.)  in_tensor = source A, w_off = first channel read from A, cin = how
+                # many; res_tensor = source B (a second INPUT, not a residual) or NO_TENSOR, b_off = first channel read from B, which gives
+                # cout - cin channels; Layer.reserved = shuffle groups g (0, 1: none): out[c] = cat[(c % g) * (cout // g) + c // g]
+POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2  # AVG: mean over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 # OP_CONV (NHWC), OP_PWCONV, OP_DENSE: Layer.reserved is where `act` stands relative to the residual -- 0: act(conv + b) + R (every
 # file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block
 RES_ACT_AFTER = 1
@@ -99,7 +103,7 @@ class Layer:
     b_off: int = 0
     # OP_POOL: the pool mode (POOL_MAX / POOL_AVG / POOL_AVG_PAD).  OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the position of `act`
     # relative to the residual -- 0: act(conv + b) + R; RES_ACT_AFTER: act(conv + b + R), which needs a residual and an activation.
-    # OP_GCONV: the group count.  0 for every other op.
+    # OP_GCONV: the group count.  OP_CONCAT: the channel shuffle's group count (0, 1: no shuffle).  0 for every other op.
     reserved: int = 0
 
 

@@ -85,15 +85,37 @@ class _Builder:
         self.layers.append(L)
         return len(self.layers)  # tensor index of this layer's output
 
-    def conv(self, tin, h, w, cin, cout, k, s, act, in_layout=0, res=mf.NO_TENSOR, gain=1.0):
+    def conv(self, tin, h, w, cin, cout, k, s, act, in_layout=0, res=mf.NO_TENSOR, gain=1.0, kw=None):
+        kw = k if kw is None else kw      # (k x kw: Inception's 1x7 / 7x1 pairs)
         oh, pt = _same_pad(h, k, s)
-        ow, pl = _same_pad(w, k, s)
-        wt = self.he((k, k, cin, cout), k * k * cin)
+        ow, pl = _same_pad(w, kw, s)
+        wt = self.he((k, kw, cin, cout), k * kw * cin)
         if gain != 1.0:
             wt = wt * np.float32(gain)
-        L = mf.Layer(mf.OP_CONV, act, tin, res, cin, cout, k, k, s, s, pt, pl, h, w, oh, ow,
+        L = mf.Layer(mf.OP_CONV, act, tin, res, cin, cout, k, kw, s, s, pt, pl, h, w, oh, ow,
                      in_layout, self.put(wt), self.put(self.bias(cout)))
         return self.add(L), oh, ow
+
+    def concat(self, parts, h, w, groups=0):
+        """Channel concatenation (mf.OP_CONCAT) of `parts` = [(tensor, first channel, channels), ...]: two parts one record, more a
+        left-to-right chain, each record reading the one before whole; `groups` > 1 shuffles the result (on the last record).
+        One part: a window and / or a shuffle of that tensor alone.  -> (tensor, channels)"""
+        (t, off, c), rest = parts[0], list(parts[1:])
+        if not rest:
+            return self.add(mf.Layer(mf.OP_CONCAT, mf.ACT_NONE, t, mf.NO_TENSOR, c, c, 1, 1, 1, 1, 0, 0, h, w, h, w, 0, off, 0, groups)), c
+        for k, (tb, offb, cb) in enumerate(rest):
+            L = mf.Layer(mf.OP_CONCAT, mf.ACT_NONE, t, tb, c, c + cb, 1, 1, 1, 1, 0, 0, h, w, h, w, 0, off, offb,
+                         groups if k == len(rest) - 1 else 0)
+            t, off, c = self.add(L), 0, c + cb
+        return t, c
+
+    def slice(self, tin, h, w, off, c):
+        """channels off .. off + c - 1 of tensor tin as a tensor of its own (what a Split / Slice output costs when a convolution reads it)"""
+        return self.concat([(tin, off, c)], h, w)[0]
+
+    def shuffle(self, tin, h, w, c, groups):
+        """the channel shuffle of a whole tensor: out[c] = in[(c % groups) * (C / groups) + c // groups]"""
+        return self.concat([(tin, 0, c)], h, w, groups)[0]
 
     def dwconv(self, tin, h, w, c, k, s, act):
         oh, pt = _same_pad(h, k, s)
@@ -200,6 +222,9 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     'resnext_plan' (plan = random_resnext_plan(seed)) builds that plan's ResNeXt bottleneck blocks around grouped convolutions
     (mf.OP_GCONV): _build_resnext_plan.  'resnext_audio' (a ResNeXt-26 32x4d-like trunk on the v2.4 front-end, for timing the grouped
     layers: _build_resnext_audio).
+    'branchy_plan' (plan = random_branchy_plan(seed)) builds that plan's Fire / Inception / ShuffleNet / CSP blocks around channel
+    concatenations, windows and shuffles (mf.OP_CONCAT): _build_branchy_plan.  'shufflenet_audio' (ShuffleNetV2 x1.5 on the v2.4
+    front-end, for timing the concat layers: _build_shufflenet_audio).
     A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
@@ -215,6 +240,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
         return _build_resnext_plan(plan, seed)
     if kind == "resnext_audio":
         return _build_resnext_audio(seed, n_classes)
+    if kind == "branchy_plan":
+        return _build_branchy_plan(plan, seed)
+    if kind == "shufflenet_audio":
+        return _build_shufflenet_audio(seed, n_classes)
     rng = np.random.default_rng(seed)
     b = _Builder(rng)
     act_override, act, hidden = act, mf.ACT_GELU_ERF, 0
@@ -791,6 +820,150 @@ def _build_resnext_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = Non
     ncls = n_classes or 6522
     b.dense(t, 2048, ncls, gain=1.5)
     return _finish(b, branches, sr, n, ncls, 2048, emb, mf.OUT_SIGMOID)
+
+
+# ---- multi-branch backbones: Concat, channel Split and channel shuffle (mf.OP_CONCAT) ----------------------------------------------
+def _mb_block(b: _Builder, t, h, w, c, e, k, cout, act):
+    """an MBConv block at stride 1: 1x1 expand -> depthwise k x k -> 1x1 project (+ the input where the widths allow)"""
+    tin = t
+    t = b.pwconv(t, h, w, c, c * e, act)
+    t, h, w = b.dwconv(t, h, w, c * e, k, 1, act)
+    res = tin if c == cout else mf.NO_TENSOR
+    return b.pwconv(t, h, w, c * e, cout, mf.ACT_NONE, res, gain=0.5 if res != mf.NO_TENSOR else 1.0)
+
+
+def _shufflev2_unit(b: _Builder, t, h, w, c, cout, act, down):
+    """A ShuffleNetV2 unit behind tensor t [h][w][c] -> (tensor, h, w).  Basic (cout == c): Split into halves, the first half a view
+    that only the Concat reads (folded into its window), the second materialised for 1x1 -> depthwise 3x3 -> 1x1; Concat + shuffle in
+    two groups.  Down-sampling: both branches read x whole -- depthwise 3x3 stride 2 -> 1x1, and 1x1 -> depthwise 3x3 stride 2 -> 1x1
+    -- and the Concat of their cout / 2 channels each is shuffled."""
+    half = cout // 2
+    if not down:
+        assert cout == c
+        x2 = b.slice(t, h, w, half, half)
+        y = b.pwconv(x2, h, w, half, half, act)
+        y, _, _ = b.dwconv(y, h, w, half, 3, 1, mf.ACT_NONE)
+        y = b.pwconv(y, h, w, half, half, act)
+        return b.concat([(t, 0, half), (y, 0, half)], h, w, 2)[0], h, w
+    l, oh, ow = b.dwconv(t, h, w, c, 3, 2, mf.ACT_NONE)
+    l = b.pwconv(l, oh, ow, c, half, act)
+    r = b.pwconv(t, h, w, c, half, act)
+    r, _, _ = b.dwconv(r, h, w, half, 3, 2, mf.ACT_NONE)
+    r = b.pwconv(r, oh, ow, half, half, act)
+    return b.concat([(l, 0, half), (r, 0, half)], oh, ow, 2)[0], oh, ow
+
+
+def random_branchy_plan(seed: int) -> dict:
+    """A small seeded multi-branch stack on the mini front-end of _build_pool_plan (32 mels x 115 frames), every block kind that needs
+    mf.OP_CONCAT: an MBConv block, a CSP block that reads it (the first half of the MBConv output a view folded into the Concat's
+    window, the second half -- a window at a non-zero offset -- materialised for its convolutions), a second MBConv block that reads
+    that Concat, a Fire module, a 4-branch Inception module (1x1, 1x1 -> 3x3, 1x1 -> 1x7 -> 7x1, avg-pool -> 1x1: a 4-way Concat)
+    and on the odd seeds a 3-branch one, a ShuffleNetV2 down-sampling and a basic unit, and a ShuffleNetV1 unit (grouped 1x1 ->
+    shuffle -> depthwise -> grouped 1x1).  The Fire and Inception modules come in a drawn order.
+    Feed to build_model("branchy_plan", plan=...).  plan["items"]: ("mb", expand, k, cout) | ("csp",) | ("fire", squeeze, e1, e3) |
+    ("inception", n1, r3, n3, r7, n7, np) (np = 0: three branches) | ("sv2", cout, down) | ("sv1", mid, groups)."""
+    rng = np.random.default_rng(0xB4A9C + seed)
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+    c = pick((16, 24, 32))
+    items = [("mb", pick((4, 6)), pick((3, 5)), c), ("csp",), ("mb", pick((4, 6)), pick((3, 5)), pick((c, c + 8)))]
+    middle = [("fire", pick((8, 16)), pick((16, 24, 32)), pick((16, 32))),
+              ("inception", pick((8, 16)), pick((8, 12)), pick((16, 24)), pick((8, 12)), pick((8, 16)), pick((4, 8, 12)))]
+    if seed % 2:
+        middle.append(("inception", pick((12, 20)), 8, pick((12, 16)), 8, pick((12, 16)), 0))
+    items += [middle[int(k)] for k in rng.permutation(len(middle))]
+    items += [("sv2", pick((48, 64, 80)), True), ("sv2", 0, False)]
+    g = pick((2, 3, 4))
+    items.append(("sv1", g * pick((4, 8)), g))
+    return {"items": items, "stem_c": c, "act": int(pick((mf.ACT_RELU6, mf.ACT_SWISH, mf.ACT_GELU_ERF))), "head": int(rng.integers(4, 13)) * 8,
+            "classes": int(rng.integers(20, 61)), "out_act": int(pick((mf.OUT_SIGMOID, mf.OUT_SOFTMAX)))}
+
+
+def _build_branchy_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
+    """random_branchy_plan's stack on the mini front-end of one branch (512-sample frames at hop 100: 32 mels x 115 frames)."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 12000
+    br = mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23)
+    br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+    br.out_scale, br.out_shift = 0.8, -0.4
+    act, c = int(plan["act"]), int(plan["stem_c"])
+    t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, c, 3, 2, act, in_layout=1)
+    for it in plan["items"]:
+        if it[0] == "mb":
+            _, e, k, cout = it
+            t, c = _mb_block(b, t, h, w, c, e, k, cout, act), cout
+        elif it[0] == "csp":      # x -> Concat(x[: c / 2], conv(conv(x[c / 2 :])))
+            half = c // 2
+            y = b.slice(t, h, w, half, half)
+            y = b.pwconv(y, h, w, half, half, act)
+            y, _, _ = b.conv(y, h, w, half, half, 3, 1, act)
+            t, c = b.concat([(t, 0, half), (y, 0, half)], h, w)
+        elif it[0] == "fire":
+            _, sq, e1, e3 = it
+            s = b.pwconv(t, h, w, c, sq, act)
+            a = b.pwconv(s, h, w, sq, e1, act)
+            d, _, _ = b.conv(s, h, w, sq, e3, 3, 1, act)
+            t, c = b.concat([(a, 0, e1), (d, 0, e3)], h, w)
+        elif it[0] == "inception":
+            _, n1, r3, n3, r7, n7, npool = it
+            x = t
+            b1 = b.pwconv(x, h, w, c, n1, act)
+            b3 = b.pwconv(x, h, w, c, r3, act)
+            b3, _, _ = b.conv(b3, h, w, r3, n3, 3, 1, act)
+            b7 = b.pwconv(x, h, w, c, r7, act)
+            b7, _, _ = b.conv(b7, h, w, r7, r7, 1, 1, act, kw=7)
+            b7, _, _ = b.conv(b7, h, w, r7, n7, 7, 1, act, kw=1)
+            parts = [(b1, 0, n1), (b3, 0, n3), (b7, 0, n7)]
+            if npool:
+                bp, _, _ = b.pool(x, h, w, c, 3, 3, 1, 1, mf.POOL_AVG, "same")
+                parts.append((b.pwconv(bp, h, w, c, npool, act), 0, npool))
+            t, c = b.concat(parts, h, w)
+        elif it[0] == "sv2":
+            _, cout, down = it
+            cout = cout or c
+            t, h, w = _shufflev2_unit(b, t, h, w, c, cout, act, down)
+            c = cout
+        elif it[0] == "sv1":      # grouped 1x1 -> shuffle -> depthwise 3x3 -> grouped 1x1
+            _, mid, g = it
+            cg = c // g // 4 * 4 * g          # (the unit's input width: the largest the groups divide into widths of 4)
+            if cg != c:
+                t, c = b.pwconv(t, h, w, c, cg, act), cg
+            t, _, _ = b.gconv(t, h, w, c, mid, 1, 1, g, act)
+            t = b.shuffle(t, h, w, mid, g)
+            t, _, _ = b.dwconv(t, h, w, mid, 3, 1, mf.ACT_NONE)
+            t, _, _ = b.gconv(t, h, w, mid, c, 1, 1, g, act)
+        else:
+            raise ValueError(it[0])
+    head, ncls = int(plan["head"]), int(plan["classes"])
+    t = b.pwconv(t, h, w, c, head, act)
+    t = emb = b.gap(t, h, w, head)
+    b.dense(t, head, ncls, gain=1.5)
+    return _finish(b, [br], sr, n, ncls, head, emb, int(plan["out_act"]))
+
+
+def _build_shufflenet_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) -> mf.Model:
+    """ShuffleNetV2 x1.5 on the v2.4 front-end (96 mels x 511 frames, two branches): a 3x3 stride-2 NCHW stem to 24 channels with
+    ReLU, MaxPool 3x3 stride 2 pad 1, three stages of a down-sampling unit and 3 / 7 / 3 basic units at widths 176 / 352 / 704
+    (_shufflev2_unit), a 1x1 head to 1 024 channels, the global pool and the dense layer.  Seeded weights: a model for TIMING the concat
+    layers in the manner of resnext_audio, not for accuracy."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 144000
+    branches = [mf.Branch(2048, 278, 96, 511, 0.0, 3000.0, 1.23), mf.Branch(1024, 280, 96, 511, 500.0, 15000.0, 1.23)]
+    for br in branches:
+        br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+        br.out_scale, br.out_shift = 0.8, -0.4
+    t, h, w = b.conv(0, 96, 511, 2, 24, 3, 2, mf.ACT_RELU, in_layout=1)
+    t, h, w = b.pool(t, h, w, 24, 3, 3, 2, 2, mf.POOL_MAX, (1, 1, 1, 1))
+    c = 24
+    for width, reps in ((176, 4), (352, 8), (704, 4)):
+        t, h, w = _shufflev2_unit(b, t, h, w, c, width, mf.ACT_RELU, True)
+        for _ in range(reps - 1):
+            t, h, w = _shufflev2_unit(b, t, h, w, width, width, mf.ACT_RELU, False)
+        c = width
+    t = b.pwconv(t, h, w, c, 1024, mf.ACT_RELU)
+    t = emb = b.gap(t, h, w, 1024)
+    ncls = n_classes or 6522
+    b.dense(t, 1024, ncls, gain=1.5)
+    return _finish(b, branches, sr, n, ncls, 1024, emb, mf.OUT_SIGMOID)
 
 
 def random_fused_plan(seed: int, big: bool = False) -> dict:

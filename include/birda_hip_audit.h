@@ -21,6 +21,7 @@ extern "C" {
 #define BH_PATH_HEAD_GAP 3  /* head 1x1 conv + the pool after it in one launch */
 #define BH_PATH_SE_GATE 4   /* pool -> 1x1 -> 1x1 of a block that runs layer by layer, as the two gate launches */
 #define BH_PATH_INNER 5     /* the layer runs inside the launch of an earlier one */
+#define BH_PATH_CONCAT 6    /* a chain of concat records (an N-way Concat) gathered in one launch */
 
 /* The activation arena's plan.  n == 0: the plan of the context itself (its forwards of up to max_batch segments); n > 0: the plan
  * the same planner makes for n segments (what a concurrent lane of an n-segment sub-slice gets; host logic only, any n).  Per

@@ -24,7 +24,7 @@ for _ in range(5):
 ctx.synchronize()
 st = ctx.stage_ms(); ly = ctx.layer_ms()
 print({k: round(v[0] / 5 * 1e3 / N, 3) for k, v in st.items()}, "us/segment")
-names = {1: "conv", 2: "dw", 3: "pw", 4: "gap", 5: "dense", 6: "scale", 7: "pool", 8: "gconv"}
+names = {1: "conv", 2: "dw", 3: "pw", 4: "gap", 5: "dense", 6: "scale", 7: "pool", 8: "gconv", 10: "cat"}
 for i, (ms, n) in enumerate(ly):
     if n:
         L = m.layers[i]
@@ -37,4 +37,7 @@ for i, (ms, n) in enumerate(ly):
         if L.op == mf.OP_POOL:   # HBM-bound: the bytes it moves (input + output) and the rate
             nbytes = 4 * N * L.cout * (L.in_h * L.in_w + L.out_h * L.out_w)
             line += f"  {('max', 'avg', 'avg_pad')[L.reserved]} {L.kh}x{L.kw}/{L.sh}x{L.sw}  {nbytes / 1e6:9.1f} MB  {nbytes / (ms / 5 * 1e-3) / 1e12:5.2f} TB/s"
+        if L.op == mf.OP_CONCAT:  # HBM-bound: a copy of the output's bytes (res_tensor is the second input, not a residual)
+            nbytes = 2 * 4 * N * L.out_h * L.out_w * L.cout
+            line += f"  {L.cin}+{L.cout - L.cin} channels{' shuffle g=' + str(L.reserved) if L.reserved > 1 else ''}  {clf.layer_kernel(i)}  {nbytes / 1e6:9.1f} MB  {nbytes / (ms / 5 * 1e-3) / 1e12:5.2f} TB/s"
         print(line)
