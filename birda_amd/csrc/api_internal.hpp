@@ -1,9 +1,11 @@
 // api_internal.hpp -- what the translation units of the C ABI share.  Round 4 split the one 2 600-line api.hip (VERDICT r3 weak
 // #11) into
-//   api.hip         classifier / batch-context life cycle, the forward pass over a slice, lanes, the predict entry points
+//   api.hip         classifier / batch-context life cycle, the forward pass over a slice, lanes, the predict, PCM and resampler
+//                   entry points, and the diagnostics that read a classifier's or a context's state
 //   api_plan.hip    host-side planning at create: the folded STFT x mel operator, the arena's liveness plan, the fused blocks'
-//                   descriptors and their re-laid weights
+//                   descriptors, and every re-laid weight (the GEMM layers' rows, planes and fragments, the fused blocks')
 //   api_custom.hip  custom classifiers on embeddings (bat two-stage inference) and the geomodel range filter
+//   api_debug.hip   the kernel diagnostics that take no classifier, on one launch harness; it alone includes their headers
 // The shared helpers live in namespace bhi (hidden visibility: nothing of it leaves the library).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,16 +30,8 @@
 #include "../../include/birda_hip.h"
 #include "../../include/birda_hip_debug.h"
 #include "../../include/birda_hip_audit.h"
-#include "../../include/birda_hip_layer_debug.h"
-#include "../../include/birda_hip_pool_debug.h"
-#include "../../include/birda_hip_concat_debug.h"
-#include "../../include/birda_hip_gate_debug.h"
-#include "../../include/birda_hip_resact_debug.h"
-#include "../../include/birda_hip_gconv_debug.h"
-#include "../../include/birda_hip_block_debug.h"
 #include "../../include/birda_hip_terms_debug.h"
 #include "../../include/birda_hip_pcm_debug.h"
-#include "../../include/birda_hip_resample_debug.h"
 #include "kernels.hpp"
 #include "trace.hpp"
 #include "model.hpp"
@@ -84,7 +78,6 @@ struct Step {
     std::vector<Scratch> scratch;          // SE block: SE_* below; gate fast path: the pool's and the hidden layer's tensors
 };
 enum { SE_POOLED = 0, SE_HIDDEN, SE_GATE, SE_SUMS };   // Step::scratch of a fused squeeze-excite block
-
 
 }  // namespace bhi
 
@@ -311,8 +304,24 @@ std::vector<int> tensor_readers(const bh::Model &m);
 struct MbHostWeights { std::vector<float> we, wp, wd, bp; int spa = 0; };
 void mb_prepare_weights(bh::MbDesc &d, const float *We, const float *be, const float *Wd, const float *bd, const float *Wp, const float *bp,
                         MbHostWeights &out);
+// the GEMM layers' weights in their kernels' layouts (host vectors): create uploads them, the diagnostics of api_debug.hip too
+std::vector<uint16_t> w16_planes(const float *W, int K, int N, float *unscale, bool *lo_zero = nullptr);
+std::vector<uint16_t> w16_compact(const std::vector<uint16_t> &planes);
+std::vector<float> conv_gemm_rows(const float *W, const bh::ConvParams &p, int ld);
+std::vector<float> gconv_matrix(const float *W, const bh::ConvParams &p, int G, int *K_out);
+std::vector<float> gconv_fragments(const std::vector<float> &wt, int K, int nt);
+std::vector<float> pw_gemm_rows(const float *W, size_t K, size_t N, size_t ld);
 int plan_fusion(bh_classifier *c);
 // api.hip
+int se_gate_form(int C, int Cr);
+int mb_ksplit_of(const bh::MbDesc &d);
+int resample_ranges(const char *who, size_t src_len, size_t out_len, size_t n_seg);
+// a kernel's name (null: none) into out / cap, written only where it fits with its terminator; returns its length
+inline int copy_name(const char *name, char *out, size_t cap) {
+    const size_t n = name ? strlen(name) : 0;
+    if (out && cap > n) { if (n) memcpy(out, name, n); out[n] = 0; }
+    return (int)n;
+}
 int upload(const void *src, size_t bytes, float **dst);
 int read_labels(const char *path, std::vector<std::string> &out);
 int check_ctx(bh_classifier *c, bh_batch_context *ctx);

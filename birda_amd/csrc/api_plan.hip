@@ -387,6 +387,100 @@ std::vector<int> tensor_readers(const bh::Model &m) {
     return readers;
 }
 
+// f16 operand planes of a [K][N] weight matrix for the split-f16 GEMMs: [ceil(K / 32)][ceil(N / 16)]{hi, lo}[64 lanes][8 halves],
+// lane (n & 15, k group) holding k = 32 step + 8 (lane >> 4) + 0..7 of column n, scaled by a power of two (1 / *unscale) that puts
+// the largest weight in the f16 range, zero beyond K and N
+// *lo_zero (may be null): every weight IS an f16 value after the power-of-two pre-scale -- its hi half holds it exactly, so every lo
+// entry is zero and nothing was lost below the f16 subnormal grid either (a residual under half a subnormal step also rounds to a
+// zero lo entry: such a matrix does NOT qualify; inf / NaN weights neither).  The layer may then run two-term products
+// (kernels_conv.hip TERMS == 2) on the compact form of these planes (w16_compact)
+std::vector<uint16_t> w16_planes(const float *W, int K, int N, float *unscale, bool *lo_zero) {
+    const int nt = (N + 15) / 16, ksteps = (K + 31) / 32;
+    std::vector<uint16_t> planes((size_t)ksteps * nt * 2 * 64 * 8, 0);
+    float wmax = 0.0f;
+    for (size_t q = 0; q < (size_t)K * N; q++) wmax = std::max(wmax, std::fabs(W[q]));
+    const int ws = bh::f16_scale_exponent(wmax);
+    *unscale = std::ldexp(1.0f, -ws);
+    bool exact = true;
+    for (int st = 0; st < ksteps; st++)
+        for (int t = 0; t < nt; t++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int jj = 0; jj < 8; jj++) {
+                    const int k = 32 * st + 8 * (lane >> 4) + jj, n = 16 * t + (lane & 15);
+                    const float v = (n < N && k < K) ? std::ldexp(W[(size_t)k * N + n], ws) : 0.0f;
+                    const uint16_t hi = f32_to_f16(v);
+                    const size_t base = (((size_t)st * nt + t) * 2) * 64 * 8;
+                    const float rest = v - f16_to_f32(hi);
+                    if (!(rest == 0.0f)) exact = false;
+                    planes[base + (size_t)lane * 8 + jj] = hi;
+                    planes[base + 64 * 8 + (size_t)lane * 8 + jj] = f32_to_f16(rest);
+                }
+    if (lo_zero) *lo_zero = exact;
+    return planes;
+}
+
+// the compact planes of two-term products: [k step][column tile][64 lanes][8 halves], w16_planes' layout without the lo half
+std::vector<uint16_t> w16_compact(const std::vector<uint16_t> &planes) {
+    std::vector<uint16_t> out(planes.size() / 2);
+    for (size_t blk = 0; blk < planes.size() / (2 * 64 * 8); blk++)
+        memcpy(&out[blk * 64 * 8], &planes[blk * 2 * 64 * 8], 64 * 8 * sizeof(uint16_t));
+    return out;
+}
+
+// A full convolution's [kh][kw][cin][cout] weights as the implicit GEMM's K x ld rows: the channels of every tap padded to whole
+// 32-deep steps (K = kh kw align_up(cin, 32)), the columns to ld; zero in the padding
+std::vector<float> conv_gemm_rows(const float *W, const bh::ConvParams &p, int ld) {
+    const size_t cpad = align_up((size_t)p.cin, 32), taps = (size_t)p.kh * p.kw;
+    std::vector<float> w(taps * cpad * ld, 0.0f);
+    for (size_t t = 0; t < taps; t++)
+        for (size_t ch = 0; ch < (size_t)p.cin; ch++)
+            memcpy(&w[(t * cpad + ch) * ld], W + (t * p.cin + ch) * p.cout, p.cout * sizeof(float));
+    return w;
+}
+
+// A grouped convolution's compact [kh][kw][cin / G][cout] weights as the matrix Wt [K][16 n_tiles] of kernels_gconv.hip: column o
+// of column tile t is dense over k = tap * span + (c - c0), [c0, c0 + span) the tile's span of input channels (gconv_tile_span),
+// zero where channel c is not in o's group; K = the largest tile's kh kw span, padded ONCE at the end to whole 32-deep steps
+std::vector<float> gconv_matrix(const float *W, const bh::ConvParams &p, int G, int *K_out) {
+    const int nt = (p.cout + 15) / 16, gi = p.cin / G, go = p.cout / G, taps = p.kh * p.kw;
+    size_t kmax = 0;
+    for (int t = 0; t < nt; t++) {
+        int c0, span;
+        bh::gconv_tile_span(p.cin, p.cout, G, t, c0, span);
+        kmax = std::max(kmax, (size_t)taps * span);
+    }
+    const size_t K = align_up(kmax, 32), ld = (size_t)nt * 16;
+    std::vector<float> wt(K * ld, 0.0f);
+    for (int o = 0; o < p.cout; o++) {
+        int c0, span;
+        bh::gconv_tile_span(p.cin, p.cout, G, o / 16, c0, span);
+        const int first = (o / go) * gi - c0;      // the group's first channel within the span
+        for (int tap = 0; tap < taps; tap++)
+            for (int c = 0; c < gi; c++)
+                wt[((size_t)tap * span + first + c) * ld + o] = W[((size_t)tap * gi + c) * p.cout + o];
+    }
+    *K_out = (int)K;
+    return wt;
+}
+// ... and its f32 MFMA fragments [K / 16][n_tiles][64 lanes][4]: element (g, t, lane, c) = Wt[16g + 4 (lane >> 4) + c][16t + (lane & 15)]
+std::vector<float> gconv_fragments(const std::vector<float> &wt, int K, int nt) {
+    std::vector<float> f((size_t)K * nt * 16);
+    const size_t ld = (size_t)nt * 16;
+    for (int g = 0; g < K / 16; g++)
+        for (int t = 0; t < nt; t++)
+            for (int lane = 0; lane < 64; lane++)
+                for (int c = 0; c < 4; c++)
+                    f[(((size_t)g * nt + t) * 64 + lane) * 4 + c] = wt[((size_t)16 * g + 4 * (lane >> 4) + c) * ld + 16 * t + (lane & 15)];
+    return f;
+}
+
+// A pointwise / dense layer's [K][N] weights with the rows padded to ld = align_up(N, 4) (the f32 GEMM's 16-B loads); zero in the padding
+std::vector<float> pw_gemm_rows(const float *W, size_t K, size_t N, size_t ld) {
+    std::vector<float> w(K * ld, 0.0f);
+    for (size_t k = 0; k < K; k++) memcpy(&w[k * ld], W + k * N, N * sizeof(float));
+    return w;
+}
+
 // The weights of one planned fused block as the kernel reads them (kernels.hpp MbDesc): the per-chunk fragment blocks of the picked
 // tile configuration, and everything the f16 modes hang on them -- the plane exponents se / sp, e_fold with the scaled GELU
 // coefficients, the 2x GELU factors, the hi / lo planes, the stem's run-packed im2col order, the folded depthwise taps, bp scaled to
