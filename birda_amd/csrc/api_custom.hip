@@ -4,27 +4,6 @@
 
 using namespace bhi;
 
-struct bh_custom_classifier {
-    bh::CustomModel model;
-    int device = 0;
-    uint32_t top_k = 0;
-    std::vector<std::string> labels;
-    float *d_blob = nullptr;
-    std::vector<float *> d_w;     // per layer: W with rows padded to a multiple of 4 (or a pointer into d_blob)
-    std::vector<int> ldw;
-    std::vector<float *> d_owned;
-    // scratch, grown on demand: activations of the two widest layers, logits, top-k rows, host copies
-    float *d_act[2] = {nullptr, nullptr};
-    float *d_in = nullptr;
-    int32_t *d_idx = nullptr;
-    float *d_conf = nullptr;
-    size_t cap_rows = 0;
-    uint32_t max_width = 0;
-    uint32_t k0 = 0;              // input width padded to a multiple of 4 (the GEMM's k step): rows of d_in have this stride
-    hipStream_t stream = nullptr;
-    std::mutex mu;
-};
-
 namespace {
 
 int cc_reserve(bh_custom_classifier *cc, size_t rows) {
@@ -40,8 +19,13 @@ int cc_reserve(bh_custom_classifier *cc, size_t rows) {
     return BH_OK;
 }
 
+}  // namespace
+
+namespace bhi {
+
 // dense stack + activation / top-k on device rows [n][input_dim] (row stride in_stride); results to the host
-int cc_run(bh_custom_classifier *cc, const float *d_emb, size_t in_stride, size_t n, hipStream_t s, bh_result *out, float *logits_out) {
+int cc_run(bh_custom_classifier *cc, const float *d_emb, size_t in_stride, size_t n, hipStream_t s, bh_result *out, float *logits_out,
+           const char **last_gemm) {
     const auto &m = cc->model;
     int rc = cc_reserve(cc, n);
     if (rc != BH_OK) return rc;
@@ -50,7 +34,8 @@ int cc_run(bh_custom_classifier *cc, const float *d_emb, size_t in_stride, size_
     for (size_t i = 0; i < m.layers.size(); i++) {
         const auto &L = m.layers[i];
         float *dst = cc->d_act[i & 1];
-        bh::launch_pw_gemm(cur, cc->d_w[i], cc->d_blob + L.b_off, nullptr, dst, (int)n, (int)(i == 0 ? cc->k0 : L.in_dim), (int)L.out_dim, cc->ldw[i], (int)L.act, s);
+        const char *name = bh::launch_pw_gemm(cur, cc->d_w[i], cc->d_blob + L.b_off, nullptr, dst, (int)n, (int)(i == 0 ? cc->k0 : L.in_dim), (int)L.out_dim, cc->ldw[i], (int)L.act, s);
+        if (last_gemm) *last_gemm = name;
         cur = dst;
     }
     if (!out) {   // every class's activated output, no ranking (the range filter: its last layer carries the sigmoid)
@@ -81,7 +66,21 @@ int cc_run(bh_custom_classifier *cc, const float *d_emb, size_t in_stride, size_
     return BH_OK;
 }
 
-}  // namespace
+// host rows [n][input_dim] -> d_in rows [n][k0] (zero padded)
+int cc_upload_rows(bh_custom_classifier *cc, const float *rows, size_t n) {
+    int rc = cc_reserve(cc, n);
+    if (rc != BH_OK) return rc;
+    const size_t in = cc->model.h.input_dim;
+    if (cc->k0 == in) {
+        HIPCHK(hipMemcpyAsync(cc->d_in, rows, n * in * sizeof(float), hipMemcpyHostToDevice, cc->stream));
+    } else {
+        HIPCHK(hipMemsetAsync(cc->d_in, 0, n * (size_t)cc->k0 * sizeof(float), cc->stream));
+        HIPCHK(hipMemcpy2DAsync(cc->d_in, (size_t)cc->k0 * sizeof(float), rows, in * sizeof(float), in * sizeof(float), n, hipMemcpyHostToDevice, cc->stream));
+    }
+    return BH_OK;
+}
+
+}  // namespace bhi
 
 extern "C" {
 
@@ -145,20 +144,6 @@ static int cc_build(bh_custom_classifier *cc, const char *labels_path, int32_t d
         }
         cc->d_w.push_back(w);
         cc->ldw.push_back(ld);
-    }
-    return BH_OK;
-}
-
-// host rows [n][input_dim] -> d_in rows [n][k0] (zero padded)
-static int cc_upload_rows(bh_custom_classifier *cc, const float *rows, size_t n) {
-    int rc = cc_reserve(cc, n);
-    if (rc != BH_OK) return rc;
-    const size_t in = cc->model.h.input_dim;
-    if (cc->k0 == in) {
-        HIPCHK(hipMemcpyAsync(cc->d_in, rows, n * in * sizeof(float), hipMemcpyHostToDevice, cc->stream));
-    } else {
-        HIPCHK(hipMemsetAsync(cc->d_in, 0, n * (size_t)cc->k0 * sizeof(float), cc->stream));
-        HIPCHK(hipMemcpy2DAsync(cc->d_in, (size_t)cc->k0 * sizeof(float), rows, in * sizeof(float), in * sizeof(float), n, hipMemcpyHostToDevice, cc->stream));
     }
     return BH_OK;
 }

@@ -11,6 +11,7 @@
 #include "../../include/birda_hip_gconv_debug.h"
 #include "../../include/birda_hip_block_debug.h"
 #include "../../include/birda_hip_resample_debug.h"
+#include "../../include/birda_hip_custom_debug.h"
 
 using namespace bhi;
 
@@ -557,6 +558,23 @@ int bh_debug_resample(int device, const float *in, size_t n_seg, size_t in_strid
     if (!h.ok) return h.no_memory();
     return h.finish(bh::launch_resample(*pl, dx, in_stride, (int)src_len, dy, out_stride, (int)out_len, (int)n_seg, split_f16 != 0, nullptr),
                     kernel, kernel_cap);
+} catch (...) { return on_exception(); }
+
+// The dense stack of a custom classifier alone: host rows through cc_upload_rows and cc_run as bh_custom_classifier_predict_batch
+// takes them, the last layer's activated output back, no ranking (include/birda_hip_custom_debug.h).
+int bh_debug_custom_logits(bh_custom_classifier *cc, const float *rows, size_t n, float *out, char *kernel, size_t kernel_cap) try {
+    if (!cc || !rows || !out || !n) return fail(BH_ERR_INVALID, "debug_custom_logits: bad arguments");
+    if (n > (size_t)INT32_MAX / std::max<size_t>(cc->max_width, 1)) return fail(BH_ERR_INVALID, "debug_custom_logits: buffers past 2^31 elements");
+    std::lock_guard<std::mutex> g(cc->mu);
+    HIPCHK(hipSetDevice(cc->device));
+    int rc = cc_upload_rows(cc, rows, n);
+    if (rc != BH_OK) return rc;
+    const char *name = nullptr;
+    rc = cc_run(cc, cc->d_in, cc->k0, n, cc->stream, nullptr, out, &name);
+    if (rc != BH_OK) return rc;
+    if (!name) return fail(BH_ERR_INTERNAL, "debug_custom_logits: no GEMM was launched");
+    if (kernel && kernel_cap) snprintf(kernel, kernel_cap, "%s", name);
+    return BH_OK;
 } catch (...) { return on_exception(); }
 
 }  // extern "C"

@@ -281,6 +281,28 @@ struct bh_batch_context {
     uint32_t stage_launches[BH_N_STAGES] = {0};
 };
 
+// api_custom.hip: a dense stack on embeddings (custom classifier) or on (latitude, longitude, week) (the geomodel)
+struct bh_custom_classifier {
+    bh::CustomModel model;
+    int device = 0;
+    uint32_t top_k = 0;
+    std::vector<std::string> labels;
+    float *d_blob = nullptr;
+    std::vector<float *> d_w;     // per layer: W with rows padded to a multiple of 4 (or a pointer into d_blob)
+    std::vector<int> ldw;
+    std::vector<float *> d_owned;
+    // scratch, grown on demand: activations of the two widest layers, logits, top-k rows, host copies
+    float *d_act[2] = {nullptr, nullptr};
+    float *d_in = nullptr;
+    int32_t *d_idx = nullptr;
+    float *d_conf = nullptr;
+    size_t cap_rows = 0;
+    uint32_t max_width = 0;
+    uint32_t k0 = 0;              // input width padded to a multiple of 4 (the GEMM's k step): rows of d_in have this stride
+    hipStream_t stream = nullptr;
+    std::mutex mu;
+};
+
 // host_pipeline.cpp: memcpy into pinned staging memory with non-temporal stores (what the DMA engine, not a core, reads next)
 extern "C" void bh_internal_stream_copy(void *dst, const void *src, size_t bytes);
 
@@ -327,5 +349,10 @@ int read_labels(const char *path, std::vector<std::string> &out);
 int check_ctx(bh_classifier *c, bh_batch_context *ctx);
 int predict_slices(bh_classifier *c, bh_batch_context *ctx, const float *const *segments, const float *contig,
                    size_t n, bh_result *out, float *logits_out, float *emb_out, bool whole_slice = false);
+// api_custom.hip: host rows into the stack's input buffer; the stack (+ activation / top-k when out is given) on device rows.
+// last_gemm (nullable) receives the name of the last GEMM launched
+int cc_upload_rows(bh_custom_classifier *cc, const float *rows, size_t n);
+int cc_run(bh_custom_classifier *cc, const float *d_emb, size_t in_stride, size_t n, hipStream_t s, bh_result *out, float *logits_out,
+           const char **last_gemm = nullptr);
 
 }  // namespace bhi

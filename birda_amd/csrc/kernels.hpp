@@ -505,6 +505,10 @@ const char *launch_head_gap16(const float *A, const void *Wf, const float *bias,
 struct TopkFilter {
     // BSG post-processing (reference classifier.rs:508-545): conf' = sigmoid(intercept[c] + slope[c] logit(conf)) (* prior[c]),
     // then re-sorted; applied before the range filter / species list stage.  bsg_intercept null = off.
+    // [EXT] The crate that owns BsgPostProcessor is not among the reference's sources: the form above is this project's restatement
+    // of it.  The confidence is clamped IN FLOAT32 to [1e-7f, 1.0f - 1e-7f]; the upper bound is 1 - 2^-23, so the largest logit the
+    // calibration sees is 15.942 (a float64 clamp at 1 - 1e-7 would let 16.118 through: 0.529 for 0.486 at intercept -16, slope 1).
+    // oracle.bsg_postprocess and tests/test_topk_tail.py (tail64) use the same two float32 numbers.
     const float *bsg_intercept = nullptr, *bsg_slope = nullptr, *bsg_prior = nullptr;
     const float *class_score = nullptr;
     const unsigned char *species_keep = nullptr;

@@ -293,11 +293,14 @@ def custom_classifier_forward(model, embeddings: np.ndarray) -> np.ndarray:
 def bsg_postprocess(index: np.ndarray, confidence: np.ndarray, intercept: np.ndarray, slope: np.ndarray,
                     prior: Optional[np.ndarray] = None):
     """BirdClassifier::apply_bsg_postprocessing (reference src/inference/classifier.rs:508-545) on one segment's kept
-    predictions: conf' = sigmoid(intercept[c] + slope[c] * logit(conf)) (* prior[c]), stable re-sort descending."""
+    predictions: conf' = sigmoid(intercept[c] + slope[c] * logit(conf)) (* prior[c]), stable re-sort descending.
+    The confidence is clamped to the FLOAT32 numbers 1e-7f and 1.0f - 1e-7f (= 1 - 2^-23: the largest logit the calibration sees is
+    15.942, not the 16.118 of a float64 clamp) as the device does (kernels.hpp, TopkFilter); everything else is float64."""
     idx = [int(i) for i in index if i >= 0]
     out = []
+    lo, hi = float(np.float32(1e-7)), float(np.float32(1.0) - np.float32(1e-7))
     for c, p in zip(idx, confidence):
-        p = min(max(float(p), 1e-7), 1.0 - 1e-7)
+        p = min(max(float(p), lo), hi)
         lg = np.log(p / (1.0 - p))
         q = 1.0 / (1.0 + np.exp(-(float(intercept[c]) + float(slope[c]) * lg)))
         if prior is not None:
