@@ -103,6 +103,8 @@ SYMBOLS = [
     ("bh_classifier_weight_summary", C.c_int, [_VP, _VP, _SZ]),
     ("bh_plan_fused_blocks", C.c_int, [C.c_char_p, C.c_uint32, _VP, _VP, _SZ]),
     ("bh_mb_config_name", C.c_int, [C.c_int32, C.c_char_p, _SZ]),
+    ("bh_mb_config_families", C.c_int, []),
+    ("bh_mb_config_name_ex", C.c_int, [C.c_int32, C.c_char_p, _SZ]),
     ("bh_classifier_frontend_kernel", C.c_int, [_VP, C.c_char_p, _SZ]),
     ("bh_debug_mb_stamps", C.c_int, [_VP, _VP, _SZ]),
     ("bh_debug_gated_gemm", C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _SZ, _SZ, _SZ, _SZ, C.c_int, C.c_int]),

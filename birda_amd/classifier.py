@@ -202,7 +202,7 @@ class BirdClassifier:
         """The block's instantiation as rocprofv3 prints it: the 19 tile arguments of bh_mb_config_name and the twentieth, SE (1 for
         pass A of a squeeze-excite block)."""
         buf = C.create_string_buffer(128)
-        self._L.bh_mb_config_name(cfg, buf, 128)
+        self._L.bh_mb_config_name_ex(cfg, buf, 128)
         name = buf.value.decode()
         return "mbconv<" + name + ("," + str(int(se)) if name else "") + ">"
 

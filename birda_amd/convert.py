@@ -3,7 +3,9 @@
 `model_from_graph` turns the classifier part of an ONNX graph -- from the spectrogram tensor
 [N, C, H, W] to the logits -- into the layer table `modelfile.py` describes: Conv (group 1 / depthwise
 / 1x1 / any other group count: OP_GCONV) with BatchNormalization folded, the activation that follows folded into the producing layer
-(Relu, Clip 0..6, Sigmoid*x, the Div-Erf-Add-Mul-Mul spelling of exact GELU, or a fused `Gelu`),
+(Relu, Clip 0..6, Sigmoid*x, the Div-Erf-Add-Mul-Mul spelling of exact GELU, a fused `Gelu`; MobileNetV3's hard swish as `HardSwish`,
+as HardSigmoid(1/6, 1/2)*x or as the Add 3 - Clip 0..6 - Mul x - Mul 1/6 chain, its hard-sigmoid gate as HardSigmoid(1/6, 1/2) or that
+chain without the Mul x),
 residual Add folded into the project conv -- with the activation that follows the Add, if any, as that layer's (Layer.reserved =
 RES_ACT_AFTER: act(conv + x), the end of a ResNet block) --, squeeze-excite blocks (GlobalAveragePool -> 1x1 Conv -> activation -> 1x1 Conv ->
 Sigmoid -> Mul with the feature map) as pool / 1x1 / 1x1 / OP_SCALE layers, MaxPool / AveragePool in floor mode (OP_POOL: any
@@ -139,10 +141,22 @@ def frontend_nodes(g: ox.Graph, m: mf.Model, spelling: str) -> None:
     node("Concat", chans, "spectrogram", axis=1)
 
 
-def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None) -> ox.Graph:
+HSWISH_SPELLINGS = ("op", "hsigmoid", "decomposed")
+
+
+def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op") -> ox.Graph:
     """The conv stack of a BHM1 model as an ONNX graph over `spectrogram` [N, C, H, W] -- or, with `frontend_spelling`
     (see `frontend_nodes`), the whole model over `audio` [N, S].
-    spell_gelu: 'erf' = Div, Erf, Add, Mul, Mul (what exporters emit below opset 20); 'gelu' = one Gelu node."""
+    spell_gelu: 'erf' = Div, Erf, Add, Mul, Mul (what exporters emit below opset 20); 'gelu' = one Gelu node.
+    spell_hswish: how ACT_HSWISH / ACT_HSIGMOID are written -- 'op' = HardSwish (opset 14) / HardSigmoid(alpha 1/6, beta 0.5);
+    'hsigmoid' = HardSigmoid * x (PyTorch below opset 14) / HardSigmoid; 'decomposed' = Add(x, 3) -> Clip(0, 6) -> Mul(., x) ->
+    Mul(., 1/6) (tf2onnx; the gate without the Mul(., x)).  Options follow 'decomposed' after a colon, comma-separated: 'div' (Div(., 6)
+    for the last Mul), 'scale_first' (the scaling in front of the Mul(., x)), 'swap' (every binary node's operands exchanged where the
+    operator commutes), 'f16' (float16 constants), 'cast' (a Cast to float32 inside the fold; 'hsigmoid' takes 'swap' and 'cast' too)."""
+    hs_kind, _, hs_opts = spell_hswish.partition(":")
+    hs_opts = set(filter(None, hs_opts.split(",")))
+    if hs_kind not in HSWISH_SPELLINGS or not hs_opts <= {"div", "scale_first", "swap", "f16", "cast"}:
+        raise ConvertError(f"unknown hard-swish spelling {spell_hswish!r}")
     g = ox.Graph(name="birda_conv_stack", producer="birda_amd.convert")
     if frontend_spelling is None:
         g.inputs.append(ox.ValueInfo("spectrogram", ox.FLOAT, ["N", len(m.branches), m.spec_h, m.spec_w]))
@@ -182,7 +196,44 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
             g.nodes.append(ox.Node("Mul", [x, tag + "_a"], [tag + "_m"]))
             g.nodes.append(ox.Node("Mul", [tag + "_m", const(tag + "_half", 0.5)], [tag + "_gelu"]))
             return tag + "_gelu"
+        if act in (mf.ACT_HSWISH, mf.ACT_HSIGMOID):
+            return hard_activation(x, act == mf.ACT_HSWISH, tag)
         raise ConvertError(f"activation {act} has no ONNX spelling here")
+
+    def hard_activation(x: str, swish: bool, tag: str) -> str:
+        def binary(op, a, b, out):
+            g.nodes.append(ox.Node(op, [b, a] if "swap" in hs_opts and op != "Div" else [a, b], [out]))
+            return out
+
+        def hconst(name, v):
+            g.initializers[name] = np.asarray(v, np.float16 if "f16" in hs_opts else np.float32)
+            return name
+
+        def cast(y):
+            if "cast" not in hs_opts:
+                return y
+            g.nodes.append(ox.Node("Cast", [y], [y + "_c"], {"to": ox.FLOAT}))
+            return y + "_c"
+        sixth = {"alpha": float(np.float32(1.0 / 6.0)), "beta": 0.5}
+        if hs_kind == "op" and swish:
+            g.nodes.append(ox.Node("HardSwish", [x], [tag + "_hswish"]))
+            return tag + "_hswish"
+        if hs_kind in ("op", "hsigmoid"):
+            g.nodes.append(ox.Node("HardSigmoid", [x], [tag + "_hsig"], dict(sixth)))
+            return binary("Mul", x, cast(tag + "_hsig"), tag + "_hswish") if swish else tag + "_hsig"
+        y = binary("Add", x, hconst(tag + "_three", 3.0), tag + "_p3")
+        g.nodes.append(ox.Node("Clip", [y, hconst(tag + "_min", 0.0), hconst(tag + "_max", 6.0)], [tag + "_r6"]))
+        y = cast(tag + "_r6")
+
+        def scale(y, out):
+            if "div" in hs_opts:
+                return binary("Div", y, hconst(tag + "_six", 6.0), out)
+            return binary("Mul", y, hconst(tag + "_sixth", 1.0 / 6.0), out)
+        if not swish:
+            return scale(y, tag + "_hsig")
+        if "scale_first" in hs_opts:
+            return binary("Mul", x, scale(y, tag + "_hs6"), tag + "_hswish")
+        return scale(binary("Mul", x, y, tag + "_hsx"), tag + "_hswish")
 
     for i, L in enumerate(m.layers):
         tag, x = f"l{i}", names[L.in_tensor]
@@ -289,9 +340,9 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
     return g
 
 
-def model_to_onnx(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None) -> bytes:
+def model_to_onnx(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op") -> bytes:
     """`graph_from_model` serialised: the bytes of the `.onnx` file `bh_classifier_create` opens."""
-    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling))
+    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling, spell_hswish))
 
 
 # ---------------------------------------------------------------------------------------
@@ -351,9 +402,37 @@ def _see_through_casts(g: ox.Graph, front_nodes: set) -> ox.Graph:
     return ox.Graph(nodes, g.initializers, g.inputs, outs, g.name, g.opset, g.producer)
 
 
-def _collapse_activations(g: ox.Graph):
+# The hard sigmoid the kernels compute is PyTorch's, min(max(x / 6 + 1/2, 0), 1): alpha within 1e-6 of 1/6 and beta = 0.5 (the ONNX
+# defaults, alpha = 0.2 and beta = 0.5, are Keras's: another function, refused by name).  The decomposed spelling's 1/6 is held to
+# 1e-6 from a float32 constant and must BE the float16 rounding of 1/6 from a float16 one.
+SIXTH_F16 = float(np.float16(1.0 / 6.0))
+
+
+def _hsig_params(n: ox.Node) -> Tuple[float, float]:
+    return float(np.float32(n.attrs.get("alpha", 0.2))), float(np.float32(n.attrs.get("beta", 0.5)))
+
+
+def _hsig_is_torch(n: ox.Node) -> bool:
+    alpha, beta = _hsig_params(n)
+    return abs(alpha - 1.0 / 6.0) <= 1e-6 and beta == 0.5
+
+
+def _fscalar(g: ox.Graph, name: str) -> Optional[float]:
+    """_scalar for a float32 or float16 initializer only (what csrc/onnx_conv.hpp's scalar() reads)"""
+    a = g.initializers.get(name)
+    return float(a.reshape(-1)[0]) if a is not None and a.size == 1 and a.dtype in (np.float32, np.float16) else None
+
+
+def _clip_is_relu6(g: ox.Graph, n: ox.Node) -> bool:
+    lo = _fscalar(g, n.inputs[1]) if len(n.inputs) > 1 and n.inputs[1] else n.attrs.get("min")
+    hi = _fscalar(g, n.inputs[2]) if len(n.inputs) > 2 and n.inputs[2] else n.attrs.get("max")
+    return lo is not None and hi is not None and float(lo) == 0.0 and float(hi) == 6.0
+
+
+def _collapse_activations(g: ox.Graph, front_nodes=frozenset()):
     """Find the multi-node activation spellings.  Returns (skip: set of node indices,
     act_of: {final output name: (input name, ACT, the pattern's own node indices)})."""
+    graph_out = {o.name for o in g.outputs}
     prod = {o: i for i, n in enumerate(g.nodes) for o in n.outputs}
     cons: Dict[str, List[int]] = {}
     for i, n in enumerate(g.nodes):
@@ -405,6 +484,50 @@ def _collapse_activations(g: ox.Graph):
             if k is not None and n.inputs[0] in g.nodes[k].inputs:
                 skip |= {i, k}
                 act_of[g.nodes[k].outputs[0]] = (n.inputs[0], mf.ACT_SWISH, (i, k))
+        elif n.op_type == "HardSigmoid" and i not in front_nodes and n.inputs and n.outputs and _hsig_is_torch(n):
+            # HardSigmoid(x) * x, PyTorch's hard swish below opset 14: folded like Sigmoid * x.  (Without that Mul the node stays in
+            # the walk: a squeeze-excite gate or a refusal; any other alpha / beta is refused there by name.)
+            k = sole_consumer(n.outputs[0], "Mul")
+            if k is not None and n.outputs[0] not in graph_out and n.inputs[0] in g.nodes[k].inputs and g.nodes[k].outputs:
+                skip |= {i, k}
+                act_of[g.nodes[k].outputs[0]] = (n.inputs[0], mf.ACT_HSWISH, (i, k))
+        elif n.op_type == "Add" and len(n.inputs) == 2 and n.outputs and i not in skip and i not in front_nodes:
+            # The decomposed hard swish of tf2onnx and older exporters: Add(x, 3) -> Clip(0, 6) -> Mul(., x) and Mul(., 1/6) or
+            # Div(., 6), the last two in either order; without the Mul(., x) it is the hard sigmoid (legal on a pooled tensor only:
+            # set_act).  Every inner tensor has exactly one reader and is no graph output.  A chain that matches only in part is left
+            # alone: its nodes meet the walk's own rules (Clip alone is ReLU6, a bare Add a residual).
+            x = None
+            for side in range(2):
+                if _fscalar(g, n.inputs[side]) == 3.0 and n.inputs[1 - side] not in g.initializers:
+                    x = n.inputs[1 - side]
+            k = sole_consumer(n.outputs[0], "Clip")
+            if x is None or n.outputs[0] in graph_out or k is None or not g.nodes[k].outputs or not _clip_is_relu6(g, g.nodes[k]):
+                continue
+            own, cur, has_scale, has_x = [i, k], g.nodes[k].outputs[0], False, False
+            for _ in range(2):
+                c = cons.get(cur, [])
+                if cur in graph_out or len(c) != 1:
+                    break
+                q = c[0]
+                nq = g.nodes[q]
+                if nq.op_type not in ("Mul", "Div") or len(nq.inputs) != 2 or not nq.outputs or q in skip:
+                    break
+                other = nq.inputs[1] if nq.inputs[0] == cur else nq.inputs[0]
+                cv = _fscalar(g, other)
+                if not has_scale and cv is not None and (
+                        (nq.op_type == "Mul" and (cv == SIXTH_F16 if _scalar_is_f16(g, other) else abs(cv - 1.0 / 6.0) <= 1e-6)) or
+                        (nq.op_type == "Div" and nq.inputs[0] == cur and cv == 6.0)):
+                    has_scale = True
+                elif not has_x and nq.op_type == "Mul" and other == x:
+                    has_x = True
+                else:
+                    break
+                own.append(q)
+                cur = nq.outputs[0]
+            if not has_scale:
+                continue
+            skip |= set(own)
+            act_of[cur] = (x, mf.ACT_HSWISH if has_x else mf.ACT_HSIGMOID, tuple(own))
     return skip, act_of
 
 
@@ -522,7 +645,7 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
     layers: List[mf.Layer] = []
     # name -> (tensor index, C, H, W) ; H = W = 0 for flattened [N, C]
     tmap: Dict[str, Tuple[int, int, int, int]] = {spec: (0, len(frontend.branches), frontend.spec_h, frontend.spec_w)}
-    skip, act_of = _collapse_activations(g)
+    skip, act_of = _collapse_activations(g, front_nodes)
     out_act, emb_tensor, emb_dim = mf.OUT_NONE, 0, 0
     graph_out = {o.name for o in g.outputs}
 
@@ -533,6 +656,9 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         t = tmap.get(name_in)
         if t is None:
             raise ConvertError(f"activation on unknown tensor {name_in!r}")
+        # (the hard sigmoid stands where the Sigmoid inside the graph may: on a pooled [N, C, 1, 1] tensor -- the gate's second 1x1, a dense layer)
+        if act == mf.ACT_HSIGMOID and t[2] * t[3] != 1:
+            raise ConvertError("HardSigmoid inside the graph that is neither HardSigmoid * x nor a squeeze-excite gate")
         L = layers[t[0] - 1] if t[0] > 0 else None
         if L is not None and L.op == mf.OP_POOL:
             raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a MaxPool / AveragePool "
@@ -794,6 +920,15 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             else:
                 act = {"Relu": mf.ACT_RELU, "Gelu": mf.ACT_GELU_ERF, "Clip": mf.ACT_RELU6}[op]
             set_act(n.inputs[0], n.outputs[0], act, (i,))
+        elif op == "HardSwish":
+            set_act(n.inputs[0], n.outputs[0], mf.ACT_HSWISH, (i,))
+        elif op == "HardSigmoid":
+            # (HardSigmoid * x was folded above; what arrives here is a gate -- set_act holds it to a pooled tensor -- or a refusal)
+            if not _hsig_is_torch(n):
+                raise ConvertError("HardSigmoid %r with alpha = %g, beta = %g: only alpha = 1/6, beta = 0.5 (PyTorch's hard sigmoid) is "
+                                   "supported; the ONNX default alpha = 0.2 is Keras's hard sigmoid, a different function that no kernel "
+                                   "here computes" % ((n.name,) + _hsig_params(n)))
+            set_act(n.inputs[0], n.outputs[0], mf.ACT_HSIGMOID, (i,))
         elif op == "Add":
             a, b = (tmap.get(x) for x in n.inputs)
             if a is None or b is None:

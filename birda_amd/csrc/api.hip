@@ -1848,7 +1848,13 @@ int bh_plan_fused_blocks(const char *model_path, uint32_t flags, int32_t *cfgs, 
     return (int)n;
 } catch (...) { return on_exception(); }
 
+// (the first three families only: callers derive n_base as a third of what this names -- birda_hip.h)
 int bh_mb_config_name(int32_t cfg, char *out, size_t cap) {
+    const int n3 = bh::mb_config_count() / bh::mb_config_families() * 3;
+    return cfg >= 0 && cfg < n3 ? bh::mb_config_name(cfg, out, cap) : 0;
+}
+int bh_mb_config_families(void) { return bh::mb_config_families(); }
+int bh_mb_config_name_ex(int32_t cfg, char *out, size_t cap) {
     return bh::mb_config_name(cfg, out, cap);
 }
 

@@ -81,8 +81,8 @@ struct DebugLaunch {
 };
 
 const char *act_name(int act) {
-    static const char *const names[] = {"none", "relu", "relu6", "swish", "gelu", "gelu_tanh", "sigmoid"};
-    return act >= 0 && act <= bh::ACT_SIGMOID ? names[act] : "?";
+    static const char *const names[] = {"none", "relu", "relu6", "swish", "gelu", "gelu_tanh", "sigmoid", "hswish", "hsigmoid"};
+    return act >= 0 && act <= bh::ACT_LAST ? names[act] : "?";
 }
 
 // A shape array's in_h, in_w, out_h, out_w, channels, kh, kw, sh, sw, pad_t, pad_l as the launchers' ConvParams.  The GEMM and
@@ -130,8 +130,8 @@ int mb_debug_plan(const int32_t *shape, int force_cfg, int variant, bh::MbDesc &
     if (rec) rec[0] = -1;
     if (name && name_cap) name[0] = 0;
     if (!shape || variant < 0 || variant > 2) return fail(BH_ERR_INVALID, "debug_mbconv: bad arguments");
-    const int nbase = bh::mb_config_count() / 3;   // (three activation copies of one list: kernels_mbconv.hip)
-    for (int k = 0; rec && force_cfg >= 0 && force_cfg < nbase && k < 3; k++) {   // the row's own facts, whatever becomes of the shape
+    const int nfam = bh::mb_config_families(), nbase = bh::mb_config_count() / nfam;   // (the activation copies of one list: kernels_mbconv.hip)
+    for (int k = 0; rec && force_cfg >= 0 && force_cfg < nbase && k < nfam; k++) {   // the row's own facts, whatever becomes of the shape
         int th = 0, has_se = 0, act = -1;
         if (bh::mb_config_row(force_cfg + k * nbase, &th, &has_se, nullptr, &act) && act == shape[11]) { rec[6] = has_se; rec[7] = th; }
     }
@@ -216,7 +216,7 @@ int bh_debug_gated_gemm(int device, const float *A, const float *gate, const flo
 // (after != 0: bh_debug_conv_gemm_after, include/birda_hip_resact_debug.h -- the activation after the residual add)
 static int debug_conv_gemm(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
                            const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap, int after) {
-    if (!X || !W || !bias || !C || !shape || !n_seg || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
+    if (!X || !W || !bias || !C || !shape || !n_seg || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_LAST)
         return fail(BH_ERR_INVALID, "debug_conv_gemm: bad arguments");
     if (after && !R) return fail(BH_ERR_INVALID, "debug_conv_gemm_after: the residual R is required");
     const bh::ConvParams p = shape_params(shape, false, 4, 0, act, after ? 1 : 0);
@@ -258,7 +258,7 @@ int bh_debug_conv_gemm_after(int device, const float *X, const float *W, const f
 // w16_planes), through the launchers a forward pass takes (include/birda_hip_gconv_debug.h).
 int bh_debug_gconv(int device, const float *X, const float *W, const float *bias, float *C, size_t n_seg, const int32_t *shape, int act,
                    int terms, char *kernel, size_t kernel_cap) try {
-    if (!X || !W || !bias || !C || !shape || !n_seg || terms < 0 || terms > 3 || act < 0 || act > bh::ACT_SIGMOID)
+    if (!X || !W || !bias || !C || !shape || !n_seg || terms < 0 || terms > 3 || act < 0 || act > bh::ACT_LAST)
         return fail(BH_ERR_INVALID, "debug_gconv: bad arguments");
     const bh::ConvParams p = shape_params(shape, false, 4, 0, act, 0);
     const int G = shape[12];
@@ -297,7 +297,7 @@ int bh_debug_gconv(int device, const float *X, const float *W, const float *bias
 static int debug_layer_gemm(int device, const float *A, const float *W, const float *bias, const float *R, float *C, size_t M, size_t K,
                             size_t N, size_t pool_rows, int act, int terms, char *kernel, size_t kernel_cap, int after) {
     if (after && (!R || pool_rows)) return fail(BH_ERR_INVALID, "debug_layer_gemm_after: the residual R is required, and no head pool");
-    if (!A || !W || !bias || !C || !M || !K || !N || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_SIGMOID)
+    if (!A || !W || !bias || !C || !M || !K || !N || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_LAST)
         return fail(BH_ERR_INVALID, "debug_layer_gemm: bad arguments");
     if (M * K > (size_t)INT32_MAX || M * N > (size_t)INT32_MAX || K * N > (size_t)INT32_MAX)
         return fail(BH_ERR_INVALID, "debug_layer_gemm: operands past 2^31 elements");
@@ -362,7 +362,7 @@ int bh_debug_pool(int device, const float *X, float *Y, size_t n_seg, const int3
 int bh_debug_se_gate(int device, const float *part, size_t n_seg, size_t tiles, size_t P, size_t C, size_t Cr, const float *W1, const float *b1,
                      int act1, const float *W2, const float *b2, int act2, int form, float *gate, char *kernel, size_t kernel_cap) try {
     if (!part || !W1 || !b1 || !W2 || !b2 || !gate || !n_seg || !tiles || !P || !C || !Cr || form < -1 || form > 2 || act1 < 0 ||
-        act1 > bh::ACT_SIGMOID || act2 < 0 || act2 > bh::ACT_SIGMOID)
+        act1 > bh::ACT_LAST || act2 < 0 || act2 > bh::ACT_LAST)
         return fail(BH_ERR_INVALID, "debug_se_gate: bad arguments");
     if (C > (1u << 24) || Cr > (1u << 24) || tiles > (1u << 24) || P > (size_t)INT32_MAX || n_seg > (size_t)INT32_MAX ||
         tiles * C > (size_t)INT32_MAX || n_seg * (tiles * C) > (size_t)INT32_MAX)
@@ -401,7 +401,7 @@ int bh_debug_se_gate(int device, const float *part, size_t n_seg, size_t tiles, 
 // caller's, through the launcher SliceRun::layer takes, refusing what create refuses for the op (include/birda_hip_gate_debug.h).
 int bh_debug_plain_layer(int device, int op, const float *X, const float *W, const float *bias, const float *gate, float *Y, size_t n_seg,
                          const int32_t *shape, int act, char *kernel, size_t kernel_cap) try {
-    if (!X || !Y || !shape || !n_seg || n_seg > (size_t)INT32_MAX || act < 0 || act > bh::ACT_SIGMOID)
+    if (!X || !Y || !shape || !n_seg || n_seg > (size_t)INT32_MAX || act < 0 || act > bh::ACT_LAST)
         return fail(BH_ERR_INVALID, "debug_plain_layer: bad arguments");
     const bool conv = op == bh::OP_CONV, dw = op == bh::OP_DWCONV, gap = op == bh::OP_GAP, scale = op == bh::OP_SCALE;
     if (!conv && !dw && !gap && !scale) return fail(BH_ERR_INVALID, "debug_plain_layer: op %d is not one of the plain layers", op);

@@ -59,7 +59,8 @@ inline int device_cu_count() {
     return n;
 }
 
-enum Act : int { ACT_NONE = 0, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SIGMOID };
+enum Act : int { ACT_NONE = 0, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SIGMOID, ACT_HSWISH = 7, ACT_HSIGMOID = 8 };
+constexpr int ACT_LAST = ACT_HSIGMOID;   // the largest code a model file or a diagnostic may carry
 
 constexpr int MAX_BRANCHES = 4;
 
@@ -283,6 +284,21 @@ __device__ __forceinline__ void bh_split8(const float (&v)[8], bh_f16x8 &hi, bh_
     }
 }
 
+// MobileNetV3's two activations (ACT_HSWISH, ACT_HSIGMOID), both through the gate g(v) = clamp(v / 6 + 1/2, 0, 1):
+//     hsigmoid(v) = g(v),    hswish(v) = v g(v) = v min(max(v + 3, 0), 6) / 6.
+// One FMA (1/6 rounded to f32: 3e-8 relative), the clamp (exact), and for hswish one multiply: three f32 roundings, no transcendental.
+// hswish is a product with v, so a NaN passes whatever the clamp returns for it, hswish(+inf) = +inf, and the before-the-add form
+// ends in (-inf) 0 = NaN at -inf as swish's fast form does (the AFTER form selects the two limits: bh_act_limits).  hsigmoid has no
+// such product: its clamp is two comparisons whose false branch keeps a NaN (bh_relu6_keep_nan's style), NOT fminf / fmaxf /
+// v_med3_f32, which return the other operand -- a NaN channel sum must leave a squeeze-excite gate as a NaN, or the segment's f16
+// overflow never reaches the logits (BH_FLAG_AUTO's re-run and BH_ERR_NONFINITE see it there).
+#define BH_SIXTH 0.16666667163372040f
+__device__ __forceinline__ float bh_hsigmoid_keep_nan(float v) {
+    const float t = __builtin_fmaf(v, BH_SIXTH, 0.5f);
+    return t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+}
+__device__ __forceinline__ float bh_hswish_slow(float v) { return v * fminf(fmaxf(__builtin_fmaf(v, BH_SIXTH, 0.5f), 0.f), 1.f); }
+
 __device__ __forceinline__ float act_apply_slow(float v, int act) {
     switch (act) {
     case ACT_RELU: return fmaxf(v, 0.f);
@@ -291,6 +307,8 @@ __device__ __forceinline__ float act_apply_slow(float v, int act) {
     case ACT_GELU_ERF: return gelu_erf_fast(v);
     case ACT_GELU_TANH: return 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v)));
     case ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
+    case ACT_HSWISH: return bh_hswish_slow(v);
+    case ACT_HSIGMOID: return bh_hsigmoid_keep_nan(v);
     default: return v;
     }
 }
@@ -306,6 +324,9 @@ __device__ __forceinline__ float bh_act(float v) {
     else if constexpr (ACT == ACT_RELU) return bh_relu1(v);
     else if constexpr (ACT == ACT_RELU6) return __builtin_amdgcn_fmed3f(v, 0.0f, 6.0f);
     else if constexpr (ACT == ACT_SWISH) return v * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v));
+    // hard swish: fma, med3, multiply -- hipcc folds the med3 into the FMA: v_fma_f32 ... clamp + v_mul_f32 -- (the same three roundings as
+    // bh_hswish_slow, value for value on finite arguments)
+    else if constexpr (ACT == ACT_HSWISH) return v * __builtin_amdgcn_fmed3f(__builtin_fmaf(v, BH_SIXTH, 0.5f), 0.0f, 1.0f);
     else return act_apply_slow(v, ACT);
 }
 template <int ACT>
@@ -319,7 +340,8 @@ __device__ __forceinline__ void bh_act4(bh_f32x2 &v0, bh_f32x2 &v1) {
     else { v0 = bh_act2<ACT>(v0); v1 = bh_act2<ACT>(v1); }
 }
 // the activations the MFMA epilogues are instantiated for (layers with any other one run on the f32 layer kernels)
-inline bool act_is_templated(int act) { return act == ACT_GELU_ERF || act == ACT_SWISH || act == ACT_RELU6; }
+// (ACT_HSIGMOID, a gate's activation, is never templated: the run-time kernels only)
+inline bool act_is_templated(int act) { return act == ACT_GELU_ERF || act == ACT_SWISH || act == ACT_RELU6 || act == ACT_HSWISH; }
 
 // The activation AFTER the residual add, act(conv + b + R) (model.hpp RES_ACT_AFTER: the end of a ResNet block).  Its argument
 // holds whatever the residual tensor held, so a NaN must come out as NaN and +inf under ReLU as +inf (BH_FLAG_AUTO and
@@ -351,10 +373,12 @@ __device__ __forceinline__ float act_apply_pos(float v, int act, bool after) {
     case ACT_GELU_ERF: { const float r = gelu_erf_fast(v); return after ? bh_act_limits(v, r) : r; }
     case ACT_GELU_TANH: { const float r = 0.5f * v * (1.0f + tanhf(0.7978845608028654f * (v + 0.044715f * v * v * v))); return after ? bh_act_limits(v, r) : r; }
     case ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
+    case ACT_HSWISH: { const float r = bh_hswish_slow(v); return after ? bh_act_limits(v, r) : r; }
+    case ACT_HSIGMOID: return bh_hsigmoid_keep_nan(v);
     default: return v;
     }
 }
-// the activations the split-f16 epilogues are instantiated for in the after-the-add form: the templated three and ReLU, which
+// the activations the split-f16 epilogues are instantiated for in the after-the-add form: the templated four and ReLU, which
 // ResNets use (ReLU BEFORE the add is not a templated activation: act_is_templated, and every unflagged layer, stay as they were)
 inline bool act_is_templated_after(int act) { return act == ACT_RELU || act_is_templated(act); }
 
@@ -617,6 +641,7 @@ struct MbDesc {
 // Y[i] = (partial[0][i] + partial[1][i] + ...) * unscale, parts in index order
 void launch_mb_reduce_partials(const float *partial, float *Y, int ksplit, size_t count, float unscale, hipStream_t s);
 int mb_config_count();
+int mb_config_families();   // activation copies of the list (4: GELU, swish, ReLU6, hard swish); mb_config_count() = families x n_base
 int mb_config_name(int ci, char *out, size_t cap);
 // picks the instantiation (force_cfg >= 0: that entry or fail) and fills the derived fields
 bool mb_plan(MbDesc &d, int force_cfg);

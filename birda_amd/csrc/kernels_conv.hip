@@ -1067,6 +1067,7 @@ const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, 
     case ACT_GELU_ERF: BH_G16(T, ACT_GELU_ERF, "GELU", false, ""); break; \
     case ACT_SWISH: BH_G16(T, ACT_SWISH, "SWISH", false, ""); break; \
     case ACT_RELU6: BH_G16(T, ACT_RELU6, "RELU6", false, ""); break; \
+    case ACT_HSWISH: BH_G16(T, ACT_HSWISH, "HSWISH", false, ""); break; \
     default: BH_G16(T, ACT_NONE, "NONE", false, ""); break;          \
     }
 #define BH_G16AA(T)                                                  \
@@ -1074,6 +1075,7 @@ const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, 
     case ACT_GELU_ERF: BH_G16(T, ACT_GELU_ERF, "GELU", true, ",AFTER"); break; \
     case ACT_SWISH: BH_G16(T, ACT_SWISH, "SWISH", true, ",AFTER"); break; \
     case ACT_RELU6: BH_G16(T, ACT_RELU6, "RELU6", true, ",AFTER"); break; \
+    case ACT_HSWISH: BH_G16(T, ACT_HSWISH, "HSWISH", true, ",AFTER"); break; \
     default: BH_G16(T, ACT_RELU, "RELU", true, ",AFTER"); break;     \
     }
     if (res_after) { if (terms == 3) { BH_G16AA(3) } else if (terms == 2) { BH_G16AA(2) } else { BH_G16AA(1) } }
@@ -1241,6 +1243,7 @@ const char *launch_head_gap16(const float *A, const void *Wf, const float *bias,
     switch (act) {                                                   \
     case ACT_SWISH: BH_HG(PTV, SWV, T, ACT_SWISH, "SWISH"); break;   \
     case ACT_RELU6: BH_HG(PTV, SWV, T, ACT_RELU6, "RELU6"); break;   \
+    case ACT_HSWISH: BH_HG(PTV, SWV, T, ACT_HSWISH, "HSWISH"); break;   \
     default: BH_HG(PTV, SWV, T, ACT_GELU_ERF, "GELU"); break;        \
     }
     if (pt <= 3) { if (terms == 3) { BH_HGA(3, 2, 3) } else if (terms == 2) { BH_HGA(3, 2, 2) } else { BH_HGA(3, 2, 1) } }
@@ -1674,6 +1677,7 @@ const char *launch_conv_gemm16(const float *X, const void *Wf, const float *bias
     case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF, "GELU", false, ""); break; \
     case ACT_SWISH: BH_CG16(T, ACT_SWISH, "SWISH", false, ""); break; \
     case ACT_RELU6: BH_CG16(T, ACT_RELU6, "RELU6", false, ""); break; \
+    case ACT_HSWISH: BH_CG16(T, ACT_HSWISH, "HSWISH", false, ""); break; \
     default: BH_CG16(T, ACT_NONE, "NONE", false, ""); break;         \
     }
 #define BH_CG16AA(T)                                                 \
@@ -1681,6 +1685,7 @@ const char *launch_conv_gemm16(const float *X, const void *Wf, const float *bias
     case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF, "GELU", true, ",AFTER"); break; \
     case ACT_SWISH: BH_CG16(T, ACT_SWISH, "SWISH", true, ",AFTER"); break; \
     case ACT_RELU6: BH_CG16(T, ACT_RELU6, "RELU6", true, ",AFTER"); break; \
+    case ACT_HSWISH: BH_CG16(T, ACT_HSWISH, "HSWISH", true, ",AFTER"); break; \
     default: BH_CG16(T, ACT_RELU, "RELU", true, ",AFTER"); break;    \
     }
     if (p.res_after) { if (terms == 3) { BH_CG16AA(3) } else if (terms == 2) { BH_CG16AA(2) } else { BH_CG16AA(1) } }

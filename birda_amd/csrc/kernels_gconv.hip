@@ -201,7 +201,7 @@ bool gconv_supports(const ConvParams &p, int groups) {
     if (p.in_layout != 0 || groups < 2 || p.cin <= 0 || p.cout <= 0 || p.cin % groups || p.cout % groups) return false;
     const int gi = p.cin / groups, go = p.cout / groups;
     if (gi % 4 || go % 4 || p.kh < 1 || p.kh > 7 || p.kw < 1 || p.kw > 7 || (p.sh != 1 && p.sh != 2) || (p.sw != 1 && p.sw != 2) ||
-        p.pad_t < 0 || p.pad_l < 0 || p.act < 0 || p.act > ACT_SIGMOID || p.res_after) return false;
+        p.pad_t < 0 || p.pad_l < 0 || p.act < 0 || p.act > ACT_LAST || p.res_after) return false;
     // the multiply-high divisions of the gather are exact while (K + a step) x span stays below 2^32
     const uint64_t span = (uint64_t)gi * (uint64_t)std::min(groups, 15 / go + 2);
     return ((uint64_t)p.kh * p.kw * span + 32) * span < (1ull << 32);

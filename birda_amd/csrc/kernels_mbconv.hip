@@ -1,5 +1,5 @@
 // Planner of the fused inverted-residual (MBConv) blocks: picks, per block, one of the tile configurations of mbconv_cfgs.inc
-// (the kernel itself is mbconv_kernel.hpp, instantiated per activation in kernels_mbconv_gelu.hip / _swish.hip / _relu6.hip).
+// (the kernel itself is mbconv_kernel.hpp, instantiated per activation in kernels_mbconv_gelu.hip / _swish.hip / _relu6.hip / _hswish.hip).
 #include <algorithm>
 #include <vector>
 #include <cstdio>
@@ -14,7 +14,7 @@ namespace {
 
 // The list (mbconv_cfgs.inc: 115 tile configurations, indices as documented there) is instantiated once per activation:
 // entry ci + k * kNBase is configuration ci with the k-th activation of kActs.
-constexpr int kActs[] = {ACT_GELU_ERF, ACT_SWISH, ACT_RELU6};
+constexpr int kActs[] = {ACT_GELU_ERF, ACT_SWISH, ACT_RELU6, ACT_HSWISH};   // (appended: a configuration's index base + k n_base is ABI)
 constexpr int kNActs = (int)(sizeof(kActs) / sizeof(kActs[0]));
 struct CfgTables {
     std::vector<MbCfg> t[kNActs];     // (each activation's list, put together from its three translation units)
@@ -23,14 +23,16 @@ struct CfgTables {
         typedef const MbCfg *(*Part)(int *);
         static const Part parts[kNActs][3] = {{mb_table_gelu_p0, mb_table_gelu_p1, mb_table_gelu_p2},
                                               {mb_table_swish_p0, mb_table_swish_p1, mb_table_swish_p2},
-                                              {mb_table_relu6_p0, mb_table_relu6_p1, mb_table_relu6_p2}};
+                                              {mb_table_relu6_p0, mb_table_relu6_p1, mb_table_relu6_p2},
+                                              {mb_table_hswish_p0, mb_table_hswish_p1, mb_table_hswish_p2}};
         for (int a = 0; a < kNActs; a++)
             for (int k = 0; k < 3; k++) {
                 int n = 0;
                 const MbCfg *p = parts[a][k](&n);
                 t[a].insert(t[a].end(), p, p + n);
             }
-        n_base = (t[0].size() == t[1].size() && t[1].size() == t[2].size()) ? (int)t[0].size() : 0;   // the three copies are the same list
+        n_base = (int)t[0].size();   // the copies are the same list
+        for (int a = 1; a < kNActs; a++) if (t[a].size() != t[0].size()) n_base = 0;
     }
     const MbCfg &operator[](int ci) const { return t[ci / n_base][ci % n_base]; }
 };
@@ -154,6 +156,7 @@ double mb_try(MbDesc &d, int ci, bool relax_kg = false) {
 }  // namespace
 
 int mb_config_count() { return kNCfgs; }
+int mb_config_families() { return kNActs; }
 
 // the instantiation's template arguments as rocprofv3 prints them ("mbconv_kernel<...>")
 int mb_config_name(int ci, char *out, size_t cap) {

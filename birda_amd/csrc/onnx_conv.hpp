@@ -6,7 +6,8 @@
 //     second witness: tests/test_onnx_native.py holds the two to the same layer table and the same weights, bit for bit):
 //     Conv (1x1 -> pointwise, group == channels -> depthwise, any other group count -> OP_GCONV, else full), BatchNormalization folded into the convolution in
 //     front of it, the activation spellings exporters emit (Relu, Clip(0, 6), Sigmoid x Mul = swish, Div / Erf / Add / Mul / Mul
-//     = GELU, the Gelu operator), residual Add folded into its 1x1 convolution, MaxPool / AveragePool (floor mode; OP_POOL),
+//     = GELU, the Gelu operator; HardSwish, HardSigmoid(1/6, 1/2) x Mul and Add 3 / Clip(0, 6) / Mul / Mul 1/6 = hard swish; HardSigmoid(1/6,
+//     1/2) or that chain without its Mul(., x) on a pooled tensor = the hard-sigmoid gate), residual Add folded into its 1x1 convolution, MaxPool / AveragePool (floor mode; OP_POOL),
 //     GlobalAveragePool / ReduceMean over H, W, Concat / Split / Slice over the channels and the Reshape -> Transpose -> Reshape channel
 //     shuffle (OP_CONCAT: a Split / Slice output that only Concat nodes read is a view folded into their windows),
 //     squeeze-excite gates (pool -> 1x1 -> 1x1 -> Sigmoid -> Mul), Flatten / Reshape / Squeeze / Identity / Dropout after the
@@ -284,6 +285,27 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     // expected value (sqrt 2 -> 1.4140625, 1 / sqrt 2 -> 0.70703125; no wider window), and the exact GELU runs: DESIGN section 5.
     const double SQRT2 = 1.4142135623730951;
     const float SQRT2_F16 = 1.4140625f, RSQRT2_F16 = 0.70703125f;
+    // The hard sigmoid the kernels compute is PyTorch's, min(max(x / 6 + 1/2, 0), 1): alpha within 1e-6 of 1/6 and beta = 0.5.  (The
+    // ONNX defaults, alpha = 0.2 and beta = 0.5, are Keras's hard sigmoid: another function, refused by name in the walk.)  The
+    // decomposed spelling's 1/6 follows the rule above: held to 1e-6 from float32, the float16 rounding of 1/6 itself from float16.
+    const float SIXTH_F16 = 0.1666259765625f;
+    // a float32 / float16 scalar initializer, WITHOUT finit()'s note for the next refusal (init_refusal): the hard-swish chain below
+    // probes the operands of every Add, and an int64 constant it passes over must not turn up in an unrelated message later
+    auto probe_scalar = [&](const std::string &name, float &out, bool *from_f16 = nullptr) {
+        auto it = g.init.find(name);
+        if (it == g.init.end() || !it->second.is_float() || it->second.count != 1) return false;
+        out = it->second.at(0);
+        if (from_f16) *from_f16 = it->second.is_f16();
+        return true;
+    };
+    auto hsig_is_torch = [](const Node &n) { return std::fabs((double)n.getf("alpha", 0.2f) - 1.0 / 6.0) <= 1e-6 && n.getf("beta", 0.5f) == 0.5f; };
+    auto is_output = [&](const std::string &name) { return std::find(outputs.begin(), outputs.end(), name) != outputs.end(); };
+    auto clip_is_relu6 = [&](const Node &n) {
+        float lo = 0.f, hi = 0.f;
+        const bool has_lo = n.in.size() > 1 && !n.in[1].empty() ? probe_scalar(n.in[1], lo) : (n.a.count("min") ? (lo = n.getf("min", 0.f), true) : false);
+        const bool has_hi = n.in.size() > 2 && !n.in[2].empty() ? probe_scalar(n.in[2], hi) : (n.a.count("max") ? (hi = n.getf("max", 0.f), true) : false);
+        return has_lo && has_hi && lo == 0.0f && hi == 6.0f;
+    };
     for (size_t i = 0; i < nodes.size(); i++) {
         const Node &n = nodes[i];
         if (n.op == "Erf" && !n.in.empty() && !n.out.empty()) {
@@ -325,6 +347,53 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                     first_of_pattern[n.in[0]].push_back(Pattern{nodes[k].out[0], A_SWISH, {i, k}});
                 }
             }
+        } else if (n.op == "HardSigmoid" && !n.in.empty() && !n.out.empty() && !front.count(i) && hsig_is_torch(n)) {
+            // HardSigmoid(x) * x, PyTorch's hard swish below opset 14: folded like Sigmoid * x.  (Without that Mul the node stays in the
+            // walk: a squeeze-excite gate or a refusal; any other alpha / beta is refused there by name.)
+            size_t k;
+            if (sole_consumer(n.out[0], "Mul", k) && !is_output(n.out[0])) {
+                bool takes_x = false;
+                for (const auto &a : nodes[k].in) if (a == n.in[0]) takes_x = true;
+                if (takes_x && !nodes[k].out.empty()) {
+                    skip.insert({i, k});
+                    first_of_pattern[n.in[0]].push_back(Pattern{nodes[k].out[0], A_HSWISH, {i, k}});
+                }
+            }
+        } else if (n.op == "Add" && n.in.size() == 2 && !n.out.empty() && !skip.count(i) && !front.count(i)) {
+            // The decomposed hard swish of tf2onnx and older exporters: Add(x, 3) -> Clip(0, 6) -> Mul(., x) and Mul(., 1/6) or
+            // Div(., 6), the last two in either order; without the Mul(., x) it is the hard sigmoid (legal on a pooled tensor only:
+            // set_act).  Every inner tensor has exactly one reader and is no graph output.  A chain that matches only in part is left
+            // alone: its nodes meet the walk's own rules (Clip alone is ReLU6, a bare Add a residual).
+            std::string x;
+            for (int side = 0; side < 2; side++) {
+                float c;
+                if (probe_scalar(n.in[side], c) && c == 3.0f && g.init.find(n.in[1 - side]) == g.init.end()) x = n.in[1 - side];
+            }
+            size_t k;
+            if (x.empty() || is_output(n.out[0]) || !sole_consumer(n.out[0], "Clip", k) || nodes[k].out.empty() || !clip_is_relu6(nodes[k])) continue;
+            std::vector<size_t> own{i, k};
+            std::string cur = nodes[k].out[0];
+            bool has_scale = false, has_x = false;
+            for (int step = 0; step < 2; step++) {
+                auto it = cons.find(cur);
+                if (is_output(cur) || it == cons.end() || it->second.size() != 1) break;
+                const size_t q = it->second[0];
+                const Node &nq = nodes[q];
+                if ((nq.op != "Mul" && nq.op != "Div") || nq.in.size() != 2 || nq.out.empty() || skip.count(q)) break;
+                const std::string &other = nq.in[0] == cur ? nq.in[1] : nq.in[0];
+                float c;
+                bool c16 = false;
+                const bool is_const = probe_scalar(other, c, &c16);
+                if (!has_scale && is_const && ((nq.op == "Mul" && (c16 ? c == SIXTH_F16 : std::fabs((double)c - 1.0 / 6.0) <= 1e-6)) ||
+                                               (nq.op == "Div" && nq.in[0] == cur && c == 6.0f))) has_scale = true;
+                else if (!has_x && nq.op == "Mul" && other == x) has_x = true;
+                else break;
+                own.push_back(q);
+                cur = nq.out[0];
+            }
+            if (!has_scale) continue;
+            for (size_t q : own) skip.insert(q);
+            first_of_pattern[x].push_back(Pattern{cur, has_x ? A_HSWISH : A_HSIGMOID, own});
         }
     }
 
@@ -392,6 +461,8 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     auto set_act = [&](const std::string &name_in, const std::string &name_out, uint32_t act, const std::vector<size_t> &own) {
         T t;
         if (!find(name_in, t)) return fail("activation on unknown tensor '" + name_in + "'");
+        // (the hard sigmoid stands where the Sigmoid inside the graph may: on a pooled [N, C, 1, 1] tensor -- the gate's second 1x1, a dense layer)
+        if (act == A_HSIGMOID && (uint64_t)t.h * t.w != 1) return fail("HardSigmoid inside the graph that is neither HardSigmoid * x nor a squeeze-excite gate");
         if (t.idx != 0 && layers[t.idx - 1].op == OP_POOL)
             return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a MaxPool / AveragePool (a pool layer carries no activation)");
         if (t.idx != 0 && layers[t.idx - 1].op == OP_CONCAT)
@@ -574,6 +645,16 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             }
             if (op == "Gelu") { const std::string ap = n.gets("approximate", "none"); if (ap != "none") act = A_GELU_TANH; }
             if (!set_act(n.in[0], n.out[0], act, {i})) return false;
+        } else if (op == "HardSwish") {
+            if (!set_act(n.in[0], n.out[0], A_HSWISH, {i})) return false;
+        } else if (op == "HardSigmoid") {
+            // (HardSigmoid * x was folded above; what arrives here is a gate -- set_act holds it to a pooled tensor -- or a refusal)
+            if (!hsig_is_torch(n)) {
+                char v[96];
+                snprintf(v, sizeof v, "alpha = %g, beta = %g", (double)n.getf("alpha", 0.2f), (double)n.getf("beta", 0.5f));
+                return fail("HardSigmoid '" + n.name + "' with " + v + ": only alpha = 1/6, beta = 0.5 (PyTorch's hard sigmoid) is supported; the ONNX default alpha = 0.2 is Keras's hard sigmoid, a different function that no kernel here computes");
+            }
+            if (!set_act(n.in[0], n.out[0], A_HSIGMOID, {i})) return false;
         } else if (op == "Add") {
             T a, b;
             if (n.in.size() != 2 || !find(n.in[0], a) || !find(n.in[1], b)) return fail("Add of '" + n.in[0] + "': operands are not both activations on the path");

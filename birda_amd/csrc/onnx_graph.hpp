@@ -26,7 +26,7 @@ using onnxd::Span;
 using onnxd::str;
 
 // activation / output-activation codes of the container (kernels.hpp Act, modelfile.py)
-enum : uint32_t { A_NONE = 0, A_RELU = 1, A_RELU6 = 2, A_SWISH = 3, A_GELU_ERF = 4, A_GELU_TANH = 5, A_SIGMOID = 6 };
+enum : uint32_t { A_NONE = 0, A_RELU = 1, A_RELU6 = 2, A_SWISH = 3, A_GELU_ERF = 4, A_GELU_TANH = 5, A_SIGMOID = 6, A_HSWISH = 7, A_HSIGMOID = 8 };
 enum : uint32_t { O_NONE = 0, O_SIGMOID = 1, O_SOFTMAX = 2 };
 
 struct Attr {

@@ -44,7 +44,7 @@ POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2  # AVG: mean over the in-image taps (
 # OP_CONV (NHWC), OP_PWCONV, OP_DENSE: Layer.reserved is where `act` stands relative to the residual -- 0: act(conv + b) + R (every
 # file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block
 RES_ACT_AFTER = 1
-ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SIGMOID = range(7)
+ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SIGMOID, ACT_HSWISH, ACT_HSIGMOID = range(9)
 OUT_NONE, OUT_SIGMOID, OUT_SOFTMAX = 0, 1, 2
 NO_TENSOR = 0xFFFFFFFF
 

@@ -225,6 +225,9 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     'branchy_plan' (plan = random_branchy_plan(seed)) builds that plan's Fire / Inception / ShuffleNet / CSP blocks around channel
     concatenations, windows and shuffles (mf.OP_CONCAT): _build_branchy_plan.  'shufflenet_audio' (ShuffleNetV2 x1.5 on the v2.4
     front-end, for timing the concat layers: _build_shufflenet_audio).
+    'mnv3_plan' (plan = random_mnv3_plan(seed)) builds that plan's MobileNetV3-style blocks -- hard swish (mf.ACT_HSWISH) between the
+    convolutions, hard-sigmoid (mf.ACT_HSIGMOID) gates: _build_mnv3_plan.  'mobilenetv3_audio' (MobileNetV3-Large's layout, ReLU blocks
+    included, on the mini front-end: _build_mobilenetv3_audio).
     A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
@@ -244,6 +247,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
         return _build_branchy_plan(plan, seed)
     if kind == "shufflenet_audio":
         return _build_shufflenet_audio(seed, n_classes)
+    if kind == "mnv3_plan":
+        return _build_mnv3_plan(plan, seed)
+    if kind == "mobilenetv3_audio":
+        return _build_mobilenetv3_audio(seed, n_classes)
     rng = np.random.default_rng(seed)
     b = _Builder(rng)
     act_override, act, hidden = act, mf.ACT_GELU_ERF, 0
@@ -964,6 +971,95 @@ def _build_shufflenet_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = 
     ncls = n_classes or 6522
     b.dense(t, 1024, ncls, gain=1.5)
     return _finish(b, branches, sr, n, ncls, 1024, emb, mf.OUT_SIGMOID)
+
+
+def _mnv3_block(b: _Builder, t, h, w, c, cexp, k, s, cout, act, se):
+    """One MobileNetV3 inverted-residual block behind tensor t [h][w][c] -> (tensor, h, w): 1x1 expand (c -> cexp, act; none where
+    cexp == c) -> depthwise k x k stride s (act) [-> gate: pool -> 1x1 (cexp -> cr, ReLU) -> 1x1 (cr -> cexp, hard sigmoid) -> scale,
+    cr = cexp / 4 rounded up to 8] -> 1x1 project (+ the input at stride 1 and equal widths)."""
+    tin = t
+    if cexp != c:
+        t = b.pwconv(t, h, w, c, cexp, act)
+    t, oh, ow = b.dwconv(t, h, w, cexp, k, s, act)
+    if se:
+        cr = -(-(cexp // 4) // 8) * 8
+        tg = b.gap(t, oh, ow, cexp)
+        tg = b.pwconv(tg, 1, 1, cexp, cr, mf.ACT_RELU)
+        tg = b.pwconv(tg, 1, 1, cr, cexp, mf.ACT_HSIGMOID)
+        t = b.scale(t, tg, oh, ow, cexp)
+    res = tin if (s == 1 and c == cout) else mf.NO_TENSOR
+    return b.pwconv(t, oh, ow, cexp, cout, mf.ACT_NONE, res, gain=0.5 if res != mf.NO_TENSOR else 1.0), oh, ow
+
+
+def _mnv3_frontend(b: _Builder):
+    """the mini front-end of _build_pool_plan: one branch, 512-sample frames at hop 100 of a quarter second (32 mels x 115 frames)"""
+    sr, n = 48000, 12000
+    br = mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23)
+    br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+    br.out_scale, br.out_shift = 0.8, -0.4
+    return sr, n, br
+
+
+def _mnv3_head(b: _Builder, t, h, w, c, head_c, hidden, ncls):
+    """MobileNetV3's head: 1x1 conv -> hard swish -> pool -> dense + hard swish -> dense"""
+    t = b.pwconv(t, h, w, c, head_c, mf.ACT_HSWISH)
+    t = emb = b.gap(t, h, w, head_c)
+    t = b.dense(t, head_c, hidden, act=mf.ACT_HSWISH, logits=False)
+    b.dense(t, hidden, ncls, gain=1.5)
+    return emb
+
+
+def random_mnv3_plan(seed: int) -> dict:
+    """A small seeded MobileNetV3-style stack on the mini front-end (32 mels x 115 frames): a 3x3 stride-2 hard-swish stem of 16 / 24
+    channels, three to five hard-swish inverted-residual blocks -- kernels 3 / 5, strides 1 / 2, expand ratios 1 .. 6, widths
+    multiples of 8 --, every second seed (the odd ones) with the hard-sigmoid gate in every block, and MobileNetV3's head.
+    Feed to build_model("mnv3_plan", plan=...).  plan["blocks"]: (expand, k, stride, cout)."""
+    rng = np.random.default_rng(0x3B33 + seed)
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+    stem = pick((16, 24))
+    blocks, c = [(1, 3, 1, stem)], stem           # (MobileNetV3 opens with an expand-ratio-1 block)
+    for _ in range(int(rng.integers(2, 5))):
+        s = pick((1, 1, 2))
+        cout = c if (s == 1 and rng.integers(0, 2)) else min(96, c + 8 * int(rng.integers(1, 4)))
+        blocks.append((pick((2, 3, 4, 6)), pick((3, 5)), s, cout))
+        c = cout
+    return {"stem": stem, "blocks": blocks, "se": bool(seed % 2), "head": 8 * int(rng.integers(8, 25)), "hidden": 8 * int(rng.integers(8, 17)),
+            "classes": int(rng.integers(20, 61)), "out_act": int(pick((mf.OUT_SIGMOID, mf.OUT_SOFTMAX)))}
+
+
+def _build_mnv3_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
+    b = _Builder(np.random.default_rng(seed))
+    sr, n, br = _mnv3_frontend(b)
+    c = int(plan["stem"])
+    t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, c, 3, 2, mf.ACT_HSWISH, in_layout=1)
+    for (e, k, s, cout) in plan["blocks"]:
+        t, h, w = _mnv3_block(b, t, h, w, c, c * e, k, s, cout, mf.ACT_HSWISH, bool(plan["se"]))
+        c = cout
+    emb = _mnv3_head(b, t, h, w, c, int(plan["head"]), int(plan["hidden"]), int(plan["classes"]))
+    return _finish(b, [br], sr, n, int(plan["classes"]), int(plan["head"]), emb, int(plan["out_act"]))
+
+
+# MobileNetV3-Large (Howard et al. 2019, table 1): (kernel, expanded width, cout, gate, hard swish, stride)
+_MNV3_LARGE = [(3, 16, 16, 0, 0, 1), (3, 64, 24, 0, 0, 2), (3, 72, 24, 0, 0, 1), (5, 72, 40, 1, 0, 2), (5, 120, 40, 1, 0, 1), (5, 120, 40, 1, 0, 1),
+               (3, 240, 80, 0, 1, 2), (3, 200, 80, 0, 1, 1), (3, 184, 80, 0, 1, 1), (3, 184, 80, 0, 1, 1), (3, 480, 112, 1, 1, 1),
+               (3, 672, 112, 1, 1, 1), (5, 672, 160, 1, 1, 2), (5, 960, 160, 1, 1, 1), (5, 960, 160, 1, 1, 1)]
+
+
+def _build_mobilenetv3_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) -> mf.Model:
+    """MobileNetV3-Large's published layout on the mini front-end: a 3x3 stride-2 hard-swish stem of 16 channels, the fifteen blocks
+    of _MNV3_LARGE -- ReLU in the first six, hard swish from the seventh on, hard-sigmoid gates where the paper has them --, the
+    960-wide 1x1 head, the pool, a 1280-wide hard-swish dense layer and the classes.  Seeded weights: the mixed route (ReLU blocks
+    layer by layer beside the hard-swish ones) on a model of the real shape, not an accurate one."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n, br = _mnv3_frontend(b)
+    c = 16
+    t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, c, 3, 2, mf.ACT_HSWISH, in_layout=1)
+    for (k, cexp, cout, se, hs, s) in _MNV3_LARGE:
+        t, h, w = _mnv3_block(b, t, h, w, c, cexp, k, s, cout, mf.ACT_HSWISH if hs else mf.ACT_RELU, bool(se))
+        c = cout
+    ncls = n_classes or 200
+    emb = _mnv3_head(b, t, h, w, c, 960, 1280, ncls)
+    return _finish(b, [br], sr, n, ncls, 960, emb, mf.OUT_SIGMOID)
 
 
 def random_fused_plan(seed: int, big: bool = False) -> dict:

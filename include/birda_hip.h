@@ -380,6 +380,12 @@ BH_API int bh_classifier_frontend_kernel(const bh_classifier *c, char *out, size
 /* Template arguments of tile configuration `cfg` as a profiler prints them after
  * "mbconv_kernel<" (to match bench timings with rocprofv3 rows); returns the string length. */
 BH_API int bh_mb_config_name(int32_t cfg, char *out, size_t cap);
+/* The configuration index space is `base + k * n_base`, k the activation family: 0 GELU, 1 swish, 2 ReLU6, 3 hard swish.  Callers of
+ * bh_mb_config_name derive n_base as ONE THIRD of the indices it names, so it keeps naming exactly the first three families
+ * (0 .. 3 n_base - 1) and answers 0 from 3 n_base on; the two entries below see the whole space: the number of families (4), and
+ * the name of any configuration 0 .. families * n_base - 1 (same text as above; 0 past the end). */
+BH_API int bh_mb_config_families(void);
+BH_API int bh_mb_config_name_ex(int32_t cfg, char *out, size_t cap);
 
 /* decode_and_stream + process_batch for source-rate input (processor.rs:84-87, 220-277): every
  * slice holds n_src_samples = ceil(sample_count * source_rate / sample_rate) samples at

@@ -22,7 +22,7 @@ extern "C" {
  * (o / (cout / groups)) * (cin / groups) + 0 .. cin / groups - 1.
  * shape = {in_h, in_w, out_h, out_w, cin, cout, kh, kw, sh, sw, pad_t, pad_l, groups}; out_h, out_w are taken as given (taps
  * outside the image read as zero, so the bottom / right padding is whatever they imply).
- * act: any activation code of the container (0 none, 1 ReLU, 2 ReLU6, 3 swish, 4 erf-GELU, 5 tanh-GELU, 6 sigmoid).
+ * act: any activation code of the container (0 none, 1 ReLU, 2 ReLU6, 3 swish, 4 erf-GELU, 5 tanh-GELU, 6 sigmoid, 7 hard swish, 8 hard sigmoid).
  * terms 0: gconv_kernel (f32 MFMA); 3: gconv16_kernel<3> (hi / lo split f16 operands); 1: gconv16_kernel<1> (plain f16).
  * There is no two-term form: terms 2, and any shape gconv_supports rejects (groups < 2, a group count that does not divide the
  * channels, a group width that is not a multiple of 4, a kernel outside 1 .. 7, a stride outside 1 .. 2), return BH_ERR_UNSUPPORTED.
