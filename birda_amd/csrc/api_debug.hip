@@ -12,6 +12,7 @@
 #include "../../include/birda_hip_block_debug.h"
 #include "../../include/birda_hip_resample_debug.h"
 #include "../../include/birda_hip_custom_debug.h"
+#include "../../include/birda_hip_gated_debug.h"
 
 using namespace bhi;
 
@@ -209,6 +210,28 @@ int bh_debug_gated_gemm(int device, const float *A, const float *gate, const flo
     const char *name = bh::launch_pw_gemm16_gated(da, dg, (int)rows_per_seg, dw, db, dr, dc, (int)M, (int)K, (int)N, terms, unscale, blocked, nullptr);
     g_last_gated_kernel.store(name, std::memory_order_relaxed);
     return h.finish(name, nullptr, 0);
+} catch (...) { return on_exception(); }
+
+// The same block's project GEMM on the f32 MFMA (a precision="f32" classifier's, and the one BH_FLAG_AUTO re-runs rows on), with
+// create's row padding of W, through the call SliceRun::fused_se makes (include/birda_hip_gated_debug.h).
+int bh_debug_gated_gemm_f32(int device, const float *A, const float *gate, const float *W, const float *bias, const float *R, float *C,
+                            size_t M, size_t K, size_t N, size_t rows_per_seg, int act, char *kernel, size_t kernel_cap) try {
+    if (!A || !gate || !W || !bias || !C || !M || !K || !N || !rows_per_seg || M % rows_per_seg || act < 0 || act > bh::ACT_LAST)
+        return fail(BH_ERR_INVALID, "debug_gated_gemm_f32: bad arguments");
+    if (M * K > (size_t)INT32_MAX || M * N > (size_t)INT32_MAX || K * N > (size_t)INT32_MAX || rows_per_seg > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_gated_gemm_f32: operands past 2^31 elements");
+    if (K % 4) return fail(BH_ERR_UNSUPPORTED, "debug_gated_gemm_f32: K %zu is not a multiple of 4", K);
+    HIPCHK(hipSetDevice(device));
+    const size_t ld = align_up(N, 4);
+    const std::vector<float> w = pw_gemm_rows(W, K, N, ld);
+    DebugLaunch h{"debug_gated_gemm_f32"};
+    const float *da = h.in(A, M * K * 4), *dg = h.in(gate, M / rows_per_seg * K * 4), *dw = h.in(w.data(), w.size() * 4), *db = h.in(bias, N * 4),
+                *dr = h.in(R, M * N * 4);
+    float *dc = h.out(M * N, "C", C);
+    if (!h.ok) return h.no_memory();
+    const char *name = bh::launch_pw_gemm_gated(da, dg, (int)rows_per_seg, dw, db, dr, dc, (int)M, (int)K, (int)N, (int)ld, act, nullptr, 0);
+    if (!name) return fail(BH_ERR_INTERNAL, "debug_gated_gemm_f32: the launcher has no instantiation for N %zu", N);
+    return h.finish(name, kernel, kernel_cap);
 } catch (...) { return on_exception(); }
 
 // One full convolution on the implicit-GEMM kernels, on operands of the caller's, with the weight preparation create does

@@ -373,6 +373,19 @@ def gemm64(A, W, bias) -> np.ndarray:
     return np.asarray(A, np.float64) @ np.asarray(W, np.float64) + np.asarray(bias, np.float64)
 
 
+def gated64(A, gate, W, bias, R, P: int) -> np.ndarray:
+    """The gated project GEMM of a squeeze-excite block in float64: (A x gate[row // P]) W + bias (+ R); A [n * P][K], gate [n][K]."""
+    Ag = np.asarray(A, np.float64) * np.repeat(np.asarray(gate, np.float64), P, axis=0)
+    out = Ag @ np.asarray(W, np.float64) + np.asarray(bias, np.float64)
+    return out if R is None else out + np.asarray(R, np.float64)
+
+
+def gated_bound64(A, gate, W, bias, P: int) -> np.ndarray:
+    """|A x gate| |W| + |bias|: what the rounding errors of gated64's GEMM scale with."""
+    Ag = np.abs(np.asarray(A, np.float64) * np.repeat(np.asarray(gate, np.float64), P, axis=0))
+    return Ag @ np.abs(np.asarray(W, np.float64)) + np.abs(np.asarray(bias, np.float64))
+
+
 def se_gate64(part, P: int, W1, b1, act1: int, W2, b2, act2: int):
     """The gate of a squeeze-excite block in float64: part [n][tiles][C] (per-tile channel sums), W1 [C][Cr], W2 [Cr][C] ->
     (gate [n][C], pooled [n][C] = sum over tiles / P, preH, H = act1(preH) [n][Cr], preG [n][C]); gate = act2(preG)."""

@@ -194,6 +194,31 @@ def test_every_gated_two_term_instantiation(case):
     _same_numbers(two, three, case)
 
 
+REACHED1 = set()
+
+
+@pytest.mark.parametrize("case", GATED2, ids=lambda c: c[5].replace("<2,", "<1,"))
+def test_every_gated_plain_f16_instantiation(case):
+    """The same 24 shapes on plain f16 (terms 1), W as it is: the instantiation by name, and every element within 1.5e-3 of
+    sum |a g||w| + |b| + |R| -- tests/test_gated_gemm_gpu.py's figure for terms 1."""
+    n_seg, P, K, N, blocked, want = case
+    A, gate, W, bias, R = TG._operands(K * 131 + N, n_seg, P, K, N, True)
+    ref, bound = TG._reference(A, gate, W, bias, R, P)
+    one, name = _gated(A, gate, W, bias, R, P, 1, blocked, want_name=True)
+    REACHED1.add(name)
+    assert name == want.replace("<2,", "<1,"), (name, want)
+    err = np.abs(one - ref) / bound
+    assert np.isfinite(one).all() and err.max() <= 1.5e-3, (case, float(err.max()))
+
+
+def test_every_gated_plain_f16_kernel_was_reached():
+    """(keep behind test_every_gated_plain_f16_instantiation: it reads what that ran)"""
+    if len(REACHED1) < 2:
+        pytest.skip("reads the kernels test_every_gated_plain_f16_instantiation ran: run the module whole")
+    want = {c[5].replace("<2,", "<1,") for c in GATED2}
+    assert len(want) == 24 and REACHED1 == want, sorted(want ^ REACHED1)
+
+
 @pytest.mark.parametrize("shape", TG.SHAPES, ids=lambda s: "n%d_P%d_K%d_N%d_r%d_b%d" % s)
 def test_gated_gemm_two_terms(shape):
     """Every kernel behind launch_pw_gemm16_gated (streaming, row-streaming over NHWC and blocked rows, staged tiles) on two terms:

@@ -83,8 +83,9 @@ def _eps_act(pre, act):
     return np.zeros_like(pre)
 
 
-def _check(got, name, pre, bound, R, act, terms, k_eff, what):
-    """Element by element against act(pre) (+ R); records the worst share of the GEMM part of the tolerance."""
+def _check(got, name, pre, bound, R, act, terms, k_eff, what, tau_extra=0.0):
+    """Element by element against act(pre) (+ R); records the worst share of the GEMM part of the tolerance.  tau_extra: added to
+    tau by a caller whose kernel rounds once more per product (tests/test_gated_gemm.py: the gate multiply, 2^-24)."""
     ref = O.act64(pre, act)
     r = np.zeros_like(ref) if R is None else R.astype(np.float64)
     ref = ref + r
@@ -92,7 +93,7 @@ def _check(got, name, pre, bound, R, act, terms, k_eff, what):
     scale = 1.2 * bound + np.abs(r)
     err = np.abs(got.astype(np.float64) - ref)
     eps = _eps_act(pre, act)
-    tol = _tau(terms, k_eff) * scale + eps
+    tol = (_tau(terms, k_eff) + tau_extra) * scale + eps
     bad = err > tol
     share = np.max(np.maximum(err - eps, 0.0) / np.maximum(scale, 1e-300))
     key = (_family(name), terms)
