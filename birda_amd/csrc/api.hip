@@ -74,12 +74,6 @@ int se_gate_form(int C, int Cr) {
     return bh::se_gate_supports(C, Cr) ? 0 : -1;
 }
 
-int upload(const void *src, size_t bytes, float **dst) {
-    HIPCHK(hipMalloc((void **)dst, bytes ? bytes : 4));
-    if (bytes) HIPCHK(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return BH_OK;
-}
-
 int read_labels(const char *path, std::vector<std::string> &out) {
     FILE *f = fopen(path, "rb");
     if (!f) return fail(BH_ERR_IO, "cannot open labels file %s", path);
@@ -120,6 +114,7 @@ void ctx_mark(bh_batch_context *ctx, int stage, int layer = -1) {
 const std::vector<Step> &schedule_of(const bh_batch_context *ctx) {
     return !ctx->keep_tensors ? ctx->c->sched : ctx->keep_fused ? ctx->c->sched_keep_fused : ctx->c->sched_layers;
 }
+// (whatever fails below, ~bh_batch_context releases what the context has taken so far, the stream set included)
 int ctx_create(bh_classifier *c, size_t max_batch, bool keep, bh_batch_context **out) {
     if (!c || !out || max_batch == 0) return fail(BH_ERR_INVALID, "batch context: bad arguments");
     HIPCHK(hipSetDevice(c->device));
@@ -172,31 +167,6 @@ int ctx_create(bh_classifier *c, size_t max_batch, bool keep, bh_batch_context *
     return BH_OK;
 }
 
-void ctx_destroy(bh_batch_context *ctx) {
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->c->device);
-    if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    for (auto e : ctx->ev) (void)hipEventDestroy(e);
-    for (auto e : ctx->copy_ev) (void)hipEventDestroy(e);
-    for (auto e : ctx->done_ev) (void)hipEventDestroy(e);
-    const bool own_streams = ctx->stream_set < 0;   // (a set of the classifier's goes back to it, below)
-    if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); if (own_streams) (void)hipStreamDestroy(ctx->copy_stream); }
-    for (int l = 1; l < bh_batch_context::MAX_LANES; l++) {
-        if (ctx->lane_stream[l]) { (void)hipStreamSynchronize(ctx->lane_stream[l]); if (own_streams || l > 2) (void)hipStreamDestroy(ctx->lane_stream[l]); }
-        if (ctx->join_ev[l]) (void)hipEventDestroy(ctx->join_ev[l]);
-    }
-    if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
-    (void)hipFree(ctx->d_input); (void)hipFree(ctx->d_minmax); (void)hipFree(ctx->d_inbad); (void)hipFree(ctx->d_arena);
-    (void)hipFree(ctx->d_logits); (void)hipFree(ctx->d_topk_idx); (void)hipFree(ctx->d_topk_conf);
-    (void)hipHostFree(ctx->h_input); (void)hipHostFree(ctx->h_topk_idx); (void)hipHostFree(ctx->h_topk_conf);
-    (void)hipFree(ctx->d_raw); (void)hipHostFree(ctx->h_raw);
-    (void)hipFree(ctx->d_pcm); (void)hipFree(ctx->d_starts); (void)hipFree(ctx->d_partial);
-    (void)hipFree(ctx->d_nonfinite); (void)hipHostFree(ctx->h_nonfinite);
-    if (ctx->stream && own_streams) (void)hipStreamDestroy(ctx->stream);
-    if (!own_streams) { std::lock_guard<std::mutex> g(ctx->c->stream_mu); ctx->c->stream_sets[ctx->stream_set].used = false; }
-    delete ctx;
-}
-
 // where a sub-slice of a host-fed slice runs: its stream, its own part of the arena with the plan of an n-segment forward, and its
 // first segment's index within the slice, which places its rows of the per-segment scratch
 struct SliceLane { hipStream_t s; float *arena; const size_t *t_off; size_t seg0; };
@@ -234,8 +204,11 @@ static bh::MbDesc mb_for_launch(const bh_classifier *c, int block, size_t n) {
 int SliceRun::layer(const Step &st) const {
     const uint32_t i = st.first;
     const auto &L = c->model.layers[i];
+    LayerState &S = c->layer[i];
     const float *in = this->in(st), *res = this->res(st), *bias = c->d_blob + L.b_off;
     float *out = this->out(st);
+    // on its f16 planes, where it has them; a context that keeps every tensor runs every layer on the f32 kernels
+    const bool f16 = !ctx->keep_tensors && S.planes;
     // (a layer with its activation after the residual add is a layer like any other: the position rides in p / after, the f32
     //  kernels branch on it at run time -- BIRDA_HIP_KEEP_TENSORS contexts and the BH_FLAG_AUTO re-run land there -- and the
     //  split-f16 launchers pick the AFTER instantiations)
@@ -247,35 +220,26 @@ int SliceRun::layer(const Step &st) const {
         // the NCHW stem on the direct kernel (when it is not fused into the first block); every NHWC full convolution is an
         // implicit GEMM on the MFMA (kernels_conv.hip), split-f16 where it has planes
         if (L.in_layout == 1)
-            launched = bh::launch_conv_direct(in, c->d_w[i], bias, out, p, (int)n, s);
-        else if (!ctx->keep_tensors && c->d_w16[i])
-            c->w16_kernel[i].store(launched = bh::launch_conv_gemm16(in, c->d_w16[i], bias, res, out, p, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+            launched = bh::launch_conv_direct(in, S.w, bias, out, p, (int)n, s);
+        else if (f16)
+            launched = bh::launch_conv_gemm16(in, S.planes, bias, res, out, p, (int)n, S.terms, S.unscale, s);
         else
-            launched = bh::launch_conv_gemm(in, c->d_w[i], bias, res, out, p, (int)n, c->ldw[i], s);
+            launched = bh::launch_conv_gemm(in, S.w, bias, res, out, p, (int)n, S.ldw, s);
         ctx_mark(ctx, ST_STEM, (int)i);
         break;
     case bh::OP_DWCONV:
-        launched = bh::launch_dwconv(in, c->d_w[i], bias, out, p, (int)n, s);
+        launched = bh::launch_dwconv(in, S.w, bias, out, p, (int)n, s);
         ctx_mark(ctx, ST_DW, (int)i);
         break;
-    case bh::OP_PWCONV:
-        if (!ctx->keep_tensors && c->d_w16[i])
-            c->w16_kernel[i].store(launched = bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin, (int)L.cout,
-                                                        (int)L.act, c->w16_terms[i], c->w16_unscale[i], s, after), std::memory_order_relaxed);
+    case bh::OP_PWCONV: case bh::OP_DENSE: {   // a 1x1 convolution is the dense layer over every pixel's row
+        const int rows = (int)(L.op == bh::OP_PWCONV ? n * L.out_h * L.out_w : n);
+        if (f16)
+            launched = bh::launch_pw_gemm16(in, S.planes, bias, res, out, rows, (int)L.cin, (int)L.cout, (int)L.act, S.terms, S.unscale, s, after);
         else
-        launched = bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)(n * L.out_h * L.out_w), (int)L.cin,
-                           (int)L.cout, c->ldw[i], (int)L.act, s, after);
-        ctx_mark(ctx, ST_PW, (int)i);
+            launched = bh::launch_pw_gemm(in, S.w, bias, res, out, rows, (int)L.cin, (int)L.cout, S.ldw, (int)L.act, s, after);
+        ctx_mark(ctx, L.op == bh::OP_PWCONV ? ST_PW : ST_DENSE, (int)i);
         break;
-    case bh::OP_DENSE:
-        if (!ctx->keep_tensors && c->d_w16[i])
-            c->w16_kernel[i].store(launched = bh::launch_pw_gemm16(in, c->d_w16[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, (int)L.act,
-                                                        c->w16_terms[i], c->w16_unscale[i], s, after), std::memory_order_relaxed);
-        else
-        launched = bh::launch_pw_gemm(in, c->d_w[i], bias, res, out, (int)n, (int)L.cin, (int)L.cout, c->ldw[i],
-                           (int)L.act, s, after);
-        ctx_mark(ctx, ST_DENSE, (int)i);
-        break;
+    }
     case bh::OP_GAP:
         bh::launch_gap(in, out, (int)n, (int)(L.in_h * L.in_w), (int)L.cout, s);
         ctx_mark(ctx, ST_GAP, (int)i);
@@ -285,10 +249,8 @@ int SliceRun::layer(const Step &st) const {
         ctx_mark(ctx, ST_DW, (int)i);
         break;
     case bh::OP_GCONV:   // a grouped convolution (L.reserved: the group count): per-tile weight blocks, split-f16 where it has planes
-        if (!ctx->keep_tensors && c->d_w16[i])
-            c->w16_kernel[i].store(launched = bh::launch_gconv16(in, c->d_w16[i], bias, out, p, (int)L.reserved, (int)n, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
-        else   // (the f32 kernel's name is kept too: bh_debug_layer_kernel tells which of the three instantiations a grouped layer ran)
-            c->w16_kernel[i].store(launched = bh::launch_gconv(in, c->d_w[i], bias, out, p, (int)L.reserved, (int)n, s), std::memory_order_relaxed);
+        launched = f16 ? bh::launch_gconv16(in, S.planes, bias, out, p, (int)L.reserved, (int)n, S.terms, S.unscale, s)
+                       : bh::launch_gconv(in, S.w, bias, out, p, (int)L.reserved, (int)n, s);
         ctx_mark(ctx, ST_STEM, (int)i);
         break;
     case bh::OP_POOL:    // MaxPool / AveragePool: f32 in every precision mode (L.reserved: the pool mode)
@@ -297,13 +259,14 @@ int SliceRun::layer(const Step &st) const {
         break;
     case bh::OP_CONCAT: {   // channel windows of one or two tensors, optionally shuffled: a copy, the same in every precision mode
         const auto src = concat_sources(c->model, L, in, res);   // (res: the second input, not a residual)
-        c->w16_kernel[i].store(launched = bh::launch_concat(src.data(), L.res_tensor == bh::NO_TENSOR ? 1 : 2, out, (int)L.out_h, (int)L.out_w,
-                                                            (int)L.reserved, (int)n, s), std::memory_order_relaxed);
+        launched = bh::launch_concat(src.data(), L.res_tensor == bh::NO_TENSOR ? 1 : 2, out, (int)L.out_h, (int)L.out_w, (int)L.reserved, (int)n, s);
         ctx_mark(ctx, ST_GAP, (int)i);
         break;
     }
     default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
     }
+    // (bh_debug_layer_kernel: the split-f16 launchers' names; a grouped convolution's and a concat's f32 kernels are kept too)
+    if (f16 || L.op == bh::OP_GCONV || L.op == bh::OP_CONCAT) S.kernel.store(launched, std::memory_order_relaxed);
     // (create's predicates and validate_model keep this from happening; if it does, the output tensor was not written)
     if (!launched && n) {
         if (L.op == bh::OP_DWCONV || (L.op == bh::OP_CONV && L.in_layout == 1))
@@ -347,6 +310,8 @@ int SliceRun::fused_se(const Step &st) const {
     const bh::MbDesc d = mb_for_launch(c, st.block, n);
     const auto &S = c->se[st.block];
     const auto &G1 = c->model.layers[S.iPw1], &G2 = c->model.layers[S.iPw2], &LP = c->model.layers[S.iP];
+    const LayerState &W1 = c->layer[S.iPw1], &W2 = c->layer[S.iPw2];
+    LayerState &WP = c->layer[S.iP];
     // (the gate: one launch, a workgroup per segment (se_gate_kernel), or the pool + the two dense layers as GEMMs over all
     //  segments, through the arena slots of the layers they stand for.  Either way every sum runs in a fixed order.)
     // (which of the two a BLOCK takes depends on its width alone, never on the launch: up to 576 expanded channels the
@@ -359,14 +324,14 @@ int SliceRun::fused_se(const Step &st) const {
     auto launch_gate = [&](const float *part, int tiles, int P, float *pooled, float *hidden, float *gate, size_t ns) {
         const int form = gate1 ? 0 : se_gate_form(d.Cexp, (int)G1.cout);
         if (form == 1)
-            bh::launch_se_gate16(part, tiles, P, pooled, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
-                                 c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+            bh::launch_se_gate16(part, tiles, P, pooled, W1.w, c->d_blob + G1.b_off, W1.ldw, (int)G1.act,
+                                 W2.w, c->d_blob + G2.b_off, W2.ldw, (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
         else if (form == 2)
-            bh::launch_se_gate_gemm(part, tiles, P, pooled, hidden, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
-                                    c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+            bh::launch_se_gate_gemm(part, tiles, P, pooled, hidden, W1.w, c->d_blob + G1.b_off, W1.ldw, (int)G1.act,
+                                    W2.w, c->d_blob + G2.b_off, W2.ldw, (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
         else
-            bh::launch_se_gate(part, tiles, P, c->d_w[S.iPw1], c->d_blob + G1.b_off, c->ldw[S.iPw1], (int)G1.act,
-                               c->d_w[S.iPw2], c->d_blob + G2.b_off, c->ldw[S.iPw2], (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
+            bh::launch_se_gate(part, tiles, P, W1.w, c->d_blob + G1.b_off, W1.ldw, (int)G1.act,
+                               W2.w, c->d_blob + G2.b_off, W2.ldw, (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
     };
     // (a block without an expand convolution computes D twice instead of keeping it: pass A leaves only the channel sums,
     //  the gated one-launch block below does the rest -- kernels.hpp MbDesc::gate)
@@ -377,7 +342,7 @@ int SliceRun::fused_se(const Step &st) const {
     static const bool stem_recompute = [] { const char *e = BH_XENV("BIRDA_HIP_SE_STEM_RECOMPUTE"); return e && e[0] == '1'; }();
     const bool recompute = d.noexp != 0 || (d.stem != 0 && stem_recompute);
     // (D blocked for the f16 gated GEMMs: kernels.hpp MbDesc::dblk)
-    const bool dblk = !recompute && c->d_w16[S.iP] && bh::pw_gemm16_gated_wants_blocked(d.Cexp, d.Cout, d.Ho * d.Wo);
+    const bool dblk = !recompute && WP.planes && bh::pw_gemm16_gated_wants_blocked(d.Cexp, d.Cout, d.Ho * d.Wo);
     // Round 6 (VERDICT r5 next #3a): a block whose D is large -- the early stages: 1.5-2.3 MB a segment -- runs its three
     // launches per GROUP of segments, so that the D pass A writes is still in the 256 MB Infinity Cache when the gated
     // project GEMM reads it (at 1 000 segments a launch it crosses HBM both ways).  The tiling -- hence every pooled sum's
@@ -411,12 +376,11 @@ int SliceRun::fused_se(const Step &st) const {
             g.se = 0; g.gate = gg; g.Y = yg; g.R = rg; g.Dout = nullptr; g.pool_part = nullptr;
             bh::launch_mbconv(g, (int)ng, s);
         } else
-        if (c->d_w16[S.iP])
-            c->w16_kernel[S.iP].store(bh::launch_pw_gemm16_gated(a.Dout, gg, (int)P, c->d_w16[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
-                                       c->w16_terms[S.iP], c->w16_unscale[S.iP], a.dblk, s), std::memory_order_relaxed);
+        if (WP.planes)
+            WP.kernel.store(bh::launch_pw_gemm16_gated(a.Dout, gg, (int)P, WP.planes, c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
+                                                       WP.terms, WP.unscale, a.dblk, s), std::memory_order_relaxed);
         else
-            bh::launch_pw_gemm_gated(a.Dout, gg, (int)P, c->d_w[S.iP], c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout,
-                                     c->ldw[S.iP], (int)LP.act, s);
+            bh::launch_pw_gemm_gated(a.Dout, gg, (int)P, WP.w, c->d_blob + LP.b_off, rg, yg, (int)(ng * P), d.Cexp, d.Cout, WP.ldw, (int)LP.act, s);
         if (!grouped) ctx_mark(ctx, ST_PW, (int)S.iP);
     };
     if (grouped) {
@@ -431,8 +395,9 @@ int SliceRun::fused_se(const Step &st) const {
 int SliceRun::head_gap(const Step &st) const {
     const uint32_t i = st.first;
     const auto &L = c->model.layers[i];
-    c->w16_kernel[i].store(bh::launch_head_gap16(in(st), c->d_w16[i], c->d_blob + L.b_off, out(st), (int)n, (int)(L.out_h * L.out_w), (int)L.cin, (int)L.cout,
-                                                 (int)L.act, c->w16_terms[i], c->w16_unscale[i], s), std::memory_order_relaxed);
+    LayerState &S = c->layer[i];
+    S.kernel.store(bh::launch_head_gap16(in(st), S.planes, c->d_blob + L.b_off, out(st), (int)n, (int)(L.out_h * L.out_w), (int)L.cin, (int)L.cout,
+                                         (int)L.act, S.terms, S.unscale, s), std::memory_order_relaxed);
     ctx_mark(ctx, ST_PW, (int)i);
     return BH_OK;
 }
@@ -448,8 +413,9 @@ int SliceRun::se_gate(const Step &st) const {
     const uint32_t i = st.first;
     const auto &L = c->model.layers[i], &G1 = c->model.layers[i + 1], &G2 = c->model.layers[i + 2];
     const int P = (int)(L.in_h * L.in_w);
-    bh::launch_se_gate16(in(st), P, P, T(st.scratch[0].t), c->d_w[i + 1], c->d_blob + G1.b_off, c->ldw[i + 1], (int)G1.act, c->d_w[i + 2],
-                         c->d_blob + G2.b_off, c->ldw[i + 2], (int)G2.act, out(st), (int)n, (int)L.cout, (int)G1.cout, s);
+    const LayerState &W1 = c->layer[i + 1], &W2 = c->layer[i + 2];
+    bh::launch_se_gate16(in(st), P, P, T(st.scratch[0].t), W1.w, c->d_blob + G1.b_off, W1.ldw, (int)G1.act, W2.w,
+                         c->d_blob + G2.b_off, W2.ldw, (int)G2.act, out(st), (int)n, (int)L.cout, (int)G1.cout, s);
     ctx_mark(ctx, ST_GAP, (int)i);
     return BH_OK;
 }
@@ -471,7 +437,7 @@ int SliceRun::concat(const Step &st) const {
         if (m.layers[j].res_tensor != bh::NO_TENSOR) leaf(m.layers[j].res_tensor, m.layers[j].b_off, m.layers[j].cout - m.layers[j].cin);
     if (n_src > 4 || (size_t)n_src != st.reads.size()) return fail(BH_ERR_INTERNAL, "layer %u: a concat chain of %d leaves", st.first, n_src);
     const char *name = bh::launch_concat(src, n_src, out(st), (int)Z.out_h, (int)Z.out_w, (int)Z.reserved, (int)n, s);
-    for (uint32_t j = st.first; j <= st.last; j++) c->w16_kernel[j].store(name, std::memory_order_relaxed);
+    for (uint32_t j = st.first; j <= st.last; j++) c->layer[j].kernel.store(name, std::memory_order_relaxed);
     ctx_mark(ctx, ST_GAP, (int)st.first);
     return BH_OK;
 }
@@ -547,7 +513,6 @@ void clear_nonfinite(bh_batch_context *ctx) {
 }
 
 // ---- BH_FLAG_AUTO: the rows the split-f16 forward could not represent, again on the f32 kernels -----------------------------
-constexpr uint32_t FLAG_INTERNAL_NO_ENV = 0x80000000u;   // (the fallback classifier: BIRDA_HIP_PRECISION must not turn it into f16 again)
 int internal_ctx(bh_classifier *c, size_t n, bh_batch_context **out);
 
 int fallback_classifier(bh_classifier *c, bh_classifier **out) {
@@ -938,6 +903,31 @@ int internal_ctx(bh_classifier *c, size_t n, bh_batch_context **out) {
 
 }  // namespace bhi
 
+// The one place a context's device and pinned memory, events and streams are released: a context ctx_create gave up half way
+// (null pointers, no stream set yet) goes through it as well.  The streams are drained before anything they may read is freed.
+bh_batch_context::~bh_batch_context() {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (auto e : ev) (void)hipEventDestroy(e);
+    for (auto e : copy_ev) (void)hipEventDestroy(e);
+    for (auto e : done_ev) (void)hipEventDestroy(e);
+    const bool own_streams = stream_set < 0;   // (a set of the classifier's goes back to it, below)
+    if (copy_stream) { (void)hipStreamSynchronize(copy_stream); if (own_streams) (void)hipStreamDestroy(copy_stream); }
+    for (int l = 1; l < MAX_LANES; l++) {
+        if (lane_stream[l]) { (void)hipStreamSynchronize(lane_stream[l]); if (own_streams || l > 2) (void)hipStreamDestroy(lane_stream[l]); }
+        if (join_ev[l]) (void)hipEventDestroy(join_ev[l]);
+    }
+    if (fork_ev) (void)hipEventDestroy(fork_ev);
+    (void)hipFree(d_input); (void)hipFree(d_minmax); (void)hipFree(d_inbad); (void)hipFree(d_arena);
+    (void)hipFree(d_logits); (void)hipFree(d_topk_idx); (void)hipFree(d_topk_conf);
+    (void)hipHostFree(h_input); (void)hipHostFree(h_topk_idx); (void)hipHostFree(h_topk_conf);
+    (void)hipFree(d_raw); (void)hipHostFree(h_raw);
+    (void)hipFree(d_pcm); (void)hipFree(d_starts); (void)hipFree(d_partial);
+    (void)hipFree(d_nonfinite); (void)hipHostFree(h_nonfinite);
+    if (stream && own_streams) (void)hipStreamDestroy(stream);
+    if (!own_streams) { std::lock_guard<std::mutex> g(c->stream_mu); c->stream_sets[stream_set].used = false; }
+}
 
 extern "C" {
 
@@ -1022,309 +1012,6 @@ size_t bh_classifier_default_batch_size(const bh_classifier *c) {
     return c ? bh_default_batch_size(c->model.h.family, "HIP") : 0;
 }
 const char *bh_last_error(void) { return g_err.c_str(); }
-
-int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
-    if (!cfg || !out || !cfg->model_path) return fail(BH_ERR_INVALID, "classifier_create: null config/model_path");
-    *out = nullptr;
-    if (cfg->top_k == 0 || cfg->top_k > BH_MAX_TOP_K) return fail(BH_ERR_INVALID, "top_k must be 1..%d", BH_MAX_TOP_K);
-    auto c = std::make_unique<bh_classifier>();
-    std::string err;
-    if (!load_any_model(cfg->model_path, c->model, err)) return fail(model_load_status(err), "%s", err.c_str());
-    const auto &m = c->model;
-    static_assert(BH_MAX_CLASSES == bh::TOPK_MAX_CLASSES, "the documented class-count ceiling is the top-k kernel's row");
-    if (m.h.n_classes > BH_MAX_CLASSES)   // (before anything touches a device: the top-k launch would fail with a bare HIP error)
-        return fail(BH_ERR_UNSUPPORTED, "the model has %u classes: the activation / top-k stage holds at most %d (a segment's logits in 128 KB of LDS)",
-                    m.h.n_classes, BH_MAX_CLASSES);
-    if (cfg->labels_path) {
-        int rc = read_labels(cfg->labels_path, c->labels);
-        if (rc != BH_OK) return rc;
-        if (c->labels.size() != m.h.n_classes)
-            return fail(BH_ERR_LABELS, "label count %zu does not match model output width %u", c->labels.size(), m.h.n_classes);
-    }
-    int ndev = bh_device_count();
-    if (ndev <= 0) return fail(BH_ERR_NO_DEVICE, "no HIP device available (libbirda_hip has no CPU path)");
-    if (cfg->device < 0 || cfg->device >= ndev) return fail(BH_ERR_NO_DEVICE, "device %d out of range (0..%d)", cfg->device, ndev - 1);
-    c->device = cfg->device;
-    c->top_k = cfg->top_k;
-    c->min_conf = cfg->min_confidence;
-    HIPCHK(hipSetDevice(c->device));
-    for (auto &ss : c->stream_sets)          // the batch contexts' streams, all of them now (api_internal.hpp)
-        for (auto &st : ss.s) HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    if (m.h.n_branches > bh::MAX_BRANCHES) return fail(BH_ERR_UNSUPPORTED, "too many front-end branches");
-    // front-end operators
-    // GEMM operand precision (decided here: the front-end operator layout depends on it)
-    // the spectrogram front-end keeps f32-grade products in every mode: f32 MFMA, or split f16 in the f16 modes
-    {
-        const uint32_t pf = cfg->flags & BH_FLAG_PRECISION_MASK;
-        c->precision = pf == BH_FLAG_F32 ? 0 : pf == BH_FLAG_F16 ? 1 : 3;
-        c->auto_fallback = pf == BH_FLAG_AUTO;
-        c->low_latency = (cfg->flags & BH_FLAG_LOW_LATENCY) != 0;
-        c->full_planes = (cfg->flags & BH_FLAG_FULL_PLANES) != 0;
-        c->model_path = cfg->model_path;
-    }
-    if (const char *pe = (cfg->flags & FLAG_INTERNAL_NO_ENV) ? nullptr : getenv("BIRDA_HIP_PRECISION")) {
-        if (!strcmp(pe, "f32")) { c->precision = 0; c->auto_fallback = false; }
-        else if (!strcmp(pe, "f16x3")) { c->precision = 3; c->auto_fallback = false; }
-        else if (!strcmp(pe, "auto")) { c->precision = 3; c->auto_fallback = true; }
-        else if (!strcmp(pe, "f16")) { c->precision = 1; c->auto_fallback = false; }
-        else return fail(BH_ERR_INVALID, "BIRDA_HIP_PRECISION must be auto, f32, f16x3 or f16");
-    }
-    // f16x3 and f16: the front-end GEMM on the split-f16 MFMA (f32-grade products, faster than the f32 MFMA;
-    // BIRDA_HIP_MEL_F32=1 keeps it on the f32 MFMA: A/B aid)
-    int fe_prec = (c->precision != 0 && !(getenv("BIRDA_HIP_MEL_F32") && getenv("BIRDA_HIP_MEL_F32")[0] == '1')) ? 3 : 0;
-    for (uint32_t b = 0; b < m.h.n_branches; b++)
-        if (m.branches[b].frame_length % 256) fe_prec = 0;   // 32-deep steps split over 4 waves
-    if (fe_prec == 3) {
-        // mel32_kernel (Y rows staged along k: no LDS bank conflicts whatever the hop) where mel_kernel's frame-strided
-        // reads collapse onto a few banks: hops that are multiples of 16 samples (Perch: 320 -> every frame on one bank;
-        // 483 -> 258 us per 600 segments).  BirdNET's hops (278 / 280) stay on mel_kernel (790 vs 1006 us per 1000).
-        // BIRDA_HIP_MEL32=0/1 forces the choice (A/B aid).
-        bool want = false, can = true;
-        for (uint32_t b = 0; b < m.h.n_branches; b++) {
-            if (m.branches[b].frame_step % 16 == 0) want = true;
-            if (align_up(m.branches[b].n_mels, 16) % 32 || m.branches[b].frame_length % 512) can = false;   // 32-mel tiles, 64-k chunks per wave
-        }
-        if (const char *e = getenv("BIRDA_HIP_MEL32")) want = e[0] == '1';
-        if (want && can) fe_prec = 32;
-    }
-    if (m.h.sample_count % 4) return fail(BH_ERR_UNSUPPORTED, "front-end: sample_count %u must be a multiple of 4 (16-byte span loads)", m.h.sample_count);
-    c->fe.prec = fe_prec;
-    c->fe.n_branches = (int)m.h.n_branches;
-    c->fe.sample_count = (int)m.h.sample_count;
-    c->fe.norm_eps = m.h.norm_eps;
-    for (uint32_t b = 0; b < m.h.n_branches; b++) {
-        const auto &br = m.branches[b];
-        const int nm_pad = (int)align_up(br.n_mels, 16);
-        if (nm_pad < 32 || nm_pad > 128)
-            return fail(BH_ERR_UNSUPPORTED, "front-end: n_mels %u not built (17 .. 128)", br.n_mels);
-        if (b > 0 && nm_pad != c->fe.br[0].nm_pad) return fail(BH_ERR_UNSUPPORTED, "front-end: branches differ in n_mels");
-        if (br.frame_length % 128 || br.fft_length != br.frame_length)
-            return fail(BH_ERR_UNSUPPORTED, "front-end: frame_length %u must be a multiple of 128 and equal fft_length", br.frame_length);
-        // (no condition on the hop: a tile's span starts at sample tile * 48 (or 32) * hop, a multiple of 4 for any hop, so the
-        //  16-byte span loads stay aligned; what bounds the hop is the span's size, checked against the LDS below)
-        int gf_s = 0;
-        std::vector<float> gf = build_gf(br, m.blob.data() + br.mel_w_off, nm_pad, fe_prec, &gf_s);
-        float *d = nullptr;
-        int rc = upload(gf.data(), gf.size() * sizeof(float), &d);
-        if (rc != BH_OK) return rc;
-        c->d_owned.push_back(d);
-        auto &p = c->fe.br[b];
-        p.gf = d; p.L = (int)br.frame_length; p.H = (int)br.frame_step; p.K = p.L / 2;
-        p.n_mels = (int)br.n_mels; p.nm_pad = nm_pad; p.n_frames = (int)br.n_frames;
-        p.expo = 1.0f / (1.0f + expf(br.mag_scale));
-        p.log2_bias = -2.0f * (float)gf_s * p.expo;
-        p.out_scale = br.out_scale; p.out_shift = br.out_shift; p.flip = (int)(br.flags & 1u);
-        c->mel_flops += 2ull * (uint64_t)p.K * nm_pad * br.n_frames;
-    }
-    if (bh::mel_lds_bytes(c->fe) > 160 * 1024)
-        return fail(BH_ERR_UNSUPPORTED, "front-end: a tile of frames at this hop and frame length spans %zu KB of samples, more than a CU's 160 KB of LDS",
-                    bh::mel_lds_bytes(c->fe) / 1024);
-    {
-        float *d = nullptr;
-        int rcf = upload(&c->fe, sizeof c->fe, &d);
-        if (rcf != BH_OK) return rcf;
-        c->d_fe = reinterpret_cast<bh::FrontendParams *>(d);
-        c->d_owned.push_back(d);
-    }
-    // weights
-    int rc = upload(m.blob.data(), m.blob.size() * sizeof(float), &c->d_blob);
-    if (rc != BH_OK) return rc;
-    c->d_w.resize(m.layers.size());
-    c->ldw.assign(m.layers.size(), 0);
-    for (size_t i = 0; i < m.layers.size(); i++) {
-        const auto &L = m.layers[i];
-        c->d_w[i] = c->d_blob + L.w_off;
-        if (L.op == bh::OP_PWCONV || L.op == bh::OP_DENSE) {
-            if (L.cin % 4) return fail(BH_ERR_UNSUPPORTED, "layer %zu: cin %u not a multiple of 4", i, L.cin);
-            const int ld = (int)align_up(L.cout, 4);
-            c->ldw[i] = ld;
-            if (ld != (int)L.cout) {  // pad rows so 16-B loads stay aligned
-                const std::vector<float> w = pw_gemm_rows(m.blob.data() + L.w_off, L.cin, L.cout, (size_t)ld);
-                float *d = nullptr;
-                rc = upload(w.data(), w.size() * sizeof(float), &d);
-                if (rc != BH_OK) return rc;
-                c->d_owned.push_back(d);
-                c->d_w[i] = d;
-            }
-        } else if (L.op == bh::OP_DWCONV) {
-            if (!bh::dwconv_supports(conv_params(L)))
-                return fail(BH_ERR_UNSUPPORTED, "layer %zu: depthwise %ux%u stride %u channels %u not built", i, L.kh, L.kw, L.sh, L.cout);
-        } else if (L.op == bh::OP_CONV && L.in_layout == 1) {   // the NCHW stem: the direct kernel, weights in LDS
-            if (!bh::conv_direct_supports(conv_params(L)))
-                return fail(BH_ERR_UNSUPPORTED, "layer %zu: direct conv shape not built", i);
-        } else if (L.op == bh::OP_CONV) {   // NHWC: the implicit GEMM, W rows padded per tap to whole 32-deep steps
-            const bh::ConvParams p = conv_params(L);
-            if (!bh::conv_gemm_supports(p))
-                return fail(BH_ERR_UNSUPPORTED, "layer %zu: full convolution %ux%u stride %ux%u, %u -> %u channels, layout %u not built "
-                            "(kernel 1..7, stride 1 / 2, channels multiples of 4, NHWC)", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout, L.in_layout);
-            const int ld = (int)align_up(L.cout, 4);
-            c->ldw[i] = ld;
-            const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, p, ld);
-            float *d = nullptr;
-            rc = upload(w.data(), w.size() * sizeof(float), &d);
-            if (rc != BH_OK) return rc;
-            c->d_owned.push_back(d);
-            c->d_w[i] = d;
-        } else if (L.op == bh::OP_GCONV) {   // per-tile weight blocks as f32 MFMA fragments (the f16 planes: below, with the other layers')
-            const bh::ConvParams p = conv_params(L);
-            if (!bh::gconv_supports(p, (int)L.reserved))
-                return fail(BH_ERR_UNSUPPORTED, "layer %zu: grouped convolution %ux%u stride %ux%u, %u -> %u channels in %u groups not built "
-                            "(kernel 1..7, stride 1 / 2, group widths multiples of 4, NHWC, no residual)", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout, L.reserved);
-            int K = 0;
-            const std::vector<float> wt = gconv_matrix(m.blob.data() + L.w_off, p, (int)L.reserved, &K);
-            const std::vector<float> w = gconv_fragments(wt, K, (int)(L.cout + 15) / 16);
-            float *d = nullptr;
-            rc = upload(w.data(), w.size() * sizeof(float), &d);
-            if (rc != BH_OK) return rc;
-            c->d_owned.push_back(d);
-            c->d_w[i] = d;
-        } else if (L.op == bh::OP_GAP || L.op == bh::OP_SCALE || L.op == bh::OP_POOL) {
-            if (L.cout % 4) return fail(BH_ERR_UNSUPPORTED, "layer %zu: channels %u not a multiple of 4", i, L.cout);
-            if (L.op == bh::OP_POOL && !bh::pool_supports(conv_params(L), (int)L.reserved))
-                return fail(BH_ERR_UNSUPPORTED, "layer %zu: pool %ux%u stride %ux%u pad %u,%u mode %u not built", i, L.kh, L.kw, L.sh, L.sw, L.pad_t, L.pad_l, L.reserved);
-        } else if (L.op == bh::OP_CONCAT) {
-            const auto src = concat_sources(m, L, nullptr, nullptr);
-            if (!bh::concat_supports((int)L.out_h, (int)L.out_w, src.data(), L.res_tensor == bh::NO_TENSOR ? 1 : 2, (int)L.reserved))
-                return fail(BH_ERR_UNSUPPORTED, "layer %zu: concat of channels %llu + %u and %llu + %u into %u (shuffle groups %u) on a %ux%u image not built "
-                            "(offsets and lengths multiples of 4, inside their sources; groups dividing the channels)", i, (unsigned long long)L.w_off, L.cin,
-                            (unsigned long long)L.b_off, L.cout - L.cin, L.cout, L.reserved, L.out_h, L.out_w);
-        }
-    }
-    if (m.layers.empty() || m.layers.back().cout != m.h.n_classes)
-        return fail(BH_ERR_IO, "model: last layer width != n_classes");
-    // (an OP_CONCAT record's res_tensor is its second input, not a residual: the check below does not look at it)
-    // a residual on a layer whose kernel cannot add one is refused, not dropped: depthwise and pool layers (a fused block's
-    // residual sits on its project convolution; the planner fuses no depthwise layer that carries one) and the NCHW stem
-    for (size_t i = 0; i < m.layers.size(); i++) {
-        const auto &L = m.layers[i];
-        if (L.res_tensor != bh::NO_TENSOR && (L.op == bh::OP_DWCONV || L.op == bh::OP_GAP || L.op == bh::OP_POOL || L.op == bh::OP_GCONV || (L.op == bh::OP_CONV && L.in_layout == 1)))
-            return fail(BH_ERR_UNSUPPORTED, "layer %zu: a residual on a %s layer is not supported (only convolutions, 1x1 and full NHWC, "
-                        "and dense layers add one)", i, L.op == bh::OP_DWCONV ? "depthwise" : (L.op == bh::OP_GAP || L.op == bh::OP_POOL) ? "pool"
-                                                        : L.op == bh::OP_GCONV ? "grouped convolution" : "stem convolution");
-    }
-    rc = plan_fusion(c.get());
-    if (rc != BH_OK) return rc;
-    // f16 operand planes for the GEMM layers that stay outside the fused blocks (head conv, dense)
-    c->d_w16.assign(m.layers.size(), nullptr);
-    c->w16_unscale.assign(m.layers.size(), 1.0f);
-    c->w16_terms.assign(m.layers.size(), c->precision == 3 ? 3 : 1);
-    c->w16_bytes.assign(m.layers.size(), 0);
-    c->w16_kernel.reset(new std::atomic<const char *>[m.layers.size()]);
-    for (size_t i = 0; i < m.layers.size(); i++) c->w16_kernel[i].store(nullptr, std::memory_order_relaxed);
-    // Two-term products: decided by the data, per layer -- a layer whose lo plane is all zero AFTER BatchNormalization folding and
-    // the power-of-two pre-scale (a float16 model file's weights, or f16 values in any container) runs TERMS == 2 on compact planes,
-    // half the bytes; every other layer, and every layer under BH_FLAG_FULL_PLANES, BH_FLAG_F16 or BH_FLAG_F32, is what it was.
-    auto upload_planes = [&](size_t i, std::vector<uint16_t> planes, bool lo_zero) {
-        if (c->precision == 3 && lo_zero && !c->full_planes) { planes = w16_compact(planes); c->w16_terms[i] = 2; }
-        float *d = nullptr;
-        const int urc = upload(planes.data(), planes.size() * sizeof(uint16_t), &d);
-        if (urc != BH_OK) return urc;
-        c->d_owned.push_back(d);
-        c->d_w16[i] = d;
-        c->w16_bytes[i] = planes.size() * sizeof(uint16_t);
-        return (int)BH_OK;
-    };
-    if (c->precision != 0) {
-        // (a squeeze-excite block: its gate layers run in se_gate_kernel (f32 weights as they are), its project convolution on the
-        //  gated GEMM, which takes planes of ANY K % 4 == 0 (zero-padded to whole 32-deep steps))
-        std::vector<char> in_block(m.layers.size(), 0), se_project(m.layers.size(), 0);
-        for (size_t i = 0; i < m.layers.size(); i++)
-            if (c->fused_at[i] >= 0) {
-                const bh::MbDesc &d = c->mb[c->fused_at[i]];
-                const size_t last = fused_block_last(i, d);
-                for (size_t k = i; k <= last; k++) in_block[k] = 1;
-                if (d.se) { in_block[last] = 0; se_project[last] = 1; }
-            }
-        for (size_t i = 0; i < m.layers.size(); i++) {
-            const auto &L = m.layers[i];
-            if (L.op == bh::OP_CONV && L.in_layout == 0) {   // a full convolution: planes over the per-tap padded K
-                // (64 output channels or fewer stay on the f32 MFMA: the split-f16 kernel's 128-column tile would idle half or more
-                //  of its MFMAs there, and the f32 kernel is the faster -- 1.08 against 2.22 ms for 3x3 32 -> 32 at 64 x 249 x 256
-                //  segments, profiles/conv_gemm.txt -- and exact; shapes alone decide)
-                //  (a layer with its activation after the add: the same rule, over the activations THAT form is instantiated for)
-                if (!(res_act_after(L) ? bh::conv_gemm16_after_supports(conv_params(L)) : bh::conv_gemm16_supports(conv_params(L))) || L.cout <= 64) continue;
-                const uint32_t cpad = (uint32_t)align_up(L.cin, 32);
-                const std::vector<float> w = conv_gemm_rows(m.blob.data() + L.w_off, conv_params(L), (int)L.cout);
-                bool lo_zero = false;
-                std::vector<uint16_t> planes = w16_planes(w.data(), (int)(L.kh * L.kw * cpad), (int)L.cout, &c->w16_unscale[i], &lo_zero);
-                rc = upload_planes(i, std::move(planes), lo_zero);
-                if (rc != BH_OK) return rc;
-                continue;
-            }
-            if (L.op == bh::OP_GCONV) {   // planes over the per-tile K: three terms (f16x3 / auto, a float16 file included) or one, never two
-                int K = 0;
-                const std::vector<float> wt = gconv_matrix(m.blob.data() + L.w_off, conv_params(L), (int)L.reserved, &K);
-                std::vector<uint16_t> planes = w16_planes(wt.data(), K, (int)((L.cout + 15) / 16 * 16), &c->w16_unscale[i]);
-                float *d = nullptr;
-                rc = upload(planes.data(), planes.size() * sizeof(uint16_t), &d);
-                if (rc != BH_OK) return rc;
-                c->d_owned.push_back(d);
-                c->d_w16[i] = d;
-                c->w16_bytes[i] = planes.size() * sizeof(uint16_t);
-                continue;
-            }
-            if (in_block[i] || (L.op != bh::OP_PWCONV && L.op != bh::OP_DENSE)) continue;
-            // (activation after the add: the AFTER instantiations' activations, and the full convolutions' width rule -- 64 output
-            //  channels or fewer stay on the f32 MFMA -- so that the end of a ResNet block runs where its 3x3 twin would)
-            if (res_act_after(L)) { if (!bh::pw_gemm16_after_supports((int)L.cin, (int)L.act) || L.cout <= 64) continue; }
-            else
-            if (!(se_project[i] ? (L.cin % 4 == 0 && L.act == bh::ACT_NONE) : bh::pw_gemm16_supports((int)L.cin, (int)L.act))) continue;
-            bool lo_zero = false;
-            std::vector<uint16_t> planes = w16_planes(m.blob.data() + L.w_off, (int)L.cin, (int)L.cout, &c->w16_unscale[i], &lo_zero);
-            rc = upload_planes(i, std::move(planes), lo_zero);
-            if (rc != BH_OK) return rc;
-        }
-    }
-    // head conv + GELU followed by the global average pool (and read by nothing else): one launch
-    c->head_gap.assign(m.layers.size(), 0);
-    {
-        const char *hg = getenv("BIRDA_HIP_HEAD_GAP");
-        for (size_t i = 0; i + 1 < m.layers.size() && !(hg && hg[0] == '0'); i++) {
-            const auto &L = m.layers[i], &G = m.layers[i + 1];
-            if (!c->d_w16[i] || L.op != bh::OP_PWCONV || L.res_tensor != bh::NO_TENSOR || G.op != bh::OP_GAP ||
-                G.in_tensor != i + 1 || !bh::head_gap16_supports((int)(L.out_h * L.out_w), (int)L.cin, (int)L.cout, (int)L.act))
-                continue;
-            bool other_reader = m.h.embedding_tensor == i + 1;
-            for (size_t j = 0; j < m.layers.size(); j++)
-                if (j != i + 1 && (m.layers[j].in_tensor == i + 1 || m.layers[j].res_tensor == i + 1)) other_reader = true;
-            if (!other_reader) c->head_gap[i] = 1;
-        }
-    }
-    c->gap_gate.assign(m.layers.size(), 0);
-    for (size_t i = 0; i < m.layers.size(); i++) c->gap_gate[i] = gap_gate_chain(m, i) ? 1 : 0;
-    c->concat_chain.assign(m.layers.size(), 0);
-    for (size_t i = 0; i < m.layers.size(); i++) c->concat_chain[i] = (char)concat_chain_len(m, i);
-    c->sched = build_schedule(*c, true, true);
-    c->sched_layers = build_schedule(*c, false, false);
-    c->sched_keep_fused = build_schedule(*c, true, false);
-    if (const char *e = BH_XENV("BIRDA_HIP_MB_NARROW_MAX")) c->narrow_max_workgroups = atoi(e);   // (A/B aid: 0 = never)
-    if (const char *e = getenv("BIRDA_HIP_SE_GROUP_MB")) c->se_group_bytes = (size_t)atol(e) << 20;   // (MB of D per group of segments; 0: whole launches)
-    if (const char *st = BH_XENV("BIRDA_HIP_MB_STAMPS"); st && st[0] == '1' && !c->mb.empty()) {
-        HIPCHK(hipMalloc((void **)&c->d_stamps, c->mb.size() * 8 * sizeof(unsigned long long)));
-        HIPCHK(hipMemset(c->d_stamps, 0, c->mb.size() * 8 * sizeof(unsigned long long)));
-        for (size_t i = 0; i < c->mb.size(); i++) { c->mb[i].stamps = c->d_stamps + i * 8; c->mb_small[i].stamps = c->mb[i].stamps; c->mb_narrow[i].stamps = c->mb[i].stamps; }
-    }
-    *out = c.release();
-    return BH_OK;
-} catch (...) { return on_exception(); }
-
-void bh_classifier_destroy(bh_classifier *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->fb) { bh_classifier_destroy(c->fb); c->fb = nullptr; }
-    if (c->internal_ctx) ctx_destroy(c->internal_ctx);
-    for (bh_batch_context *p : c->parked_ctx)
-        if (p) ctx_destroy(p);
-    for (auto &ss : c->stream_sets)
-        for (auto &st : ss.s) if (st) { (void)hipStreamDestroy(st); st = nullptr; }
-    for (float *d : c->d_owned) (void)hipFree(d);
-    (void)hipFree(c->d_blob);
-    (void)hipFree(c->d_stamps);
-    (void)hipFree(c->d_class_score);
-    (void)hipFree(c->d_species_keep);
-    (void)hipFree(c->d_bsg);
-    delete c;
-}
 
 // ---- range filter / species list (reference classifier.rs:587-645) -------------------------
 int bh_classifier_set_range_filter(bh_classifier *c, const float *scores, size_t n_classes, float threshold,
@@ -1794,11 +1481,11 @@ int bh_classifier_weight_summary(const bh_classifier *c, uint64_t *out, size_t c
     if (!c) return fail(BH_ERR_INVALID, "weight_summary: null classifier");
     uint64_t v[BH_WS_COUNT] = {0};
     v[BH_WS_FLOAT16_FILE] = c->model.file_f16 ? 1 : 0;
-    for (size_t i = 0; i < c->d_w16.size(); i++) {
-        if (!c->d_w16[i]) continue;
+    for (const LayerState &S : c->layer) {
+        if (!S.planes) continue;
         v[BH_WS_GEMM_LAYERS]++;
-        v[BH_WS_PLANE_BYTES] += c->w16_bytes[i];
-        if (c->w16_terms[i] == 2) { v[BH_WS_TWO_TERM_LAYERS]++; v[BH_WS_TWO_TERM_PLANE_BYTES] += c->w16_bytes[i]; }
+        v[BH_WS_PLANE_BYTES] += S.plane_bytes;
+        if (S.terms == 2) { v[BH_WS_TWO_TERM_LAYERS]++; v[BH_WS_TWO_TERM_PLANE_BYTES] += S.plane_bytes; }
     }
     for (size_t i = 0; i < cap && i < (size_t)BH_WS_COUNT; i++)
         if (out) out[i] = v[i];
@@ -1808,16 +1495,16 @@ int bh_classifier_weight_summary(const bh_classifier *c, uint64_t *out, size_t c
 // per layer: the terms its split-f16 GEMM runs (1, 2 or 3), 0 for a layer without operand planes (inside a fused block, f32, ...)
 int bh_debug_layer_terms(const bh_classifier *c, int32_t *terms, size_t cap) {
     if (!c) return fail(BH_ERR_INVALID, "debug_layer_terms: null classifier");
-    for (size_t i = 0; i < c->d_w16.size() && i < cap; i++)
-        if (terms) terms[i] = c->d_w16[i] ? c->w16_terms[i] : 0;
-    return (int)c->d_w16.size();
+    for (size_t i = 0; i < c->layer.size() && i < cap; i++)
+        if (terms) terms[i] = c->layer[i].terms;
+    return (int)c->layer.size();
 }
 
 // the instantiation the split-f16 GEMM of `layer` launched last (a launcher's name string), "" before any forward / for a layer
 // that takes none of those launchers; a grouped convolution names its f32 kernel as well; returns its length
 int bh_debug_layer_kernel(const bh_classifier *c, uint32_t layer, char *out, size_t cap) {
-    if (!c || layer >= c->d_w16.size()) return fail(BH_ERR_INVALID, "debug_layer_kernel: bad arguments");
-    return copy_name(c->w16_kernel[layer].load(std::memory_order_relaxed), out, cap);
+    if (!c || layer >= c->layer.size()) return fail(BH_ERR_INVALID, "debug_layer_kernel: bad arguments");
+    return copy_name(c->layer[layer].kernel.load(std::memory_order_relaxed), out, cap);
 }
 
 int bh_plan_fused_blocks(const char *model_path, uint32_t flags, int32_t *cfgs, int32_t *layers, size_t cap) try {

@@ -82,17 +82,19 @@ int cc_upload_rows(bh_custom_classifier *cc, const float *rows, size_t n) {
 
 }  // namespace bhi
 
+// (of a half-built one too: whatever cc_build refuses, nothing stays on the device)
+bh_custom_classifier::~bh_custom_classifier() {
+    if (device < 0) return;
+    (void)hipSetDevice(device);
+    if (stream) { (void)hipStreamSynchronize(stream); (void)hipStreamDestroy(stream); }
+    for (float *p : d_owned) (void)hipFree(p);
+    for (float *p : d_act) (void)hipFree(p);
+    (void)hipFree(d_in); (void)hipFree(d_idx); (void)hipFree(d_conf);
+}
+
 extern "C" {
 
-void bh_custom_classifier_destroy(bh_custom_classifier *cc) {
-    if (!cc) return;
-    (void)hipSetDevice(cc->device);
-    if (cc->stream) { (void)hipStreamSynchronize(cc->stream); (void)hipStreamDestroy(cc->stream); }
-    for (float *p : cc->d_owned) (void)hipFree(p);
-    for (float *p : cc->d_act) (void)hipFree(p);
-    (void)hipFree(cc->d_in); (void)hipFree(cc->d_idx); (void)hipFree(cc->d_conf); (void)hipFree(cc->d_blob);
-    delete cc;
-}
+void bh_custom_classifier_destroy(bh_custom_classifier *cc) { delete cc; }
 
 // labels, device, stream, weights on the device: everything after the model itself has been read into cc->model
 static int cc_build(bh_custom_classifier *cc, const char *labels_path, int32_t device, uint32_t top_k, bool drop_blank_labels) {
@@ -120,7 +122,7 @@ static int cc_build(bh_custom_classifier *cc, const char *labels_path, int32_t d
     cc->top_k = top_k ? std::min<uint32_t>(top_k, BH_MAX_TOP_K) : std::min<uint32_t>(m.h.n_classes, BH_MAX_TOP_K);
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&cc->stream, hipStreamNonBlocking));
-    int rc = upload(m.blob.data(), m.blob.size() * sizeof(float), &cc->d_blob);
+    int rc = upload_owned(cc->d_owned, m.blob.data(), m.blob.size() * sizeof(float), &cc->d_blob);
     if (rc != BH_OK) return rc;
     cc->k0 = (uint32_t)align_up(m.h.input_dim, 4);
     cc->max_width = cc->k0;
@@ -136,11 +138,8 @@ static int cc_build(bh_custom_classifier *cc, const char *labels_path, int32_t d
         if (ld != (int)L.out_dim || (L.w_off % 4) || k_rows != L.in_dim) {   // rows padded / 16-byte aligned for the GEMM's loads
             std::vector<float> wp((size_t)k_rows * ld, 0.0f);
             for (uint32_t k = 0; k < L.in_dim; k++) memcpy(&wp[(size_t)k * ld], m.blob.data() + L.w_off + (size_t)k * L.out_dim, L.out_dim * sizeof(float));
-            float *d = nullptr;
-            rc = upload(wp.data(), wp.size() * sizeof(float), &d);
+            rc = upload_owned(cc->d_owned, wp.data(), wp.size() * sizeof(float), &w);
             if (rc != BH_OK) return rc;
-            cc->d_owned.push_back(d);
-            w = d;
         }
         cc->d_w.push_back(w);
         cc->ldw.push_back(ld);
@@ -152,7 +151,7 @@ int bh_custom_classifier_create(const char *model_path, const char *labels_path,
                                 bh_custom_classifier **out) try {
     if (!model_path || !out) return fail(BH_ERR_INVALID, "custom_classifier_create: null argument");
     *out = nullptr;
-    std::unique_ptr<bh_custom_classifier, void (*)(bh_custom_classifier *)> cc(new bh_custom_classifier(), bh_custom_classifier_destroy);
+    auto cc = std::make_unique<bh_custom_classifier>();
     std::string err;
     if (!bh::load_custom_model(model_path, cc->model, err)) return fail(BH_ERR_IO, "%s", err.c_str());
     if (cc->model.h.n_classes > BH_MAX_CLASSES)   // (a geomodel's scores are never ranked: bh_range_filter_create is not held to this)

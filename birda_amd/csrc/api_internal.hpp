@@ -1,7 +1,8 @@
 // api_internal.hpp -- what the translation units of the C ABI share.  Round 4 split the one 2 600-line api.hip (VERDICT r3 weak
 // #11) into
-//   api.hip         classifier / batch-context life cycle, the forward pass over a slice, lanes, the predict, PCM and resampler
-//                   entry points, and the diagnostics that read a classifier's or a context's state
+//   api.hip         the batch contexts, the forward pass over a slice, lanes, the predict, PCM and resampler entry points, and the
+//                   diagnostics that read a classifier's or a context's state
+//   api_create.hip  bh_classifier_create, phase by phase (config, front end, fused blocks, layers, schedules), and what undoes it
 //   api_plan.hip    host-side planning at create: the folded STFT x mel operator, the arena's liveness plan, the fused blocks'
 //                   descriptors, and every re-laid weight (the GEMM layers' rows, planes and fragments, the fused blocks')
 //   api_custom.hip  custom classifiers on embeddings (bat two-stage inference) and the geomodel range filter
@@ -11,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
@@ -58,6 +60,36 @@ enum Stage { ST_MINMAX = 0, ST_MEL, ST_STEM, ST_DW, ST_PW, ST_GAP, ST_DENSE, ST_
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// A device copy of a host buffer, owned by the object whose list `owned` is: its destructor frees the list, so whatever create
+// refuses afterwards, nothing is left on the device.  *dst is written on success only.
+template <class P> int upload_owned(std::vector<float *> &owned, const void *src, size_t bytes, P *dst) {
+    float *d = nullptr;
+    owned.reserve(owned.size() + 1);         // (so that nothing can fail between the allocation and its entry in the list)
+    HIPCHK(hipMalloc((void **)&d, bytes ? bytes : 4));
+    const hipError_t e = bytes ? hipMemcpy(d, src, bytes, hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) { (void)hipFree(d); return fail(BH_ERR_HIP, "hipMemcpy of %zu bytes to the device failed: %s", bytes, hipGetErrorString(e)); }
+    owned.push_back(d);
+    *dst = (P)d;
+    return BH_OK;
+}
+
+// What create has made of one layer (api_create.hip prepare_layer, plan_fusion, mark_paths): the weights its kernels read, and the
+// path it starts.  build_schedule (api_plan.hip) turns the marks into the schedules; SliceRun (api.hip) launches from the rest.
+struct LayerState {
+    float *w = nullptr;                      // f32 weights as the kernels want them: re-laid (owned), or the layer's part of d_blob
+    int ldw = 0;                             // padded row length of w (pw / dense / full convolutions)
+    void *planes = nullptr;                  // f16 hi / lo fragment planes (GEMM layers outside fused blocks), or null
+    float unscale = 1.0f;                    // 2^-s of those planes (they hold W * 2^s, kernels.hpp f16_scale_exponent)
+    int terms = 0;                           // the terms the planes are run with -- 3 (1 under BH_FLAG_F16), or 2 on compact planes; 0: no planes
+    size_t plane_bytes = 0;                  // device bytes of the planes
+    std::atomic<const char *> kernel{nullptr};   // what its GEMM / grouped / concat launcher launched last (a string literal), or null
+    int fused_at = -1;                       // index into mb (expand layer of a fused block) or -1 (plan_fusion's record)
+    char head_gap = 0;                       // 1 = this 1x1 conv + GELU and the global average pool after it run as one launch
+    // 1 = this pool layer and the two 1x1 layers after it (the gate of a squeeze-excite block that runs layer by layer) run as the two
+    char gap_gate = 0;                       // gate launches (gap_gate_chain): the pool's tensor holds the hidden partial sums until the gate is written
+    char concat_chain = 0;                   // records of the concat chain that starts here and runs as ONE launch (0: none; concat_chain_len)
+};
+
 // squeeze-excite gates of at least this many channels take the two-launch gate (launch_se_gate16) where it supports their shape
 #ifndef BH_SE_GATE16_MIN
 #define BH_SE_GATE16_MIN 577
@@ -82,37 +114,22 @@ enum { SE_POOLED = 0, SE_HIDDEN, SE_GATE, SE_SUMS };   // Step::scratch of a fus
 }  // namespace bhi
 
 struct bh_classifier {
+    ~bh_classifier();                        // (api_create.hip) releases everything below, of a half-built classifier too
     bh::Model model;
-    int device = 0;
+    int device = -1;                         // (-1: create has not reached the device yet)
     uint32_t top_k = 5;
     float min_conf = 0.1f;
     std::vector<std::string> labels;
-    float *d_blob = nullptr;                 // raw model blob (dw / conv weights, biases)
-    std::vector<float *> d_w;                // per layer: weights as the kernels want them
-    std::vector<int> ldw;                    // per layer: padded row length of d_w (pw / dense)
-    std::vector<void *> d_w16;               // per layer: f16 hi / lo fragment planes (pw / dense outside fused blocks), or null
-    std::vector<float> w16_unscale;          // per layer: 2^-s of those planes (they hold W * 2^s, kernels.hpp f16_scale_exponent)
-    std::vector<int> w16_terms;              // per layer: the terms its planes are run with -- 3 (1 under BH_FLAG_F16), or 2 on compact planes
-    std::vector<size_t> w16_bytes;           // per layer: device bytes of those planes
+    float *d_blob = nullptr;                 // raw model blob (dw / conv weights, biases); one of d_owned
+    std::vector<bhi::LayerState> layer;      // per layer, sized once at create (the record holds an atomic: it does not move)
     bool full_planes = false;                // BH_FLAG_FULL_PLANES: no layer takes two terms
-    std::unique_ptr<std::atomic<const char *>[]> w16_kernel;   // per layer: what its split-f16 launcher launched last (a string literal), or null
-    // The per-path decisions of create, as made: build_schedule (api_plan.hip) turns them into the schedules below, and nothing
-    // but it and the exported queries reads them afterwards.
-    std::vector<char> head_gap;              // per layer: 1 = this 1x1 conv + GELU and the global average pool after it run as one launch
-    // per layer: 1 = this pool layer and the two 1x1 layers after it (a squeeze-excite gate of a block that runs layer by layer) run as
-    // the two gate launches (launch_se_gate16): the pool layer's tensor holds the hidden partial sums until the gate is written
-    // (gap_gate_chain)
-    std::vector<char> gap_gate;
-    // records of the concat chain that starts at layer i and runs as ONE launch (0: none; concat_chain_len)
-    std::vector<char> concat_chain;
     // What a forward launches: the product's schedule (fused blocks, head conv + pool, the gate fast path), the layer-by-layer one of
     // BIRDA_HIP_KEEP_TENSORS contexts, and the one of debug contexts that still run the fused blocks (BIRDA_HIP_KEEP_FUSED)
     std::vector<bhi::Step> sched, sched_layers, sched_keep_fused;
-    std::vector<float *> d_owned;            // re-laid buffers to free
+    std::vector<float *> d_owned;            // every upload_owned buffer: the blob, the re-laid weights, the front-end operators
     bh::FrontendParams fe{};
     bh::FrontendParams *d_fe = nullptr;      // device copy read by the mel kernel
     std::atomic<const char *> fe_kernel{nullptr};   // what launch_mel launched last (a string literal); nullptr before any forward
-    std::vector<int> fused_at;               // per layer: index into mb (expand layer of a fused block) or -1 (plan_fusion's record)
     std::vector<bh::MbDesc> mb;              // fused MBConv blocks (kernels_mbconv.hip)
     int twin_max_segments = 256;             // launches up to this size take the twins (one workgroup per CU at most either way)
     std::vector<bh::MbDesc> mb_small;        // per block: its small-launch twin (cfg < 0: none), same weights (mb_plan_twin)
@@ -218,6 +235,7 @@ struct GatherPool {
 };
 
 struct bh_batch_context {
+    ~bh_batch_context();                     // (api.hip) frees the buffers, hands the stream set back; of a half-built context too
     bh_classifier *c = nullptr;
     std::unique_ptr<GatherPool> pool;        // (created by the first host-fed call that wants workers)
     size_t max_batch = 0;        // what the buffers hold
@@ -283,14 +301,15 @@ struct bh_batch_context {
 
 // api_custom.hip: a dense stack on embeddings (custom classifier) or on (latitude, longitude, week) (the geomodel)
 struct bh_custom_classifier {
+    ~bh_custom_classifier();
     bh::CustomModel model;
-    int device = 0;
+    int device = -1;              // (-1: create has not reached the device yet)
     uint32_t top_k = 0;
     std::vector<std::string> labels;
     float *d_blob = nullptr;
     std::vector<float *> d_w;     // per layer: W with rows padded to a multiple of 4 (or a pointer into d_blob)
     std::vector<int> ldw;
-    std::vector<float *> d_owned;
+    std::vector<float *> d_owned; // every upload_owned buffer, the blob included
     // scratch, grown on demand: activations of the two widest layers, logits, top-k rows, host copies
     float *d_act[2] = {nullptr, nullptr};
     float *d_in = nullptr;
@@ -335,6 +354,13 @@ std::vector<float> gconv_fragments(const std::vector<float> &wt, int K, int nt);
 std::vector<float> pw_gemm_rows(const float *W, size_t K, size_t N, size_t ld);
 int plan_fusion(bh_classifier *c);
 // api.hip
+constexpr uint32_t FLAG_INTERNAL_NO_ENV = 0x80000000u;   // (the fallback classifier: BIRDA_HIP_PRECISION must not turn it into f16 again)
+bool res_act_after(const bh::LayerRec &L);
+bh::ConvParams conv_params(const bh::LayerRec &L);
+std::array<bh::ConcatSource, 2> concat_sources(const bh::Model &m, const bh::LayerRec &L, const float *a, const float *b);
+bool load_any_model(const char *path, bh::Model &m, std::string &err);
+int model_load_status(const std::string &err);
+inline void ctx_destroy(bh_batch_context *ctx) { delete ctx; }
 int se_gate_form(int C, int Cr);
 int mb_ksplit_of(const bh::MbDesc &d);
 int resample_ranges(const char *who, size_t src_len, size_t out_len, size_t n_seg);
@@ -344,7 +370,6 @@ inline int copy_name(const char *name, char *out, size_t cap) {
     if (out && cap > n) { if (n) memcpy(out, name, n); out[n] = 0; }
     return (int)n;
 }
-int upload(const void *src, size_t bytes, float **dst);
 int read_labels(const char *path, std::vector<std::string> &out);
 int check_ctx(bh_classifier *c, bh_batch_context *ctx);
 int predict_slices(bh_classifier *c, bh_batch_context *ctx, const float *const *segments, const float *contig,

@@ -90,8 +90,8 @@ std::vector<float> build_gf(const bh::BranchRec &b, const float *W, int nm_pad, 
                 }
     return frag;
 }
-// What a forward launches, from the decisions create has made (plan_fusion: fused_at / mb / se; head_gap; gap_gate): no decision is
-// made here.  fused: the fused blocks run as such; chains: so do head conv + pool and the gate fast path.
+// What a forward launches, from the decisions create has made (plan_fusion: LayerState::fused_at / mb / se; api_create.hip mark_paths:
+// head_gap, gap_gate, concat_chain): no decision is made here.  fused: the fused blocks run as such; chains: so do head conv + pool and the gate fast path.
 std::vector<Step> build_schedule(const bh_classifier &c, bool fused, bool chains) {
     const auto &m = c.model;
     const uint32_t nl = (uint32_t)m.layers.size();
@@ -99,9 +99,9 @@ std::vector<Step> build_schedule(const bh_classifier &c, bool fused, bool chains
     for (uint32_t i = 0; i < nl; i++) {
         Step st;
         st.first = st.last = i;
-        if (fused && c.fused_at[i] >= 0) {
+        if (fused && c.layer[i].fused_at >= 0) {
             // one launch reads the block input while it writes the project's output; the tensors in between stay in LDS
-            st.block = c.fused_at[i];
+            st.block = c.layer[i].fused_at;
             st.path = c.mb[st.block].se ? BH_PATH_FUSED_SE : BH_PATH_FUSED;
             st.last = (uint32_t)fused_block_last(i, c.mb[st.block]);
             if (c.mb[st.block].se) {
@@ -113,23 +113,23 @@ std::vector<Step> build_schedule(const bh_classifier &c, bool fused, bool chains
                 st.writes = {S.iD + 1};
                 st.scratch = {{S.iGap + 1, 0}, {S.iPw1 + 1, 0}, {S.iPw2 + 1, 0}, {S.iScale + 1, S.part_floats}};
             }
-        } else if (chains && c.head_gap[i]) {
+        } else if (chains && c.layer[i].head_gap) {
             // head conv + pool in one launch: workgroups still read the conv's input while finished ones store pooled rows; the
             // conv's output never exists
             st.path = BH_PATH_HEAD_GAP;
             st.last = i + 1;
-        } else if (chains && c.gap_gate[i]) {
+        } else if (chains && c.layer[i].gap_gate) {
             // the gate of a block that runs layer by layer in two launches (gap_gate_chain): se_hidden_kernel reads the pool's input
             // and writes its partial sums into the pool layer's tensor, se_gate16_kernel reads them while it writes the gate -- the
             // same n x C floats.  (The hidden layer's slot is kept as well: its values stay in LDS.)
             st.path = BH_PATH_SE_GATE;
             st.last = i + 2;
             st.scratch = {{i + 1, 0}, {i + 2, 0}};
-        } else if (chains && c.concat_chain[i]) {
+        } else if (chains && c.layer[i].concat_chain) {
             // an N-way Concat: one launch gathers the leaves straight into the last record's tensor; the records' own outputs in
             // between never exist (they get no bytes, as a fused block's inner tensors get none)
             st.path = BH_PATH_CONCAT;
-            st.last = i + (uint32_t)c.concat_chain[i] - 1;
+            st.last = i + (uint32_t)c.layer[i].concat_chain - 1;
         }
         st.reads = {m.layers[i].in_tensor};
         if (st.path == BH_PATH_CONCAT) {          // every leaf: A of the first record, then every record's B
@@ -608,10 +608,10 @@ void mb_prepare_weights(bh::MbDesc &d, const float *We, const float *be, const f
 }
 
 // Prepares a fused launch for every block describe_fused_block accepts (weights re-laid fragment-major for the picked tile config).
+// It reads the model and d_blob alone, so create runs it before the layers: whether a layer takes planes depends on its result.
 int plan_fusion(bh_classifier *c) {
     const auto &m = c->model;
     const size_t nl = m.layers.size();
-    c->fused_at.assign(nl, -1);
     const char *fuse_env = getenv("BIRDA_HIP_FUSE");
     if (fuse_env && fuse_env[0] == '0') return BH_OK;
     const char *cfg_env = getenv("BIRDA_HIP_MB_CFG");
@@ -627,27 +627,14 @@ int plan_fusion(bh_classifier *c) {
         MbHostWeights hw;
         mb_prepare_weights(d, m.blob.data() + E.w_off, m.blob.data() + E.b_off, m.blob.data() + D.w_off, m.blob.data() + D.b_off,
                            m.blob.data() + P.w_off, m.blob.data() + P.b_off, hw);
-        const std::vector<float> &wef = hw.we, &wpf = hw.wp, &wdf = hw.wd;
-        float *dwe = nullptr, *dwp = nullptr, *dwd = nullptr;
-        int rc = upload(wef.data(), wef.size() * sizeof(float), &dwe);
-        if (rc != BH_OK) return rc;
-        c->d_owned.push_back(dwe);
-        rc = upload(wpf.data(), wpf.size() * sizeof(float), &dwp);
-        if (rc != BH_OK) return rc;
-        c->d_owned.push_back(dwp);
-        rc = upload(wdf.data(), wdf.size() * sizeof(float), &dwd);
-        if (rc != BH_OK) return rc;
-        c->d_owned.push_back(dwd);
-        d.We = dwe; d.Wp = dwp; d.Wd = dwd;
+        auto own = [&](const std::vector<float> &v, const float **dst) { return upload_owned(c->d_owned, v.data(), v.size() * sizeof(float), dst); };
         d.bp = c->d_blob + P.b_off;
-        if (hw.spa != 0) {   // bp * 2^spa (mb_prepare_weights)
-            float *dbp = nullptr;
-            rc = upload(hw.bp.data(), hw.bp.size() * sizeof(float), &dbp);
-            if (rc != BH_OK) return rc;
-            c->d_owned.push_back(dbp);
-            d.bp = dbp;
-        }
-        c->fused_at[i] = (int)c->mb.size();
+        int rc = own(hw.we, &d.We);
+        if (rc == BH_OK) rc = own(hw.wp, &d.Wp);
+        if (rc == BH_OK) rc = own(hw.wd, &d.Wd);
+        if (rc == BH_OK && hw.spa != 0) rc = own(hw.bp, &d.bp);   // bp * 2^spa (mb_prepare_weights)
+        if (rc != BH_OK) return rc;
+        c->layer[i].fused_at = (int)c->mb.size();
         c->mb.push_back(d);
         {
             bh::MbDesc tw{};

@@ -250,7 +250,7 @@ def case_segments(c):
 
 
 def plan_kernel(c):
-    """bh_classifier_create's choice restated (api.hip): the test module on the GPU holds it to what launch_mel reports"""
+    """bh_classifier_create's choice restated (api_create.hip build_front_end): the test module on the GPU holds it to what launch_mel reports"""
     nm_pad = (c["n_mels"] + 15) // 16 * 16
     prec = 0 if c["prec"] == "f32" else 3
     if any(L % 256 for L, _ in c["branches"]):
