@@ -251,11 +251,12 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
             else:
                 w = m.weight(L.w_off, L.cin * L.cout).reshape(L.cin, L.cout).T[:, :, None, None]
                 group = 1
-            pad_b = max((L.out_h - 1) * L.sh + L.kh - L.in_h - L.pad_t, 0)
-            pad_r = max((L.out_w - 1) * L.sw + L.kw - L.in_w - L.pad_l, 0)
+            # (a dilated layer -- OP_CONV on an NHWC tensor, OP_DWCONV -- spans (k - 1) dil + 1 pixels; either reader reads the attribute back)
+            pad_b = max((L.out_h - 1) * L.sh + (L.kh - 1) * L.dil_h + 1 - L.in_h - L.pad_t, 0)
+            pad_r = max((L.out_w - 1) * L.sw + (L.kw - 1) * L.dil_w + 1 - L.in_w - L.pad_l, 0)
             g.nodes.append(ox.Node("Conv", [x, const(tag + "_w", w), const(tag + "_b", m.weight(L.b_off, L.cout))], [tag + "_conv"],
                                    {"group": group, "kernel_shape": [L.kh, L.kw], "strides": [L.sh, L.sw],
-                                    "pads": [L.pad_t, L.pad_l, pad_b, pad_r], "dilations": [1, 1]}, name=tag))
+                                    "pads": [L.pad_t, L.pad_l, pad_b, pad_r], "dilations": [L.dil_h, L.dil_w]}, name=tag))
             y = tag + "_conv"
             if L.res_tensor != mf.NO_TENSOR and L.reserved == mf.RES_ACT_AFTER and L.op != mf.OP_DWCONV:
                 # act(conv + residual), the end of a ResNet block: Conv -> Add -> activation
@@ -845,26 +846,41 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             B = g.initializers.get(n.inputs[2]) if len(n.inputs) > 2 else np.zeros(cout, np.float32)
             group = int(n.attrs.get("group", 1))
             sh, sw = (n.attrs.get("strides") or [1, 1])
-            if any(d != 1 for d in (n.attrs.get("dilations") or [1, 1])):
-                raise ConvertError(f"Conv {n.name!r}: dilation")
+            # dilation (csrc/onnx_conv.hpp has the same branch, refusal for refusal): a group-1 convolution of an NHWC activation or a
+            # depthwise one, 1 .. 16 per axis; an axis with one tap is dilation 1 whatever the file says (one spelling of the record)
+            dil = [int(d) for d in (n.attrs.get("dilations") or [1, 1])]
+            if any(d != 1 for d in dil) and len(dil) != 2:
+                raise ConvertError(f"Conv {n.name!r}: dilations must be two values")
+            dh, dw = dil if len(dil) == 2 else (1, 1)
+            if not (1 <= dh <= mf.MAX_DILATION and 1 <= dw <= mf.MAX_DILATION):
+                raise ConvertError(f"Conv {n.name!r}: dilation {dh}x{dw} (1 .. 16 are supported)")
+            dh, dw = (1 if kh == 1 else dh), (1 if kw == 1 else dw)
+            if (dh, dw) != (1, 1):
+                if t_in == 0:
+                    raise ConvertError(f"Conv {n.name!r}: dilation on the stem convolution (the spectrogram, tensor 0) is not supported")
+                if group != 1 and not (group == cin and cin_g == 1 and cout == cin):
+                    raise ConvertError(f"Conv {n.name!r}: dilation on a grouped convolution is not supported")
+            ekh, ekw = (kh - 1) * dh + 1, (kw - 1) * dw + 1        # the window's extent over the image
             oh, ow = -(-h // sh), -(-w // sw)
             auto = n.attrs.get("auto_pad", "NOTSET")
             if auto in ("SAME_UPPER", "SAME_LOWER"):
-                th, tw = max((oh - 1) * sh + kh - h, 0), max((ow - 1) * sw + kw - w, 0)
+                th, tw = max((oh - 1) * sh + ekh - h, 0), max((ow - 1) * sw + ekw - w, 0)
                 pt, pl = (th // 2, tw // 2) if auto == "SAME_UPPER" else (th - th // 2, tw - tw // 2)
             else:
                 pads = n.attrs.get("pads") or [0, 0, 0, 0]
                 pt, pl = pads[0], pads[1]
-                oh, ow = (h + pads[0] + pads[2] - kh) // sh + 1, (w + pads[1] + pads[3] - kw) // sw + 1
+                if h + pads[0] + pads[2] < ekh or w + pads[1] + pads[3] < ekw:
+                    raise ConvertError(f"Conv {n.name!r}: kernel larger than the padded input")
+                oh, ow = (h + pads[0] + pads[2] - ekh) // sh + 1, (w + pads[1] + pads[3] - ekw) // sw + 1
             if group == 1 and kh == 1 and kw == 1 and sh == 1 and sw == 1:
                 L = mf.Layer(mf.OP_PWCONV, mf.ACT_NONE, t_in, mf.NO_TENSOR, cin, cout, 1, 1, 1, 1, 0, 0, h, w, h, w, 0,
                              blob.put(W[:, :, 0, 0].T), blob.put(B))
             elif group == cin and cin_g == 1 and cout == cin:
                 L = mf.Layer(mf.OP_DWCONV, mf.ACT_NONE, t_in, mf.NO_TENSOR, cin, cout, kh, kw, sh, sw, pt, pl, h, w, oh, ow, 0,
-                             blob.put(W[:, 0].transpose(1, 2, 0)), blob.put(B))
+                             blob.put(W[:, 0].transpose(1, 2, 0)), blob.put(B), dil_h=dh, dil_w=dw)
             elif group == 1:
                 L = mf.Layer(mf.OP_CONV, mf.ACT_NONE, t_in, mf.NO_TENSOR, cin, cout, kh, kw, sh, sw, pt, pl, h, w, oh, ow,
-                             1 if t_in == 0 else 0, blob.put(W.transpose(2, 3, 1, 0)), blob.put(B))
+                             1 if t_in == 0 else 0, blob.put(W.transpose(2, 3, 1, 0)), blob.put(B), dil_h=dh, dil_w=dw)
             else:
                 # a grouped convolution -> OP_GCONV (csrc/onnx_conv.hpp has the same branch, refusal for refusal)
                 who = f"Conv {n.name!r}: group {group} with {cin} -> {cout} channels"

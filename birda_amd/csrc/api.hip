@@ -49,7 +49,8 @@ bool res_act_after(const bh::LayerRec &L) {
 
 bh::ConvParams conv_params(const bh::LayerRec &L) {
     return bh::ConvParams{(int)L.in_h, (int)L.in_w, (int)L.out_h, (int)L.out_w, (int)L.cin, (int)L.cout, (int)L.kh, (int)L.kw,
-                          (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l, (int)L.in_layout, (int)L.act, res_act_after(L) ? 1 : 0};
+                          (int)L.sh, (int)L.sw, (int)L.pad_t, (int)L.pad_l, (int)L.in_layout, (int)L.act, res_act_after(L) ? 1 : 0,
+                          (int)L.skip_h + 1, (int)L.skip_w + 1};   // (the record holds dilation - 1: model.hpp)
 }
 
 // The sources of an OP_CONCAT record as launch_concat takes them (model.hpp: w_off / b_off are channel offsets there, res_tensor a
@@ -266,7 +267,8 @@ int SliceRun::layer(const Step &st) const {
     default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
     }
     // (bh_debug_layer_kernel: the split-f16 launchers' names; a grouped convolution's and a concat's f32 kernels are kept too)
-    if (f16 || L.op == bh::OP_GCONV || L.op == bh::OP_CONCAT) S.kernel.store(launched, std::memory_order_relaxed);
+    // (... and a dilated depthwise layer's, the dilated form of dwconv_kernel)
+    if (f16 || L.op == bh::OP_GCONV || L.op == bh::OP_CONCAT || (L.op == bh::OP_DWCONV && bh::conv_dilated(p))) S.kernel.store(launched, std::memory_order_relaxed);
     // (create's predicates and validate_model keep this from happening; if it does, the output tensor was not written)
     if (!launched && n) {
         if (L.op == bh::OP_DWCONV || (L.op == bh::OP_CONV && L.in_layout == 1))

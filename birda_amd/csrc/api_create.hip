@@ -161,17 +161,18 @@ int prepare_layer(bh_classifier *c, size_t i, bool in_block, bool se_project) {
     }
     case bh::OP_DWCONV:
         if (!bh::dwconv_supports(p))
-            return fail(BH_ERR_UNSUPPORTED, "layer %zu: depthwise %ux%u stride %u channels %u not built", i, L.kh, L.kw, L.sh, L.cout);
+            return fail(BH_ERR_UNSUPPORTED, "layer %zu: depthwise %ux%u stride %u dilation %dx%d channels %u not built", i, L.kh, L.kw, L.sh, p.dil_h, p.dil_w, L.cout);
         return BH_OK;
     case bh::OP_CONV: {
         if (L.in_layout == 1) {   // the NCHW stem: the direct kernel, weights in LDS
+            if (bh::conv_dilated(p)) return fail(BH_ERR_UNSUPPORTED, "layer %zu: dilation %dx%d on the NCHW stem convolution is not built", i, p.dil_h, p.dil_w);
             if (!bh::conv_direct_supports(p)) return fail(BH_ERR_UNSUPPORTED, "layer %zu: direct conv shape not built", i);
             return BH_OK;
         }
         // NHWC: the implicit GEMM, W rows padded per tap to whole 32-deep steps
         if (!bh::conv_gemm_supports(p))
-            return fail(BH_ERR_UNSUPPORTED, "layer %zu: full convolution %ux%u stride %ux%u, %u -> %u channels, layout %u not built "
-                        "(kernel 1..7, stride 1 / 2, channels multiples of 4, NHWC)", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout, L.in_layout);
+            return fail(BH_ERR_UNSUPPORTED, "layer %zu: full convolution %ux%u stride %ux%u dilation %dx%d, %u -> %u channels, layout %u not built "
+                        "(kernel 1..7, stride 1 / 2, dilation 1..16, channels multiples of 4, NHWC)", i, L.kh, L.kw, L.sh, L.sw, p.dil_h, p.dil_w, L.cin, L.cout, L.in_layout);
         S.ldw = (int)align_up(L.cout, 4);
         const int rc = own_rows(conv_gemm_rows(W, p, S.ldw));
         if (rc != BH_OK) return rc;

@@ -13,6 +13,7 @@
 #include "../../include/birda_hip_resample_debug.h"
 #include "../../include/birda_hip_custom_debug.h"
 #include "../../include/birda_hip_gated_debug.h"
+#include "../../include/birda_hip_dilated_debug.h"
 
 using namespace bhi;
 
@@ -237,18 +238,22 @@ int bh_debug_gated_gemm_f32(int device, const float *A, const float *gate, const
 // One full convolution on the implicit-GEMM kernels, on operands of the caller's, with the weight preparation create does
 // (conv_gemm_rows, w16_planes) -- tests drive every shape, precision and epilogue instantiation without a model around it.
 // (after != 0: bh_debug_conv_gemm_after, include/birda_hip_resact_debug.h -- the activation after the residual add)
+// (dil_h, dil_w: bh_debug_dilated_layer, include/birda_hip_dilated_debug.h -- the taps' pitch; 1, 1 from the other two entry points)
 static int debug_conv_gemm(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
-                           const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap, int after) {
+                           const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap, int after, int dil_h = 1, int dil_w = 1) {
     if (!X || !W || !bias || !C || !shape || !n_seg || (terms != 0 && terms != 1 && terms != 2 && terms != 3) || act < 0 || act > bh::ACT_LAST)
         return fail(BH_ERR_INVALID, "debug_conv_gemm: bad arguments");
     if (after && !R) return fail(BH_ERR_INVALID, "debug_conv_gemm_after: the residual R is required");
-    const bh::ConvParams p = shape_params(shape, false, 4, 0, act, after ? 1 : 0);
+    bh::ConvParams p = shape_params(shape, false, 4, 0, act, after ? 1 : 0);
+    p.dil_h = dil_h; p.dil_w = dil_w;
     if (p.in_h < 1 || p.in_w < 1 || p.out_h < 1 || p.out_w < 1)
         return fail(BH_ERR_INVALID, "debug_conv_gemm: image %dx%d -> %dx%d", p.in_h, p.in_w, p.out_h, p.out_w);
+    if ((p.kh == 1 && p.dil_h != 1) || (p.kw == 1 && p.dil_w != 1))   // (validate_model: one spelling of the undilated axis)
+        return fail(BH_ERR_UNSUPPORTED, "debug_conv_gemm: dilation %dx%d on a %dx%d kernel: an axis with one tap is dilation 1", p.dil_h, p.dil_w, p.kh, p.kw);
     if (after ? (terms ? !bh::conv_gemm16_after_supports(p) : (!bh::conv_gemm_supports(p) || act == bh::ACT_NONE))
               : (terms ? !bh::conv_gemm16_supports(p) : !bh::conv_gemm_supports(p)))
-        return fail(BH_ERR_UNSUPPORTED, "debug_conv_gemm%s: %dx%d stride %dx%d pad %d,%d, %d -> %d channels, %s not built for terms %d",
-                    after ? "_after" : "", p.kh, p.kw, p.sh, p.sw, p.pad_t, p.pad_l, p.cin, p.cout, act_name(act), terms);
+        return fail(BH_ERR_UNSUPPORTED, "debug_conv_gemm%s: %dx%d stride %dx%d pad %d,%d dilation %dx%d, %d -> %d channels, %s not built for terms %d",
+                    after ? "_after" : "", p.kh, p.kw, p.sh, p.sw, p.pad_t, p.pad_l, p.dil_h, p.dil_w, p.cin, p.cout, act_name(act), terms);
     const size_t M = n_seg * (size_t)p.out_h * p.out_w, x_floats = n_seg * (size_t)p.in_h * p.in_w * p.cin;
     if (M * (size_t)p.cout > (size_t)INT32_MAX || x_floats > (size_t)INT32_MAX)
         return fail(BH_ERR_INVALID, "debug_conv_gemm: tensors past 2^31 elements");
@@ -275,6 +280,40 @@ int bh_debug_conv_gemm(int device, const float *X, const float *W, const float *
 int bh_debug_conv_gemm_after(int device, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
                              const int32_t *shape, int act, int terms, char *kernel, size_t kernel_cap) try {
     return debug_conv_gemm(device, X, W, bias, R, C, n_seg, shape, act, terms, kernel, kernel_cap, 1);
+} catch (...) { return on_exception(); }
+
+// One dilated layer alone (include/birda_hip_dilated_debug.h): a full convolution through debug_conv_gemm with the taps' pitch, or a
+// depthwise one through launch_dwconv, refusing what validate_model and create refuse.
+int bh_debug_dilated_layer(int device, int op, const float *X, const float *W, const float *bias, const float *R, float *C, size_t n_seg,
+                           const int32_t *shape, int act, int terms, int after, char *kernel, size_t kernel_cap) try {
+    if (!shape || (op != bh::OP_CONV && op != bh::OP_DWCONV)) return fail(BH_ERR_INVALID, "debug_dilated_layer: op %d is neither a full nor a depthwise convolution", op);
+    const int dil_h = shape[12], dil_w = shape[13];
+    if (op == bh::OP_CONV) return debug_conv_gemm(device, X, W, bias, R, C, n_seg, shape, act, terms, kernel, kernel_cap, after ? 1 : 0, dil_h, dil_w);
+    if (!X || !W || !bias || !C || !n_seg || n_seg > (size_t)INT32_MAX || act < 0 || act > bh::ACT_LAST || R || terms || after)
+        return fail(BH_ERR_INVALID, "debug_dilated_layer: a depthwise layer takes X, W, bias and C, no residual, terms 0");
+    bh::ConvParams p = shape_params(shape, false, 4, 0, act, 0);
+    p.dil_h = dil_h; p.dil_w = dil_w;
+    // (validate_model's ranges)
+    if (p.in_h < 1 || p.in_w < 1 || p.out_h < 1 || p.out_w < 1 || p.in_h > 65536 || p.in_w > 65536 || p.out_h > 65536 || p.out_w > 65536 || p.cout < 1 ||
+        p.cout > (1 << 24) || p.cin != p.cout || p.kh < 1 || p.kw < 1 || p.kh > 64 || p.kw > 64 || p.sh < 1 || p.sw < 1 || p.sh > 16 || p.sw > 16 ||
+        p.pad_t < 0 || p.pad_l < 0 || p.pad_t > 64 || p.pad_l > 64)
+        return fail(BH_ERR_INVALID, "debug_dilated_layer: layer dimensions out of range");
+    if (p.dil_h < 1 || p.dil_w < 1 || p.dil_h > (int)bh::MAX_DILATION || p.dil_w > (int)bh::MAX_DILATION)
+        return fail(BH_ERR_UNSUPPORTED, "debug_dilated_layer: dilation %dx%d (1 .. 16 are supported)", p.dil_h, p.dil_w);
+    if (!bh::dwconv_supports(p))
+        return fail(BH_ERR_UNSUPPORTED, "debug_dilated_layer: depthwise %dx%d stride %dx%d dilation %dx%d channels %d not built (square 3x3 / 5x5 windows, one "
+                    "stride of 1 or 2, channels a multiple of 4)", p.kh, p.kw, p.sh, p.sw, p.dil_h, p.dil_w, p.cout);
+    const size_t x_seg = (size_t)p.in_h * p.in_w * p.cout, y_seg = (size_t)p.out_h * p.out_w * p.cout;
+    if (x_seg > (size_t)INT32_MAX || y_seg > (size_t)INT32_MAX || n_seg * x_seg > (size_t)INT32_MAX || n_seg * y_seg > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_dilated_layer: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    DebugLaunch h{"debug_dilated_layer"};
+    const float *dx = h.in(X, n_seg * x_seg * 4), *dwt = h.in(W, (size_t)p.kh * p.kw * p.cout * 4), *db = h.in(bias, (size_t)p.cout * 4);
+    float *dy = h.out(n_seg * y_seg, "C", C);
+    if (!h.ok) return h.no_memory();
+    const char *name = bh::launch_dwconv(dx, dwt, db, dy, p, (int)n_seg, nullptr);
+    if (!name) return fail(BH_ERR_INTERNAL, "debug_dilated_layer: the launcher has no instantiation for a shape dwconv_supports accepts");
+    return h.finish(name, kernel, kernel_cap);
 } catch (...) { return on_exception(); }
 
 // One grouped convolution alone on operands of the caller's, with create's weight preparation (gconv_matrix, gconv_fragments,

@@ -191,6 +191,11 @@ void plan_arena(const bh::Model &m, const std::vector<Step> &sched, size_t max_b
         total = std::max(total, pos + sz[t]);
     }
 }
+// A record with dilation (model.hpp skip_h / skip_w) is never part of a launch that stands for several layers: the fused tile kernel's
+// depthwise phase, pass A of a squeeze-excite block, the channel split of a low-latency launch (a fused launch, split) and the gate
+// launches all compute the undilated layer.  Every matcher below asks here; such a block runs layer by layer.
+static bool layer_dilated(const bh::LayerRec &L) { return L.skip_h != 0 || L.skip_w != 0; }
+
 // The pool layer i opens a squeeze-excite gate that runs as the two gate launches (se_hidden_kernel, se_gate16_kernel) instead of pool
 // + two GEMMs: an image of at most 64 pixels, at least BH_SE_GATE16_MIN channels, pool -> 1x1 (C -> Cr) -> 1x1 (Cr -> C) with no
 // other reader of the pooled or the hidden tensor, and a shape se_gate16 supports.  Shapes alone decide; the answer is recorded in
@@ -200,6 +205,7 @@ bool gap_gate_chain(const bh::Model &m, size_t i) {
     if (i + 2 >= nl) return false;
     const auto &L = m.layers[i], &G1 = m.layers[i + 1], &G2 = m.layers[i + 2];
     if (L.op != bh::OP_GAP || L.in_h * L.in_w > 64 || L.cout < BH_SE_GATE16_MIN) return false;
+    if (layer_dilated(L) || layer_dilated(G1) || layer_dilated(G2)) return false;   // (validate_model refuses such records; the matcher does not rely on it)
     bool ok = G1.op == bh::OP_PWCONV && G2.op == bh::OP_PWCONV && G1.in_h * G1.in_w == 1 && G2.in_h * G2.in_w == 1 &&
               G1.in_tensor == i + 1 && G2.in_tensor == i + 2 && G1.res_tensor == bh::NO_TENSOR && G2.res_tensor == bh::NO_TENSOR &&
               G1.cin == L.cout && G2.cin == G1.cout && G2.cout == L.cout && m.h.embedding_tensor != i + 1 && m.h.embedding_tensor != i + 2 &&
@@ -275,6 +281,7 @@ bool match_se_block(const bh::Model &m, const std::vector<int> &readers, size_t 
     if (iD + 5 >= nl) return false;
     const auto &D = m.layers[iD], &G = m.layers[iD + 1], &A1 = m.layers[iD + 2], &A2 = m.layers[iD + 3], &SC = m.layers[iD + 4], &P = m.layers[iD + 5];
     if (D.op != bh::OP_DWCONV || G.op != bh::OP_GAP || A1.op != bh::OP_PWCONV || A2.op != bh::OP_PWCONV || SC.op != bh::OP_SCALE || P.op != bh::OP_PWCONV) return false;
+    if (layer_dilated(D)) return false;   // pass A's depthwise phase is the undilated layer: the block runs layer by layer
     const uint32_t tD = (uint32_t)iD + 1;   // the depthwise output tensor
     if (G.in_tensor != tD || A1.in_tensor != iD + 2 || A2.in_tensor != iD + 3 || SC.in_tensor != tD || SC.res_tensor != iD + 4 || P.in_tensor != iD + 5) return false;
     if (readers[tD] != 2 || readers[iD + 2] != 1 || readers[iD + 3] != 1 || readers[iD + 4] != 1 || readers[iD + 5] != 1) return false;
@@ -339,7 +346,7 @@ bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, s
         // first): fused with the block input standing in for the expanded tensor (MbDesc::noexp)
         const auto &D = m.layers[i], &P = m.layers[i + 1];
         if (P.in_tensor != i + 1 || readers[i + 1] != 1 || D.res_tensor != bh::NO_TENSOR) return false;
-        if (D.kh != D.kw || D.sh != D.sw || D.cout != P.cin || D.in_layout != 0) return false;
+        if (D.kh != D.kw || D.sh != D.sw || D.cout != P.cin || D.in_layout != 0 || layer_dilated(D)) return false;
         if (P.reserved == bh::RES_ACT_AFTER) return false;   // act(project + x): never a fused block's project convolution
         d = bh::MbDesc{};
         d.noexp = 1;
@@ -357,7 +364,7 @@ bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, s
     if ((E.op != bh::OP_PWCONV && !stem) || D.op != bh::OP_DWCONV || P.op != bh::OP_PWCONV) return false;
     if (D.in_tensor != i + 1 || P.in_tensor != i + 2 || readers[i + 1] != 1 || readers[i + 2] != 1) return false;
     if (E.res_tensor != bh::NO_TENSOR || D.res_tensor != bh::NO_TENSOR) return false;
-    if (D.kh != D.kw || D.sh != D.sw || E.cout != D.cout || D.cout != P.cin) return false;
+    if (D.kh != D.kw || D.sh != D.sw || E.cout != D.cout || D.cout != P.cin || layer_dilated(D) || layer_dilated(E)) return false;
     if (P.reserved == bh::RES_ACT_AFTER) return false;   // act(project + x): never a fused block's project convolution
     d = bh::MbDesc{};
     d.H = (int)E.in_h; d.W = (int)E.in_w; d.Cin = (int)E.cin; d.Cexp = (int)E.cout; d.Cout = (int)P.cout;

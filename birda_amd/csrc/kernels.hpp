@@ -5,7 +5,9 @@
 
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <mutex>
+#include <type_traits>
 
 // Environment switches.  The PRODUCT library reads a short, documented list (tests/test_abi_and_host.py holds the shipped .so to
 // it): BIRDA_HIP_PRECISION, BIRDA_HIP_COPY_THREADS, BIRDA_HOST_PIPELINE_DEPTH, BIRDA_INFERENCE_TIMEOUT, BIRDA_HIP_ROCTX,
@@ -418,10 +420,26 @@ const char *launch_mel(const float *x, const float *minmax, float *spec, const F
                        const FrontendParams *d_p, int n_seg, hipStream_t s);
 
 
+// What the kernels take BY VALUE: the fifteen words ConvParams had before the dilation, in its order.  The undilated instantiations
+// of every kernel keep this argument, so their code is what it was (an argument 8 bytes longer moved conv_gemm_kernel's register
+// allocation: 0.2-1.4 % on resnet18_audio's f32 layers, profiles/dilated_layers.txt); the dilated ones take the whole ConvParams.
+struct ConvKernelParams {
+    int in_h, in_w, out_h, out_w, cin, cout, kh, kw, sh, sw, pad_t, pad_l, in_layout, act, res_after;
+};
 struct ConvParams {
     int in_h, in_w, out_h, out_w, cin, cout, kh, kw, sh, sw, pad_t, pad_l, in_layout, act;
     int res_after = 0;   // 1: act(conv + b + R) instead of act(conv + b) + R (the GEMM convolutions only; needs R and an activation)
+    // the tap pitch: tap (dy, dx) reads pixel (oy sh - pad_t + dy dil_h, ox sw - pad_l + dx dil_w).  The NHWC GEMM convolutions and
+    // the depthwise layer only (1 .. 16 each); every other launcher takes the undilated layer and does not read them
+    int dil_h = 1, dil_w = 1;
 };
+inline bool conv_dilated(const ConvParams &p) { return p.dil_h != 1 || p.dil_w != 1; }
+static_assert(offsetof(ConvParams, dil_h) == sizeof(ConvKernelParams), "ConvKernelParams is ConvParams' leading part");
+template <bool DIL> using ConvKernelArg = std::conditional_t<DIL, ConvParams, ConvKernelParams>;
+template <bool DIL> inline ConvKernelArg<DIL> conv_kernel_arg(const ConvParams &p) {
+    if constexpr (DIL) return p;
+    else return ConvKernelParams{p.in_h, p.in_w, p.out_h, p.out_w, p.cin, p.cout, p.kh, p.kw, p.sh, p.sw, p.pad_t, p.pad_l, p.in_layout, p.act, p.res_after};
+}
 // direct conv for the small-Cin NCHW stem; w [kh][kw][cin][cout], all of it in LDS: cout % 4 == 0 and at most 64 KB of weights
 // (conv_direct_supports: create's rule).  Returns the instantiation's name ("conv_direct_kernel<NC=8>"); nullptr: nothing launched.
 bool conv_direct_supports(const ConvParams &p);
@@ -430,6 +448,9 @@ const char *launch_conv_direct(const float *in, const float *w, const float *b, 
 // full convolution NHWC (group 1) as an implicit GEMM: out = act(im2col(in) . W + b) (+ R).  W is K x N with K = kh kw cpad,
 // cpad = align_up(cin, 32), the channels of every tap zero-padded to whole 32-deep steps: f32 rows [K][ldw] (ldw % 4 == 0), or
 // the split-f16 planes of launch_pw_gemm16 over that K.  kh, kw 1 .. 7, strides 1 / 2, cin and cout multiples of 4, NHWC input.
+// p.dil_h, p.dil_w (1 .. 16) space the taps: K, the planes and the k order do not depend on them.  A dilated layer runs the
+// dilated tap walk, a compile-time flag of the same kernels with names of their own ("conv_gemm_kernel<BM=64,NT=5,DIL>",
+// "conv_gemm16_kernel<3,GELU,DIL>", "conv_gemm16_kernel<3,RELU,AFTER,DIL>"); an undilated one the instantiation it always ran.
 bool conv_gemm_supports(const ConvParams &p);
 bool conv_gemm16_supports(const ConvParams &p);   // ... and an activation the f16 epilogue is instantiated for
 bool conv_gemm16_after_supports(const ConvParams &p);   // the same for a layer with p.res_after: ReLU, ReLU6, swish, erf-GELU
@@ -459,6 +480,8 @@ const char *launch_gconv16(const float *in, const void *Wf, const float *b, floa
                            float w_unscale, hipStream_t s);
 // depthwise conv NHWC; w [kh][kw][c]: square 3x3 / 5x5 windows, one stride 1 / 2, c % 4 == 0 (dwconv_supports: create's rule).
 // Returns the instantiation's name ("dwconv_kernel<3,2>"); nullptr when no instantiation matches and nothing was launched.
+// A dilated layer (p.dil_h, p.dil_w, 1 .. 16 each, run-time arguments) takes the dilated form of the same windows and strides,
+// "dwconv_kernel<3,2,DIL>"; dwconv_supports does not look at the dilation.
 bool dwconv_supports(const ConvParams &p);
 const char *launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p,
                    int n_seg, hipStream_t s);

@@ -1257,10 +1257,11 @@ const char *launch_head_gap16(const float *A, const void *Wf, const float *bias,
 // Depthwise conv, NHWC.  One lane = one output pixel x 4 channels; lanes run over the
 // channel groups first, so a wave reads/writes contiguous 16-B pieces of NHWC rows.
 // ---------------------------------------------------------------------------------------
-template <int KS, int ST>
+// DIL: the taps stand p.dil_h rows and p.dil_w columns apart (run-time, 1 .. 16 each); the undilated instantiations never read them.
+template <int KS, int ST, bool DIL = false>
 __global__ __launch_bounds__(256) void dwconv_kernel(const float *__restrict__ in, const float *__restrict__ w,
                                                       const float *__restrict__ b, float *__restrict__ out,
-                                                      ConvParams p, int n_seg) {
+                                                      ConvKernelArg<DIL> p, int n_seg) {
     const int c4n = p.cout >> 2;
     const long total = (long)n_seg * p.out_h * p.out_w * c4n;
     for (long g = (long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long)gridDim.x * 256) {
@@ -1274,13 +1275,15 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float *__restrict__ i
         float4 acc = *reinterpret_cast<const float4 *>(b + c);
         const float *ib = in + (size_t)seg * p.in_h * p.in_w * p.cout + c;
         const int iy0 = oy * ST - p.pad_t, ix0 = ox * ST - p.pad_l;
+        int ph = 1, pw = 1;
+        if constexpr (DIL) { ph = p.dil_h; pw = p.dil_w; }
 #pragma unroll
         for (int dy = 0; dy < KS; dy++) {
-            const int iy = iy0 + dy;
+            const int iy = iy0 + dy * ph;
             if (iy < 0 || iy >= p.in_h) continue;
 #pragma unroll
             for (int dx = 0; dx < KS; dx++) {
-                const int ix = ix0 + dx;
+                const int ix = ix0 + dx * pw;
                 if (ix < 0 || ix >= p.in_w) continue;
                 const float4 a = *reinterpret_cast<const float4 *>(ib + ((size_t)iy * p.in_w + ix) * p.cout);
                 const float4 ww = *reinterpret_cast<const float4 *>(w + (size_t)(dy * KS + dx) * p.cout + c);
@@ -1305,10 +1308,18 @@ const char *launch_dwconv(const float *in, const float *w, const float *b, float
     dim3 grid((unsigned)blocks), block(256);
 #define BH_DW_CASE(KSV, STV)                                                                       \
     if (p.kh == KSV && p.sh == STV) {                                                               \
-        hipLaunchKernelGGL((dwconv_kernel<KSV, STV>), grid, block, 0, s, in, w, b, out, p, n_seg);  \
+        hipLaunchKernelGGL((dwconv_kernel<KSV, STV>), grid, block, 0, s, in, w, b, out, conv_kernel_arg<false>(p), n_seg);  \
         return "dwconv_kernel<" #KSV "," #STV ">";                                                  \
     }
+#define BH_DW_DIL_CASE(KSV, STV)                                                                        \
+    if (p.kh == KSV && p.sh == STV) {                                                                    \
+        hipLaunchKernelGGL((dwconv_kernel<KSV, STV, true>), grid, block, 0, s, in, w, b, out, conv_kernel_arg<true>(p), n_seg); \
+        return "dwconv_kernel<" #KSV "," #STV ",DIL>";                                                   \
+    }
+    if (!dwconv_supports(p)) return nullptr;
+    if (conv_dilated(p)) { BH_DW_DIL_CASE(3, 1) BH_DW_DIL_CASE(3, 2) BH_DW_DIL_CASE(5, 1) BH_DW_DIL_CASE(5, 2) }
     BH_DW_CASE(3, 1) BH_DW_CASE(3, 2) BH_DW_CASE(5, 1) BH_DW_CASE(5, 2)
+#undef BH_DW_DIL_CASE
 #undef BH_DW_CASE
     return nullptr;
 }
@@ -1320,7 +1331,7 @@ const char *launch_dwconv(const float *in, const float *w, const float *b, float
 template <int NC>
 __global__ __launch_bounds__(256) void conv_direct_kernel(const float *__restrict__ in, const float *__restrict__ w,
                                                            const float *__restrict__ b, float *__restrict__ out,
-                                                           ConvParams p, int n_seg) {
+                                                           ConvKernelParams p, int n_seg) {
     extern __shared__ __attribute__((aligned(16))) float ws[];
     const int wn = p.kh * p.kw * p.cin * p.cout;
     for (int i = threadIdx.x; i < wn; i += 256) ws[i] = w[i];
@@ -1374,8 +1385,8 @@ const char *launch_conv_direct(const float *in, const float *w, const float *b, 
     long blocks = (total + 255) / 256;
     if (blocks > 256L * 32) blocks = 256L * 32;
     const size_t smem = (size_t)p.kh * p.kw * p.cin * p.cout * sizeof(float);
-    if (nc == 8) hipLaunchKernelGGL(conv_direct_kernel<8>, dim3((unsigned)blocks), dim3(256), smem, s, in, w, b, out, p, n_seg);
-    else hipLaunchKernelGGL(conv_direct_kernel<4>, dim3((unsigned)blocks), dim3(256), smem, s, in, w, b, out, p, n_seg);
+    if (nc == 8) hipLaunchKernelGGL(conv_direct_kernel<8>, dim3((unsigned)blocks), dim3(256), smem, s, in, w, b, out, conv_kernel_arg<false>(p), n_seg);
+    else hipLaunchKernelGGL(conv_direct_kernel<4>, dim3((unsigned)blocks), dim3(256), smem, s, in, w, b, out, conv_kernel_arg<false>(p), n_seg);
     return nc == 8 ? "conv_direct_kernel<NC=8>" : "conv_direct_kernel<NC=4>";
 }
 
@@ -1385,7 +1396,13 @@ const char *launch_conv_direct(const float *in, const float *w, const float *b, 
 // W keeps the loaders' [kh][kw][cin][cout] layout read as K x N, with the channels of every tap padded on the host to whole
 // 32-deep steps (cpad = align_up(cin, 32), zero rows): K = kh kw cpad, and a k step never straddles two taps.  The im2col
 // matrix never exists: the A loader walks the steps tap by tap (dy, dx, channel step) and gathers each row's input pixel
-// (oy sh - pad_t + dy, ox sw - pad_l + dx); taps outside the image and channels past cin read as zero.
+// (oy sh - pad_t + dy dil_h, ox sw - pad_l + dx dil_w); taps outside the image and channels past cin read as zero.  The dilation is
+// a pitch of the tap walk alone (ConvTap: wave-uniform, scalar registers): K, the weight rows and the k order do not know it.  It is
+// a COMPILE-TIME flag of the walk (DIL, the kernels' last template argument; names end in ",DIL>"): as a run-time pitch of the one
+// walk it cost the undilated layers of resnet18_audio 0.5-0.9 % on conv_gemm16_kernel, outside the parent's own spread of 0.1-0.6 %
+// (profiles/dilated_layers.txt), so an undilated layer runs the instantiation, under the name, that it always did.  The
+// undilated instantiations also keep the fifteen-word by-value argument they had (ConvKernelParams; the dilated ones take the whole
+// ConvParams): with the longer struct the undilated conv_gemm_kernel, re-allocated around it, measured 0.2-1.4 % behind.
 // Two kernels, one per operand precision, each the twin of a pointwise GEMM (the same tiles, MFMAs, k order inside a step
 // and epilogue; the same plane layout): conv_gemm_kernel of pw_gemm_kernel (f32 MFMA, LDS-staged 32-deep chunks) and
 // conv_gemm16_kernel of pw_gemm16_kernel (split-f16 MFMA, register-direct).  They are kernels of their own rather than an
@@ -1399,30 +1416,42 @@ struct ConvRows {   // one output row's gather origin: its segment's image and t
     const float *x;
     int iy0, ix0;
 };
-__device__ __forceinline__ ConvRows conv_row(const float *X, const ConvParams &p, int m) {
+template <class P>
+__device__ __forceinline__ ConvRows conv_row(const float *X, const P &p, int m) {
     const int opix = p.out_h * p.out_w;
     const int seg = m / opix, r = m - seg * opix;
     const int oy = r / p.out_w, ox = r - oy * p.out_w;
     return ConvRows{X + (size_t)seg * p.in_h * p.in_w * p.cin, oy * p.sh - p.pad_t, ox * p.sw - p.pad_l};
 }
-// four consecutive channels ch .. ch + 3 of tap (dy, dx) of a row (cin % 4 == 0: a float4 is wholly inside or wholly past cin)
-__device__ __forceinline__ float4 conv_gather4(const ConvRows &r, const ConvParams &p, int dy, int dx, int ch) {
-    const int iy = r.iy0 + dy, ix = r.ix0 + dx;
+// four consecutive channels ch .. ch + 3 of the tap oy rows and ox columns from a row's window origin (cin % 4 == 0: a float4 is
+// wholly inside or wholly past cin)
+template <class P>
+__device__ __forceinline__ float4 conv_gather4(const ConvRows &r, const P &p, int oy, int ox, int ch) {
+    const int iy = r.iy0 + oy, ix = r.ix0 + ox;
     if ((unsigned)iy >= (unsigned)p.in_h || (unsigned)ix >= (unsigned)p.in_w || ch >= p.cin) return make_float4(0.f, 0.f, 0.f, 0.f);
     return *reinterpret_cast<const float4 *>(r.x + ((size_t)iy * p.in_w + ix) * p.cin + ch);
 }
-// the tap walk: (channel step, dx, dy) advanced one 32-deep step at a time, in the order the steps are loaded
+// the tap walk: (channel step, column offset, row offset) advanced one 32-deep step at a time, in the order the steps are loaded;
+// the offsets are the tap's index times the dilation (ox = dx dil_w < xspan = kw dil_w, oy = dy dil_h)
+// (DIL false: the offsets are the tap's indices, xspan = kw, and p.dil_h / p.dil_w are never read)
+template <bool DIL>
+__device__ __forceinline__ int conv_xspan(const ConvKernelArg<DIL> &p) {
+    if constexpr (DIL) return p.kw * p.dil_w;
+    else return p.kw;
+}
 struct ConvTap {
-    int cs = 0, dx = 0, dy = 0;
-    __device__ __forceinline__ void next(int csteps, int kw) {
-        if (++cs == csteps) { cs = 0; if (++dx == kw) { dx = 0; ++dy; } }
+    int cs = 0, ox = 0, oy = 0;
+    template <bool DIL>
+    __device__ __forceinline__ void next(int csteps, int xspan, const ConvKernelArg<DIL> &p) {
+        if constexpr (DIL) { if (++cs == csteps) { cs = 0; ox += p.dil_w; if (ox == xspan) { ox = 0; oy += p.dil_h; } } }
+        else { if (++cs == csteps) { cs = 0; if (++ox == xspan) { ox = 0; ++oy; } } }
     }
 };
 
-template <int BM, int NT>
+template <int BM, int NT, bool DIL = false>
 __global__ __launch_bounds__(256) void conv_gemm_kernel(const float *__restrict__ X, const float *__restrict__ W,
                                                          const float *__restrict__ bias, const float *__restrict__ R,
-                                                         float *__restrict__ C, ConvParams p, int M, int ldw) {
+                                                         float *__restrict__ C, ConvKernelArg<DIL> p, int M, int ldw) {
     constexpr int BN = NT * 16;
     constexpr int WM = BM / 4;
     constexpr int MT = WM / 16;
@@ -1436,7 +1465,7 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const float *__restrict_
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
     const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
-    const int N = p.cout, csteps = (p.cin + 31) >> 5;
+    const int N = p.cout, csteps = (p.cin + 31) >> 5, xspan = conv_xspan<DIL>(p);
     const int K = p.kh * p.kw * csteps * PW_BK;
 
     ConvRows rows[A4];
@@ -1446,8 +1475,8 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const float *__restrict_
     float4 pa[A4], pb[B4];
     auto load_chunk = [&](int k0) {
 #pragma unroll
-        for (int i = 0; i < A4; i++) pa[i] = conv_gather4(rows[i], p, tap.dy, tap.dx, tap.cs * PW_BK + ((tid & 7) << 2));
-        tap.next(csteps, p.kw);
+        for (int i = 0; i < A4; i++) pa[i] = conv_gather4(rows[i], p, tap.oy, tap.ox, tap.cs * PW_BK + ((tid & 7) << 2));
+        tap.next<DIL>(csteps, xspan, p);
 #pragma unroll
         for (int i = 0; i < B4; i++) {
             const int f = tid + 256 * i;
@@ -1538,17 +1567,17 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(const float *__restrict_
 // consecutive channels of its four rows' tap straight into registers one step ahead and splits them there.  Blocks run
 // column block fastest: the blocks that read the same rows of X are adjacent (X is gathered kh kw times per row; those
 // re-reads come from L2), and W -- at most a few MB -- stays in L2 for all of them.
-template <int TERMS, int ACT, bool AFTER = false>
+template <int TERMS, int ACT, bool AFTER = false, bool DIL = false>
 __global__ __launch_bounds__(256) void conv_gemm16_kernel(const float *__restrict__ X, const f16x8 *__restrict__ Wf,
                                                            const float *__restrict__ bias, const float *__restrict__ R,
-                                                           float *__restrict__ C, ConvParams p, int M, int n_tiles, float w_unscale) {
+                                                           float *__restrict__ C, ConvKernelArg<DIL> p, int M, int n_tiles, float w_unscale) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
     const int wm = wave >> 1, wn = wave & 1;
     const int n_xb = (n_tiles + 7) / 8;
     const int yb = (int)(blockIdx.x / (unsigned)n_xb), xb = (int)(blockIdx.x % (unsigned)n_xb);
     const int m0 = yb * 128 + wm * 64, t0 = xb * 8 + wn * 4;   // first row, first column tile
-    const int N = p.cout, csteps = (p.cin + 31) >> 5;
+    const int N = p.cout, csteps = (p.cin + 31) >> 5, xspan = conv_xspan<DIL>(p);
     const int steps = p.kh * p.kw * csteps;
 
     f32x4 acc[4][4];
@@ -1568,10 +1597,10 @@ __global__ __launch_bounds__(256) void conv_gemm16_kernel(const float *__restric
         const int ch = tap.cs * 32 + 8 * kq;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
-            ra[i][0] = conv_gather4(rows[i], p, tap.dy, tap.dx, ch);
-            ra[i][1] = conv_gather4(rows[i], p, tap.dy, tap.dx, ch + 4);
+            ra[i][0] = conv_gather4(rows[i], p, tap.oy, tap.ox, ch);
+            ra[i][1] = conv_gather4(rows[i], p, tap.oy, tap.ox, ch + 4);
         }
-        tap.next(csteps, p.kw);
+        tap.next<DIL>(csteps, xspan, p);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             const int t = min(t0 + j, n_tiles - 1);
@@ -1629,16 +1658,17 @@ __global__ __launch_bounds__(256) void conv_gemm16_kernel(const float *__restric
 
 bool conv_gemm_supports(const ConvParams &p) {
     return p.in_layout == 0 && p.cin % 4 == 0 && p.cout % 4 == 0 && p.cin > 0 && p.cout > 0 && p.kh >= 1 && p.kh <= 7 && p.kw >= 1 &&
-           p.kw <= 7 && (p.sh == 1 || p.sh == 2) && (p.sw == 1 || p.sw == 2) && p.pad_t >= 0 && p.pad_l >= 0;
+           p.kw <= 7 && (p.sh == 1 || p.sh == 2) && (p.sw == 1 || p.sw == 2) && p.pad_t >= 0 && p.pad_l >= 0 && p.dil_h >= 1 && p.dil_h <= 16 &&
+           p.dil_w >= 1 && p.dil_w <= 16;
 }
 bool conv_gemm16_supports(const ConvParams &p) { return conv_gemm_supports(p) && (p.act == ACT_NONE || act_is_templated(p.act)); }
 bool conv_gemm16_after_supports(const ConvParams &p) { return conv_gemm_supports(p) && act_is_templated_after(p.act); }
 
-template <int BM, int NT>
+template <int BM, int NT, bool DIL>
 static void conv_launch(const float *X, const float *W, const float *bias, const float *R, float *C, const ConvParams &p, int M, int ldw,
                         hipStream_t s) {
     dim3 grid((p.cout + NT * 16 - 1) / (NT * 16), (M + BM - 1) / BM), block(256);
-    hipLaunchKernelGGL((conv_gemm_kernel<BM, NT>), grid, block, 0, s, X, W, bias, R, C, p, M, ldw);
+    hipLaunchKernelGGL((conv_gemm_kernel<BM, NT, DIL>), grid, block, 0, s, X, W, bias, R, C, conv_kernel_arg<DIL>(p), M, ldw);
 }
 
 const char *launch_conv_gemm(const float *X, const float *W, const float *bias, const float *R, float *C, const ConvParams &p, int n_seg,
@@ -1648,11 +1678,18 @@ const char *launch_conv_gemm(const float *X, const float *W, const float *bias, 
     const int nt = pick_nt(p.cout);
     const long blocks128 = (long)((M + 127) / 128) * ((p.cout + nt * 16 - 1) / (nt * 16));
     const bool small = blocks128 < 512;   // the tile is the layer's shape alone: the same bits at any launch size either way
+    const bool dil = conv_dilated(p);   // (the dilated walk: instantiations and names of their own)
     const char *name = nullptr;
 #define BH_CG_CASE(NTV)                                                                       \
     case NTV:                                                                                 \
-        if (small) conv_launch<64, NTV>(X, W, bias, R, C, p, M, ldw, s);                     \
-        else conv_launch<128, NTV>(X, W, bias, R, C, p, M, ldw, s);                          \
+        if (dil) {                                                                            \
+            if (small) conv_launch<64, NTV, true>(X, W, bias, R, C, p, M, ldw, s);           \
+            else conv_launch<128, NTV, true>(X, W, bias, R, C, p, M, ldw, s);                \
+            name = small ? "conv_gemm_kernel<BM=64,NT=" #NTV ",DIL>" : "conv_gemm_kernel<BM=128,NT=" #NTV ",DIL>"; \
+            break;                                                                            \
+        }                                                                                     \
+        if (small) conv_launch<64, NTV, false>(X, W, bias, R, C, p, M, ldw, s);              \
+        else conv_launch<128, NTV, false>(X, W, bias, R, C, p, M, ldw, s);                   \
         name = small ? "conv_gemm_kernel<BM=64,NT=" #NTV ">" : "conv_gemm_kernel<BM=128,NT=" #NTV ">"; \
         break;
     switch (nt) {
@@ -1669,9 +1706,13 @@ const char *launch_conv_gemm16(const float *X, const void *Wf, const float *bias
     if (M <= 0 || (p.res_after && (!R || !act_is_templated_after(p.act)))) return nullptr;   // (no such instantiation: nothing launched)
     const int n_tiles = (p.cout + 15) / 16;
     const dim3 grid((unsigned)(((n_tiles + 7) / 8) * ((M + 127) / 128))), block(256);
+    const bool dil = conv_dilated(p);   // (the dilated walk: instantiations and names of their own)
     const char *name = nullptr;
-#define BH_CG16(T, ACTV, AN, AFT, AFN) do { hipLaunchKernelGGL((conv_gemm16_kernel<T, ACTV, AFT>), grid, block, 0, s, X, (const f16x8 *)Wf, bias, R, C, p, M, n_tiles, w_unscale); \
-                                            name = "conv_gemm16_kernel<" #T "," AN AFN ">"; } while (0)
+#define BH_CG16(T, ACTV, AN, AFT, AFN) do { \
+        if (dil) { hipLaunchKernelGGL((conv_gemm16_kernel<T, ACTV, AFT, true>), grid, block, 0, s, X, (const f16x8 *)Wf, bias, R, C, conv_kernel_arg<true>(p), M, n_tiles, w_unscale); \
+                   name = "conv_gemm16_kernel<" #T "," AN AFN ",DIL>"; } \
+        else { hipLaunchKernelGGL((conv_gemm16_kernel<T, ACTV, AFT, false>), grid, block, 0, s, X, (const f16x8 *)Wf, bias, R, C, conv_kernel_arg<false>(p), M, n_tiles, w_unscale); \
+               name = "conv_gemm16_kernel<" #T "," AN AFN ">"; } } while (0)
 #define BH_CG16A(T)                                                  \
     switch (p.act) {                                                 \
     case ACT_GELU_ERF: BH_CG16(T, ACT_GELU_ERF, "GELU", false, ""); break; \

@@ -43,7 +43,7 @@ struct GconvTile {       // what a workgroup's column tile reads: wave-uniform
     int c0, span, K;     // first input channel, channels, kh kw span
     unsigned rcp_span, rcp_kw;
 };
-__device__ __forceinline__ GconvTile gconv_tile(const ConvParams &p, int groups, int t) {
+__device__ __forceinline__ GconvTile gconv_tile(const ConvKernelParams &p, int groups, int t) {
     GconvTile g;
     gconv_tile_span(p.cin, p.cout, groups, t, g.c0, g.span);
     g.K = p.kh * p.kw * g.span;
@@ -55,7 +55,7 @@ struct GconvRow {        // one output row's gather origin: its segment's image 
     const float *x;
     int iy0, ix0;
 };
-__device__ __forceinline__ GconvRow gconv_row(const float *X, const ConvParams &p, int m) {
+__device__ __forceinline__ GconvRow gconv_row(const float *X, const ConvKernelParams &p, int m) {
     const int opix = p.out_h * p.out_w;
     const int seg = m / opix, r = m - seg * opix;
     const int oy = r / p.out_w, ox = r - oy * p.out_w;
@@ -63,7 +63,7 @@ __device__ __forceinline__ GconvRow gconv_row(const float *X, const ConvParams &
 }
 // k .. k + 3 of the tile's flattened (tap, channel in span) index, k % 4 == 0: four channels of one tap.  Zero past K (the padding
 // of the last step) and outside the image.
-__device__ __forceinline__ float4 gconv_gather4(const GconvRow &r, const ConvParams &p, const GconvTile &g, int k) {
+__device__ __forceinline__ float4 gconv_gather4(const GconvRow &r, const ConvKernelParams &p, const GconvTile &g, int k) {
     if (k >= g.K) return make_float4(0.f, 0.f, 0.f, 0.f);
     const int tap = (int)__umulhi((unsigned)k, g.rcp_span), ch = k - tap * g.span;
     const int dy = p.kw > 1 ? (int)__umulhi((unsigned)tap, g.rcp_kw) : tap, dx = tap - dy * p.kw;
@@ -80,7 +80,7 @@ constexpr int GC_BM = 4 * 16 * GC_MT;   // rows a workgroup
 // f32 MFMA.  Wf: fragments [K16 / 16][n_tiles][64 lanes][4], element (g, t, lane, c) = Wt[k = 16g + 4(lane >> 4) + c][16t + (lane & 15)]
 // of gconv_matrix's Wt: MFMA step c of lane quad q takes k = 16g + 4q + c, so a lane's four A operands are one float4 gather.
 __global__ __launch_bounds__(256) void gconv_kernel(const float *__restrict__ X, const float4 *__restrict__ Wf, const float *__restrict__ bias,
-                                                     float *__restrict__ C, ConvParams p, int groups, int M, int n_tiles) {
+                                                     float *__restrict__ C, ConvKernelParams p, int groups, int M, int n_tiles) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
     const int t = (int)(blockIdx.x % (unsigned)n_tiles), yb = (int)(blockIdx.x / (unsigned)n_tiles);
@@ -134,7 +134,7 @@ __global__ __launch_bounds__(256) void gconv_kernel(const float *__restrict__ X,
 // (each inside one tap; the two may lie in different taps), split into hi / lo halves in registers.
 template <int TERMS>
 __global__ __launch_bounds__(256) void gconv16_kernel(const float *__restrict__ X, const f16x8 *__restrict__ Wf, const float *__restrict__ bias,
-                                                       float *__restrict__ C, ConvParams p, int groups, int M, int n_tiles, float w_unscale) {
+                                                       float *__restrict__ C, ConvKernelParams p, int groups, int M, int n_tiles, float w_unscale) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, kq = lane >> 4;
     const int t = (int)(blockIdx.x % (unsigned)n_tiles), yb = (int)(blockIdx.x / (unsigned)n_tiles);
@@ -221,7 +221,7 @@ const char *launch_gconv(const float *in, const float *Wf, const float *b, float
     int M, n_tiles;
     unsigned blocks;
     if (!gconv_supports(p, groups) || !gconv_grid(p, n_seg, M, n_tiles, blocks)) return nullptr;
-    hipLaunchKernelGGL(gconv_kernel, dim3(blocks), dim3(256), 0, s, in, (const float4 *)Wf, b, out, p, groups, M, n_tiles);
+    hipLaunchKernelGGL(gconv_kernel, dim3(blocks), dim3(256), 0, s, in, (const float4 *)Wf, b, out, conv_kernel_arg<false>(p), groups, M, n_tiles);
     return "gconv_kernel";
 }
 
@@ -231,10 +231,10 @@ const char *launch_gconv16(const float *in, const void *Wf, const float *b, floa
     unsigned blocks;
     if (!gconv_supports(p, groups) || (terms != 1 && terms != 3) || !gconv_grid(p, n_seg, M, n_tiles, blocks)) return nullptr;
     if (terms == 3) {
-        hipLaunchKernelGGL(gconv16_kernel<3>, dim3(blocks), dim3(256), 0, s, in, (const f16x8 *)Wf, b, out, p, groups, M, n_tiles, w_unscale);
+        hipLaunchKernelGGL(gconv16_kernel<3>, dim3(blocks), dim3(256), 0, s, in, (const f16x8 *)Wf, b, out, conv_kernel_arg<false>(p), groups, M, n_tiles, w_unscale);
         return "gconv16_kernel<3>";
     }
-    hipLaunchKernelGGL(gconv16_kernel<1>, dim3(blocks), dim3(256), 0, s, in, (const f16x8 *)Wf, b, out, p, groups, M, n_tiles, w_unscale);
+    hipLaunchKernelGGL(gconv16_kernel<1>, dim3(blocks), dim3(256), 0, s, in, (const f16x8 *)Wf, b, out, conv_kernel_arg<false>(p), groups, M, n_tiles, w_unscale);
     return "gconv16_kernel<1>";
 }
 

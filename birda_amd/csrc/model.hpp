@@ -25,6 +25,11 @@ constexpr uint32_t RES_ACT_AFTER = 1;
 // channels; a source's channel count is its tensor's floats / (in_h in_w).  `reserved` = the shuffle's group count g (0, 1: none):
 // out[p][c] = cat[p][(c % g) * (cout / g) + c / g], cat = A's window then B's.  Offsets and lengths are multiples of 4.
 constexpr uint32_t NO_TENSOR = 0xFFFFFFFFu;
+// Dilation (OP_CONV on an NHWC tensor, OP_DWCONV): the record's words at bytes 88 .. 95, skip_h and skip_w, are the rows and the columns
+// SKIPPED between neighbouring taps, dilation - 1 per axis -- tap (dy, dx) reads pixel (oy sh - pad_t + dy (skip_h + 1),
+// ox sw - pad_l + dx (skip_w + 1)).  Zero, the tail of every file written before the words existed, is the undilated layer: one
+// spelling of it.  At most MAX_DILATION per axis, zero on an axis with one tap, zero on every other op.
+constexpr uint32_t MAX_DILATION = 16;
 
 #pragma pack(push, 1)
 struct HeaderRec {
@@ -46,8 +51,10 @@ struct LayerRec {
     uint32_t op, act, in_tensor, res_tensor, cin, cout, kh, kw, sh, sw, pad_t, pad_l;
     uint32_t in_h, in_w, out_h, out_w, in_layout, reserved;
     uint64_t w_off, b_off;
+    uint32_t skip_h, skip_w;   // dilation - 1 per axis (above); the rest of the 128-byte record is not read
 };
 #pragma pack(pop)
+static_assert(sizeof(LayerRec) == 96, "the layer record's read part: 96 of its 128 bytes");
 
 struct Model {
     HeaderRec h{};
@@ -159,6 +166,14 @@ inline bool validate_model(Model &m, std::string &err) {
             if (L.reserved > RES_ACT_AFTER) { err = "layer with an unknown activation position"; return false; }
             if (L.reserved == RES_ACT_AFTER && L.res_tensor == NO_TENSOR) { err = "activation after the residual on a layer without a residual"; return false; }
             if (L.reserved == RES_ACT_AFTER && L.act == 0) { err = "activation after the residual without an activation (a plain residual is position 0)"; return false; }
+        }
+        if (L.skip_h || L.skip_w) {
+            static const char *const names[] = {"?", "stem convolution", "depthwise", "pointwise", "global pool", "dense", "scale", "pool", "grouped convolution", "?", "concat"};
+            if (!(L.op == OP_DWCONV || (L.op == OP_CONV && L.in_layout == 0))) {
+                err = std::string("dilation on a ") + names[L.op] + " layer"; return false;
+            }
+            if (L.skip_h >= MAX_DILATION || L.skip_w >= MAX_DILATION) { err = "dilation above 16"; return false; }
+            if ((L.kh == 1 && L.skip_h) || (L.kw == 1 && L.skip_w)) { err = "dilation on an axis with one tap (dilation 1 is its one spelling)"; return false; }
         }
         if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && L.op != OP_CONCAT && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
                                                    L.b_off + L.cout > m.h.blob_floats)) {

@@ -539,20 +539,38 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             int64_t sh = 1, sw = 1;
             if (const auto *st = n.ints("strides")) { if (st->size() != 2) return fail("Conv '" + n.name + "': strides"); sh = (*st)[0]; sw = (*st)[1]; }
             if (sh <= 0 || sw <= 0 || sh > 16 || sw > 16) return fail("Conv '" + n.name + "': strides");
-            if (const auto *dl = n.ints("dilations")) for (int64_t d : *dl) if (d != 1) return fail("Conv '" + n.name + "': dilation");
             const int64_t h = x.h, w = x.w, cin = x.c;
+            // dilation (convert.py has the same branch, refusal for refusal): a group-1 convolution of an NHWC activation or a depthwise
+            // one, 1 .. 16 per axis; an axis with one tap is dilation 1 whatever the file says (one spelling of the record)
+            int64_t dh = 1, dw = 1;
+            if (const auto *dl = n.ints("dilations")) {
+                bool any = false;
+                for (int64_t d : *dl) any = any || d != 1;
+                if (any && dl->size() != 2) return fail("Conv '" + n.name + "': dilations must be two values");
+                if (any) { dh = (*dl)[0]; dw = (*dl)[1]; }
+            }
+            if (dh < 1 || dw < 1 || dh > 16 || dw > 16)
+                return fail("Conv '" + n.name + "': dilation " + std::to_string(dh) + "x" + std::to_string(dw) + " (1 .. 16 are supported)");
+            if (kh == 1) dh = 1;
+            if (kw == 1) dw = 1;
+            if (dh != 1 || dw != 1) {
+                if (x.idx == 0) return fail("Conv '" + n.name + "': dilation on the stem convolution (the spectrogram, tensor 0) is not supported");
+                if (group != 1 && !(group == cin && cin_g == 1 && cout == cin))
+                    return fail("Conv '" + n.name + "': dilation on a grouped convolution is not supported");
+            }
+            const int64_t ekh = (kh - 1) * dh + 1, ekw = (kw - 1) * dw + 1;   // the window's extent over the image
             int64_t oh = (h + sh - 1) / sh, ow = (w + sw - 1) / sw, pt = 0, pl = 0;
             const std::string autop = n.gets("auto_pad", "NOTSET");
             if (autop == "SAME_UPPER" || autop == "SAME_LOWER") {
-                const int64_t th = std::max<int64_t>((oh - 1) * sh + kh - h, 0), tw = std::max<int64_t>((ow - 1) * sw + kw - w, 0);
+                const int64_t th = std::max<int64_t>((oh - 1) * sh + ekh - h, 0), tw = std::max<int64_t>((ow - 1) * sw + ekw - w, 0);
                 if (autop == "SAME_UPPER") { pt = th / 2; pl = tw / 2; } else { pt = th - th / 2; pl = tw - tw / 2; }
             } else {
                 int64_t pads[4] = {0, 0, 0, 0};
                 if (const auto *pd = n.ints("pads")) { if (pd->size() != 4) return fail("Conv '" + n.name + "': pads"); for (int q = 0; q < 4; q++) pads[q] = (*pd)[q]; }
                 for (int64_t p : pads) if (p < 0 || p > 64) return fail("Conv '" + n.name + "': pads");
                 pt = pads[0]; pl = pads[1];
-                if (h + pads[0] + pads[2] < kh || w + pads[1] + pads[3] < kw) return fail("Conv '" + n.name + "': kernel larger than the padded input");
-                oh = (h + pads[0] + pads[2] - kh) / sh + 1; ow = (w + pads[1] + pads[3] - kw) / sw + 1;
+                if (h + pads[0] + pads[2] < ekh || w + pads[1] + pads[3] < ekw) return fail("Conv '" + n.name + "': kernel larger than the padded input");
+                oh = (h + pads[0] + pads[2] - ekh) / sh + 1; ow = (w + pads[1] + pads[3] - ekw) / sw + 1;
             }
             tmpb.assign((size_t)cout, 0.0f);
             if (B) for (int64_t o = 0; o < cout; o++) tmpb[(size_t)o] = B->at((uint64_t)o);
@@ -572,6 +590,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 const uint64_t wo = blob.put(tmp), bo = blob.put(tmpb);
                 li = new_layer(OP_DWCONV, x.idx, NO_TENSOR, (uint32_t)cin, (uint32_t)cout, (uint32_t)kh, (uint32_t)kw, (uint32_t)sh, (uint32_t)sw, (uint32_t)pt, (uint32_t)pl,
                                (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, 0, wo, bo);
+                layers[li - 1].skip_h = (uint32_t)(dh - 1); layers[li - 1].skip_w = (uint32_t)(dw - 1);
             } else if (group == 1) {
                 if (cin_g != cin) return fail("Conv '" + n.name + "': " + std::to_string(cin_g) + " input channels, activation has " + std::to_string(cin));
                 tmp.resize((size_t)kh * kw * cin * cout);                         // W[cout][cin][kh][kw] -> [kh][kw][cin][cout]
@@ -583,6 +602,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 const uint64_t wo = blob.put(tmp), bo = blob.put(tmpb);
                 li = new_layer(OP_CONV, x.idx, NO_TENSOR, (uint32_t)cin, (uint32_t)cout, (uint32_t)kh, (uint32_t)kw, (uint32_t)sh, (uint32_t)sw, (uint32_t)pt, (uint32_t)pl,
                                (uint32_t)h, (uint32_t)w, (uint32_t)oh, (uint32_t)ow, x.idx == 0 ? 1u : 0u, wo, bo);
+                layers[li - 1].skip_h = (uint32_t)(dh - 1); layers[li - 1].skip_w = (uint32_t)(dw - 1);
             } else {
                 // a grouped convolution -> OP_GCONV (convert.py has the same branch, refusal for refusal): compact weights
                 // W[cout][cin / G][kh][kw] -> [kh][kw][cin / G][cout], the group count in the record's reserved word

@@ -57,8 +57,11 @@ HEADER_FMT = "<4sIIIIfIIIIIIQQIIf"
 # mag_scale, out_scale, out_shift, flags, mel_w_off
 BRANCH_FMT = "<IIIIIIfffffIQ"
 # op, act, in_tensor, res_tensor, cin, cout, kh, kw, sh, sw, pad_t, pad_l,
-# in_h, in_w, out_h, out_w, in_layout, reserved, w_off, b_off
-LAYER_FMT = "<IIIIIIIIIIIIIIIIIIQQ"
+# in_h, in_w, out_h, out_w, in_layout, reserved, w_off, b_off, skip_h, skip_w
+# (skip_h, skip_w at bytes 88 .. 95: the rows / columns skipped between neighbouring taps, Layer.dil_h - 1 and Layer.dil_w - 1 -- zero,
+#  the tail of every record written before the words existed, is the undilated layer; the rest of the 128 bytes stays zero)
+LAYER_FMT = "<IIIIIIIIIIIIIIIIIIQQII"
+MAX_DILATION = 16
 
 
 @dataclass
@@ -105,6 +108,10 @@ class Layer:
     # relative to the residual -- 0: act(conv + b) + R; RES_ACT_AFTER: act(conv + b + R), which needs a residual and an activation.
     # OP_GCONV: the group count.  OP_CONCAT: the channel shuffle's group count (0, 1: no shuffle).  0 for every other op.
     reserved: int = 0
+    # dilation per axis (OP_CONV on an NHWC tensor and OP_DWCONV only, 1 .. MAX_DILATION, 1 on an axis with one tap): tap (dy, dx) reads
+    # pixel (oy sh - pad_t + dy dil_h, ox sw - pad_l + dx dil_w).  Written as dil - 1.
+    dil_h: int = 1
+    dil_w: int = 1
 
 
 @dataclass
@@ -162,7 +169,7 @@ def write_model(path: str, m: Model) -> None:
         for L in m.layers:
             rec = struct.pack(LAYER_FMT, L.op, L.act, L.in_tensor, L.res_tensor, L.cin, L.cout,
                               L.kh, L.kw, L.sh, L.sw, L.pad_t, L.pad_l, L.in_h, L.in_w,
-                              L.out_h, L.out_w, L.in_layout, L.reserved, L.w_off, L.b_off)
+                              L.out_h, L.out_w, L.in_layout, L.reserved, L.w_off, L.b_off, L.dil_h - 1, L.dil_w - 1)
             f.write(rec.ljust(LAYER_SIZE, b"\0"))
         f.write(b"\0" * (blob_offset - f.tell()))
         f.write(blob.tobytes())
@@ -184,7 +191,7 @@ def read_model(path: str) -> Model:
     for _ in range(n_l):
         r = struct.unpack_from(LAYER_FMT, raw, off)
         m.layers.append(Layer(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9], r[10],
-                              r[11], r[12], r[13], r[14], r[15], r[16], r[18], r[19], r[17]))
+                              r[11], r[12], r[13], r[14], r[15], r[16], r[18], r[19], r[17], r[20] + 1, r[21] + 1))
         off += LAYER_SIZE
     m.blob = np.frombuffer(raw, dtype="<f4", count=bfl, offset=boff).copy()
     return m

@@ -85,15 +85,16 @@ class _Builder:
         self.layers.append(L)
         return len(self.layers)  # tensor index of this layer's output
 
-    def conv(self, tin, h, w, cin, cout, k, s, act, in_layout=0, res=mf.NO_TENSOR, gain=1.0, kw=None):
+    def conv(self, tin, h, w, cin, cout, k, s, act, in_layout=0, res=mf.NO_TENSOR, gain=1.0, kw=None, dil=(1, 1)):
         kw = k if kw is None else kw      # (k x kw: Inception's 1x7 / 7x1 pairs)
-        oh, pt = _same_pad(h, k, s)
-        ow, pl = _same_pad(w, kw, s)
+        dh, dw = (1 if k == 1 else dil[0]), (1 if kw == 1 else dil[1])   # (dil: the taps' pitch per axis; SAME padding of the dilated extent)
+        oh, pt = _same_pad(h, (k - 1) * dh + 1, s)
+        ow, pl = _same_pad(w, (kw - 1) * dw + 1, s)
         wt = self.he((k, kw, cin, cout), k * kw * cin)
         if gain != 1.0:
             wt = wt * np.float32(gain)
         L = mf.Layer(mf.OP_CONV, act, tin, res, cin, cout, k, kw, s, s, pt, pl, h, w, oh, ow,
-                     in_layout, self.put(wt), self.put(self.bias(cout)))
+                     in_layout, self.put(wt), self.put(self.bias(cout)), dil_h=dh, dil_w=dw)
         return self.add(L), oh, ow
 
     def concat(self, parts, h, w, groups=0):
@@ -117,12 +118,12 @@ class _Builder:
         """the channel shuffle of a whole tensor: out[c] = in[(c % groups) * (C / groups) + c // groups]"""
         return self.concat([(tin, 0, c)], h, w, groups)[0]
 
-    def dwconv(self, tin, h, w, c, k, s, act):
-        oh, pt = _same_pad(h, k, s)
-        ow, pl = _same_pad(w, k, s)
+    def dwconv(self, tin, h, w, c, k, s, act, dil=(1, 1)):
+        oh, pt = _same_pad(h, (k - 1) * dil[0] + 1, s)
+        ow, pl = _same_pad(w, (k - 1) * dil[1] + 1, s)
         wt = self.he((k, k, c), k * k)
         L = mf.Layer(mf.OP_DWCONV, act, tin, mf.NO_TENSOR, c, c, k, k, s, s, pt, pl, h, w, oh, ow,
-                     0, self.put(wt), self.put(self.bias(c)))
+                     0, self.put(wt), self.put(self.bias(c)), dil_h=dil[0], dil_w=dil[1])
         return self.add(L), oh, ow
 
     def gconv(self, tin, h, w, cin, cout, k, s, groups, act, gain=1.0, kw=None, pad="same"):
@@ -228,6 +229,8 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     'mnv3_plan' (plan = random_mnv3_plan(seed)) builds that plan's MobileNetV3-style blocks -- hard swish (mf.ACT_HSWISH) between the
     convolutions, hard-sigmoid (mf.ACT_HSIGMOID) gates: _build_mnv3_plan.  'mobilenetv3_audio' (MobileNetV3-Large's layout, ReLU blocks
     included, on the mini front-end: _build_mobilenetv3_audio).
+    'dilated_plan' (a small trunk of dilated full and depthwise convolutions on the mini front-end: _build_dilated_plan).
+    'dilated_resnet_audio' (resnet18_audio at output stride 8, the last two stages dilated 2 and 4: _build_dilated_resnet_audio).
     A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
@@ -251,6 +254,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
         return _build_mnv3_plan(plan, seed)
     if kind == "mobilenetv3_audio":
         return _build_mobilenetv3_audio(seed, n_classes)
+    if kind == "dilated_plan":
+        return _build_dilated_plan(seed)
+    if kind == "dilated_resnet_audio":
+        return _build_dilated_resnet_audio(seed, n_classes)
     rng = np.random.default_rng(seed)
     b = _Builder(rng)
     act_override, act, hidden = act, mf.ACT_GELU_ERF, 0
@@ -576,29 +583,34 @@ def _build_pool_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
     return _finish(b, [br], sr, n, ncls, head, emb, int(plan["out_act"]))
 
 
-def _res_block(b: _Builder, t, h, w, c, kind, shortcut, cout, mid, act, pool_mode=mf.POOL_AVG):
+def _res_block(b: _Builder, t, h, w, c, kind, shortcut, cout, mid, act, pool_mode=mf.POOL_AVG, dil=1):
     """One ResNet block behind tensor t [h][w][c], ending in act(main + shortcut) -- the layer the residual folds into carries `act`
     and Layer.reserved = RES_ACT_AFTER.  kind 'basic': 3x3 (act) -> 3x3; 'bottleneck': 1x1 (act) -> 3x3 (act) -> 1x1, `mid` channels
     inside.  shortcut 'identity' (stride 1, cout == c: the main branch's last convolution is the flagged layer), 'proj' (the main
     branch at stride 2, then a 1x1 stride-2 convolution of the block input, emitted AFTER the main branch as PyTorch exports do: the
     residual folds into the shortcut convolution, which is the flagged layer) or 'resnetd' (conv1x1(avgpool 2x2 stride 2 (x)), ResNet-D;
-    flagged likewise).  The main branch's last convolution is damped by half, as every residual branch of these synthetic nets is."""
-    x, st = t, 1 if shortcut == "identity" else 2
+    flagged likewise) or 'proj1' (a dilated ResNet's stage that widens WITHOUT down-sampling: the main branch at stride 1, the shortcut
+    a 1x1 stride-1 convolution of the block input, flagged).  The main branch's last convolution is damped by half, as every residual
+    branch of these synthetic nets is.  dil: the dilation of the block's 3x3 convolutions, both axes."""
+    x, st = t, 1 if shortcut in ("identity", "proj1") else 2
     assert shortcut != "identity" or cout == c
     last_res = x if shortcut == "identity" else mf.NO_TENSOR
     last_act = act if shortcut == "identity" else mf.ACT_NONE
     if kind == "basic":
-        t, oh, ow = b.conv(x, h, w, c, cout, 3, st, act)
-        t, oh, ow = b.conv(t, oh, ow, cout, cout, 3, 1, last_act, res=last_res, gain=0.5)
+        t, oh, ow = b.conv(x, h, w, c, cout, 3, st, act, dil=(dil, dil))
+        t, oh, ow = b.conv(t, oh, ow, cout, cout, 3, 1, last_act, res=last_res, gain=0.5, dil=(dil, dil))
     else:
         t = b.pwconv(x, h, w, c, mid, act)
-        t, oh, ow = b.conv(t, h, w, mid, mid, 3, st, act)
+        t, oh, ow = b.conv(t, h, w, mid, mid, 3, st, act, dil=(dil, dil))
         t = b.pwconv(t, oh, ow, mid, cout, last_act, last_res, gain=0.5)
     if shortcut == "identity":
         b.layers[-1].reserved = mf.RES_ACT_AFTER
     elif shortcut == "proj":
         t, ph, pw_ = b.conv(x, h, w, c, cout, 1, 2, act, res=t)
         assert (ph, pw_) == (oh, ow)
+        b.layers[-1].reserved = mf.RES_ACT_AFTER
+    elif shortcut == "proj1":
+        t = b.pwconv(x, h, w, c, cout, act, t)
         b.layers[-1].reserved = mf.RES_ACT_AFTER
     elif shortcut == "resnetd":
         tp, ph, pw_ = b.pool(x, h, w, c, 2, 2, 2, 2, pool_mode, "same")
@@ -702,6 +714,69 @@ def _build_resnet18_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = No
     ncls = n_classes or 6522
     b.dense(t, 512, ncls, gain=1.5)
     return _finish(b, branches, sr, n, ncls, 512, emb, mf.OUT_SIGMOID)
+
+
+def _build_dilated_resnet_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) -> mf.Model:
+    """resnet18_audio's trunk at output stride 8, the way sound-event models keep their frames: the stem, the pool and the stages of 64
+    and 128 channels as they are (a 12 x 64 image), the stages of 256 and 512 channels at stride 1 with every 3x3 convolution dilated
+    2 and 4 (their first blocks' shortcuts 1x1 stride-1 convolutions).  Seeded weights: a model for TIMING the dilated layers."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 144000
+    branches = [mf.Branch(2048, 278, 96, 511, 0.0, 3000.0, 1.23), mf.Branch(1024, 280, 96, 511, 500.0, 15000.0, 1.23)]
+    for br in branches:
+        br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+        br.out_scale, br.out_shift = 0.8, -0.4
+    t, h, w = b.conv(0, 96, 511, 2, 64, 7, 2, mf.ACT_RELU, in_layout=1)
+    t, h, w = b.pool(t, h, w, 64, 3, 3, 2, 2, mf.POOL_MAX, (1, 1, 1, 1))
+    c = 64
+    for width, shortcut, dil in ((64, "identity", 1), (128, "proj", 1), (256, "proj1", 2), (512, "proj1", 4)):
+        t, h, w = _res_block(b, t, h, w, c, "basic", shortcut, width, width, mf.ACT_RELU, dil=dil)
+        t, h, w = _res_block(b, t, h, w, width, "basic", "identity", width, width, mf.ACT_RELU, dil=dil)
+        c = width
+    t = emb = b.gap(t, h, w, 512)
+    ncls = n_classes or 6522
+    b.dense(t, 512, ncls, gain=1.5)
+    return _finish(b, branches, sr, n, ncls, 512, emb, mf.OUT_SIGMOID)
+
+
+def _build_dilated_plan(seed: int = WEIGHT_SEED) -> mf.Model:
+    """A small trunk of dilated layers on the quarter-second front end of _build_resnet_plan (32 mels x 115 frames): a 3x3 stem to 24
+    channels; a basic block at dilation 1 ending in relu(conv + x) and one at dilation 2 ending in relu(conv) + x (the residual after
+    and before the activation); a 3x3 stride-2 convolution at dilation 2 to 72 channels; the same two blocks at dilation 4 and 2 with
+    swish, 72 wide (above 64 output channels the f16 modes run the split-f16 kernel); a 3x3 layer at dilation (1, 2) and one at (2, 1);
+    an inverted-residual block whose depthwise 3x3 is dilated 2 (it runs layer by layer: the fused kernel computes the undilated
+    depthwise); a 1x1 head, the global pool and the dense layer."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 12000
+    br = mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23)
+    br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+    br.out_scale, br.out_shift = 0.8, -0.4
+
+    def block(t, h, w, c, act, dil, after):
+        x = t
+        t, h, w = b.conv(x, h, w, c, c, 3, 1, act, dil=(dil, dil))
+        t, h, w = b.conv(t, h, w, c, c, 3, 1, act, res=x, gain=0.5, dil=(dil, dil))
+        if after:
+            b.layers[-1].reserved = mf.RES_ACT_AFTER
+        return t, h, w
+
+    t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, 24, 3, 1, mf.ACT_RELU, in_layout=1)
+    t, h, w = block(t, h, w, 24, mf.ACT_RELU, 1, True)
+    t, h, w = block(t, h, w, 24, mf.ACT_RELU, 2, False)
+    t, h, w = b.conv(t, h, w, 24, 72, 3, 2, mf.ACT_SWISH, dil=(2, 2))
+    t, h, w = block(t, h, w, 72, mf.ACT_SWISH, 4, True)
+    t, h, w = block(t, h, w, 72, mf.ACT_SWISH, 2, False)
+    t, h, w = b.conv(t, h, w, 72, 72, 3, 1, mf.ACT_SWISH, dil=(1, 2))
+    t, h, w = b.conv(t, h, w, 72, 72, 3, 1, mf.ACT_SWISH, dil=(2, 1))
+    x = t
+    t = b.pwconv(t, h, w, 72, 144, mf.ACT_RELU6)
+    t, h, w = b.dwconv(t, h, w, 144, 3, 1, mf.ACT_RELU6, dil=(2, 2))
+    t = b.pwconv(t, h, w, 144, 72, mf.ACT_NONE, x, gain=0.5)
+    head, ncls = 64, 40
+    t = b.pwconv(t, h, w, 72, head, mf.ACT_SWISH)
+    t = emb = b.gap(t, h, w, head)
+    b.dense(t, head, ncls, gain=1.5)
+    return _finish(b, [br], sr, n, ncls, head, emb, mf.OUT_SIGMOID)
 
 
 def _resnext_block(b: _Builder, t, h, w, c, shortcut, cout, mid_in, mid_out, groups, act, se=False):
