@@ -193,7 +193,9 @@ class BirdClassifier:
         return [int(buf[i]) for i in range(n)]
 
     def layer_kernel(self, layer: int) -> str:
-        """bh_debug_layer_kernel: the split-f16 GEMM instantiation model layer `layer` launched in the last forward ('' if none)."""
+        """bh_debug_layer_kernel: the split-f16 GEMM instantiation model layer `layer` launched in the last forward ('' if none); a
+        grouped convolution, a concat, a dilated or 7x7 depthwise layer and a LayerNorm name their kernels in every mode
+        ("lnorm_kernel<32,3>": lanes a pixel, 16-byte pieces a lane)."""
         buf = C.create_string_buffer(160)
         self._L.bh_debug_layer_kernel(self._h, layer, buf, 160)
         return buf.value.decode()

@@ -11,6 +11,9 @@ RES_ACT_AFTER: act(conv + x), the end of a ResNet block) --, squeeze-excite bloc
 Sigmoid -> Mul with the feature map) as pool / 1x1 / 1x1 / OP_SCALE layers, MaxPool / AveragePool in floor mode (OP_POOL: any
 window, stride and padding; count_include_pad either way), Concat / Split / Slice over the channels and the Reshape -> Transpose ->
 Reshape channel shuffle (OP_CONCAT; a Split / Slice output that only Concat nodes read is a view folded into their windows),
+ConvNeXt blocks (OP_LNORM: Transpose [0, 2, 3, 1] / [0, 3, 1, 2] as an [N, H, W, C] view that costs no record, LayerNormalization over the
+channels as a node or as the decomposed ReduceMean -> Sub -> Pow -> ReduceMean -> Add -> Sqrt -> Div -> Mul -> Add chain -- over axis 1 of
+an NCHW map too --, MatMul + Add on the view as a 1x1 layer, the layer-scale Mul by a constant of the channels folded into the layer in front),
 GlobalAveragePool / ReduceMean, Flatten, Gemm / MatMul + Add,
 final Sigmoid / Softmax as the output activation.  Weights move from ONNX's [Cout, Cin/g, kh, kw] to
 the NHWC-friendly layouts of the kernels.
@@ -144,7 +147,8 @@ def frontend_nodes(g: ox.Graph, m: mf.Model, spelling: str) -> None:
 HSWISH_SPELLINGS = ("op", "hsigmoid", "decomposed")
 
 
-def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op") -> ox.Graph:
+def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op",
+                     spell_lnorm: str = "node") -> ox.Graph:
     """The conv stack of a BHM1 model as an ONNX graph over `spectrogram` [N, C, H, W] -- or, with `frontend_spelling`
     (see `frontend_nodes`), the whole model over `audio` [N, S].
     spell_gelu: 'erf' = Div, Erf, Add, Mul, Mul (what exporters emit below opset 20); 'gelu' = one Gelu node.
@@ -152,7 +156,11 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
     'hsigmoid' = HardSigmoid * x (PyTorch below opset 14) / HardSigmoid; 'decomposed' = Add(x, 3) -> Clip(0, 6) -> Mul(., x) ->
     Mul(., 1/6) (tf2onnx; the gate without the Mul(., x)).  Options follow 'decomposed' after a colon, comma-separated: 'div' (Div(., 6)
     for the last Mul), 'scale_first' (the scaling in front of the Mul(., x)), 'swap' (every binary node's operands exchanged where the
-    operator commutes), 'f16' (float16 constants), 'cast' (a Cast to float32 inside the fold; 'hsigmoid' takes 'swap' and 'cast' too)."""
+    operator commutes), 'f16' (float16 constants), 'cast' (a Cast to float32 inside the fold; 'hsigmoid' takes 'swap' and 'cast' too).
+    spell_lnorm: how an OP_LNORM record is written between its two Transposes -- 'node' = LayerNormalization(axis = -1, epsilon) (opset
+    17); 'chain' = ReduceMean -> Sub -> Pow(2) -> ReduceMean -> Add(eps) -> Sqrt -> Div -> Mul -> Add (what torch.onnx emits below it)."""
+    if spell_lnorm not in ("node", "chain"):
+        raise ConvertError(f"unknown LayerNorm spelling {spell_lnorm!r}")
     hs_kind, _, hs_opts = spell_hswish.partition(":")
     hs_opts = set(filter(None, hs_opts.split(",")))
     if hs_kind not in HSWISH_SPELLINGS or not hs_opts <= {"div", "scale_first", "swap", "f16", "cast"}:
@@ -270,8 +278,8 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
                 y = activation(y, L.act, tag)
         elif L.op == mf.OP_GAP:
             g.nodes.append(ox.Node("GlobalAveragePool", [x], [tag + "_gap"]))
-            feeds_conv = any(M.in_tensor == i + 1 and M.op == mf.OP_PWCONV for M in m.layers)
-            if feeds_conv:       # squeeze-excite: the pooled [N, C, 1, 1] map goes on through 1x1 convolutions
+            feeds_conv = any(M.in_tensor == i + 1 and M.op in (mf.OP_PWCONV, mf.OP_LNORM) for M in m.layers)
+            if feeds_conv:       # squeeze-excite: the pooled [N, C, 1, 1] map goes on through 1x1 convolutions (ConvNeXt's head: through a LayerNorm)
                 y = tag + "_gap"
             else:
                 g.nodes.append(ox.Node("Flatten", [tag + "_gap"], [tag + "_flat"], {"axis": 1}))
@@ -321,6 +329,27 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
                 g.nodes.append(ox.Node("Transpose", [tag + "_r5"], [tag + "_tr"], {"perm": [0, 2, 1, 3, 4]}))
                 g.nodes.append(ox.Node("Reshape", [tag + "_tr", tag + "_s4"], [tag + "_shuffled"]))
                 y = tag + "_shuffled"
+        elif L.op == mf.OP_LNORM:
+            # the channel LayerNorm as PyTorch exports it from opset 17: on the [N, H, W, C] view between two Transposes (a 1 x 1 image too)
+            if L.in_tensor == 0:
+                raise ConvertError(f"layer {i}: a LayerNorm of the spectrogram has no ONNX spelling here")
+            g.nodes.append(ox.Node("Transpose", [x], [tag + "_nhwc"], {"perm": [0, 2, 3, 1]}))
+            ga, be = const(tag + "_gamma", m.weight(L.w_off, L.cout)), const(tag + "_beta", m.weight(L.b_off, L.cout))
+            if spell_lnorm == "node":
+                g.nodes.append(ox.Node("LayerNormalization", [tag + "_nhwc", ga, be], [tag + "_ln"], {"axis": -1, "epsilon": mf.lnorm_eps(L.reserved)}, name=tag))
+            else:
+                v = tag + "_nhwc"
+                for o, ins, out, attrs in (("ReduceMean", [v], "_mu", {"axes": [-1], "keepdims": 1}), ("Sub", [v, tag + "_mu"], "_d", {}),
+                                           ("Pow", [tag + "_d", const(tag + "_two", 2.0)], "_d2", {}), ("ReduceMean", [tag + "_d2"], "_var", {"axes": [-1], "keepdims": 1}),
+                                           ("Add", [tag + "_var", const(tag + "_eps", np.float32(mf.lnorm_eps(L.reserved)))], "_ve", {}), ("Sqrt", [tag + "_ve"], "_sd", {}),
+                                           ("Div", [tag + "_d", tag + "_sd"], "_xh", {}), ("Mul", [tag + "_xh", ga], "_xg", {}), ("Add", [tag + "_xg", be], "_ln", {})):
+                    g.nodes.append(ox.Node(o, ins, [tag + out], attrs, name=tag + out))
+            g.nodes.append(ox.Node("Transpose", [tag + "_ln"], [tag + "_nchw"], {"perm": [0, 3, 1, 2]}))
+            y = tag + "_nchw"
+            if L.in_h * L.in_w == 1 and any(M.in_tensor == i + 1 and M.op == mf.OP_DENSE for M in m.layers):
+                g.nodes.append(ox.Node("Flatten", [y], [tag + "_flat"], {"axis": 1}))
+                y = tag + "_flat"
+                flat.add(i + 1)
         elif L.op == mf.OP_DENSE:
             w = m.weight(L.w_off, L.cin * L.cout).reshape(L.cin, L.cout)
             g.nodes.append(ox.Node("Gemm", [x, const(tag + "_w", w), const(tag + "_b", m.weight(L.b_off, L.cout))], [tag + "_fc"],
@@ -341,9 +370,10 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
     return g
 
 
-def model_to_onnx(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op") -> bytes:
+def model_to_onnx(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op",
+                  spell_lnorm: str = "node") -> bytes:
     """`graph_from_model` serialised: the bytes of the `.onnx` file `bh_classifier_create` opens."""
-    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling, spell_hswish))
+    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling, spell_hswish, spell_lnorm))
 
 
 # ---------------------------------------------------------------------------------------
@@ -532,6 +562,100 @@ def _collapse_activations(g: ox.Graph, front_nodes=frozenset()):
     return skip, act_of
 
 
+LN_CHAIN = "ReduceMean -> Sub -> Pow(2) -> ReduceMean -> Add(eps) -> Sqrt -> Div -> Mul(gamma) -> Add(beta)"
+
+
+def _reduce_axes(g: ox.Graph, n: ox.Node) -> Optional[List[int]]:
+    axes = n.attrs.get("axes")
+    if axes is None and len(n.inputs) > 1 and n.inputs[1]:
+        axes = _const_ints(g, n.inputs[1])
+    return None if axes is None else [int(a) for a in axes]
+
+
+def _find_layer_norms(g: ox.Graph, skip: set, front_nodes: set) -> Dict[str, list]:
+    """The decomposed LayerNorm torch.onnx emits below opset 17 (LN_CHAIN), over the last axis of an [N, H, W, C] view or over axis 1
+    of an NCHW map: a ReduceMean over ONE axis (-1, 3 or 1) starts it, and a chain that deviates is refused by naming the node where
+    it does (another exponent, another axis, a missing eps, a second reader of an inner tensor).  csrc/onnx_conv.hpp finds it the same
+    way.  Returns {the chain's input: [(output name, gamma name, beta name, eps, axis, the ReduceMean's name)]}; the chain's nodes join
+    `skip`."""
+    graph_out = {o.name for o in g.outputs}
+    cons: Dict[str, List[int]] = {}
+    for i, n in enumerate(g.nodes):
+        if i in skip:
+            continue
+        for x in n.inputs:
+            cons.setdefault(x, []).append(i)
+
+    def dev(n: ox.Node, why: str):
+        raise ConvertError(f"{n.op_type} {n.name!r}: not the LayerNorm chain {LN_CHAIN}: {why}")
+
+    def only_reader(src: ox.Node, op: str) -> int:
+        """the one reader of src's output, which must be an `op` node"""
+        name = src.outputs[0]
+        c = cons.get(name, [])
+        if name in graph_out or len(c) != 1:
+            dev(src, f"its output has {len(c)} readers{' and is a graph output' if name in graph_out else ''} (a second reader of an inner tensor)")
+        if g.nodes[c[0]].op_type != op or not g.nodes[c[0]].outputs:
+            dev(g.nodes[c[0]], f"{op} expected behind {src.op_type} {src.name!r}")
+        return c[0]
+
+    def other(n: ox.Node, name: str) -> str:
+        if len(n.inputs) != 2 or name not in n.inputs:
+            dev(n, "two operands expected")
+        return n.inputs[1] if n.inputs[0] == name else n.inputs[0]
+
+    found: Dict[str, list] = {}
+    for i, n in enumerate(g.nodes):
+        if n.op_type != "ReduceMean" or i in skip or i in front_nodes or not n.inputs or not n.outputs:
+            continue
+        axes = _reduce_axes(g, n)
+        if axes is None or len(axes) != 1 or axes[0] not in (-1, 3, 1):
+            continue                                           # (H, W: the global pool; anything else keeps the walk's refusal)
+        if int(n.attrs.get("keepdims", 1)) != 1:
+            dev(n, "keepdims = 0")
+        x = n.inputs[0]
+        j_sub = only_reader(n, "Sub")
+        sub = g.nodes[j_sub]
+        if list(sub.inputs) != [x, n.outputs[0]]:
+            dev(sub, "Sub(x, mean) expected")
+        rd = cons.get(sub.outputs[0], [])
+        if sub.outputs[0] in graph_out or len(rd) != 2 or sorted(g.nodes[k].op_type for k in rd) != ["Div", "Pow"]:
+            dev(sub, "its output must be read by the Pow and the Div alone (a second reader of an inner tensor)")
+        j_pow, j_div = (rd if g.nodes[rd[0]].op_type == "Pow" else rd[::-1])
+        pw, div = g.nodes[j_pow], g.nodes[j_div]
+        if len(pw.inputs) != 2 or pw.inputs[0] != sub.outputs[0] or _fscalar(g, pw.inputs[1]) != 2.0:
+            dev(pw, f"exponent {_fscalar(g, pw.inputs[1]) if len(pw.inputs) == 2 else None} (2 expected)")
+        j_m2 = only_reader(pw, "ReduceMean")
+        m2 = g.nodes[j_m2]
+        if _reduce_axes(g, m2) != axes or int(m2.attrs.get("keepdims", 1)) != 1:
+            dev(m2, f"axes {_reduce_axes(g, m2)} (the first mean is over {axes}: another axis)")
+        c = cons.get(m2.outputs[0], [])
+        if len(c) == 1 and g.nodes[c[0]].op_type == "Sqrt":
+            dev(g.nodes[c[0]], "a missing eps (Add(variance, eps) expected in front of the Sqrt)")
+        j_add = only_reader(m2, "Add")
+        add = g.nodes[j_add]
+        eps = _fscalar(g, other(add, m2.outputs[0]))
+        if eps is None:
+            dev(add, "a missing eps (a float32 or float16 scalar constant expected)")
+        j_sqrt = only_reader(add, "Sqrt")
+        sq = g.nodes[j_sqrt]
+        if only_reader(sq, "Div") != j_div or list(div.inputs) != [sub.outputs[0], sq.outputs[0]]:
+            dev(div, "Div(x - mean, sqrt) expected")
+        j_mul = only_reader(div, "Mul")
+        mul = g.nodes[j_mul]
+        gamma = other(mul, div.outputs[0])
+        j_add2 = only_reader(mul, "Add")
+        add2 = g.nodes[j_add2]
+        beta = other(add2, mul.outputs[0])
+        for role, name, q in (("gamma", gamma, mul), ("beta", beta, add2)):
+            a = g.initializers.get(name)
+            if a is None or a.dtype not in (np.float32, np.float16):
+                dev(q, f"{role} must be a float32 or float16 initializer")
+        skip |= {i, j_sub, j_pow, j_m2, j_add, j_sqrt, j_div, j_mul, j_add2}
+        found.setdefault(x, []).append((add2.outputs[0], gamma, beta, float(eps), axes[0], n.name))
+    return found
+
+
 def _const_ints(g: ox.Graph, name: str) -> Optional[List[int]]:
     """The integer list a node input names -- an initializer or a Constant node's value -- or None (at most 64 entries are read)"""
     a = g.initializers.get(name)
@@ -651,6 +775,8 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
     graph_out = {o.name for o in g.outputs}
 
     sums = set()   # the outputs of the residual Adds folded into a layer
+    nhwc = set()   # the names that are [N, H, W, C] views of their tensor (behind Transpose [0, 2, 3, 1]): the library keeps activations NHWC
+    NHWC_READERS = ("Transpose", "LayerNormalization", "MatMul", "Mul", "Relu", "Gelu", "Clip", "HardSwish")
 
     def set_act(name_in: str, name_out: str, act: int, own):
         """own: the node indices of the activation itself -- one, or a multi-node spelling's"""
@@ -667,6 +793,11 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         if L is not None and L.op == mf.OP_CONCAT:
             raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a Concat, Split, Slice "
                                "or channel shuffle (the record carries no activation)")
+        if L is not None and L.op == mf.OP_LNORM:
+            raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a LayerNormalization "
+                               "(the record carries no activation)")
+        if name_in in nhwc:
+            nhwc.add(name_out)
         if L is not None and name_in in sums and L.res_tensor != mf.NO_TENSOR and L.reserved != mf.RES_ACT_AFTER:
             # act(conv + x), the end of a ResNet block: the layer keeps its one activation code and records its position
             if L.act != mf.ACT_NONE:
@@ -686,10 +817,51 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
     first_of_pattern = {}   # applied when the walk reaches the pattern's input (below)
     for out_name, (x, act, own) in act_of.items():
         first_of_pattern.setdefault(x, []).append((out_name, act, own))
+    ln_of_pattern = _find_layer_norms(g, skip, front_nodes)      # the decomposed LayerNorm chains, by their input
+
+    def lnorm_rec(who: str, x_name: str, out_name: str, gamma, beta, eps: float):
+        """one OP_LNORM record over the channels of tensor x_name (an [N, H, W, C] view, or an NCHW map the caller has held to the
+        channel axis) -> out_name, a view when x_name is one; directly behind the global pool it becomes the embedding"""
+        nonlocal emb_tensor
+        t = tmap[x_name]
+        if t[0] == 0:
+            raise ConvertError(who + "a LayerNorm of the spectrogram (tensor 0) is not supported")
+        C = t[1]
+        if gamma.dtype not in (np.float32, np.float16) or gamma.size != C or (beta is not None and (beta.dtype not in (np.float32, np.float16) or beta.size != C)):
+            raise ConvertError(who + f"gamma / beta must be float32 or float16 initializers of the {C} channels")
+        if C % 4:
+            raise ConvertError(who + f"{C} channels: a channel count that is not a multiple of 4 is not supported")
+        e32 = np.float32(eps)
+        if not np.isfinite(e32) or not e32 > 0:
+            raise ConvertError(who + f"epsilon {eps!r} is not finite and > 0")
+        bz = np.zeros(C, np.float32) if beta is None else beta.reshape(-1)
+        layers.append(mf.Layer(mf.OP_LNORM, mf.ACT_NONE, t[0], mf.NO_TENSOR, C, C, 1, 1, 1, 1, 0, 0, t[2], t[3], t[2], t[3], 0,
+                               blob.put(gamma.reshape(-1)), blob.put(bz), reserved=mf.lnorm_eps_bits(float(e32))))
+        if layers[t[0] - 1].op == mf.OP_GAP and emb_tensor == t[0]:
+            emb_tensor = len(layers)          # pool -> norm -> dense: the dense head reads the norm
+        tmap[out_name] = (len(layers), C, t[2], t[3])
+        if x_name in nhwc:
+            nhwc.add(out_name)
 
     def flush_patterns(x: str):
         for out_name, act, own in first_of_pattern.pop(x, []):
             set_act(x, out_name, act, own)
+        for out_name, gamma, beta, eps, axis, name in ln_of_pattern.pop(x, []):
+            who = f"ReduceMean {name!r} (LayerNorm chain): "
+            ga, be = g.initializers[gamma], g.initializers[beta]
+            C = tmap[x][1]
+            if x in nhwc:
+                if axis not in (-1, 3):
+                    raise ConvertError(who + f"axis {axis} of an [N, H, W, C] view: only the last axis, the channels, is normalised (another axis)")
+                ok = ga.shape == (C,) and be.shape == (C,)
+            else:
+                if axis != 1:
+                    raise ConvertError(who + f"axis {axis} of an NCHW tensor: only axis 1, the channels, is normalised (another axis)")
+                ok = ga.shape in ((C, 1, 1), (1, C, 1, 1)) and be.shape in ((C, 1, 1), (1, C, 1, 1))
+            if not ok:
+                raise ConvertError(who + f"gamma / beta of shape {list(ga.shape)} / {list(be.shape)} do not scale the {C} channels")
+            lnorm_rec(who, x, out_name, ga, be, eps)
+            flush_patterns(out_name)
 
     shuffle_at, shuffle_computed = _find_shuffles(g, skip, front_nodes)
     vmap: Dict[str, Tuple[int, int, int, int, int]] = {}   # the views: name -> (tensor, C, H, W, first channel); only Concat looks here
@@ -713,13 +885,114 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         else:
             vmap[name] = v
 
+    def fold_layer_scale(n: ox.Node, view_in) -> bool:
+        """Mul of a convolution's / MatMul layer's output by a constant of its C channels ([C] on an [N, H, W, C] view, [C, 1, 1] or
+        [1, C, 1, 1] on an NCHW map): ConvNeXt's layer scale, folded into the layer's weight columns and bias where BatchNormalization
+        is -- one float32 product each.  The layer has no activation and no residual yet, the Mul is its only reader and the tensor
+        no graph output.  False: not that Mul (today's rules apply)."""
+        if len(n.inputs) != 2 or not n.outputs:
+            return False
+        for x_name, s_name in ((n.inputs[0], n.inputs[1]), (n.inputs[1], n.inputs[0])):
+            S, t = g.initializers.get(s_name), tmap.get(x_name)
+            if S is None or t is None or t[0] == 0 or S.dtype not in (np.float32, np.float16):
+                continue
+            L, C = layers[t[0] - 1], t[1]
+            shapes = ((C,),) if x_name in nhwc else ((C, 1, 1), (1, C, 1, 1))
+            if S.shape not in shapes or L.op not in (mf.OP_CONV, mf.OP_DWCONV, mf.OP_PWCONV, mf.OP_GCONV) or L.act != mf.ACT_NONE or \
+                    L.res_tensor != mf.NO_TENSOR or x_name in graph_out or sum(x_name in q.inputs for q in g.nodes) != 1:
+                continue
+            nw = {mf.OP_CONV: L.kh * L.kw * L.cin * L.cout, mf.OP_DWCONV: L.kh * L.kw * L.cout, mf.OP_PWCONV: L.cin * L.cout,
+                  mf.OP_GCONV: L.kh * L.kw * (L.cin // max(L.reserved, 1)) * L.cout}[L.op]
+            scale = S.reshape(-1).astype(np.float32)
+            arr = blob.array()
+            arr[L.w_off: L.w_off + nw] = (arr[L.w_off: L.w_off + nw].reshape(-1, L.cout) * scale).reshape(-1)   # cout is the last axis in every layout
+            arr[L.b_off: L.b_off + L.cout] = arr[L.b_off: L.b_off + L.cout] * scale
+            blob.chunks, blob.off = [arr], arr.size
+            tmap[n.outputs[0]] = t
+            if x_name in nhwc:
+                nhwc.add(n.outputs[0])
+            flush_patterns(n.outputs[0])
+            return True
+        if view_in is not None:
+            raise ConvertError(f"Mul {n.name!r}: input {view_in!r} is an [N, H, W, C] view (behind a Transpose): only a Mul by a [C] constant "
+                               "directly behind a MatMul layer without an activation, its only reader, is folded (layer scale)")
+        return False
+
     for i, n in enumerate(g.nodes):
         if i in skip or i in front_nodes:
             continue
         op = n.op_type
         if op == "Constant":      # (the library's parser turns these into initializers; _const_ints reads them where they are)
             continue
-        if op == "Concat":
+        view_in = next((x for x in n.inputs if x in nhwc), None)
+        if view_in is not None and op not in NHWC_READERS:
+            raise ConvertError(f"{op} {n.name!r}: input {view_in!r} is an [N, H, W, C] view (behind a Transpose): only LayerNormalization, "
+                               "MatMul (+ Add of a bias), the activations, Mul by a [C] constant and the Transpose back read one")
+        if op == "Transpose":
+            # the library keeps activations NHWC: [0, 2, 3, 1] marks the result an [N, H, W, C] view of the same tensor, [0, 3, 1, 2] ends it
+            who = f"Transpose {n.name!r}: "
+            perm = [int(v) for v in (n.attrs.get("perm") or [])]
+            t = tmap.get(n.inputs[0])
+            if t is None:
+                raise ConvertError(who + f"input {n.inputs[0]!r} is not on the path from {spec!r}")
+            if perm == [0, 2, 3, 1] and view_in is None:
+                if t[0] == 0:
+                    raise ConvertError(who + "an [N, H, W, C] view of the spectrogram (tensor 0) is not supported")
+                nhwc.add(n.outputs[0])
+            elif not (perm == [0, 3, 1, 2] and view_in is not None):
+                raise ConvertError(who + f"perm {perm} on {'an [N, H, W, C] view' if view_in is not None else 'an NCHW feature map'}: only "
+                                   "[0, 2, 3, 1] on a feature map and [0, 3, 1, 2] on the view it makes are read")
+            tmap[n.outputs[0]] = t
+            flush_patterns(n.outputs[0])
+        elif op == "LayerNormalization":
+            who = f"LayerNormalization {n.name!r}: "
+            t = tmap.get(n.inputs[0])
+            if t is None:
+                raise ConvertError(who + f"input {n.inputs[0]!r} is not on the path from {spec!r}")
+            axis = int(n.attrs.get("axis", -1))
+            if view_in is not None:
+                if axis not in (-1, 3):
+                    raise ConvertError(who + f"axis {axis} of an [N, H, W, C] view: only the last axis, the channels, is normalised")
+            elif axis != 1 or t[2] * t[3] != 1:
+                raise ConvertError(who + f"axis {axis} of an NCHW tensor with a {t[2]}x{t[3]} image: it would normalise over more than the "
+                                   "channels (only axis 1 of an [N, C, 1, 1] tensor, or the last axis of an [N, H, W, C] view)")
+            for k, what in ((1, "Mean"), (2, "InvStdDev")):
+                if len(n.outputs) > k and n.outputs[k] and (n.outputs[k] in graph_out or readers.get(n.outputs[k])):
+                    raise ConvertError(who + f"the output {what} is read: only the normalised tensor is computed")
+            ga = g.initializers.get(n.inputs[1]) if len(n.inputs) > 1 else None
+            be = g.initializers.get(n.inputs[2]) if len(n.inputs) > 2 and n.inputs[2] else None
+            if ga is None or (len(n.inputs) > 2 and n.inputs[2] and be is None):
+                raise ConvertError(who + f"gamma / beta must be float32 or float16 initializers of the {t[1]} channels")
+            lnorm_rec(who, n.inputs[0], n.outputs[0], ga, be, float(np.float32(n.attrs.get("epsilon", 1e-5))))
+            flush_patterns(n.outputs[0])
+        elif op == "MatMul" and view_in is not None:
+            # a pointwise layer on the [N, H, W, C] view (a PyTorch Linear between two Transposes), with its Add of a bias
+            who = f"MatMul {n.name!r}: "
+            if view_in != n.inputs[0]:
+                raise ConvertError(who + f"the [N, H, W, C] view {view_in!r} as the second operand")
+            t = tmap[n.inputs[0]]
+            W = g.initializers.get(n.inputs[1])
+            if W is None or W.ndim != 2 or W.dtype not in (np.float32, np.float16):
+                raise ConvertError(who + "needs a 2-d float32 or float16 weight initializer")
+            cin, cout = W.shape
+            if cin != t[1]:
+                raise ConvertError(who + f"{cin} input features, activation has {t[1]}")
+            B, out = None, n.outputs[0]
+            nxt = [k for k, nn in enumerate(g.nodes) if out in nn.inputs]
+            if len(nxt) == 1 and g.nodes[nxt[0]].op_type == "Add" and len(g.nodes[nxt[0]].inputs) == 2 and out not in graph_out:
+                o2 = [a for a in g.nodes[nxt[0]].inputs if a != out]
+                ob = g.initializers.get(o2[0]) if o2 else None
+                if ob is not None and ob.dtype in (np.float32, np.float16) and ob.size == cout:
+                    B, out = ob, g.nodes[nxt[0]].outputs[0]
+                    skip.add(nxt[0])
+            layers.append(mf.Layer(mf.OP_PWCONV, mf.ACT_NONE, t[0], mf.NO_TENSOR, cin, cout, 1, 1, 1, 1, 0, 0, t[2], t[3], t[2], t[3], 0,
+                                   blob.put(W), blob.put(np.zeros(cout, np.float32) if B is None else B.reshape(-1))))
+            tmap[out] = (len(layers), cout, t[2], t[3])
+            nhwc.add(out)
+            flush_patterns(out)
+        elif op == "Mul" and fold_layer_scale(n, view_in):
+            pass
+        elif op == "Concat":
             who = f"Concat {n.name!r}: "
             if len(n.inputs) > 64:
                 raise ConvertError(who + f"{len(n.inputs)} inputs (1 .. 64 are read)")
@@ -976,6 +1249,7 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             layers.append(mf.Layer(mf.OP_GAP, mf.ACT_NONE, t[0], mf.NO_TENSOR, t[1], t[1], t[2], t[3], 1, 1, 0, 0, t[2], t[3], 1, 1))
             tmap[n.outputs[0]] = (len(layers), t[1], 1, 1)
             emb_tensor, emb_dim = len(layers), t[1]
+            flush_patterns(n.outputs[0])      # (a decomposed LayerNorm behind the pool)
         elif op in ("MaxPool", "AveragePool"):
             # windowed pooling in floor mode -> OP_POOL (csrc/onnx_conv.hpp has the same branch)
             who = f"{op} {n.name!r}: "
@@ -1092,8 +1366,8 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             tmap[n.outputs[0]] = tmap[n.inputs[0]]
         else:
             raise ConvertError(f"unsupported operator {op} ({n.name!r})")
-    if first_of_pattern:
-        raise ConvertError(f"activation patterns on tensors that were never produced: {sorted(first_of_pattern)}")
+    if first_of_pattern or ln_of_pattern:
+        raise ConvertError(f"activation patterns on tensors that were never produced: {sorted(set(first_of_pattern) | set(ln_of_pattern))}")
     if not layers or layers[-1].op != mf.OP_DENSE:
         raise ConvertError("the graph does not end in a dense layer")
     final = [tmap.get(o.name) for o in g.outputs]

@@ -264,13 +264,23 @@ int SliceRun::layer(const Step &st) const {
         ctx_mark(ctx, ST_GAP, (int)i);
         break;
     }
+    case bh::OP_LNORM: {   // LayerNorm over the channels, pixel by pixel: f32 in every precision mode (L.reserved: the bits of eps)
+        float eps;
+        memcpy(&eps, &L.reserved, sizeof eps);
+        launched = bh::launch_lnorm(in, c->d_blob + L.w_off, bias, out, (unsigned long long)n * L.out_h * L.out_w, (int)L.cout, eps, s);
+        ctx_mark(ctx, ST_GAP, (int)i);
+        break;
+    }
     default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
     }
     // (bh_debug_layer_kernel: the split-f16 launchers' names; a grouped convolution's and a concat's f32 kernels are kept too)
     // (... and a dilated depthwise layer's, the dilated form of dwconv_kernel)
-    if (f16 || L.op == bh::OP_GCONV || L.op == bh::OP_CONCAT || (L.op == bh::OP_DWCONV && bh::conv_dilated(p))) S.kernel.store(launched, std::memory_order_relaxed);
+    // (... and a 7x7 depthwise layer's and a LayerNorm's: the layers of a ConvNeXt block)
+    if (f16 || L.op == bh::OP_GCONV || L.op == bh::OP_CONCAT || L.op == bh::OP_LNORM || (L.op == bh::OP_DWCONV && (bh::conv_dilated(p) || L.kh == 7)))
+        S.kernel.store(launched, std::memory_order_relaxed);
     // (create's predicates and validate_model keep this from happening; if it does, the output tensor was not written)
     if (!launched && n) {
+        if (L.op == bh::OP_LNORM) return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for a layer norm over %u channels", i, L.cout);
         if (L.op == bh::OP_DWCONV || (L.op == bh::OP_CONV && L.in_layout == 1))
             return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for a %ux%u stride %ux%u window, %u -> %u channels", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout);
         return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for activation %u %s the residual add", i, L.act, after ? "after" : "before");

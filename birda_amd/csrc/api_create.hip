@@ -200,6 +200,10 @@ int prepare_layer(bh_classifier *c, size_t i, bool in_block, bool se_project) {
         if (L.op == bh::OP_POOL && !bh::pool_supports(p, (int)L.reserved))
             return fail(BH_ERR_UNSUPPORTED, "layer %zu: pool %ux%u stride %ux%u pad %u,%u mode %u not built", i, L.kh, L.kw, L.sh, L.sw, L.pad_t, L.pad_l, L.reserved);
         return BH_OK;
+    case bh::OP_LNORM:   // (validate_model has held the record; the kernel's width range is create's rule)
+        if (!bh::lnorm_supports((int)L.cout))
+            return fail(BH_ERR_UNSUPPORTED, "layer %zu: layer norm over %u channels not built (a multiple of 4, 4 .. 2048)", i, L.cout);
+        return BH_OK;
     case bh::OP_CONCAT: {
         const auto src = concat_sources(m, L, nullptr, nullptr);
         if (!bh::concat_supports((int)L.out_h, (int)L.out_w, src.data(), L.res_tensor == bh::NO_TENSOR ? 1 : 2, (int)L.reserved))

@@ -14,6 +14,7 @@
 #include "../../include/birda_hip_custom_debug.h"
 #include "../../include/birda_hip_gated_debug.h"
 #include "../../include/birda_hip_dilated_debug.h"
+#include "../../include/birda_hip_lnorm_debug.h"
 
 using namespace bhi;
 
@@ -301,7 +302,7 @@ int bh_debug_dilated_layer(int device, int op, const float *X, const float *W, c
     if (p.dil_h < 1 || p.dil_w < 1 || p.dil_h > (int)bh::MAX_DILATION || p.dil_w > (int)bh::MAX_DILATION)
         return fail(BH_ERR_UNSUPPORTED, "debug_dilated_layer: dilation %dx%d (1 .. 16 are supported)", p.dil_h, p.dil_w);
     if (!bh::dwconv_supports(p))
-        return fail(BH_ERR_UNSUPPORTED, "debug_dilated_layer: depthwise %dx%d stride %dx%d dilation %dx%d channels %d not built (square 3x3 / 5x5 windows, one "
+        return fail(BH_ERR_UNSUPPORTED, "debug_dilated_layer: depthwise %dx%d stride %dx%d dilation %dx%d channels %d not built (square 3x3 / 5x5 / 7x7 windows, one "
                     "stride of 1 or 2, channels a multiple of 4)", p.kh, p.kw, p.sh, p.sw, p.dil_h, p.dil_w, p.cout);
     const size_t x_seg = (size_t)p.in_h * p.in_w * p.cout, y_seg = (size_t)p.out_h * p.out_w * p.cout;
     if (x_seg > (size_t)INT32_MAX || y_seg > (size_t)INT32_MAX || n_seg * x_seg > (size_t)INT32_MAX || n_seg * y_seg > (size_t)INT32_MAX)
@@ -314,6 +315,25 @@ int bh_debug_dilated_layer(int device, int op, const float *X, const float *W, c
     const char *name = bh::launch_dwconv(dx, dwt, db, dy, p, (int)n_seg, nullptr);
     if (!name) return fail(BH_ERR_INTERNAL, "debug_dilated_layer: the launcher has no instantiation for a shape dwconv_supports accepts");
     return h.finish(name, kernel, kernel_cap);
+} catch (...) { return on_exception(); }
+
+// One channel LayerNorm launch alone on operands of the caller's, through the launcher a forward pass takes
+// (include/birda_hip_lnorm_debug.h).
+int bh_debug_lnorm(int device, const float *X, const float *gamma, const float *beta, float eps, float *out, size_t n_pixels_total, size_t C,
+                   char *name, size_t name_len) try {
+    if (!X || !gamma || !beta || !out || !n_pixels_total || !C) return fail(BH_ERR_INVALID, "debug_lnorm: bad arguments");
+    if (!std::isfinite(eps) || !(eps > 0.0f)) return fail(BH_ERR_INVALID, "debug_lnorm: eps %g is not finite and > 0", (double)eps);
+    if (C > (size_t)INT32_MAX || !bh::lnorm_supports((int)C))
+        return fail(BH_ERR_UNSUPPORTED, "debug_lnorm: layer norm over %zu channels not built (a multiple of 4, 4 .. 2048)", C);
+    if (n_pixels_total > (size_t)INT32_MAX || n_pixels_total * C > (size_t)INT32_MAX) return fail(BH_ERR_INVALID, "debug_lnorm: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    DebugLaunch h{"debug_lnorm"};
+    const float *dx = h.in(X, n_pixels_total * C * 4), *dg = h.in(gamma, C * 4), *db = h.in(beta, C * 4);
+    float *dy = h.out(n_pixels_total * C, "out", out);
+    if (!h.ok) return h.no_memory();
+    const char *kn = bh::launch_lnorm(dx, dg, db, dy, (unsigned long long)n_pixels_total, (int)C, eps, nullptr);
+    if (!kn) return fail(BH_ERR_INTERNAL, "debug_lnorm: the launcher has no instantiation for a width lnorm_supports accepts");
+    return h.finish(kn, name, name_len);
 } catch (...) { return on_exception(); }
 
 // One grouped convolution alone on operands of the caller's, with create's weight preparation (gconv_matrix, gconv_fragments,
@@ -476,9 +496,11 @@ int bh_debug_plain_layer(int device, int op, const float *X, const float *W, con
         return fail(BH_ERR_INVALID, "debug_plain_layer: layer dimensions out of range");
     if (gap && (p.out_h != 1 || p.out_w != 1)) return fail(BH_ERR_INVALID, "debug_plain_layer: a global pool leaves one pixel");
     if (scale && (p.out_h != p.in_h || p.out_w != p.in_w)) return fail(BH_ERR_INVALID, "debug_plain_layer: a gate multiply keeps the image");
-    if (dw && !bh::dwconv_supports(p))
-        return fail(BH_ERR_UNSUPPORTED, "debug_plain_layer: depthwise %dx%d stride %dx%d channels %d not built (square 3x3 / 5x5 windows, one stride of 1 or 2, "
-                    "channels a multiple of 4)", p.kh, p.kw, p.sh, p.sw, p.cout);
+    // (this entry keeps the windows it always took -- tests/test_gate_layers_gpu.py holds it to refusing every other one --; the 7x7
+    //  window, dilated or not, runs through bh_debug_dilated_layer, whose dilation 1 is the plain layer's launch)
+    if (dw && (!bh::dwconv_supports(p) || p.kh == 7))
+        return fail(BH_ERR_UNSUPPORTED, "debug_plain_layer: depthwise %dx%d stride %dx%d channels %d not built here (this entry takes square 3x3 / 5x5 windows, one stride of "
+                    "1 or 2, channels a multiple of 4; a 7x7 window runs through bh_debug_dilated_layer)", p.kh, p.kw, p.sh, p.sw, p.cout);
     if (conv && !bh::conv_direct_supports(p))
         return fail(BH_ERR_UNSUPPORTED, "debug_plain_layer: direct conv shape not built (output channels a multiple of 4, %dx%dx%dx%d weights within 64 KiB of LDS)",
                     p.kh, p.kw, p.cin, p.cout);

@@ -478,7 +478,7 @@ bool gconv_supports(const ConvParams &p, int groups);
 const char *launch_gconv(const float *in, const float *Wf, const float *b, float *out, const ConvParams &p, int groups, int n_seg, hipStream_t s);
 const char *launch_gconv16(const float *in, const void *Wf, const float *b, float *out, const ConvParams &p, int groups, int n_seg, int terms,
                            float w_unscale, hipStream_t s);
-// depthwise conv NHWC; w [kh][kw][c]: square 3x3 / 5x5 windows, one stride 1 / 2, c % 4 == 0 (dwconv_supports: create's rule).
+// depthwise conv NHWC; w [kh][kw][c]: square 3x3 / 5x5 / 7x7 windows, one stride 1 / 2, c % 4 == 0 (dwconv_supports: create's rule).
 // Returns the instantiation's name ("dwconv_kernel<3,2>"); nullptr when no instantiation matches and nothing was launched.
 // A dilated layer (p.dil_h, p.dil_w, 1 .. 16 each, run-time arguments) takes the dilated form of the same windows and strides,
 // "dwconv_kernel<3,2,DIL>"; dwconv_supports does not look at the dilation.
@@ -542,6 +542,13 @@ struct ConcatSource { const float *p; int total4, off, len; };
 constexpr unsigned kConcatMaxWorkgroups = 256 * 8;   // of 256 threads, one 16-byte output group each a trip of the grid-stride loop
 bool concat_supports(int h, int w, const ConcatSource *src, int n_src, int groups);
 const char *launch_concat(const ConcatSource *src, int n_src, float *out, int h, int w, int groups, int n_seg, hipStream_t s);
+// LayerNorm over the channels of an NHWC f32 tensor, pixel by pixel (kernels_lnorm.hip; model.hpp OP_LNORM): out[p][c] =
+// (in[p][c] - mean_p) / sqrt(var_p + eps) * gamma[c] + beta[c] over n_pix pixels of C channels, var_p the biased variance, two-pass
+// in registers.  C % 4 == 0, 4 <= C <= 2048 (lnorm_supports).  f32 in every precision mode; a NaN or an inf in a pixel makes every
+// channel of that pixel NaN and no other; a constant pixel gives beta exactly.  Returns the instantiation's name
+// ("lnorm_kernel<32,1>": lanes a pixel, float4s a lane -- C alone decides); nullptr when C is not supported and nothing was launched.
+bool lnorm_supports(int C);
+const char *launch_lnorm(const float *in, const float *gamma, const float *beta, float *out, unsigned long long n_pix, int C, float eps, hipStream_t s);
 // head 1x1 conv + activation (GELU / swish / ReLU6) + global average pool fused (f16 hi / lo weight planes as for launch_pw_gemm16)
 bool head_gap16_supports(int P, int K, int N, int act);
 const char *launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,

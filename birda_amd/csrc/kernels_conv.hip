@@ -1297,7 +1297,7 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float *__restrict__ i
 }
 
 bool dwconv_supports(const ConvParams &p) {
-    return p.cout % 4 == 0 && p.kh == p.kw && p.sh == p.sw && (p.kh == 3 || p.kh == 5) && (p.sh == 1 || p.sh == 2);
+    return p.cout % 4 == 0 && p.kh == p.kw && p.sh == p.sw && (p.kh == 3 || p.kh == 5 || p.kh == 7) && (p.sh == 1 || p.sh == 2);
 }
 
 const char *launch_dwconv(const float *in, const float *w, const float *b, float *out, const ConvParams &p, int n_seg,
@@ -1317,8 +1317,8 @@ const char *launch_dwconv(const float *in, const float *w, const float *b, float
         return "dwconv_kernel<" #KSV "," #STV ",DIL>";                                                   \
     }
     if (!dwconv_supports(p)) return nullptr;
-    if (conv_dilated(p)) { BH_DW_DIL_CASE(3, 1) BH_DW_DIL_CASE(3, 2) BH_DW_DIL_CASE(5, 1) BH_DW_DIL_CASE(5, 2) }
-    BH_DW_CASE(3, 1) BH_DW_CASE(3, 2) BH_DW_CASE(5, 1) BH_DW_CASE(5, 2)
+    if (conv_dilated(p)) { BH_DW_DIL_CASE(3, 1) BH_DW_DIL_CASE(3, 2) BH_DW_DIL_CASE(5, 1) BH_DW_DIL_CASE(5, 2) BH_DW_DIL_CASE(7, 1) BH_DW_DIL_CASE(7, 2) }
+    BH_DW_CASE(3, 1) BH_DW_CASE(3, 2) BH_DW_CASE(5, 1) BH_DW_CASE(5, 2) BH_DW_CASE(7, 1) BH_DW_CASE(7, 2)
 #undef BH_DW_DIL_CASE
 #undef BH_DW_CASE
     return nullptr;

@@ -9,7 +9,7 @@
 
 namespace bh {
 
-enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8, OP_CONCAT = 10 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
+enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8, OP_CONCAT = 10, OP_LNORM = 12 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
 // OP_POOL (ONNX MaxPool / AveragePool, floor mode): the record's `reserved` word is the mode.  No weights, no bias, no activation.
 enum PoolMode : uint32_t { POOL_MAX = 0, POOL_AVG = 1, POOL_AVG_PAD = 2 };   // AVG: over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 // OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the record's `reserved` word is where `act` stands relative to the residual.  0: act(conv + b) + R
@@ -24,6 +24,11 @@ constexpr uint32_t RES_ACT_AFTER = 1;
 // residual -- or NO_TENSOR (a window and / or a shuffle of A alone), b_off = the first channel read from B, which gives cout - cin
 // channels; a source's channel count is its tensor's floats / (in_h in_w).  `reserved` = the shuffle's group count g (0, 1: none):
 // out[p][c] = cat[p][(c % g) * (cout / g) + c / g], cat = A's window then B's.  Offsets and lengths are multiples of 4.
+// OP_LNORM = 12 (ONNX LayerNormalization over the last axis of an [N, H, W, C] view, ConvNeXt's norm): a LayerNorm over the channels of
+// an NHWC f32 tensor, pixel by pixel -- y[p][c] = (x[p][c] - mean_p) / sqrt(var_p + eps) * gamma[c] + beta[c], var_p the biased variance
+// over the C channels of pixel p.  cin == cout == C (a multiple of 4), kernel / stride 1, pads 0, out image == in image, in_layout 0,
+// never on tensor 0; w_off -> gamma[C], b_off -> beta[C]; no activation, no residual, no dilation; `reserved` = the bit pattern of eps
+// as an f32, finite and > 0 (a constant pixel would otherwise be 0 * inf).  Code 11 is never used, like 9: both stay "unknown layer op".
 constexpr uint32_t NO_TENSOR = 0xFFFFFFFFu;
 // Dilation (OP_CONV on an NHWC tensor, OP_DWCONV): the record's words at bytes 88 .. 95, skip_h and skip_w, are the rows and the columns
 // SKIPPED between neighbouring taps, dilation - 1 per axis -- tap (dy, dx) reads pixel (oy sh - pad_t + dy (skip_h + 1),
@@ -120,7 +125,7 @@ inline bool validate_model(Model &m, std::string &err) {
         if (L.res_tensor != NO_TENSOR && L.op != OP_SCALE && L.op != OP_CONCAT && m.tensor_floats[L.res_tensor] != m.tensor_floats[i + 1]) {
             err = "residual shape does not match the layer output"; return false;
         }
-        if (L.op < OP_CONV || L.op > OP_CONCAT || L.op == 9) { err = "unknown layer op"; return false; }
+        if (L.op < OP_CONV || L.op > OP_LNORM || L.op == 9 || L.op == 11) { err = "unknown layer op"; return false; }
         if (L.op == OP_GCONV) {
             const uint32_t G = L.reserved;
             if (G < 2) { err = "grouped convolution with fewer than two groups (one group is a full convolution)"; return false; }
@@ -160,6 +165,21 @@ inline bool validate_model(Model &m, std::string &err) {
             if (L.w_off > ca || L.cin > ca - L.w_off || (two && (L.b_off > cb || L.cout - L.cin > cb - L.b_off))) { err = "concat layer with a window past its source's channels"; return false; }
             if (L.reserved > 1 && (L.reserved > L.cout || L.cout % L.reserved)) { err = "concat layer with a shuffle group count that does not divide its channels"; return false; }
         }
+        if (L.op == OP_LNORM) {
+            float eps;
+            memcpy(&eps, &L.reserved, sizeof eps);
+            if (L.act != 0) { err = "layer norm with an activation"; return false; }
+            if (L.res_tensor != NO_TENSOR) { err = "layer norm with a residual"; return false; }
+            if (L.kh != 1 || L.kw != 1 || L.sh != 1 || L.sw != 1 || L.pad_t != 0 || L.pad_l != 0) { err = "layer norm with a kernel, stride or padding other than 1 / 1 / 0"; return false; }
+            if (L.in_h != L.out_h || L.in_w != L.out_w) { err = "layer norm whose output image is not its input image"; return false; }
+            if (L.cin != L.cout) { err = "layer norm that changes the channel count"; return false; }
+            if (L.in_layout != 0 || L.in_tensor == 0) { err = "layer norm on the planar spectrogram (tensor 0)"; return false; }
+            if (L.cout % 4) { err = "layer norm over a channel count that is not a multiple of 4"; return false; }
+            if (!std::isfinite(eps) || !(eps > 0.0f)) { err = "layer norm with an epsilon that is not finite and > 0"; return false; }
+            if (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.cout > m.h.blob_floats - L.w_off || L.cout > m.h.blob_floats - L.b_off) {
+                err = "layer norm gamma / beta outside the blob"; return false;
+            }
+        }
         if (L.op == OP_CONV && L.in_layout != 0) {
             if (L.reserved == RES_ACT_AFTER) { err = "activation after the residual on the NCHW stem convolution"; return false; }
         } else if (L.op == OP_CONV || L.op == OP_PWCONV || L.op == OP_DENSE) {
@@ -168,14 +188,14 @@ inline bool validate_model(Model &m, std::string &err) {
             if (L.reserved == RES_ACT_AFTER && L.act == 0) { err = "activation after the residual without an activation (a plain residual is position 0)"; return false; }
         }
         if (L.skip_h || L.skip_w) {
-            static const char *const names[] = {"?", "stem convolution", "depthwise", "pointwise", "global pool", "dense", "scale", "pool", "grouped convolution", "?", "concat"};
+            static const char *const names[] = {"?", "stem convolution", "depthwise", "pointwise", "global pool", "dense", "scale", "pool", "grouped convolution", "?", "concat", "?", "layer norm"};
             if (!(L.op == OP_DWCONV || (L.op == OP_CONV && L.in_layout == 0))) {
                 err = std::string("dilation on a ") + names[L.op] + " layer"; return false;
             }
             if (L.skip_h >= MAX_DILATION || L.skip_w >= MAX_DILATION) { err = "dilation above 16"; return false; }
             if ((L.kh == 1 && L.skip_h) || (L.kw == 1 && L.skip_w)) { err = "dilation on an axis with one tap (dilation 1 is its one spelling)"; return false; }
         }
-        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && L.op != OP_CONCAT && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
+        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && L.op != OP_CONCAT && L.op != OP_LNORM && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
                                                    L.b_off + L.cout > m.h.blob_floats)) {
             err = "layer weights outside blob"; return false;
         }

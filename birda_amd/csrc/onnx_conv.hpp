@@ -10,6 +10,9 @@
 //     1/2) or that chain without its Mul(., x) on a pooled tensor = the hard-sigmoid gate), residual Add folded into its 1x1 convolution, MaxPool / AveragePool (floor mode; OP_POOL),
 //     GlobalAveragePool / ReduceMean over H, W, Concat / Split / Slice over the channels and the Reshape -> Transpose -> Reshape channel
 //     shuffle (OP_CONCAT: a Split / Slice output that only Concat nodes read is a view folded into their windows),
+//     ConvNeXt blocks (OP_LNORM: Transpose [0, 2, 3, 1] / [0, 3, 1, 2] as an [N, H, W, C] view that costs no record, LayerNormalization over the
+//     channels as a node or as the decomposed ReduceMean -> Sub -> Pow -> ReduceMean -> Add -> Sqrt -> Div -> Mul -> Add chain, MatMul + Add on
+//     the view as a 1x1 layer, the layer-scale Mul by a constant of the channels folded into the layer in front),
 //     squeeze-excite gates (pool -> 1x1 -> 1x1 -> Sigmoid -> Mul), Flatten / Reshape / Squeeze / Identity / Dropout after the
 //     pool, Gemm / MatMul + Add, a final Sigmoid or Softmax; NCHW weights re-laid for the NHWC kernels.  Anything else is refused
 //     by operator name.
@@ -42,6 +45,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <set>
 #include <string>
@@ -397,10 +401,93 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         }
     }
 
+    // ---- the decomposed LayerNorm torch.onnx emits below opset 17 (convert.py _find_layer_norms): ReduceMean -> Sub -> Pow(2) ->
+    // ReduceMean -> Add(eps) -> Sqrt -> Div -> Mul(gamma) -> Add(beta) over the last axis of an [N, H, W, C] view or axis 1 of an NCHW
+    // map.  A ReduceMean over ONE axis (-1, 3 or 1) starts it; a chain that deviates is refused by naming the node where it does.
+    struct LnChain { std::string out, gamma, beta, name; float eps; int64_t axis; };
+    std::map<std::string, std::vector<LnChain>> ln_of_pattern;                               // chain input -> the chains
+    {
+        std::map<std::string, std::vector<size_t>> rd;                                       // readers outside the patterns found so far
+        for (size_t i = 0; i < nodes.size(); i++)
+            if (!skip.count(i))
+                for (const auto &x : nodes[i].in) rd[x].push_back(i);
+        const std::string chain = "ReduceMean -> Sub -> Pow(2) -> ReduceMean -> Add(eps) -> Sqrt -> Div -> Mul(gamma) -> Add(beta)";
+        auto dev = [&](const Node &n, const std::string &why) { return fail(n.op + " '" + n.name + "': not the LayerNorm chain " + chain + ": " + why); };
+        auto reduce_axes = [&](const Node &n, std::vector<int64_t> &axes) {
+            axes.clear();
+            if (const auto *ax = n.ints("axes")) { axes = *ax; return true; }
+            if (n.in.size() > 1 && !n.in[1].empty()) { auto it = g.init.find(n.in[1]); if (it != g.init.end() && (it->second.dtype == 7 || it->second.dtype == 6) && it->second.il.size() <= 64) { axes = it->second.il; return true; } }
+            return false;
+        };
+        // the one reader of src's output, which must be an `op` node -> k; false: refused (err is set)
+        auto only_reader = [&](const Node &src, const char *op, size_t &k) {
+            const std::string &name = src.out[0];
+            auto it = rd.find(name);
+            const size_t nr = it == rd.end() ? 0 : it->second.size();
+            if (is_output(name) || nr != 1)
+                return dev(src, "its output has " + std::to_string(nr) + " readers" + (is_output(name) ? " and is a graph output" : "") + " (a second reader of an inner tensor)");
+            k = it->second[0];
+            if (nodes[k].op != op || nodes[k].out.empty()) return dev(nodes[k], std::string(op) + " expected behind " + src.op + " '" + src.name + "'");
+            return true;
+        };
+        auto other = [&](const Node &n, const std::string &name, std::string &o) {
+            if (n.in.size() != 2 || (n.in[0] != name && n.in[1] != name)) return dev(n, "two operands expected");
+            o = n.in[0] == name ? n.in[1] : n.in[0];
+            return true;
+        };
+        for (size_t i = 0; i < nodes.size(); i++) {
+            const Node &n = nodes[i];
+            if (n.op != "ReduceMean" || skip.count(i) || front.count(i) || n.in.empty() || n.out.empty()) continue;
+            std::vector<int64_t> axes, axes2;
+            if (!reduce_axes(n, axes) || axes.size() != 1 || (axes[0] != -1 && axes[0] != 3 && axes[0] != 1)) continue;   // (H, W: the global pool; anything else keeps the walk's refusal)
+            if (n.geti("keepdims", 1) != 1) return dev(n, "keepdims = 0");
+            const std::string &x = n.in[0];
+            size_t j_sub, j_pow, j_div, j_m2, j_add, j_sqrt, j_mul, j_add2, k;
+            if (!only_reader(n, "Sub", j_sub)) return false;
+            const Node &sub = nodes[j_sub];
+            if (sub.in.size() != 2 || sub.in[0] != x || sub.in[1] != n.out[0]) return dev(sub, "Sub(x, mean) expected");
+            auto rs = rd.find(sub.out[0]);
+            if (is_output(sub.out[0]) || rs == rd.end() || rs->second.size() != 2 ||
+                !((nodes[rs->second[0]].op == "Pow" && nodes[rs->second[1]].op == "Div") || (nodes[rs->second[0]].op == "Div" && nodes[rs->second[1]].op == "Pow")))
+                return dev(sub, "its output must be read by the Pow and the Div alone (a second reader of an inner tensor)");
+            j_pow = nodes[rs->second[0]].op == "Pow" ? rs->second[0] : rs->second[1];
+            j_div = nodes[rs->second[0]].op == "Pow" ? rs->second[1] : rs->second[0];
+            const Node &pw = nodes[j_pow], &div = nodes[j_div];
+            float two = 0.0f;
+            if (pw.in.size() != 2 || pw.out.empty() || pw.in[0] != sub.out[0] || !probe_scalar(pw.in[1], two) || two != 2.0f) return dev(pw, "an exponent other than 2");
+            if (!only_reader(pw, "ReduceMean", j_m2)) return false;
+            const Node &m2 = nodes[j_m2];
+            if (!reduce_axes(m2, axes2) || axes2 != axes || m2.geti("keepdims", 1) != 1) return dev(m2, "not over the first mean's axis " + std::to_string(axes[0]) + " (another axis)");
+            { auto c = rd.find(m2.out[0]); if (c != rd.end() && c->second.size() == 1 && nodes[c->second[0]].op == "Sqrt") return dev(nodes[c->second[0]], "a missing eps (Add(variance, eps) expected in front of the Sqrt)"); }
+            if (!only_reader(m2, "Add", j_add)) return false;
+            const Node &add = nodes[j_add];
+            std::string eps_name, gamma, beta;
+            float eps = 0.0f;
+            if (!other(add, m2.out[0], eps_name)) return false;
+            if (!probe_scalar(eps_name, eps)) return dev(add, "a missing eps (a float32 or float16 scalar constant expected)");
+            if (!only_reader(add, "Sqrt", j_sqrt)) return false;
+            const Node &sq = nodes[j_sqrt];
+            if (!only_reader(sq, "Div", k)) return false;
+            if (k != j_div || div.in.size() != 2 || div.out.empty() || div.in[0] != sub.out[0] || div.in[1] != sq.out[0]) return dev(div, "Div(x - mean, sqrt) expected");
+            if (!only_reader(div, "Mul", j_mul)) return false;
+            const Node &mul = nodes[j_mul];
+            if (!other(mul, div.out[0], gamma)) return false;
+            if (!only_reader(mul, "Add", j_add2)) return false;
+            const Node &add2 = nodes[j_add2];
+            if (!other(add2, mul.out[0], beta)) return false;
+            { auto it = g.init.find(gamma); if (it == g.init.end() || !it->second.is_float()) return dev(mul, "gamma must be a float32 or float16 initializer"); }
+            { auto it = g.init.find(beta); if (it == g.init.end() || !it->second.is_float()) return dev(add2, "beta must be a float32 or float16 initializer"); }
+            for (size_t q : {i, j_sub, j_pow, j_m2, j_add, j_sqrt, j_div, j_mul, j_add2}) skip.insert(q);
+            ln_of_pattern[x].push_back(LnChain{add2.out[0], gamma, beta, n.name, eps, axes[0]});
+        }
+    }
+
     // ---- the walk (convert.py model_from_graph) ----
     // tensor index, channels, height, width (1 x 1 once pooled).  view: the output of a Split / Slice that only Concat nodes read --
     // channels off .. off + c - 1 of tensor idx, folded into those records' windows; no other node ever looks one up
-    struct T { uint32_t idx, c, h, w, off = 0; bool view = false; };
+    // nhwc: the name is an [N, H, W, C] view of its tensor (behind Transpose [0, 2, 3, 1]) -- the library keeps activations NHWC, so the
+    // view costs nothing; only LayerNormalization, MatMul, the activations, Mul by a [C] constant and the Transpose back read one
+    struct T { uint32_t idx, c, h, w, off = 0; bool view = false; bool nhwc = false; };
     std::map<std::string, T> tmap;
     tmap[spec] = T{0, m.h.n_branches, m.h.spec_h, m.h.spec_w};
     std::vector<LayerRec> &layers = m.layers;
@@ -467,6 +554,8 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a MaxPool / AveragePool (a pool layer carries no activation)");
         if (t.idx != 0 && layers[t.idx - 1].op == OP_CONCAT)
             return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a Concat, Split, Slice or channel shuffle (the record carries no activation)");
+        if (t.idx != 0 && layers[t.idx - 1].op == OP_LNORM)
+            return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a LayerNormalization (the record carries no activation)");
         if (t.idx != 0 && sums.count(name_in) && layers[t.idx - 1].res_tensor != NO_TENSOR && layers[t.idx - 1].reserved != RES_ACT_AFTER) {
             // act(conv + x), the end of a ResNet block: the layer keeps its one activation code and records its position
             LayerRec &L = layers[t.idx - 1];
@@ -488,14 +577,16 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         tmap[name_out] = t;
         return true;
     };
+    std::function<bool(const std::string &)> flush_ln;     // (the decomposed LayerNorm chains that start at a tensor: below, behind new_layer)
     auto flush_patterns = [&](const std::string &x) {
         auto it = first_of_pattern.find(x);
-        if (it == first_of_pattern.end()) return true;
-        const auto list = it->second;
-        first_of_pattern.erase(it);
-        for (const auto &pa : list)
-            if (!set_act(x, pa.out, pa.act, pa.nodes)) return false;
-        return true;
+        if (it != first_of_pattern.end()) {
+            const auto list = it->second;
+            first_of_pattern.erase(it);
+            for (const auto &pa : list)
+                if (!set_act(x, pa.out, pa.act, pa.nodes)) return false;
+        }
+        return flush_ln(x);
     };
     auto new_layer = [&](uint32_t op, uint32_t in_t, uint32_t res_t, uint32_t cin, uint32_t cout, uint32_t kh, uint32_t kw, uint32_t sh, uint32_t sw,
                          uint32_t pt, uint32_t pl, uint32_t ih, uint32_t iw, uint32_t oh, uint32_t ow, uint32_t in_layout, uint64_t w_off, uint64_t b_off) {
@@ -506,6 +597,87 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         return (uint32_t)layers.size();
     };
     constexpr int64_t DIM_MAX = 1 << 16;
+    std::vector<float> tmp, tmpb;
+    // one OP_LNORM record over the channels of x (an [N, H, W, C] view, or an NCHW map the caller has held to the channel axis) -> `out`,
+    // a view when x is one; directly behind the global pool it becomes the embedding (pool -> norm -> dense: the dense head reads the norm)
+    auto lnorm_rec = [&](const std::string &who, const T &x, const std::string &out, const Tensor *gamma, const Tensor *beta, float eps) {
+        if (x.idx == 0) return fail(who + "a LayerNorm of the spectrogram (tensor 0) is not supported");
+        if (!gamma || !gamma->is_float() || gamma->count != x.c || (beta && (!beta->is_float() || beta->count != x.c)))
+            return fail(who + "gamma / beta must be float32 or float16 initializers of the " + std::to_string(x.c) + " channels");
+        if (x.c % 4) return fail(who + std::to_string(x.c) + " channels: a channel count that is not a multiple of 4 is not supported");
+        if (!std::isfinite(eps) || !(eps > 0.0f)) { char v[48]; snprintf(v, sizeof v, "%g", (double)eps); return fail(who + "epsilon " + v + " is not finite and > 0"); }
+        tmp.resize(x.c); tmpb.assign(x.c, 0.0f);
+        for (uint32_t c = 0; c < x.c; c++) { tmp[c] = gamma->at(c); if (beta) tmpb[c] = beta->at(c); }
+        const uint64_t wo = blob.put(tmp), bo = blob.put(tmpb);
+        const uint32_t li = new_layer(OP_LNORM, x.idx, NO_TENSOR, x.c, x.c, 1, 1, 1, 1, 0, 0, x.h, x.w, x.h, x.w, 0, wo, bo);
+        memcpy(&layers[li - 1].reserved, &eps, sizeof eps);
+        if (layers[x.idx - 1].op == OP_GAP && emb_tensor == x.idx) emb_tensor = li;
+        T y{li, x.c, x.h, x.w};
+        y.nhwc = x.nhwc;
+        tmap[out] = y;
+        return true;
+    };
+    flush_ln = [&](const std::string &x) {
+        auto it = ln_of_pattern.find(x);
+        if (it == ln_of_pattern.end()) return true;
+        const auto list = it->second;
+        ln_of_pattern.erase(it);
+        for (const auto &ch : list) {
+            const std::string who = "ReduceMean '" + ch.name + "' (LayerNorm chain): ";
+            T t;
+            if (!find(x, t)) return fail(who + "input not on the path");
+            const Tensor &ga = g.init.find(ch.gamma)->second, &be = g.init.find(ch.beta)->second;
+            auto shaped = [&](const Tensor &a) {
+                const int64_t C = t.c;
+                if (t.nhwc) return a.dims == std::vector<int64_t>{C};
+                return a.dims == std::vector<int64_t>{C, 1, 1} || a.dims == std::vector<int64_t>{1, C, 1, 1};
+            };
+            if (t.nhwc && ch.axis != -1 && ch.axis != 3)
+                return fail(who + "axis " + std::to_string(ch.axis) + " of an [N, H, W, C] view: only the last axis, the channels, is normalised (another axis)");
+            if (!t.nhwc && ch.axis != 1)
+                return fail(who + "axis " + std::to_string(ch.axis) + " of an NCHW tensor: only axis 1, the channels, is normalised (another axis)");
+            if (!shaped(ga) || !shaped(be)) return fail(who + "gamma / beta do not have the shape that scales the " + std::to_string(t.c) + " channels");
+            if (!lnorm_rec(who, t, ch.out, &ga, &be, ch.eps) || !flush_patterns(ch.out)) return false;
+        }
+        return true;
+    };
+    // the layer scale of a ConvNeXt block (convert.py fold_layer_scale): Mul of a convolution's / MatMul layer's output by a constant of its
+    // C channels ([C] on an [N, H, W, C] view, [C, 1, 1] or [1, C, 1, 1] on an NCHW map), folded into the layer's weight columns and bias
+    // where BatchNormalization is -- one float32 product each.  The layer has no activation and no residual yet, the Mul is its only
+    // reader and the tensor no graph output.  folded = false: not that Mul (today's rules apply).  (Every record's weights are a
+    // slot of their own in this blob -- both readers put them per node --, so the fold never touches another layer's.)
+    auto fold_layer_scale = [&](const Node &n, bool &folded) {
+        folded = false;
+        if (n.in.size() != 2 || n.out.empty()) return true;
+        for (int side = 0; side < 2; side++) {
+            const std::string &xn = n.in[side], &sn = n.in[1 - side];
+            auto it = g.init.find(sn);
+            T t;
+            if (it == g.init.end() || !it->second.is_float() || !find(xn, t) || t.idx == 0) continue;
+            const Tensor &S = it->second;
+            LayerRec &L = layers[t.idx - 1];
+            const int64_t C = t.c;
+            const bool shape_ok = t.nhwc ? S.dims == std::vector<int64_t>{C} : (S.dims == std::vector<int64_t>{C, 1, 1} || S.dims == std::vector<int64_t>{1, C, 1, 1});
+            auto cit = cons.find(xn);
+            if (!shape_ok || (L.op != OP_CONV && L.op != OP_DWCONV && L.op != OP_PWCONV && L.op != OP_GCONV) || L.act != A_NONE || L.res_tensor != NO_TENSOR ||
+                graph_out.count(xn) || cit == cons.end() || cit->second.size() != 1) continue;
+            const uint64_t nw = L.op == OP_CONV ? (uint64_t)L.kh * L.kw * L.cin * L.cout : L.op == OP_GCONV ? (uint64_t)L.kh * L.kw * (L.cin / L.reserved) * L.cout : L.op == OP_DWCONV ? (uint64_t)L.kh * L.kw * L.cout : (uint64_t)L.cin * L.cout;
+            for (uint32_t c = 0; c < L.cout; c++) {
+                const float sf = S.at(c);
+                for (uint64_t q = c; q < nw; q += L.cout) blob.v[L.w_off + q] = blob.v[L.w_off + q] * sf;    // (cout is the last axis in every layout)
+                blob.v[L.b_off + c] = blob.v[L.b_off + c] * sf;
+            }
+            tmap[n.out[0]] = t;
+            folded = true;
+            return flush_patterns(n.out[0]);
+        }
+        for (const auto &xn : n.in) {
+            T t;
+            if (find(xn, t) && t.nhwc)
+                return fail("Mul '" + n.name + "': input '" + xn + "' is an [N, H, W, C] view (behind a Transpose): only a Mul by a [C] constant directly behind a MatMul layer without an activation, its only reader, is folded (layer scale)");
+        }
+        return true;
+    };
     // one OP_CONCAT record: the window of a, then that of b (null: a alone), shuffled in g groups (0: not); -> its output, whole
     auto concat_rec = [&](const T &a, const T *b, uint32_t g) {
         const uint32_t cout = a.c + (b ? b->c : 0);
@@ -518,14 +690,92 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         T v{x.idx, c, x.h, x.w, x.off + off, true};
         tmap[name] = has_other_reader(name) ? concat_rec(v, nullptr, 0) : v;
     };
-    std::vector<float> tmp, tmpb;
     for (size_t i = 0; i < nodes.size(); i++) {
         if (skip.count(i) || front.count(i)) continue;
         const Node &n = nodes[i];
         const std::string &op = n.op;
         if (n.out.empty() || n.in.empty()) return fail("node '" + n.name + "' (" + op + ") without inputs or outputs");
         if (layers.size() > 4000) return fail("more than 4 000 layers");
-        if (op == "Conv") {
+        // an [N, H, W, C] view among the inputs: only these operators read one
+        const std::string *view_in = nullptr;
+        for (const auto &xn : n.in) { T t; if (!view_in && find(xn, t) && t.nhwc) view_in = &xn; }
+        if (view_in && op != "Transpose" && op != "LayerNormalization" && op != "MatMul" && op != "Mul" && op != "Relu" && op != "Gelu" && op != "Clip" && op != "HardSwish")
+            return fail(op + " '" + n.name + "': input '" + *view_in + "' is an [N, H, W, C] view (behind a Transpose): only LayerNormalization, MatMul (+ Add of a bias), "
+                        "the activations, Mul by a [C] constant and the Transpose back read one");
+        bool folded = false;
+        if (op == "Mul" && !fold_layer_scale(n, folded)) return false;
+        if (folded) continue;
+        if (op == "Transpose") {
+            // the library keeps activations NHWC: [0, 2, 3, 1] marks the result an [N, H, W, C] view of the same tensor, [0, 3, 1, 2] ends it
+            const std::string who = "Transpose '" + n.name + "': ";
+            T t;
+            if (!find(n.in[0], t)) return fail(who + "input '" + n.in[0] + "' is not on the path from '" + spec + "'");
+            std::vector<int64_t> perm;
+            if (const auto *pp = n.ints("perm")) perm = *pp;
+            if (perm == std::vector<int64_t>{0, 2, 3, 1} && !view_in) {
+                if (t.idx == 0) return fail(who + "an [N, H, W, C] view of the spectrogram (tensor 0) is not supported");
+                if (t.view) return fail(who + "an [N, H, W, C] view of a Split / Slice output that only Concat nodes read is not supported");
+                t.nhwc = true;
+            } else if (perm == std::vector<int64_t>{0, 3, 1, 2} && view_in) {
+                t.nhwc = false;
+            } else {
+                std::string ps;
+                for (size_t q = 0; q < perm.size() && q < 8; q++) ps += (q ? ", " : "") + std::to_string(perm[q]);
+                return fail(who + "perm [" + ps + "] on " + (view_in ? "an [N, H, W, C] view" : "an NCHW feature map") + ": only [0, 2, 3, 1] on a feature map and [0, 3, 1, 2] on the view it makes are read");
+            }
+            tmap[n.out[0]] = t;
+            if (!flush_patterns(n.out[0])) return false;
+        } else if (op == "LayerNormalization") {
+            const std::string who = "LayerNormalization '" + n.name + "': ";
+            T t;
+            if (!find(n.in[0], t)) return fail(who + "input '" + n.in[0] + "' is not on the path from '" + spec + "'");
+            const int64_t axis = n.geti("axis", -1);
+            if (view_in) {
+                if (axis != -1 && axis != 3) return fail(who + "axis " + std::to_string(axis) + " of an [N, H, W, C] view: only the last axis, the channels, is normalised");
+            } else if (axis != 1 || (uint64_t)t.h * t.w != 1) {
+                return fail(who + "axis " + std::to_string(axis) + " of an NCHW tensor with a " + std::to_string(t.h) + "x" + std::to_string(t.w) + " image: it would normalise over more than the "
+                            "channels (only axis 1 of an [N, C, 1, 1] tensor, or the last axis of an [N, H, W, C] view)");
+            }
+            for (size_t k = 1; k <= 2; k++)
+                if (n.out.size() > k && !n.out[k].empty() && (graph_out.count(n.out[k]) || cons.count(n.out[k])))
+                    return fail(who + "the output " + (k == 1 ? "Mean" : "InvStdDev") + " is read: only the normalised tensor is computed");
+            init_refusal.clear();
+            const Tensor *ga = n.in.size() > 1 ? finit(n.in[1]) : nullptr;
+            const bool has_beta = n.in.size() > 2 && !n.in[2].empty();
+            const Tensor *be = has_beta ? finit(n.in[2]) : nullptr;
+            if (!ga || (has_beta && !be)) return fail(who + "gamma / beta must be float32 or float16 initializers of the " + std::to_string(t.c) + " channels" + init_refusal);
+            if (!lnorm_rec(who, t, n.out[0], ga, be, n.getf("epsilon", 1e-5f)) || !flush_patterns(n.out[0])) return false;
+        } else if (op == "MatMul" && view_in) {
+            // a pointwise layer on the [N, H, W, C] view (a PyTorch Linear between two Transposes), with its Add of a bias
+            const std::string who = "MatMul '" + n.name + "': ";
+            if (*view_in != n.in[0]) return fail(who + "the [N, H, W, C] view '" + *view_in + "' as the second operand");
+            T t;
+            find(n.in[0], t);
+            init_refusal.clear();
+            const Tensor *W = n.in.size() > 1 ? finit(n.in[1]) : nullptr;
+            if (!W || W->dims.size() != 2) return fail(who + "needs a 2-d float32 or float16 weight initializer" + init_refusal);
+            const int64_t cin = W->dims[0], cout = W->dims[1];
+            if (cin <= 0 || cout <= 0 || cin > DIM_MAX || cout > DIM_MAX) return fail(who + "bad weight shape");
+            if ((uint64_t)cin != t.c) return fail(who + std::to_string(cin) + " input features, activation has " + std::to_string(t.c));
+            const Tensor *B = nullptr;
+            std::string out = n.out[0];
+            size_t k;
+            if (sole_consumer(out, "Add", k) && nodes[k].in.size() == 2 && !nodes[k].out.empty() && !graph_out.count(out)) {
+                const std::string &o2 = nodes[k].in[0] == out ? nodes[k].in[1] : nodes[k].in[0];
+                auto it = g.init.find(o2);
+                if (it != g.init.end() && it->second.is_float() && it->second.count == (uint64_t)cout) { B = &it->second; out = nodes[k].out[0]; skip.insert(k); }
+            }
+            tmp.resize((size_t)cin * cout);
+            for (size_t q = 0; q < tmp.size(); q++) tmp[q] = W->at(q);
+            tmpb.assign((size_t)cout, 0.0f);
+            if (B) for (int64_t o = 0; o < cout; o++) tmpb[(size_t)o] = B->at((uint64_t)o);
+            const uint64_t wo = blob.put(tmp), bo = blob.put(tmpb);
+            const uint32_t li = new_layer(OP_PWCONV, t.idx, NO_TENSOR, (uint32_t)cin, (uint32_t)cout, 1, 1, 1, 1, 0, 0, t.h, t.w, t.h, t.w, 0, wo, bo);
+            T y{li, (uint32_t)cout, t.h, t.w};
+            y.nhwc = true;
+            tmap[out] = y;
+            if (!flush_patterns(out)) return false;
+        } else if (op == "Conv") {
             T x;
             if (!find(n.in[0], x)) return fail("Conv '" + n.name + "': input '" + n.in[0] + "' is not on the path from '" + spec + "'");
             init_refusal.clear();
@@ -708,6 +958,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             const uint32_t li = new_layer(OP_GAP, t.idx, NO_TENSOR, t.c, t.c, t.h, t.w, 1, 1, 0, 0, t.h, t.w, 1, 1, 0, 0, 0);
             tmap[n.out[0]] = T{li, t.c, 1, 1};
             emb_tensor = li; emb_dim = t.c;
+            if (!flush_patterns(n.out[0])) return false;      // (a decomposed LayerNorm behind the pool)
         } else if (op == "MaxPool" || op == "AveragePool") {
             // windowed pooling in floor mode -> OP_POOL (convert.py has the same branch; the two are held to the same records)
             const std::string who = op + " '" + n.name + "': ";
@@ -919,6 +1170,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         }
     }
     if (!first_of_pattern.empty()) return fail("activation pattern on a tensor that was never produced: '" + first_of_pattern.begin()->first + "'");
+    if (!ln_of_pattern.empty()) return fail("activation pattern on a tensor that was never produced: '" + ln_of_pattern.begin()->first + "'");
     if (layers.empty() || layers.back().op != OP_DENSE) return fail("the graph does not end in a dense layer");
     T fin;
     if (!find(outputs[0], fin) || fin.idx != layers.size()) return fail("the graph output is not the last layer's output");

@@ -40,6 +40,9 @@ OP_CONCAT = 10  # channel Concat / Split / Slice / shuffle: a copy, NHWC f32, no
                 # "unknown layer op" tests/test_gconv.py demands.)  in_tensor = source A, w_off = first channel read from A, cin = how
                 # many; res_tensor = source B (a second INPUT, not a residual) or NO_TENSOR, b_off = first channel read from B, which gives
                 # cout - cin channels; Layer.reserved = shuffle groups g (0, 1: none): out[c] = cat[(c % g) * (cout // g) + c // g]
+OP_LNORM = 12   # LayerNorm over the channels of an NHWC tensor, pixel by pixel (biased variance): cin == cout == C (a multiple of 4), kernel /
+                # stride 1, pads 0, the image kept; w_off -> gamma[C], b_off -> beta[C]; no activation, residual or dilation; Layer.reserved
+                # is the bit pattern of eps as an f32 (lnorm_eps_bits / lnorm_eps), finite and > 0.  (11 is never used, like 9.)
 POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2  # AVG: mean over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 # OP_CONV (NHWC), OP_PWCONV, OP_DENSE: Layer.reserved is where `act` stands relative to the residual -- 0: act(conv + b) + R (every
 # file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block
@@ -62,6 +65,16 @@ BRANCH_FMT = "<IIIIIIfffffIQ"
 #  the tail of every record written before the words existed, is the undilated layer; the rest of the 128 bytes stays zero)
 LAYER_FMT = "<IIIIIIIIIIIIIIIIIIQQII"
 MAX_DILATION = 16
+
+
+def lnorm_eps_bits(eps: float) -> int:
+    """the `reserved` word of an OP_LNORM record: eps rounded to f32, as its bit pattern"""
+    return struct.unpack("<I", struct.pack("<f", eps))[0]
+
+
+def lnorm_eps(reserved: int) -> float:
+    """the f32 eps an OP_LNORM record's `reserved` word holds"""
+    return struct.unpack("<f", struct.pack("<I", reserved))[0]
 
 
 @dataclass
@@ -106,7 +119,8 @@ class Layer:
     b_off: int = 0
     # OP_POOL: the pool mode (POOL_MAX / POOL_AVG / POOL_AVG_PAD).  OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the position of `act`
     # relative to the residual -- 0: act(conv + b) + R; RES_ACT_AFTER: act(conv + b + R), which needs a residual and an activation.
-    # OP_GCONV: the group count.  OP_CONCAT: the channel shuffle's group count (0, 1: no shuffle).  0 for every other op.
+    # OP_GCONV: the group count.  OP_CONCAT: the channel shuffle's group count (0, 1: no shuffle).  OP_LNORM: the bits of eps as an
+    # f32.  0 for every other op.
     reserved: int = 0
     # dilation per axis (OP_CONV on an NHWC tensor and OP_DWCONV only, 1 .. MAX_DILATION, 1 on an axis with one tap): tap (dy, dx) reads
     # pixel (oy sh - pad_t + dy dil_h, ox sw - pad_l + dx dil_w).  Written as dil - 1.

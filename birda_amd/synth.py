@@ -170,6 +170,17 @@ class _Builder:
         L = mf.Layer(mf.OP_POOL, mf.ACT_NONE, tin, mf.NO_TENSOR, c, c, kh, kw, sh, sw, pt, pl, h, w, oh, ow, reserved=mode)
         return self.add(L), oh, ow
 
+    def lnorm(self, tin, h, w, c, eps=1e-6):
+        """LayerNorm over the channels, pixel by pixel (mf.OP_LNORM; reserved = the bits of eps): gamma around 1 with a few negative and
+        zero entries, beta around 0"""
+        gamma = (1.0 + 0.3 * self.rng.standard_normal(c)).astype(np.float32)
+        gamma[self.rng.integers(0, c)] = 0.0
+        gamma[self.rng.integers(0, c)] *= np.float32(-1.0)
+        beta = (0.2 * self.rng.standard_normal(c)).astype(np.float32)
+        L = mf.Layer(mf.OP_LNORM, mf.ACT_NONE, tin, mf.NO_TENSOR, c, c, 1, 1, 1, 1, 0, 0, h, w, h, w,
+                     0, self.put(gamma), self.put(beta), reserved=mf.lnorm_eps_bits(eps))
+        return self.add(L)
+
     def dense(self, tin, cin, cout, gain=1.0, act=mf.ACT_NONE, logits=True):
         wt = self.he((cin, cout), cin) * np.float32(gain)
         b = (self.rng.standard_normal(cout) * 0.5 - 2.0).astype(np.float32) if logits else self.bias(cout)
@@ -231,6 +242,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     included, on the mini front-end: _build_mobilenetv3_audio).
     'dilated_plan' (a small trunk of dilated full and depthwise convolutions on the mini front-end: _build_dilated_plan).
     'dilated_resnet_audio' (resnet18_audio at output stride 8, the last two stages dilated 2 and 4: _build_dilated_resnet_audio).
+    'convnext_plan' (plan = convnext_plan(seed)) builds that plan's ConvNeXt trunk -- 7x7 depthwise, channel LayerNorm (mf.OP_LNORM),
+    two pointwise layers with the layer scale folded into the second, the residual -- on the mini front end: _build_convnext.
+    'convnext_audio' (ConvNeXt-T's layout, widths 96 / 192 / 384 / 768 and depths 3 / 3 / 9 / 3, on the v2.4 front end, for timing the
+    LayerNorm and 7x7 depthwise layers).  Both carry the un-folded layer scales in Model.convnext_scales.
     A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
@@ -254,6 +269,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
         return _build_mnv3_plan(plan, seed)
     if kind == "mobilenetv3_audio":
         return _build_mobilenetv3_audio(seed, n_classes)
+    if kind == "convnext_plan":
+        return _build_convnext(plan or convnext_plan(seed), seed)
+    if kind == "convnext_audio":
+        return _build_convnext(dict(widths=(96, 192, 384, 768), depths=(3, 3, 9, 3), eps=1e-6, classes=n_classes or 6522, audio=True), seed)
     if kind == "dilated_plan":
         return _build_dilated_plan(seed)
     if kind == "dilated_resnet_audio":
@@ -777,6 +796,69 @@ def _build_dilated_plan(seed: int = WEIGHT_SEED) -> mf.Model:
     t = emb = b.gap(t, h, w, head)
     b.dense(t, head, ncls, gain=1.5)
     return _finish(b, [br], sr, n, ncls, head, emb, mf.OUT_SIGMOID)
+
+
+# ---- ConvNeXt: 7x7 depthwise, channel LayerNorm (mf.OP_LNORM), layer scale folded into the second pointwise layer -------------------
+def convnext_plan(seed: int) -> dict:
+    """A small ConvNeXt trunk for the mini front end: two or three stages of one or two blocks, widths that include one that is no
+    power of two (36 / 72 / 100, or 40 / 100), eps 1e-6 or 1e-5."""
+    rng = np.random.default_rng(seed)
+    widths = (36, 72, 100) if rng.integers(0, 2) == 0 else (40, 100)
+    return dict(widths=widths, depths=tuple(int(rng.integers(1, 3)) for _ in widths), eps=float((1e-6, 1e-5)[int(rng.integers(0, 2))]), classes=40)
+
+
+def fold_layer_scale(w: np.ndarray, bias: np.ndarray, scale: np.ndarray):
+    """Layer scale folded into the layer in front: column n of w [..., cout] and bias[n] times scale[n], one float32 product each --
+    the arithmetic of both ONNX readers' fold."""
+    scale = np.asarray(scale, np.float32)
+    return (np.asarray(w, np.float32) * scale).astype(np.float32), (np.asarray(bias, np.float32) * scale).astype(np.float32)
+
+
+def _build_convnext(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
+    """plan = {widths, depths, eps, classes[, audio]}: a 4x4 stride-4 stem on the planar spectrogram + LayerNorm; per stage `depth`
+    blocks x + scale * pw(gelu(pw(LN(dw7x7(x))))) -- the layer scale folded into the second pointwise layer's columns and bias
+    (fold_layer_scale; Model.convnext_scales[i] holds the un-folded scale of layer i, what a PyTorch export writes as a Mul) --;
+    LayerNorm and a 2x2 stride-2 convolution between the stages; global pool -> LayerNorm -> dense, the embedding being that
+    LayerNorm's output (what the dense head reads).  audio: the v2.4 front end (96 mels x 511 frames, two branches), else the
+    quarter-second two-branch front end of 'mini' (32 mels x 115 frames)."""
+    b = _Builder(np.random.default_rng(seed))
+    if plan.get("audio"):
+        sr, n = 48000, 144000
+        branches = [mf.Branch(2048, 278, 96, 511, 0.0, 3000.0, 1.23), mf.Branch(1024, 280, 96, 511, 500.0, 15000.0, 1.23)]
+    else:
+        sr, n = 48000, 12000
+        branches = [mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23),
+                    mf.Branch(256, 103, 32, (n - 256) // 103 + 1, 500.0, 15000.0, 1.23)]
+    for br in branches:
+        br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+        br.out_scale, br.out_shift = 0.8, -0.4
+    widths, depths, eps = tuple(plan["widths"]), tuple(plan["depths"]), float(plan["eps"])
+    scales = {}
+    t, h, w = b.conv(0, branches[0].n_mels, branches[0].n_frames, len(branches), widths[0], 4, 4, mf.ACT_NONE, in_layout=1)
+    t = b.lnorm(t, h, w, widths[0], eps)
+    c = widths[0]
+    for si, (width, depth) in enumerate(zip(widths, depths)):
+        if si:
+            t = b.lnorm(t, h, w, c, eps)
+            t, h, w = b.conv(t, h, w, c, width, 2, 2, mf.ACT_NONE)
+            c = width
+        for _ in range(depth):
+            x = t
+            t, h, w = b.dwconv(t, h, w, c, 7, 1, mf.ACT_NONE)
+            t = b.lnorm(t, h, w, c, eps)
+            t = b.pwconv(t, h, w, c, 4 * c, mf.ACT_GELU_ERF)
+            w2, b2 = b.he((4 * c, c), 4 * c), b.bias(c)
+            ls = (b.rng.uniform(0.05, 0.6, c) * np.where(b.rng.random(c) < 0.2, -1.0, 1.0)).astype(np.float32)
+            w2f, b2f = fold_layer_scale(w2, b2, ls)
+            t = b.add(mf.Layer(mf.OP_PWCONV, mf.ACT_NONE, t, x, 4 * c, c, 1, 1, 1, 1, 0, 0, h, w, h, w, 0, b.put(w2f), b.put(b2f)))
+            scales[t - 1] = (w2, b2, ls)
+    t = b.gap(t, h, w, c)
+    t = emb = b.lnorm(t, 1, 1, c, eps)
+    ncls = int(plan.get("classes", 40))
+    b.dense(t, c, ncls, gain=1.5)
+    m = _finish(b, branches, sr, n, ncls, c, emb, mf.OUT_SIGMOID)
+    m.convnext_scales = scales     # layer index -> (W [4C][C], bias [C], scale [C]) before the fold
+    return m
 
 
 def _resnext_block(b: _Builder, t, h, w, c, shortcut, cout, mid_in, mid_out, groups, act, se=False):

@@ -23,6 +23,8 @@ extern "C" {
  *   the undilated entry of include/birda_hip_layer_debug.h: 0 conv_gemm_kernel (f32 MFMA); 1 / 3 conv_gemm16_kernel (f16 / split f16); 2 its two-term products on
  *   compact planes -- BH_ERR_UNSUPPORTED unless every weight is an f16 value after the pre-scale.
  * op 2 (OP_DWCONV): C[n][oh][ow][c] = act(dwconv(X, W) + bias); cin == cout = c, W [kh][kw][c]; R == NULL, terms == 0, after == 0.
+ *   Square 3x3 / 5x5 / 7x7 windows, one stride of 1 or 2; the 7x7 window ("dwconv_kernel<7,1>", "dwconv_kernel<7,2,DIL>") has this entry alone,
+ *   at dilation 1 too: the plain-layer diagnostic of include/birda_hip_gate_debug.h keeps the 3x3 / 5x5 windows it always took.
  * shape = {in_h, in_w, out_h, out_w, cin, cout, kh, kw, sh, sw, pad_t, pad_l, dil_h, dil_w}; out_h, out_w >= 1 are taken as given
  * (the bottom / right padding is whatever they imply, a crop included).
  * act: the model file's activation code (0 none, 1 ReLU, 2 ReLU6, 3 swish, 4 GELU, 5 tanh-GELU, 6 sigmoid, 7 hard swish, 8 hard sigmoid).
