@@ -14,7 +14,8 @@ Reshape channel shuffle (OP_CONCAT; a Split / Slice output that only Concat node
 ConvNeXt blocks (OP_LNORM: Transpose [0, 2, 3, 1] / [0, 3, 1, 2] as an [N, H, W, C] view that costs no record, LayerNormalization over the
 channels as a node or as the decomposed ReduceMean -> Sub -> Pow -> ReduceMean -> Add -> Sqrt -> Div -> Mul -> Add chain -- over axis 1 of
 an NCHW map too --, MatMul + Add on the view as a 1x1 layer, the layer-scale Mul by a constant of the channels folded into the layer in front),
-GlobalAveragePool / ReduceMean, Flatten, Gemm / MatMul + Add,
+GlobalAveragePool / ReduceMean, ReduceMax / ReduceMean over H or W or both, GlobalMaxPool and the max + mean pair Add(ReduceMax, ReduceMean)
+of the PANNs head (OP_REDUCE), Flatten, Gemm / MatMul + Add,
 final Sigmoid / Softmax as the output activation.  Weights move from ONNX's [Cout, Cin/g, kh, kw] to
 the NHWC-friendly layouts of the kernels.
 
@@ -147,8 +148,11 @@ def frontend_nodes(g: ox.Graph, m: mf.Model, spelling: str) -> None:
 HSWISH_SPELLINGS = ("op", "hsigmoid", "decomposed")
 
 
+REDUCE_SPELLING_OPTIONS = {"keep", "input", "neg", "gmp", "swap", "argmax"}
+
+
 def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op",
-                     spell_lnorm: str = "node") -> ox.Graph:
+                     spell_lnorm: str = "node", spell_reduce: str = "") -> ox.Graph:
     """The conv stack of a BHM1 model as an ONNX graph over `spectrogram` [N, C, H, W] -- or, with `frontend_spelling`
     (see `frontend_nodes`), the whole model over `audio` [N, S].
     spell_gelu: 'erf' = Div, Erf, Add, Mul, Mul (what exporters emit below opset 20); 'gelu' = one Gelu node.
@@ -158,9 +162,17 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
     for the last Mul), 'scale_first' (the scaling in front of the Mul(., x)), 'swap' (every binary node's operands exchanged where the
     operator commutes), 'f16' (float16 constants), 'cast' (a Cast to float32 inside the fold; 'hsigmoid' takes 'swap' and 'cast' too).
     spell_lnorm: how an OP_LNORM record is written between its two Transposes -- 'node' = LayerNormalization(axis = -1, epsilon) (opset
-    17); 'chain' = ReduceMean -> Sub -> Pow(2) -> ReduceMean -> Add(eps) -> Sqrt -> Div -> Mul -> Add (what torch.onnx emits below it)."""
+    17); 'chain' = ReduceMean -> Sub -> Pow(2) -> ReduceMean -> Add(eps) -> Sqrt -> Div -> Mul -> Add (what torch.onnx emits below it).
+    spell_reduce: how an OP_REDUCE record is written, comma-separated options over PyTorch's default spelling -- x.mean(dim) / torch.max(x,
+    dim) as ReduceMean / ReduceMax(axes = [2] or [3], keepdims = 0) with the axes as an attribute, the pair as Add(max, mean) --: 'keep'
+    (keepdims = 1), 'input' (the axes as the opset-18 input), 'neg' (negative axes), 'gmp' (a max over both axes as GlobalMaxPool), 'swap'
+    (Add(mean, max)), 'argmax' (the ArgMax that torch.max leaves behind, read by nothing)."""
     if spell_lnorm not in ("node", "chain"):
         raise ConvertError(f"unknown LayerNorm spelling {spell_lnorm!r}")
+    red_opts = set(filter(None, spell_reduce.split(",")))
+    if not red_opts <= REDUCE_SPELLING_OPTIONS:
+        raise ConvertError(f"unknown reduce spelling {spell_reduce!r}")
+    rank = {}   # tensor -> 3 or 2 where a reduction with keepdims = 0 left fewer than four axes
     hs_kind, _, hs_opts = spell_hswish.partition(":")
     hs_opts = set(filter(None, hs_opts.split(",")))
     if hs_kind not in HSWISH_SPELLINGS or not hs_opts <= {"div", "scale_first", "swap", "f16", "cast"}:
@@ -350,6 +362,53 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
                 g.nodes.append(ox.Node("Flatten", [y], [tag + "_flat"], {"axis": 1}))
                 y = tag + "_flat"
                 flat.add(i + 1)
+        elif L.op == mf.OP_REDUCE:
+            if L.in_tensor == 0:
+                raise ConvertError(f"layer {i}: a reduction of the spectrogram has no ONNX spelling here")
+            rk = rank.get(L.in_tensor, 4)
+            rh, rw = L.kh > 1, L.kw > 1
+            if rk == 4:
+                axes = ([2] if rh else []) + ([3] if rw else [])
+            elif rk == 3 and not (rh and rw):
+                axes = [2]
+            else:
+                raise ConvertError(f"layer {i}: a reduction of a rank-{rk} tensor over {L.kh}x{L.kw} has no ONNX spelling")
+            if "neg" in red_opts:
+                axes = [a - rk for a in axes]
+            keep = 1 if "keep" in red_opts else 0
+
+            def reduce_node(op, out):
+                if op == "ReduceMax" and "gmp" in red_opts and rk == 4 and rh and rw and L.reserved == mf.REDUCE_MAX:
+                    g.nodes.append(ox.Node("GlobalMaxPool", [x], [out], name=out))
+                    return 1
+                if op == "ReduceMax" and "argmax" in red_opts:
+                    g.nodes.append(ox.Node("ArgMax", [x], [out + "_idx"], {"axis": axes[0], "keepdims": keep}, name=out + "_idx"))
+                if "input" in red_opts:
+                    g.initializers[out + "_axes"] = np.asarray(axes, np.int64)
+                    g.nodes.append(ox.Node(op, [x, out + "_axes"], [out], {"keepdims": keep}, name=out))
+                else:
+                    g.nodes.append(ox.Node(op, [x], [out], {"axes": list(axes), "keepdims": keep}, name=out))
+                return keep
+            if L.reserved == mf.REDUCE_MAXMEAN:
+                reduce_node("ReduceMax", tag + "_max")
+                kept = reduce_node("ReduceMean", tag + "_mean")
+                g.nodes.append(ox.Node("Add", [tag + "_mean", tag + "_max"] if "swap" in red_opts else [tag + "_max", tag + "_mean"], [tag + "_red"], name=tag))
+                y = tag + "_red"
+            else:
+                y = tag + "_red"
+                kept = reduce_node("ReduceMax" if L.reserved == mf.REDUCE_MAX else "ReduceMean", y)
+            rk_out = rk if kept else rk - len(axes)
+            if rk_out != 4:
+                rank[i + 1] = rk_out
+            if L.out_h * L.out_w == 1:
+                feeds_conv = any(M.in_tensor == i + 1 and M.op in (mf.OP_PWCONV, mf.OP_LNORM) for M in m.layers)
+                if feeds_conv and rk_out != 4:
+                    raise ConvertError(f"layer {i}: a rank-{rk_out} tensor in front of a 1x1 convolution or a LayerNorm has no ONNX spelling here")
+                if not feeds_conv and rk_out != 2:
+                    g.nodes.append(ox.Node("Flatten", [y], [tag + "_flat"], {"axis": 1}))
+                    y = tag + "_flat"
+                if not feeds_conv:
+                    flat.add(i + 1)
         elif L.op == mf.OP_DENSE:
             w = m.weight(L.w_off, L.cin * L.cout).reshape(L.cin, L.cout)
             g.nodes.append(ox.Node("Gemm", [x, const(tag + "_w", w), const(tag + "_b", m.weight(L.b_off, L.cout))], [tag + "_fc"],
@@ -371,9 +430,9 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
 
 
 def model_to_onnx(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op",
-                  spell_lnorm: str = "node") -> bytes:
+                  spell_lnorm: str = "node", spell_reduce: str = "") -> bytes:
     """`graph_from_model` serialised: the bytes of the `.onnx` file `bh_classifier_create` opens."""
-    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling, spell_hswish, spell_lnorm))
+    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling, spell_hswish, spell_lnorm, spell_reduce))
 
 
 # ---------------------------------------------------------------------------------------
@@ -572,13 +631,15 @@ def _reduce_axes(g: ox.Graph, n: ox.Node) -> Optional[List[int]]:
     return None if axes is None else [int(a) for a in axes]
 
 
-def _find_layer_norms(g: ox.Graph, skip: set, front_nodes: set) -> Dict[str, list]:
+def _find_layer_norms(g: ox.Graph, skip: set, front_nodes: set, deferred: Optional[Dict[int, str]] = None) -> Dict[str, list]:
     """The decomposed LayerNorm torch.onnx emits below opset 17 (LN_CHAIN), over the last axis of an [N, H, W, C] view or over axis 1
     of an NCHW map: a ReduceMean over ONE axis (-1, 3 or 1) starts it, and a chain that deviates is refused by naming the node where
     it does (another exponent, another axis, a missing eps, a second reader of an inner tensor).  csrc/onnx_conv.hpp finds it the same
     way.  Returns {the chain's input: [(output name, gamma name, beta name, eps, axis, the ReduceMean's name)]}; the chain's nodes join
-    `skip`."""
+    `skip`.  A ReduceMean over the last axis (-1, 3) with no Sub(x, mean) behind it is no chain -- a reduction over W of an NCHW map, the
+    walk's OP_REDUCE --; `deferred` receives node -> the refusal it stays on an [N, H, W, C] view, which the walk raises."""
     graph_out = {o.name for o in g.outputs}
+    deferred = {} if deferred is None else deferred
     cons: Dict[str, List[int]] = {}
     for i, n in enumerate(g.nodes):
         if i in skip:
@@ -611,9 +672,17 @@ def _find_layer_norms(g: ox.Graph, skip: set, front_nodes: set) -> Dict[str, lis
         axes = _reduce_axes(g, n)
         if axes is None or len(axes) != 1 or axes[0] not in (-1, 3, 1):
             continue                                           # (H, W: the global pool; anything else keeps the walk's refusal)
+        x = n.inputs[0]
+        if axes[0] != 1 and not any(g.nodes[q].op_type == "Sub" and x in g.nodes[q].inputs for q in cons.get(n.outputs[0], [])):
+            try:
+                if int(n.attrs.get("keepdims", 1)) != 1:
+                    dev(n, "keepdims = 0")
+                dev(g.nodes[only_reader(n, "Sub")], "Sub(x, mean) expected")
+            except ConvertError as e:
+                deferred[i] = str(e)
+            continue
         if int(n.attrs.get("keepdims", 1)) != 1:
             dev(n, "keepdims = 0")
-        x = n.inputs[0]
         j_sub = only_reader(n, "Sub")
         sub = g.nodes[j_sub]
         if list(sub.inputs) != [x, n.outputs[0]]:
@@ -765,6 +834,10 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             stack.extend(gr.nodes[i].inputs)
         return found
     g = _see_through_casts(g, producers_of(g, spec))
+    # the unused second output of torch.max(x, dim): an ArgMax none of whose outputs anything reads.  The walk ignores no other dead node
+    # -- an operator it does not know is refused wherever it stands --, so this one is taken out by name, and is no reader of x.
+    spec_nodes, read_names = producers_of(g, spec), {x for q in g.nodes for x in q.inputs} | {o.name for o in g.outputs}
+    g.nodes[:] = [n for i, n in enumerate(g.nodes) if i in spec_nodes or n.op_type != "ArgMax" or any(o in read_names for o in n.outputs)]
     front_nodes = producers_of(g, spec)
     blob = _Blob(frontend.blob[: max((b.mel_w_off + b.n_bins * b.n_mels for b in frontend.branches), default=0)])
     layers: List[mf.Layer] = []
@@ -775,6 +848,7 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
     graph_out = {o.name for o in g.outputs}
 
     sums = set()   # the outputs of the residual Adds folded into a layer
+    r3: Dict[str, int] = {}   # the names that are rank-3 tensors behind a reduction with keepdims = 0 -- 1: [N, C, H] (W is gone), 2: [N, C, W]
     nhwc = set()   # the names that are [N, H, W, C] views of their tensor (behind Transpose [0, 2, 3, 1]): the library keeps activations NHWC
     NHWC_READERS = ("Transpose", "LayerNormalization", "MatMul", "Mul", "Relu", "Gelu", "Clip", "HardSwish")
 
@@ -796,6 +870,9 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         if L is not None and L.op == mf.OP_LNORM:
             raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a LayerNormalization "
                                "(the record carries no activation)")
+        if L is not None and L.op == mf.OP_REDUCE:
+            raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a ReduceMax / ReduceMean / "
+                               "GlobalMaxPool (a reduce layer carries no activation)")
         if name_in in nhwc:
             nhwc.add(name_out)
         if L is not None and name_in in sums and L.res_tensor != mf.NO_TENSOR and L.reserved != mf.RES_ACT_AFTER:
@@ -817,7 +894,8 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
     first_of_pattern = {}   # applied when the walk reaches the pattern's input (below)
     for out_name, (x, act, own) in act_of.items():
         first_of_pattern.setdefault(x, []).append((out_name, act, own))
-    ln_of_pattern = _find_layer_norms(g, skip, front_nodes)      # the decomposed LayerNorm chains, by their input
+    ln_deferred: Dict[int, str] = {}
+    ln_of_pattern = _find_layer_norms(g, skip, front_nodes, ln_deferred)      # the decomposed LayerNorm chains, by their input
 
     def lnorm_rec(who: str, x_name: str, out_name: str, gamma, beta, eps: float):
         """one OP_LNORM record over the channels of tensor x_name (an [N, H, W, C] view, or an NCHW map the caller has held to the
@@ -837,7 +915,7 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         bz = np.zeros(C, np.float32) if beta is None else beta.reshape(-1)
         layers.append(mf.Layer(mf.OP_LNORM, mf.ACT_NONE, t[0], mf.NO_TENSOR, C, C, 1, 1, 1, 1, 0, 0, t[2], t[3], t[2], t[3], 0,
                                blob.put(gamma.reshape(-1)), blob.put(bz), reserved=mf.lnorm_eps_bits(float(e32))))
-        if layers[t[0] - 1].op == mf.OP_GAP and emb_tensor == t[0]:
+        if layers[t[0] - 1].op in (mf.OP_GAP, mf.OP_REDUCE) and emb_tensor == t[0]:
             emb_tensor = len(layers)          # pool -> norm -> dense: the dense head reads the norm
         tmap[out_name] = (len(layers), C, t[2], t[3])
         if x_name in nhwc:
@@ -864,6 +942,11 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             flush_patterns(out_name)
 
     shuffle_at, shuffle_computed = _find_shuffles(g, skip, front_nodes)
+    prod_idx = {o: k for k, q in enumerate(g.nodes) for o in q.outputs}
+    cons_idx: Dict[str, List[int]] = {}
+    for k, q in enumerate(g.nodes):
+        for x in q.inputs:
+            cons_idx.setdefault(x, []).append(k)
     vmap: Dict[str, Tuple[int, int, int, int, int]] = {}   # the views: name -> (tensor, C, H, W, first channel); only Concat looks here
     readers: Dict[str, List[str]] = {}
     for q in g.nodes:
@@ -925,9 +1008,16 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         if op == "Constant":      # (the library's parser turns these into initializers; _const_ints reads them where they are)
             continue
         view_in = next((x for x in n.inputs if x in nhwc), None)
+        if view_in is not None and i in ln_deferred:
+            raise ConvertError(ln_deferred[i])
         if view_in is not None and op not in NHWC_READERS:
             raise ConvertError(f"{op} {n.name!r}: input {view_in!r} is an [N, H, W, C] view (behind a Transpose): only LayerNormalization, "
                                "MatMul (+ Add of a bias), the activations, Mul by a [C] constant and the Transpose back read one")
+        for x in n.inputs:
+            if x in r3 and x in tmap and op not in ("ReduceMean", "ReduceMax", "Add", "Squeeze", "Unsqueeze", "Flatten", "Reshape"):
+                raise ConvertError(f"{op} {n.name!r}: input {x!r} is a rank-3 tensor [N, C, T] (behind a reduction with keepdims = 0): only further "
+                                   "reductions, the max + mean Add, and Squeeze / Unsqueeze / Flatten / Reshape once one pixel is left read one "
+                                   "(1-D convolutions and pools are not supported)")
         if op == "Transpose":
             # the library keeps activations NHWC: [0, 2, 3, 1] marks the result an [N, H, W, C] view of the same tensor, [0, 3, 1, 2] ends it
             who = f"Transpose {n.name!r}: "
@@ -1236,16 +1326,104 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             else:
                 raise ConvertError(f"Add of {n.inputs}: no convolution to fold the residual into")
             flush_patterns(n.outputs[0])   # (a multi-node activation behind the sum: act(conv + x))
-        elif op in ("GlobalAveragePool", "ReduceMean"):
+        elif op in ("ReduceMean", "ReduceMax", "GlobalMaxPool"):
+            # max / mean over H, over W or over both -> OP_REDUCE, and Add(ReduceMax(x, a), ReduceMean(x, a)) -> one MAXMEAN record
+            # (csrc/onnx_conv.hpp has the same branch; the two are held to the same records).  The mean over both axes of an NCHW map stays OP_GAP.
+            who = f"{op} {n.name!r}: "
+            t = tmap.get(n.inputs[0])
+            if t is None:
+                raise ConvertError(who + f"input {n.inputs[0]!r} is not on the path from {spec!r}")
+            x_r3 = r3.get(n.inputs[0], 0)
+
+            def image_axes(q: ox.Node):
+                """the image axes a node reduces, against its input's rank: (over H, over W)"""
+                w2 = f"{q.op_type} {q.name!r}: "
+                if q.op_type == "GlobalMaxPool":
+                    axes = [2, 3]
+                else:
+                    axes = _reduce_axes(g, q)
+                    if axes is None and len(q.inputs) > 1 and q.inputs[1]:
+                        raise ConvertError(w2 + f"axes {q.inputs[1]!r} that are not a constant")
+                    axes = axes or []
+                if not 1 <= len(axes) <= 2:
+                    raise ConvertError(w2 + f"{len(axes)} axes: only the image axes, H (2) or W (3) or both, are reduced")
+                rank, qh, qw = (3 if x_r3 else 4), False, False
+                for a in axes:
+                    b = a + rank if a < 0 else a
+                    if b < 2 or b >= rank:
+                        raise ConvertError(w2 + f"axis {a} of a rank-{rank} tensor: only the image axes are reduced (never the batch or the channels)")
+                    is_h = (x_r3 == 1) if x_r3 else b == 2
+                    if qh if is_h else qw:
+                        raise ConvertError(w2 + f"axis {a} named twice")
+                    qh, qw = (True, qw) if is_h else (qh, True)
+                return qh, qw
+
+            if op == "GlobalMaxPool" and x_r3:
+                raise ConvertError(who + "a rank-3 input")
+            if op == "GlobalMaxPool" and len(n.outputs) > 1:
+                raise ConvertError(who + "more than one output")
+            rh, rw = image_axes(n)
+            keep = 1 if op == "GlobalMaxPool" else int(n.attrs.get("keepdims", 1))
+            if keep not in (0, 1):
+                raise ConvertError(who + "keepdims must be 0 or 1")
+            mode, out = (mf.REDUCE_MEAN if op == "ReduceMean" else mf.REDUCE_MAX), n.outputs[0]
+            # the max + mean pair: an Add reads this reduce and another one
+            for k in (cons_idx.get(n.outputs[0], []) if op != "GlobalMaxPool" else []):
+                add = g.nodes[k]
+                if add.op_type != "Add" or len(add.inputs) != 2 or not add.outputs or k in skip:
+                    continue
+                o2 = add.inputs[1] if add.inputs[0] == n.outputs[0] else add.inputs[0]
+                j = prod_idx.get(o2)
+                if j is None or j == i or j in skip or g.nodes[j].op_type not in ("ReduceMean", "ReduceMax"):
+                    continue
+                q = g.nodes[j]
+                wa = f"Add {add.name!r} (max + mean pair): "
+                if q.op_type == op:
+                    raise ConvertError(wa + f"two {op} nodes: one ReduceMax and one ReduceMean of the same tensor are expected")
+                if not q.inputs or not q.outputs or q.inputs[0] != n.inputs[0]:
+                    raise ConvertError(wa + f"{n.name!r} and {q.name!r} reduce different tensors")
+                if len(cons_idx.get(n.outputs[0], [])) != 1 or len(cons_idx.get(q.outputs[0], [])) != 1 or n.outputs[0] in graph_out or q.outputs[0] in graph_out:
+                    raise ConvertError(wa + "a reduce that another node reads too, or that is a graph output (each is read by the Add alone)")
+                if image_axes(q) != (rh, rw):
+                    raise ConvertError(wa + f"{n.name!r} and {q.name!r} reduce different axes")
+                if int(q.attrs.get("keepdims", 1)) != keep:
+                    raise ConvertError(wa + f"{n.name!r} and {q.name!r} differ in keepdims")
+                mode, out = mf.REDUCE_MAXMEAN, add.outputs[0]
+                skip |= {j, k}
+                break
+            t_in, C, h, w = t
+            if mode == mf.REDUCE_MEAN and rh and rw and not x_r3:
+                # the global average pool: OP_GAP, as ever
+                layers.append(mf.Layer(mf.OP_GAP, mf.ACT_NONE, t_in, mf.NO_TENSOR, C, C, h, w, 1, 1, 0, 0, h, w, 1, 1))
+                tmap[out] = (len(layers), C, 1, 1)
+                emb_tensor, emb_dim = len(layers), C
+                flush_patterns(out)
+                continue
+            if t_in == 0:
+                raise ConvertError(who + "a reduction of the spectrogram (tensor 0) is not supported")
+            if C % 4:
+                raise ConvertError(who + f"{C} channels: a channel count that is not a multiple of 4 is not supported")
+            kh, kw = (h if rh else 1), (w if rw else 1)
+            if kh * kw == 1:
+                raise ConvertError(who + "a window of one pixel (the reduced axes have extent 1): nothing to reduce")
+            if kh * kw > 65536:
+                raise ConvertError(who + "a window of more than 65 536 pixels")
+            oh, ow = h // kh, w // kw
+            layers.append(mf.Layer(mf.OP_REDUCE, mf.ACT_NONE, t_in, mf.NO_TENSOR, C, C, kh, kw, 1, 1, 0, 0, h, w, oh, ow, reserved=mode))
+            tmap[out] = (len(layers), C, oh, ow)
+            # (the pair over both axes, or one that finishes the image, is [N, C, 1, 1]: no rank-3 tensor of one pixel is kept)
+            whole = mode == mf.REDUCE_MAXMEAN and oh * ow == 1
+            if keep == 0 and not x_r3 and not (rh and rw) and not whole:
+                r3[out] = 2 if rh else 1
+            if keep == 1 and x_r3 and not whole:
+                r3[out] = x_r3
+            if oh * ow == 1:
+                emb_tensor, emb_dim = len(layers), C
+            flush_patterns(out)
+        elif op == "GlobalAveragePool":
             t = tmap.get(n.inputs[0])
             if t is None:
                 raise ConvertError(f"{op}: input not on the path")
-            if op == "ReduceMean":
-                axes = n.attrs.get("axes")
-                if axes is None and len(n.inputs) > 1:
-                    axes = g.initializers[n.inputs[1]].tolist()
-                if sorted(a % 4 for a in axes) != [2, 3]:
-                    raise ConvertError("ReduceMean over axes other than H, W")
             layers.append(mf.Layer(mf.OP_GAP, mf.ACT_NONE, t[0], mf.NO_TENSOR, t[1], t[1], t[2], t[3], 1, 1, 0, 0, t[2], t[3], 1, 1))
             tmap[n.outputs[0]] = (len(layers), t[1], 1, 1)
             emb_tensor, emb_dim = len(layers), t[1]
@@ -1308,7 +1486,7 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             mode = mf.POOL_MAX if op == "MaxPool" else (mf.POOL_AVG_PAD if cip else mf.POOL_AVG)
             layers.append(mf.Layer(mf.OP_POOL, mf.ACT_NONE, t_in, mf.NO_TENSOR, c, c, kh, kw, sh, sw, pt, pl, h, w, oh, ow, reserved=mode))
             tmap[n.outputs[0]] = (len(layers), c, oh, ow)
-        elif op in ("Flatten", "Reshape", "Squeeze", "Identity", "Dropout"):
+        elif op in ("Flatten", "Reshape", "Squeeze", "Unsqueeze", "Identity", "Dropout"):
             t = tmap.get(n.inputs[0])
             if t is None:
                 raise ConvertError(f"{op}: input not on the path")

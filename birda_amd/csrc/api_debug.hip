@@ -15,6 +15,7 @@
 #include "../../include/birda_hip_gated_debug.h"
 #include "../../include/birda_hip_dilated_debug.h"
 #include "../../include/birda_hip_lnorm_debug.h"
+#include "../../include/birda_hip_reduce_debug.h"
 
 using namespace bhi;
 
@@ -436,6 +437,45 @@ int bh_debug_pool(int device, const float *X, float *Y, size_t n_seg, const int3
     float *dy = h.out(y_floats, "Y", Y);
     if (!h.ok) return h.no_memory();
     return h.finish(bh::launch_pool(dx, dy, p, mode, (int)n_seg, nullptr), kernel, kernel_cap);
+} catch (...) { return on_exception(); }
+
+// One reduce layer alone on operands of the caller's, through the launcher a forward pass takes (include/birda_hip_reduce_debug.h).
+int bh_debug_reduce(int device, const float *X, float *Y, size_t n_seg, const int32_t *shape, int mode, int split, char *kernel, size_t kernel_cap) try {
+    if (!X || !Y || !shape || !n_seg) return fail(BH_ERR_INVALID, "debug_reduce: bad arguments");
+    const bh::ConvParams p{shape[0], shape[1], shape[2], shape[3], shape[4], shape[4], shape[5], shape[6], 1, 1, 0, 0, 0, 0};
+    if (!bh::reduce_supports(p, mode))
+        return fail(BH_ERR_UNSUPPORTED, "debug_reduce: %dx%d -> %dx%d, %d channels, window %dx%d, mode %d: not a reduce the model validator accepts (not built: "
+                    "channels a multiple of 4, mode 0..2, a window of the whole axis or 1 along each axis and not 1x1, at most 65 536 taps, the mean over "
+                    "both axes is the global pool's)", p.in_h, p.in_w, p.out_h, p.out_w, p.cout, p.kh, p.kw, mode);
+    if (split != 0 && split != 1 && split != 8) return fail(BH_ERR_INVALID, "debug_reduce: split %d (0: the launcher's choice; 1 or 8)", split);
+    const size_t x_floats = n_seg * (size_t)p.in_h * p.in_w * p.cout, y_floats = n_seg * (size_t)p.out_h * p.out_w * p.cout;
+    if (x_floats > (size_t)INT32_MAX || y_floats > (size_t)INT32_MAX || n_seg > (size_t)INT32_MAX)
+        return fail(BH_ERR_INVALID, "debug_reduce: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    DebugLaunch h{"debug_reduce"};
+    const float *dx = h.in(X, x_floats * 4);
+    float *dy = h.out(y_floats, "Y", Y);
+    if (!h.ok) return h.no_memory();
+    const char *kn = bh::launch_reduce(dx, dy, p, mode, (int)n_seg, nullptr, split);
+    if (!kn) return fail(BH_ERR_INTERNAL, "debug_reduce: the launcher has no instantiation for a shape reduce_supports accepts");
+    return h.finish(kn, kernel, kernel_cap);
+} catch (...) { return on_exception(); }
+
+// The same launch on DEVICE buffers of the caller's, for the timing tool (include/birda_hip_reduce_debug.h): no copies, no guard bands.
+int bh_debug_reduce_on_device(int device, const float *dX, float *dY, size_t n_seg, const int32_t *shape, int mode, int split, char *kernel,
+                              size_t kernel_cap) try {
+    if (!dX || !dY || !shape || !n_seg || n_seg > (size_t)INT32_MAX) return fail(BH_ERR_INVALID, "debug_reduce_on_device: bad arguments");
+    const bh::ConvParams p{shape[0], shape[1], shape[2], shape[3], shape[4], shape[4], shape[5], shape[6], 1, 1, 0, 0, 0, 0};
+    const bool gap = mode == 3;     // the yardstick: gap_kernel, the mean over the whole image
+    if (!bh::reduce_supports(p, gap ? 0 : mode) || (gap && (p.kh != p.in_h || p.kw != p.in_w)))
+        return fail(BH_ERR_UNSUPPORTED, "debug_reduce_on_device: %dx%d, %d channels, window %dx%d, mode %d not built", p.in_h, p.in_w, p.cout, p.kh, p.kw, mode);
+    if (split != 0 && split != 1 && split != 8) return fail(BH_ERR_INVALID, "debug_reduce_on_device: split %d (0, 1 or 8)", split);
+    HIPCHK(hipSetDevice(device));
+    const char *kn = gap ? bh::launch_gap(dX, dY, (int)n_seg, p.in_h * p.in_w, p.cout, nullptr) : bh::launch_reduce(dX, dY, p, mode, (int)n_seg, nullptr, split);
+    if (!kn) return fail(BH_ERR_INTERNAL, "debug_reduce_on_device: the launcher has no instantiation for this shape");
+    HIPCHK(hipGetLastError());
+    if (kernel && kernel_cap) snprintf(kernel, kernel_cap, "%s", kn);
+    return BH_OK;
 } catch (...) { return on_exception(); }
 
 // The gate of one squeeze-excite block alone on operands of the caller's, in the form a forward pass takes for its widths

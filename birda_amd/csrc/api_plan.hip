@@ -195,6 +195,8 @@ void plan_arena(const bh::Model &m, const std::vector<Step> &sched, size_t max_b
 // depthwise phase, pass A of a squeeze-excite block, the channel split of a low-latency launch (a fused launch, split) and the gate
 // launches all compute the undilated layer.  Every matcher below asks here; such a block runs layer by layer.
 static bool layer_dilated(const bh::LayerRec &L) { return L.skip_h != 0 || L.skip_w != 0; }
+// (An OP_REDUCE record -- like OP_POOL and OP_LNORM -- is in none of the op lists the matchers below accept, the global pool's places
+//  included: a gate or a head whose pool is a reduce runs layer by layer, and its tensors have ordinary liveness.)
 
 // The pool layer i opens a squeeze-excite gate that runs as the two gate launches (se_hidden_kernel, se_gate16_kernel) instead of pool
 // + two GEMMs: an image of at most 64 pixels, at least BH_SE_GATE16_MIN channels, pool -> 1x1 (C -> Cr) -> 1x1 (Cr -> C) with no

@@ -549,6 +549,17 @@ const char *launch_concat(const ConcatSource *src, int n_src, float *out, int h,
 // ("lnorm_kernel<32,1>": lanes a pixel, float4s a lane -- C alone decides); nullptr when C is not supported and nothing was launched.
 bool lnorm_supports(int C);
 const char *launch_lnorm(const float *in, const float *gamma, const float *beta, float *out, unsigned long long n_pix, int C, float eps, hipStream_t s);
+// max / mean / max + mean over one image axis or both of an NHWC f32 tensor (kernels_reduce.hip; model.hpp OP_REDUCE):
+// [n][in_h][in_w][c] -> [n][in_h / kh][in_w / kw][c], kh = in_h or 1 and kw = in_w or 1 the window (not 1x1), c % 4 == 0, at most 65 536
+// taps; mode 0 max (a NaN tap makes the output NaN), 1 mean (not over both axes: that is launch_gap's), 2 max + mean of the same
+// window.  f32 in every precision mode; one read of the input.  reduce_split: the lanes that share one output float4 (1 or 8),
+// from the shape alone -- never from n_seg --, so a segment's bits are the same at every launch size.  Returns the instantiation's
+// name ("reduce_kernel<MAXMEAN,8>"); nullptr when the shape is not supported and nothing was launched.  split: 0, the launcher's
+// own choice (every forward); 1 / 8 force a form (the timing tool's comparison, through bh_debug_reduce).
+constexpr int kReduceSplitMin = 32, kReduceKeptMax = 4096;
+bool reduce_supports(const ConvParams &p, int mode);
+int reduce_split(const ConvParams &p);
+const char *launch_reduce(const float *in, float *out, const ConvParams &p, int mode, int n_seg, hipStream_t s, int split = 0);
 // head 1x1 conv + activation (GELU / swish / ReLU6) + global average pool fused (f16 hi / lo weight planes as for launch_pw_gemm16)
 bool head_gap16_supports(int P, int K, int N, int act);
 const char *launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,

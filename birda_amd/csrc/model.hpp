@@ -9,7 +9,7 @@
 
 namespace bh {
 
-enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8, OP_CONCAT = 10, OP_LNORM = 12 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
+enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8, OP_CONCAT = 10, OP_LNORM = 12, OP_REDUCE = 13 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
 // OP_POOL (ONNX MaxPool / AveragePool, floor mode): the record's `reserved` word is the mode.  No weights, no bias, no activation.
 enum PoolMode : uint32_t { POOL_MAX = 0, POOL_AVG = 1, POOL_AVG_PAD = 2 };   // AVG: over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 // OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the record's `reserved` word is where `act` stands relative to the residual.  0: act(conv + b) + R
@@ -29,6 +29,13 @@ constexpr uint32_t RES_ACT_AFTER = 1;
 // over the C channels of pixel p.  cin == cout == C (a multiple of 4), kernel / stride 1, pads 0, out image == in image, in_layout 0,
 // never on tensor 0; w_off -> gamma[C], b_off -> beta[C]; no activation, no residual, no dilation; `reserved` = the bit pattern of eps
 // as an f32, finite and > 0 (a constant pixel would otherwise be 0 * inf).  Code 11 is never used, like 9: both stay "unknown layer op".
+// OP_REDUCE = 13 (ONNX ReduceMax / ReduceMean over H, over W or over both, GlobalMaxPool, and Add(ReduceMax, ReduceMean) of one window --
+// the head of the PANNs audio CNNs): a reduction of an NHWC f32 tensor over a window that spans the whole image along each reduced
+// axis.  Spelled like OP_GAP: cin == cout == C (a multiple of 4), kh = in_h or 1 and kw = in_w or 1 the window, stride 1, pads 0,
+// out_h = in_h / kh, out_w = in_w / kw, in_layout 0, never on tensor 0; no weights, bias, activation, residual or dilation; at most
+// 65 536 taps.  `reserved` is the mode; REDUCE_MAXMEAN is max + mean of the same window as one value.  One spelling each: the mean
+// over both axes stays OP_GAP, and a 1x1 window is no reduction.
+enum ReduceMode : uint32_t { REDUCE_MAX = 0, REDUCE_MEAN = 1, REDUCE_MAXMEAN = 2 };
 constexpr uint32_t NO_TENSOR = 0xFFFFFFFFu;
 // Dilation (OP_CONV on an NHWC tensor, OP_DWCONV): the record's words at bytes 88 .. 95, skip_h and skip_w, are the rows and the columns
 // SKIPPED between neighbouring taps, dilation - 1 per axis -- tap (dy, dx) reads pixel (oy sh - pad_t + dy (skip_h + 1),
@@ -107,7 +114,7 @@ inline bool validate_model(Model &m, std::string &err) {
     for (uint32_t i = 0; i < m.h.n_layers; i++) {
         const auto &L = m.layers[i];
         // (a global pool's "kernel" is its whole input image -- the squeeze of a squeeze-excite gate in an early block pools 64 x 249)
-        const uint32_t kmax = L.op == OP_GAP ? (1u << 16) : 64;
+        const uint32_t kmax = L.op == OP_GAP || L.op == OP_REDUCE ? (1u << 16) : 64;
         if ((L.cin == 0 && L.op != OP_CONCAT) || L.cout == 0 || L.cin > (1u << 16) || L.cout > (1u << 24) || L.kh == 0 || L.kw == 0 || L.kh > kmax || L.kw > kmax ||
             L.sh == 0 || L.sw == 0 || L.sh > 16 || L.sw > 16 || L.pad_t > 64 || L.pad_l > 64 || L.in_h == 0 || L.in_w == 0 || L.out_h == 0 ||
             L.out_w == 0 || L.in_h > (1u << 16) || L.in_w > (1u << 16) || L.out_h > (1u << 16) || L.out_w > (1u << 16) ||
@@ -117,7 +124,7 @@ inline bool validate_model(Model &m, std::string &err) {
         m.tensor_floats[i + 1] = (uint64_t)L.out_h * L.out_w * L.cout;
         if (L.in_tensor > i || (L.res_tensor != NO_TENSOR && L.res_tensor > i)) { err = "layer reads a later tensor"; return false; }
         // what the layer reads must be what its input tensor holds (a pool reads in_h x in_w x cout, a dense layer cin values)
-        const uint64_t in_floats = L.op == OP_GAP || L.op == OP_DWCONV || L.op == OP_SCALE || L.op == OP_POOL ? (uint64_t)L.in_h * L.in_w * L.cout
+        const uint64_t in_floats = L.op == OP_GAP || L.op == OP_DWCONV || L.op == OP_SCALE || L.op == OP_POOL || L.op == OP_REDUCE ? (uint64_t)L.in_h * L.in_w * L.cout
                                  : L.op == OP_DENSE ? (uint64_t)L.cin
                                  : L.op == OP_CONCAT ? m.tensor_floats[L.in_tensor]   // (a window of its source: held below)
                                  : (uint64_t)L.in_h * L.in_w * L.cin;
@@ -125,7 +132,7 @@ inline bool validate_model(Model &m, std::string &err) {
         if (L.res_tensor != NO_TENSOR && L.op != OP_SCALE && L.op != OP_CONCAT && m.tensor_floats[L.res_tensor] != m.tensor_floats[i + 1]) {
             err = "residual shape does not match the layer output"; return false;
         }
-        if (L.op < OP_CONV || L.op > OP_LNORM || L.op == 9 || L.op == 11) { err = "unknown layer op"; return false; }
+        if (L.op < OP_CONV || L.op > OP_REDUCE || L.op == 9 || L.op == 11) { err = "unknown layer op"; return false; }
         if (L.op == OP_GCONV) {
             const uint32_t G = L.reserved;
             if (G < 2) { err = "grouped convolution with fewer than two groups (one group is a full convolution)"; return false; }
@@ -180,6 +187,24 @@ inline bool validate_model(Model &m, std::string &err) {
                 err = "layer norm gamma / beta outside the blob"; return false;
             }
         }
+        if (L.op == OP_REDUCE) {
+            // (the mode word selects the operation -- three of them share the code --, so a mode outside the table is an operation the
+            //  table does not hold: refused first and in the words of an unknown code, whatever else the record says)
+            if (L.reserved > REDUCE_MAXMEAN) { err = "unknown layer op: a reduce layer with an unknown mode"; return false; }
+            if (L.cin != L.cout) { err = "reduce layer that changes the channel count"; return false; }
+            if (L.cout % 4) { err = "reduce layer over a channel count that is not a multiple of 4"; return false; }
+            if (L.act != 0) { err = "reduce layer with an activation"; return false; }
+            if (L.res_tensor != NO_TENSOR) { err = "reduce layer with a residual"; return false; }
+            if (L.in_layout != 0 || L.in_tensor == 0) { err = "reduce layer on the planar spectrogram (tensor 0)"; return false; }
+            if (L.sh != 1 || L.sw != 1 || L.pad_t != 0 || L.pad_l != 0) { err = "reduce layer with a stride or padding other than 1 / 0"; return false; }
+            if ((L.kh != 1 && L.kh != L.in_h) || (L.kw != 1 && L.kw != L.in_w)) { err = "reduce layer with a window that is neither the whole axis nor 1"; return false; }
+            if (L.kh == 1 && L.kw == 1) { err = "reduce layer with a 1x1 window (no reduction)"; return false; }
+            if (L.out_h != L.in_h / L.kh || L.out_w != L.in_w / L.kw) { err = "reduce layer whose output image is not its input image over its window"; return false; }
+            if ((uint64_t)L.kh * L.kw > (1u << 16)) { err = "reduce layer over more than 65 536 taps"; return false; }
+            if (L.reserved == REDUCE_MEAN && L.kh == L.in_h && L.kw == L.in_w && L.kh > 1 && L.kw > 1) {
+                err = "reduce layer that is the mean over both axes (OP_GAP is its one spelling)"; return false;
+            }
+        }
         if (L.op == OP_CONV && L.in_layout != 0) {
             if (L.reserved == RES_ACT_AFTER) { err = "activation after the residual on the NCHW stem convolution"; return false; }
         } else if (L.op == OP_CONV || L.op == OP_PWCONV || L.op == OP_DENSE) {
@@ -188,14 +213,14 @@ inline bool validate_model(Model &m, std::string &err) {
             if (L.reserved == RES_ACT_AFTER && L.act == 0) { err = "activation after the residual without an activation (a plain residual is position 0)"; return false; }
         }
         if (L.skip_h || L.skip_w) {
-            static const char *const names[] = {"?", "stem convolution", "depthwise", "pointwise", "global pool", "dense", "scale", "pool", "grouped convolution", "?", "concat", "?", "layer norm"};
+            static const char *const names[] = {"?", "stem convolution", "depthwise", "pointwise", "global pool", "dense", "scale", "pool", "grouped convolution", "?", "concat", "?", "layer norm", "reduce"};
             if (!(L.op == OP_DWCONV || (L.op == OP_CONV && L.in_layout == 0))) {
                 err = std::string("dilation on a ") + names[L.op] + " layer"; return false;
             }
             if (L.skip_h >= MAX_DILATION || L.skip_w >= MAX_DILATION) { err = "dilation above 16"; return false; }
             if ((L.kh == 1 && L.skip_h) || (L.kw == 1 && L.skip_w)) { err = "dilation on an axis with one tap (dilation 1 is its one spelling)"; return false; }
         }
-        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && L.op != OP_CONCAT && L.op != OP_LNORM && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
+        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && L.op != OP_CONCAT && L.op != OP_LNORM && L.op != OP_REDUCE && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
                                                    L.b_off + L.cout > m.h.blob_floats)) {
             err = "layer weights outside blob"; return false;
         }

@@ -8,7 +8,8 @@
 //     front of it, the activation spellings exporters emit (Relu, Clip(0, 6), Sigmoid x Mul = swish, Div / Erf / Add / Mul / Mul
 //     = GELU, the Gelu operator; HardSwish, HardSigmoid(1/6, 1/2) x Mul and Add 3 / Clip(0, 6) / Mul / Mul 1/6 = hard swish; HardSigmoid(1/6,
 //     1/2) or that chain without its Mul(., x) on a pooled tensor = the hard-sigmoid gate), residual Add folded into its 1x1 convolution, MaxPool / AveragePool (floor mode; OP_POOL),
-//     GlobalAveragePool / ReduceMean over H, W, Concat / Split / Slice over the channels and the Reshape -> Transpose -> Reshape channel
+//     GlobalAveragePool / ReduceMean over H, W, ReduceMax / ReduceMean over H or W or both, GlobalMaxPool and the max + mean pair Add(ReduceMax,
+//     ReduceMean) of the PANNs head (OP_REDUCE), Concat / Split / Slice over the channels and the Reshape -> Transpose -> Reshape channel
 //     shuffle (OP_CONCAT: a Split / Slice output that only Concat nodes read is a view folded into their windows),
 //     ConvNeXt blocks (OP_LNORM: Transpose [0, 2, 3, 1] / [0, 3, 1, 2] as an [N, H, W, C] view that costs no record, LayerNormalization over the
 //     channels as a node or as the decomposed ReduceMean -> Sub -> Pow -> ReduceMean -> Add -> Sqrt -> Div -> Mul -> Add chain, MatMul + Add on
@@ -232,6 +233,18 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         }
         for (auto &o : outputs) o = resolve(o);
     }
+    // ---- the unused second output of torch.max(x, dim): an ArgMax none of whose outputs anything reads.  The walk ignores no other dead
+    // node -- an operator it does not know is refused wherever it stands --, so this one is taken out by name, and is no reader of x.
+    for (size_t i = 0; i < nodes.size(); i++) {
+        if (skip.count(i) || front.count(i) || nodes[i].op != "ArgMax") continue;
+        bool read = false;
+        for (const auto &o : nodes[i].out) {
+            if (std::find(outputs.begin(), outputs.end(), o) != outputs.end()) read = true;
+            for (size_t k = 0; k < nodes.size() && !read; k++)
+                if (!skip.count(k) && std::find(nodes[k].in.begin(), nodes[k].in.end(), o) != nodes[k].in.end()) read = true;
+        }
+        if (!read) skip.insert(i);
+    }
     for (size_t i = 0; i < nodes.size(); i++)
         if (!skip.count(i))
             for (const auto &x : nodes[i].in) cons[x].push_back(i);
@@ -406,6 +419,9 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     // map.  A ReduceMean over ONE axis (-1, 3 or 1) starts it; a chain that deviates is refused by naming the node where it does.
     struct LnChain { std::string out, gamma, beta, name; float eps; int64_t axis; };
     std::map<std::string, std::vector<LnChain>> ln_of_pattern;                               // chain input -> the chains
+    // A ReduceMean over the last axis (-1, 3) with no Sub(x, mean) behind it is no chain: a reduction over W of an NCHW map (OP_REDUCE; the
+    // walk).  On an [N, H, W, C] view it stays refused as the chain it is not -- node -> that refusal, raised by the walk.
+    std::map<size_t, std::string> ln_deferred;
     {
         std::map<std::string, std::vector<size_t>> rd;                                       // readers outside the patterns found so far
         for (size_t i = 0; i < nodes.size(); i++)
@@ -440,9 +456,23 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             if (n.op != "ReduceMean" || skip.count(i) || front.count(i) || n.in.empty() || n.out.empty()) continue;
             std::vector<int64_t> axes, axes2;
             if (!reduce_axes(n, axes) || axes.size() != 1 || (axes[0] != -1 && axes[0] != 3 && axes[0] != 1)) continue;   // (H, W: the global pool; anything else keeps the walk's refusal)
-            if (n.geti("keepdims", 1) != 1) return dev(n, "keepdims = 0");
             const std::string &x = n.in[0];
             size_t j_sub, j_pow, j_div, j_m2, j_add, j_sqrt, j_mul, j_add2, k;
+            if (axes[0] != 1) {
+                bool has_sub = false;
+                auto rn = rd.find(n.out[0]);
+                if (rn != rd.end())
+                    for (size_t q : rn->second)
+                        if (nodes[q].op == "Sub" && std::find(nodes[q].in.begin(), nodes[q].in.end(), x) != nodes[q].in.end()) has_sub = true;
+                if (!has_sub) {
+                    if (n.geti("keepdims", 1) != 1) dev(n, "keepdims = 0");
+                    else if (only_reader(n, "Sub", j_sub)) dev(nodes[j_sub], "Sub(x, mean) expected");
+                    ln_deferred[i] = err;
+                    err.clear();
+                    continue;
+                }
+            }
+            if (n.geti("keepdims", 1) != 1) return dev(n, "keepdims = 0");
             if (!only_reader(n, "Sub", j_sub)) return false;
             const Node &sub = nodes[j_sub];
             if (sub.in.size() != 2 || sub.in[0] != x || sub.in[1] != n.out[0]) return dev(sub, "Sub(x, mean) expected");
@@ -487,7 +517,8 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     // channels off .. off + c - 1 of tensor idx, folded into those records' windows; no other node ever looks one up
     // nhwc: the name is an [N, H, W, C] view of its tensor (behind Transpose [0, 2, 3, 1]) -- the library keeps activations NHWC, so the
     // view costs nothing; only LayerNormalization, MatMul, the activations, Mul by a [C] constant and the Transpose back read one
-    struct T { uint32_t idx, c, h, w, off = 0; bool view = false; bool nhwc = false; };
+    // r3: the name is a rank-3 tensor behind a reduction with keepdims = 0 -- 1: [N, C, H] (W is gone), 2: [N, C, W] (H is gone)
+    struct T { uint32_t idx, c, h, w, off = 0; bool view = false; bool nhwc = false; uint32_t r3 = 0; };
     std::map<std::string, T> tmap;
     tmap[spec] = T{0, m.h.n_branches, m.h.spec_h, m.h.spec_w};
     std::vector<LayerRec> &layers = m.layers;
@@ -556,6 +587,8 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a Concat, Split, Slice or channel shuffle (the record carries no activation)");
         if (t.idx != 0 && layers[t.idx - 1].op == OP_LNORM)
             return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a LayerNormalization (the record carries no activation)");
+        if (t.idx != 0 && layers[t.idx - 1].op == OP_REDUCE)
+            return fail("activation after '" + name_in + "' cannot be folded into its producer: directly after a ReduceMax / ReduceMean / GlobalMaxPool (a reduce layer carries no activation)");
         if (t.idx != 0 && sums.count(name_in) && layers[t.idx - 1].res_tensor != NO_TENSOR && layers[t.idx - 1].reserved != RES_ACT_AFTER) {
             // act(conv + x), the end of a ResNet block: the layer keeps its one activation code and records its position
             LayerRec &L = layers[t.idx - 1];
@@ -611,7 +644,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         const uint64_t wo = blob.put(tmp), bo = blob.put(tmpb);
         const uint32_t li = new_layer(OP_LNORM, x.idx, NO_TENSOR, x.c, x.c, 1, 1, 1, 1, 0, 0, x.h, x.w, x.h, x.w, 0, wo, bo);
         memcpy(&layers[li - 1].reserved, &eps, sizeof eps);
-        if (layers[x.idx - 1].op == OP_GAP && emb_tensor == x.idx) emb_tensor = li;
+        if ((layers[x.idx - 1].op == OP_GAP || layers[x.idx - 1].op == OP_REDUCE) && emb_tensor == x.idx) emb_tensor = li;
         T y{li, x.c, x.h, x.w};
         y.nhwc = x.nhwc;
         tmap[out] = y;
@@ -699,9 +732,17 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         // an [N, H, W, C] view among the inputs: only these operators read one
         const std::string *view_in = nullptr;
         for (const auto &xn : n.in) { T t; if (!view_in && find(xn, t) && t.nhwc) view_in = &xn; }
+        if (view_in) { auto d = ln_deferred.find(i); if (d != ln_deferred.end()) return fail(d->second); }
         if (view_in && op != "Transpose" && op != "LayerNormalization" && op != "MatMul" && op != "Mul" && op != "Relu" && op != "Gelu" && op != "Clip" && op != "HardSwish")
             return fail(op + " '" + n.name + "': input '" + *view_in + "' is an [N, H, W, C] view (behind a Transpose): only LayerNormalization, MatMul (+ Add of a bias), "
                         "the activations, Mul by a [C] constant and the Transpose back read one");
+        // a rank-3 tensor [N, C, T] among the inputs (behind a reduction with keepdims = 0): only these operators read one
+        for (const auto &xn : n.in) {
+            T t;
+            if (find(xn, t) && t.r3 && op != "ReduceMean" && op != "ReduceMax" && op != "Add" && op != "Squeeze" && op != "Unsqueeze" && op != "Flatten" && op != "Reshape")
+                return fail(op + " '" + n.name + "': input '" + xn + "' is a rank-3 tensor [N, C, T] (behind a reduction with keepdims = 0): only further reductions, the max + mean "
+                            "Add, and Squeeze / Unsqueeze / Flatten / Reshape once one pixel is left read one (1-D convolutions and pools are not supported)");
+        }
         bool folded = false;
         if (op == "Mul" && !fold_layer_scale(n, folded)) return false;
         if (folded) continue;
@@ -944,17 +985,94 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             }
             if (!done) return fail("Add of '" + n.in[0] + "', '" + n.in[1] + "': no convolution to fold the residual into");
             if (!flush_patterns(n.out[0])) return false;   // (a multi-node activation behind the sum: act(conv + x))
-        } else if (op == "GlobalAveragePool" || op == "ReduceMean") {
+        } else if (op == "ReduceMean" || op == "ReduceMax" || op == "GlobalMaxPool") {
+            // max / mean over H, over W or over both -> OP_REDUCE, and Add(ReduceMax(x, a), ReduceMean(x, a)) -> one MAXMEAN record (convert.py
+            // has the same branch; the two are held to the same records).  The mean over both axes of an NCHW map stays OP_GAP.
+            const std::string who = op + " '" + n.name + "': ";
+            T t;
+            if (!find(n.in[0], t)) return fail(who + "input '" + n.in[0] + "' is not on the path from '" + spec + "'");
+            // the image axes a node reduces, against its input's rank: (over H, over W); false: refused (err is set)
+            auto image_axes = [&](const Node &q, const T &x, bool &rh, bool &rw) {
+                const std::string w2 = q.op + " '" + q.name + "': ";
+                std::vector<int64_t> axes;
+                if (q.op == "GlobalMaxPool") axes = {2, 3};
+                else if (const auto *ax = q.ints("axes")) axes = *ax;
+                else if (q.in.size() > 1 && !q.in[1].empty()) { const auto *ax2 = const_ints(q.in[1]); if (!ax2) return fail(w2 + "axes '" + q.in[1] + "' that are not a constant"); axes = *ax2; }
+                if (axes.empty() || axes.size() > 2) return fail(w2 + std::to_string(axes.size()) + " axes: only the image axes, H (2) or W (3) or both, are reduced");
+                const int64_t rank = x.r3 ? 3 : 4;
+                rh = rw = false;
+                for (int64_t a : axes) {
+                    const int64_t b = a < 0 ? a + rank : a;
+                    if (b < 2 || b >= rank) return fail(w2 + "axis " + std::to_string(a) + " of a rank-" + std::to_string(rank) + " tensor: only the image axes are reduced (never the batch or the channels)");
+                    const bool is_h = x.r3 ? x.r3 == 1 : b == 2;
+                    if (is_h ? rh : rw) return fail(w2 + "axis " + std::to_string(a) + " named twice");
+                    (is_h ? rh : rw) = true;
+                }
+                return true;
+            };
+            if (op == "GlobalMaxPool" && t.r3) return fail(who + "a rank-3 input");
+            if (op == "GlobalMaxPool" && n.out.size() > 1) return fail(who + "more than one output");
+            bool rh = false, rw = false;
+            if (!image_axes(n, t, rh, rw)) return false;
+            const int64_t keep = op == "GlobalMaxPool" ? 1 : n.geti("keepdims", 1);
+            if (keep != 0 && keep != 1) return fail(who + "keepdims must be 0 or 1");
+            uint32_t mode = op == "ReduceMean" ? REDUCE_MEAN : REDUCE_MAX;
+            std::string out = n.out[0];
+            // the max + mean pair: an Add reads this reduce and another one
+            if (op != "GlobalMaxPool") {
+                auto cit = cons.find(n.out[0]);
+                if (cit != cons.end())
+                    for (size_t k : cit->second) {
+                        const Node &add = nodes[k];
+                        if (add.op != "Add" || add.in.size() != 2 || add.out.empty() || skip.count(k)) continue;
+                        const std::string &o2 = add.in[0] == n.out[0] ? add.in[1] : add.in[0];
+                        auto pj = prod.find(o2);
+                        if (pj == prod.end() || pj->second == i || skip.count(pj->second) || (nodes[pj->second].op != "ReduceMean" && nodes[pj->second].op != "ReduceMax")) continue;
+                        const size_t j = pj->second;
+                        const Node &q = nodes[j];
+                        const std::string wa = "Add '" + add.name + "' (max + mean pair): ";
+                        if (q.op == op) return fail(wa + "two " + op + " nodes: one ReduceMax and one ReduceMean of the same tensor are expected");
+                        if (q.in.empty() || q.out.empty() || q.in[0] != n.in[0]) return fail(wa + "'" + n.name + "' and '" + q.name + "' reduce different tensors");
+                        auto c2 = cons.find(q.out[0]);
+                        if (cit->second.size() != 1 || c2 == cons.end() || c2->second.size() != 1 || graph_out.count(n.out[0]) || graph_out.count(q.out[0]))
+                            return fail(wa + "a reduce that another node reads too, or that is a graph output (each is read by the Add alone)");
+                        bool qh = false, qw = false;
+                        if (!image_axes(q, t, qh, qw)) return false;
+                        if (qh != rh || qw != rw) return fail(wa + "'" + n.name + "' and '" + q.name + "' reduce different axes");
+                        if (q.geti("keepdims", 1) != keep) return fail(wa + "'" + n.name + "' and '" + q.name + "' differ in keepdims");
+                        mode = REDUCE_MAXMEAN;
+                        out = add.out[0];
+                        skip.insert(j); skip.insert(k);
+                        break;
+                    }
+            }
+            if (mode == REDUCE_MEAN && rh && rw && !t.r3) {
+                // the global average pool: OP_GAP, as ever
+                const uint32_t li = new_layer(OP_GAP, t.idx, NO_TENSOR, t.c, t.c, t.h, t.w, 1, 1, 0, 0, t.h, t.w, 1, 1, 0, 0, 0);
+                tmap[out] = T{li, t.c, 1, 1};
+                emb_tensor = li; emb_dim = t.c;
+                if (!flush_patterns(out)) return false;
+                continue;
+            }
+            if (t.idx == 0) return fail(who + "a reduction of the spectrogram (tensor 0) is not supported");
+            if (t.view) return fail(who + "a reduction of a Split / Slice output that only Concat nodes read is not supported");
+            if (t.c % 4) return fail(who + std::to_string(t.c) + " channels: a channel count that is not a multiple of 4 is not supported");
+            const uint32_t kh = rh ? t.h : 1, kw = rw ? t.w : 1;
+            if ((uint64_t)kh * kw == 1) return fail(who + "a window of one pixel (the reduced axes have extent 1): nothing to reduce");
+            if ((uint64_t)kh * kw > (1u << 16)) return fail(who + "a window of more than 65 536 pixels");
+            const uint32_t oh = t.h / kh, ow = t.w / kw;
+            const uint32_t li = new_layer(OP_REDUCE, t.idx, NO_TENSOR, t.c, t.c, kh, kw, 1, 1, 0, 0, t.h, t.w, oh, ow, 0, 0, 0);
+            layers[li - 1].reserved = mode;
+            T y{li, t.c, oh, ow};
+            // (the pair over both axes, or one that finishes the image, is [N, C, 1, 1]: no rank-3 tensor of one pixel is kept)
+            if (keep == 0 && !t.r3 && !(rh && rw) && !(mode == REDUCE_MAXMEAN && (uint64_t)oh * ow == 1)) y.r3 = rh ? 2 : 1;
+            if (keep == 1 && t.r3 && !(mode == REDUCE_MAXMEAN && (uint64_t)oh * ow == 1)) y.r3 = t.r3;
+            tmap[out] = y;
+            if ((uint64_t)oh * ow == 1) { emb_tensor = li; emb_dim = t.c; }
+            if (!flush_patterns(out)) return false;
+        } else if (op == "GlobalAveragePool") {
             T t;
             if (!find(n.in[0], t)) return fail(op + ": input not on the path");
-            if (op == "ReduceMean") {
-                std::vector<int64_t> axes;
-                if (const auto *ax = n.ints("axes")) axes = *ax;
-                else if (n.in.size() > 1) { auto it = g.init.find(n.in[1]); if (it != g.init.end()) axes = it->second.il; }
-                if (axes.size() != 2) return fail("ReduceMean over axes other than H, W");
-                int64_t a0 = ((axes[0] % 4) + 4) % 4, a1 = ((axes[1] % 4) + 4) % 4;
-                if (!((a0 == 2 && a1 == 3) || (a0 == 3 && a1 == 2))) return fail("ReduceMean over axes other than H, W");
-            }
             const uint32_t li = new_layer(OP_GAP, t.idx, NO_TENSOR, t.c, t.c, t.h, t.w, 1, 1, 0, 0, t.h, t.w, 1, 1, 0, 0, 0);
             tmap[n.out[0]] = T{li, t.c, 1, 1};
             emb_tensor = li; emb_dim = t.c;
@@ -1106,10 +1224,11 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             if (!flush_patterns(sh.out)) return false;
         } else if (op == "Reshape" && shuffle_computed.count(i)) {
             return fail("Reshape '" + n.name + "': a channel shuffle whose shape is computed (Shape -> Gather -> Concat) is not read: the shapes must be constants");
-        } else if (op == "Flatten" || op == "Reshape" || op == "Squeeze" || op == "Identity" || op == "Dropout") {
+        } else if (op == "Flatten" || op == "Reshape" || op == "Squeeze" || op == "Unsqueeze" || op == "Identity" || op == "Dropout") {
             T t;
             if (!find(n.in[0], t)) return fail(op + ": input not on the path");
             if ((uint64_t)t.h * t.w != 1) return fail(op + " of a " + std::to_string(t.h) + "x" + std::to_string(t.w) + " map (only after the global pool)");
+            t.r3 = 0;
             tmap[n.out[0]] = t;
         } else if (op == "Gemm" || op == "MatMul") {
             T t;

@@ -43,6 +43,10 @@ OP_CONCAT = 10  # channel Concat / Split / Slice / shuffle: a copy, NHWC f32, no
 OP_LNORM = 12   # LayerNorm over the channels of an NHWC tensor, pixel by pixel (biased variance): cin == cout == C (a multiple of 4), kernel /
                 # stride 1, pads 0, the image kept; w_off -> gamma[C], b_off -> beta[C]; no activation, residual or dilation; Layer.reserved
                 # is the bit pattern of eps as an f32 (lnorm_eps_bits / lnorm_eps), finite and > 0.  (11 is never used, like 9.)
+OP_REDUCE = 13  # ReduceMax / ReduceMean over H, over W or over both of an NHWC tensor, GlobalMaxPool, and max + mean of one window (the PANNs
+                # head): spelled like OP_GAP -- cin == cout == C (a multiple of 4), kh = in_h or 1, kw = in_w or 1, stride 1, pads 0, out = in / window;
+                # Layer.reserved is the mode.  The mean over both axes stays OP_GAP and a 1x1 window is refused: one spelling each.
+REDUCE_MAX, REDUCE_MEAN, REDUCE_MAXMEAN = 0, 1, 2  # MAXMEAN: max + mean of the same window, as one value
 POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2  # AVG: mean over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 # OP_CONV (NHWC), OP_PWCONV, OP_DENSE: Layer.reserved is where `act` stands relative to the residual -- 0: act(conv + b) + R (every
 # file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block
@@ -120,7 +124,7 @@ class Layer:
     # OP_POOL: the pool mode (POOL_MAX / POOL_AVG / POOL_AVG_PAD).  OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the position of `act`
     # relative to the residual -- 0: act(conv + b) + R; RES_ACT_AFTER: act(conv + b + R), which needs a residual and an activation.
     # OP_GCONV: the group count.  OP_CONCAT: the channel shuffle's group count (0, 1: no shuffle).  OP_LNORM: the bits of eps as an
-    # f32.  0 for every other op.
+    # f32.  OP_REDUCE: the mode (REDUCE_MAX / REDUCE_MEAN / REDUCE_MAXMEAN).  0 for every other op.
     reserved: int = 0
     # dilation per axis (OP_CONV on an NHWC tensor and OP_DWCONV only, 1 .. MAX_DILATION, 1 on an axis with one tap): tap (dy, dx) reads
     # pixel (oy sh - pad_t + dy dil_h, ox sw - pad_l + dx dil_w).  Written as dil - 1.

@@ -170,6 +170,14 @@ class _Builder:
         L = mf.Layer(mf.OP_POOL, mf.ACT_NONE, tin, mf.NO_TENSOR, c, c, kh, kw, sh, sw, pt, pl, h, w, oh, ow, reserved=mode)
         return self.add(L), oh, ow
 
+    def reduce(self, tin, h, w, c, mode, over_h=True, over_w=True):
+        """max / mean / max + mean (mode: mf.REDUCE_MAX / REDUCE_MEAN / REDUCE_MAXMEAN) over the rows, the columns or both of an h x w image
+        (mf.OP_REDUCE; reserved = mode): the window is the whole axis or 1.  The mean over both axes is gap()'s record.  -> (tensor, h, w)"""
+        kh, kw = (h if over_h else 1), (w if over_w else 1)
+        assert kh * kw > 1 and not (mode == mf.REDUCE_MEAN and kh > 1 and kw > 1), "a 1x1 window, or the global average pool's record"
+        L = mf.Layer(mf.OP_REDUCE, mf.ACT_NONE, tin, mf.NO_TENSOR, c, c, kh, kw, 1, 1, 0, 0, h, w, h // kh, w // kw, reserved=mode)
+        return self.add(L), h // kh, w // kw
+
     def lnorm(self, tin, h, w, c, eps=1e-6):
         """LayerNorm over the channels, pixel by pixel (mf.OP_LNORM; reserved = the bits of eps): gamma around 1 with a few negative and
         zero entries, beta around 0"""
@@ -227,6 +235,9 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     'birdnet_v30_sized' (the same contract on a trunk of the published file's size, every stage MBConv),
     'birdnet_v30_v2l' (the same contract on EfficientNetV2-L's stage plan: three Fused-MBConv stages, 132 M parameters),
     'cnn_pool' (a conv + pool backbone in the VGG / PANNs style on the v2.4 front-end, for timing the pool layers: _build_cnn_pool).
+    'cnn14_audio' (the cnn_pool body under the head of the PANNs audio CNNs -- the mean over the frequency axis, max + mean over time
+    (mf.OP_REDUCE), a dense layer with ReLU, the dense classes, a sigmoid --, for timing the reduce layers: _build_cnn14_audio).
+    'reduce_plan' (plan = random_reduce_plan(seed)) builds that plan's small stack and reduce head on the mini front end: _build_reduce_plan.
     'pool_plan' (plan = random_pool_plan(seed)) builds that plan's stack of convolutions, MBConv blocks and pools: _build_pool_plan.
     'resnet_plan' (plan = random_resnet_plan(seed)) builds that plan's ResNet blocks -- act(conv + shortcut), Layer.reserved =
     RES_ACT_AFTER -- on the same mini front-end: _build_resnet_plan.  'resnet18_audio' (a ResNet-18 on the v2.4 front-end, for timing
@@ -251,6 +262,10 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     EfficientNet / MobileNet spellings of the same stack)."""
     if kind == "cnn_pool":
         return _build_cnn_pool(seed, n_classes)
+    if kind == "cnn14_audio":
+        return _build_cnn14_audio(seed, n_classes)
+    if kind == "reduce_plan":
+        return _build_reduce_plan(plan or random_reduce_plan(seed), seed)
     if kind == "pool_plan":
         return _build_pool_plan(plan, seed)
     if kind == "resnet_plan":
@@ -481,6 +496,30 @@ def _build_cnn_pool(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) ->
     ReLU convolutions and a 2x2 stride-2 pool -- widths 32 / 64 / 128 / 256, max pools behind stages 1 and 3, average pools behind
     2 and 4 --, a 1x1 head of 512 channels, the global pool and the dense layer.  Seeded weights: a model for TIMING the pool
     layers beside the convolutions they sit between, not for accuracy."""
+    b, branches, sr, n, t, h, w = _cnn_pool_body(seed)
+    t = emb = b.gap(t, h, w, 512)
+    ncls = n_classes or 6522
+    b.dense(t, 512, ncls, gain=1.5)
+    return _finish(b, branches, sr, n, ncls, 512, emb, mf.OUT_SIGMOID)
+
+
+def _build_cnn14_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) -> mf.Model:
+    """cnn_pool's body (a 3 x 16 image of 512 channels behind its 1x1 head) under the head of the PANNs audio CNNs (Kong et al. 2020,
+    CNN6 / CNN10 / CNN14): x = mean over the frequency axis; x = max over time + mean over time; x = relu(fc1(x)); y = sigmoid(fc2(x)).
+    Two mf.OP_REDUCE records -- MEAN over H, MAXMEAN over W --, the second the embedding.  Seeded weights: a model for TIMING, not for
+    accuracy."""
+    b, branches, sr, n, t, h, w = _cnn_pool_body(seed)
+    t, h, w = b.reduce(t, h, w, 512, mf.REDUCE_MEAN, over_h=True, over_w=False)
+    t, h, w = b.reduce(t, h, w, 512, mf.REDUCE_MAXMEAN, over_h=False, over_w=True)
+    emb = t
+    t = b.dense(t, 512, 512, act=mf.ACT_RELU, logits=False)
+    ncls = n_classes or 6522
+    b.dense(t, 512, ncls, gain=1.5)
+    return _finish(b, branches, sr, n, ncls, 512, emb, mf.OUT_SIGMOID)
+
+
+def _cnn_pool_body(seed: int):
+    """cnn_pool up to its 1x1 head of 512 channels -> (builder, branches, sample rate, samples, tensor, h, w)"""
     b = _Builder(np.random.default_rng(seed))
     sr, n = 48000, 144000
     branches = [mf.Branch(2048, 278, 96, 511, 0.0, 3000.0, 1.23), mf.Branch(1024, 280, 96, 511, 500.0, 15000.0, 1.23)]
@@ -495,10 +534,59 @@ def _build_cnn_pool(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) ->
         t, h, w = b.pool(t, h, w, width, 2, 2, 2, 2, mf.POOL_MAX if si % 2 == 0 else mf.POOL_AVG, "valid")
         c = width
     t = b.pwconv(t, h, w, c, 512, mf.ACT_RELU)
-    t = emb = b.gap(t, h, w, 512)
-    ncls = n_classes or 6522
-    b.dense(t, 512, ncls, gain=1.5)
-    return _finish(b, branches, sr, n, ncls, 512, emb, mf.OUT_SIGMOID)
+    return b, branches, sr, n, t, h, w
+
+
+REDUCE_HEADS = ("panns", "global_max", "mean_then_max", "maxmean_both")
+
+
+def random_reduce_plan(seed: int) -> dict:
+    """A small seeded stack under a reduce head on the mini front end (one 32-mel branch, 115 frames of a quarter-second segment): a 3x3
+    stem, a 3x3 stride-2 convolution, a 2x2 pool (an 8 x 29 image), then the head -- its form ('panns': the mean over one axis, then max +
+    mean over the other; 'global_max': the max over both; 'mean_then_max': the mean over one axis, then the max over the other;
+    'maxmean_both': max + mean over both), which axis goes first ('h': the frequency axis, as PANNs; 'w') and the keepdims its .onnx file
+    is written with -- a dense layer with ReLU and the dense classes.  Seeds 0 .. 3 take the four forms in turn.  Feed to
+    build_model("reduce_plan", plan=...)."""
+    rng = np.random.default_rng(0x9e00 + seed)
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+    return {"stem": pick((8, 16)), "width": pick((12, 20, 32, 68)), "pool": int(pick((mf.POOL_MAX, mf.POOL_AVG))), "head": REDUCE_HEADS[seed % 4],
+            "first": pick(("h", "w")), "keepdims": int(rng.integers(0, 2)), "hidden": int(rng.integers(3, 9)) * 8, "classes": int(rng.integers(20, 61)),
+            "act": int(pick((mf.ACT_RELU, mf.ACT_RELU6, mf.ACT_GELU_ERF))), "out_act": int(pick((mf.OUT_SIGMOID, mf.OUT_SOFTMAX)))}
+
+
+def _build_reduce_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
+    """random_reduce_plan's stack on the mini front-end of one branch (512-sample frames at hop 100: 32 mels x 115 frames).  The model
+    carries the spelling of its .onnx file in Model.reduce_spelling (convert.graph_from_model spell_reduce: 'keep' or '')."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 12000
+    br = mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23)
+    br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+    br.out_scale, br.out_shift = 0.8, -0.4
+    act, c = int(plan["act"]), int(plan["width"])
+    t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, int(plan["stem"]), 3, 1, act, in_layout=1)
+    t, h, w = b.conv(t, h, w, int(plan["stem"]), c, 3, 2, act)
+    t, h, w = b.pool(t, h, w, c, 2, 2, 2, 2, int(plan["pool"]), "valid")
+    first_h = plan["first"] == "h"
+    head = plan["head"]
+    if head == "panns":
+        t, h, w = b.reduce(t, h, w, c, mf.REDUCE_MEAN, over_h=first_h, over_w=not first_h)
+        t, h, w = b.reduce(t, h, w, c, mf.REDUCE_MAXMEAN, over_h=not first_h, over_w=first_h)
+    elif head == "global_max":
+        t, h, w = b.reduce(t, h, w, c, mf.REDUCE_MAX)
+    elif head == "mean_then_max":
+        t, h, w = b.reduce(t, h, w, c, mf.REDUCE_MEAN, over_h=first_h, over_w=not first_h)
+        t, h, w = b.reduce(t, h, w, c, mf.REDUCE_MAX, over_h=not first_h, over_w=first_h)
+    elif head == "maxmean_both":
+        t, h, w = b.reduce(t, h, w, c, mf.REDUCE_MAXMEAN)
+    else:
+        raise ValueError(head)
+    emb = t
+    hidden, ncls = int(plan["hidden"]), int(plan["classes"])
+    t = b.dense(t, c, hidden, act=mf.ACT_RELU, logits=False)
+    b.dense(t, hidden, ncls, gain=1.5)
+    m = _finish(b, [br], sr, n, ncls, c, emb, int(plan["out_act"]))
+    m.reduce_spelling = "keep" if plan["keepdims"] else ""
+    return m
 
 
 def random_pool_plan(seed: int) -> dict:
