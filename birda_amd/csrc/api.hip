@@ -103,9 +103,8 @@ void ctx_mark(bh_batch_context *ctx, int stage, int layer = -1) {
     if (!ctx->profiling) return;
     hipEvent_t e;
     // timing-only events: without the system-scope fence (an L2 write-back + invalidate between every two kernels, which the
-    // un-profiled pipeline never sees; BIRDA_HIP_EVENT_FENCE=1 restores the default events: A/B aid)
-    static const bool fence = BH_XENV("BIRDA_HIP_EVENT_FENCE") && BH_XENV("BIRDA_HIP_EVENT_FENCE")[0] == '1';
-    if (hipEventCreateWithFlags(&e, fence ? hipEventDefault : hipEventDisableSystemFence) != hipSuccess) return;
+    // un-profiled pipeline never sees)
+    if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return;
     (void)hipEventRecord(e, ctx->stream);
     ctx->ev.push_back(e);
     ctx->ev_stage.push_back(stage);
@@ -149,7 +148,6 @@ int ctx_create(bh_classifier *c, size_t max_batch, bool keep, bh_batch_context *
     //  16 sub-plans fit, beyond that lanes_begin falls back to one stream and counts it: bh_batch_context_lane_fallbacks)
     ctx->arena_cap = ctx->arena_floats + 16 * 64 * (m.layers.size() + 1);
     HIPCHK(hipMalloc((void **)&ctx->d_arena, ctx->arena_cap * sizeof(float)));
-    if (const char *e = BH_XENV("BIRDA_HIP_NLANES")) ctx->n_lanes = std::max(1, std::min((int)bh_batch_context::MAX_LANES, atoi(e)));
     ctx->lane_stream[0] = ctx->stream;   // (the other lanes' streams are created when a slice first needs them: lanes_begin)
     HIPCHK(hipEventCreateWithFlags(&ctx->fork_ev, hipEventDisableTiming));
     HIPCHK(hipMalloc((void **)&ctx->d_logits, max_batch * (size_t)m.h.n_classes * sizeof(float)));
@@ -175,9 +173,7 @@ struct SliceLane { hipStream_t s; float *arena; const size_t *t_off; size_t seg0
 // chunks, 4 deep from 12, 8 deep from 32 (fused blocks without a gate: pass A of a squeeze-excite block has no project sums to split)
 constexpr size_t kLowLatencyMaxSegments = 32;
 int mb_ksplit_of(const bh::MbDesc &d) {
-    static const int cap = [] { const char *e = BH_XENV("BIRDA_HIP_KSPLIT_MAX"); return e ? atoi(e) : 8; }();     // (tuning aid of the EXPERIMENTS build)
-    const int k = (d.se || d.Cout % 4) ? 1 : d.nchunks >= 32 ? 8 : d.nchunks >= 12 ? 4 : d.nchunks >= 6 ? 2 : 1;
-    return std::min(k, std::max(cap, 1));
+    return (d.se || d.Cout % 4) ? 1 : d.nchunks >= 32 ? 8 : d.nchunks >= 12 ? 4 : d.nchunks >= 6 ? 2 : 1;
 }
 // What the steps of one slice share.  T(t): where tensor t of a step's lists lives -- its planned bytes of the arena, and for the
 // last layer's output the caller's logits buffer.
@@ -338,9 +334,8 @@ int SliceRun::fused_se(const Step &st) const {
     // (round 6: beyond 576 channels two launches of sixteen-segment workgroups -- the pooled rows x W1 split over channel
     //  slices, then hidden x W2 -- instead of pool + two GEMMs of a handful of tiles: kernels_conv.hip se_hidden_kernel)
     // (one selection for whole launches and for the groups below: a segment's bits do not depend on how its launch is cut)
-    static const bool gate1 = [] { const char *e = BH_XENV("BIRDA_HIP_SE_GATE1"); return e && e[0] == '1'; }();
     auto launch_gate = [&](const float *part, int tiles, int P, float *pooled, float *hidden, float *gate, size_t ns) {
-        const int form = gate1 ? 0 : se_gate_form(d.Cexp, (int)G1.cout);
+        const int form = se_gate_form(d.Cexp, (int)G1.cout);
         if (form == 1)
             bh::launch_se_gate16(part, tiles, P, pooled, W1.w, c->d_blob + G1.b_off, W1.ldw, (int)G1.act,
                                  W2.w, c->d_blob + G2.b_off, W2.ldw, (int)G2.act, gate, (int)ns, d.Cexp, (int)G1.cout, s);
@@ -356,9 +351,8 @@ int SliceRun::fused_se(const Step &st) const {
     // (round 6: the same for the STEM block -- its input, the planar spectrogram, is a tenth of its D -- was built (the stem
     //  instantiations take MbDesc::gate) and measured on the Perch-sized plan: 38.75 -> 38.45 k segments/s, three alternations
     //  on one box at one clock, profiles/r6_n_stem_recompute.txt: the sums-only pass costs more than D's round trip saves.
-    //  Not taken; BIRDA_HIP_SE_STEM_RECOMPUTE=1 in the EXPERIMENTS build.)
-    static const bool stem_recompute = [] { const char *e = BH_XENV("BIRDA_HIP_SE_STEM_RECOMPUTE"); return e && e[0] == '1'; }();
-    const bool recompute = d.noexp != 0 || (d.stem != 0 && stem_recompute);
+    //  Not taken: the forward pass keeps a stem block's D.)
+    const bool recompute = d.noexp != 0;
     // (D blocked for the f16 gated GEMMs: kernels.hpp MbDesc::dblk)
     const bool dblk = !recompute && WP.planes && bh::pw_gemm16_gated_wants_blocked(d.Cexp, d.Cout, d.Ho * d.Wo);
     // Round 6 (VERDICT r5 next #3a): a block whose D is large -- the early stages: 1.5-2.3 MB a segment -- runs its three
@@ -667,14 +661,12 @@ unsigned copy_threads() {
 //         has arrived, so it must be small: equal quarters (12.9 ms against 14.8 for the growing split).
 // Boundaries are multiples of `align` segments.
 bool lanes_possible(const bh_batch_context *ctx) {
-    static const bool off = BH_XENV("BIRDA_HIP_LANES") && BH_XENV("BIRDA_HIP_LANES")[0] == '0';
-    return !off && !ctx->profiling && !ctx->keep_tensors && ctx->n_lanes >= 2;
+    return !ctx->profiling && !ctx->keep_tensors && ctx->n_lanes >= 2;
 }
 std::vector<size_t> sub_slice_cuts(const bh_classifier *c, size_t nb, size_t align, bool single, size_t bytes_per_segment, bool lanes = false,
                                    uint32_t ctx_forced = 0) {
     std::vector<size_t> cuts;
-    static const int env_forced = BH_XENV("BIRDA_HIP_SUBSLICES") ? atoi(BH_XENV("BIRDA_HIP_SUBSLICES")) : 0;   // (A/B aid: n equal sub-slices)
-    const int forced = ctx_forced ? (int)ctx_forced : env_forced;
+    const int forced = (int)ctx_forced;   // (bh_batch_context_set_sub_slices: n equal sub-slices; 0: the automatic split)
     auto up = [&](size_t v) { return std::min(nb, (v + align - 1) / align * align); };
     if (forced == 1) {
     } else if (!single && forced > 1 && nb >= 256) {
@@ -685,13 +677,12 @@ std::vector<size_t> sub_slice_cuts(const bh_classifier *c, size_t nb, size_t ali
         // a first sub-slice of 64 segments where the upload is the shorter side (PCM16: 5.2 against 6.3 us per segment): the device
         // starts after 0.33 ms instead of 0.65 and the short forward's floor runs under the next sub-slices (pinned PCM16
         // 111-114 k -> 115-117 k segments/s; 32 or 96 segments: no gain; pinned f32 segments, upload-bound, lose 2 % to it)
-        static const int first_env = BH_XENV("BIRDA_HIP_FIRST_SUBSLICE") ? atoi(BH_XENV("BIRDA_HIP_FIRST_SUBSLICE")) : -1;   // (A/B aid)
         const double upload_us = (double)bytes_per_segment / 55e3;
         const double compute_us = (2.0 * (double)c->model.macs_per_segment() + (double)c->mel_flops) / 130e6;
-        const size_t first = first_env >= 0 ? (size_t)first_env : (upload_us < compute_us ? 64 : 0);
+        const size_t first = upload_us < compute_us ? 64 : 0;
         size_t v0 = sub;
         constexpr double growth = 1.5;
-        if (upload_us < compute_us && nb >= 512 && first_env < 0) {
+        if (upload_us < compute_us && nb >= 512) {
             // the upload is the SHORTER side (PCM16: 5.2 against 6.5 us per segment): after the first sub-slices the data is always
             // there, and what a sub-slice costs beyond its segments (the launch chain, the late blocks' half-empty grids) is paid
             // per sub-slice -- so the sizes GROW, 64, 96, 160, 224, 320 ..., each next one arriving about when the one before
@@ -713,7 +704,7 @@ std::vector<size_t> sub_slice_cuts(const bh_classifier *c, size_t nb, size_t ali
         }
         // the upload is the LONGER side (f32 segments): what is left when the last byte has arrived is the last sub-slice's forward,
         // so that one is kept short -- 64 segments (a forward of 64 lasts 0.9 ms, one of 128 1.2: tools/gpu_latency.py)
-        if (upload_us >= compute_us && first_env < 0) {
+        if (upload_us >= compute_us) {
             const size_t last = cuts.empty() ? 0 : cuts.back();
             const size_t tail = (nb - 64) / align * align;
             if (tail > last + 32 && nb - tail >= 32) cuts.push_back(tail);
@@ -1574,16 +1565,6 @@ int bh_classifier_frontend_kernel(const bh_classifier *c, char *out, size_t cap)
     return copy_name(buf, out, cap);
 }
 
-int bh_debug_mb_stamps(bh_classifier *c, uint64_t *out, size_t cap) {
-    if (!c || !c->d_stamps) return 0;
-    const size_t n = std::min(cap, c->mb.size() * 8);
-    (void)hipSetDevice(c->device);
-    (void)hipDeviceSynchronize();
-    if (out && hipMemcpy(out, c->d_stamps, n * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    (void)hipMemset(c->d_stamps, 0, c->mb.size() * 8 * sizeof(unsigned long long));
-    return (int)(n / 8);
-}
-
 int bh_batch_context_set_profiling(bh_batch_context *ctx, int enabled) try {
     if (!ctx) return fail(BH_ERR_INVALID, "set_profiling: null context");
     if (enabled) {   // a new measurement: drop the events of the previous one (after they have fired)
@@ -2064,7 +2045,7 @@ int bh_resample_device(bh_classifier *c, bh_batch_context *ctx, const float *d_i
     const bh::ResamplePlan *pl = bh::resample_plan(from_rate, to_rate, &err);
     if (!pl) return fail(BH_ERR_UNSUPPORTED, "%s (%u -> %u Hz)", err ? err : "resampler", from_rate, to_rate);
     bh::launch_resample(*pl, d_in, in_stride, (int)src_len, d_out, out_stride, (int)out_len, (int)n_seg,
-                        c->precision != 0 && !(BH_XENV("BIRDA_HIP_RESAMPLE_F32") && BH_XENV("BIRDA_HIP_RESAMPLE_F32")[0] == '1'), ctx->stream);
+                        c->precision != 0, ctx->stream);
     HIPCHK(hipGetLastError());
     return BH_OK;
 } catch (...) { return on_exception(); }

@@ -15,7 +15,7 @@ bh_classifier::~bh_classifier() {
     for (auto &ss : stream_sets)
         for (auto &st : ss.s) if (st) (void)hipStreamDestroy(st);
     for (float *d : d_owned) (void)hipFree(d);
-    (void)hipFree(d_stamps); (void)hipFree(d_class_score); (void)hipFree(d_species_keep); (void)hipFree(d_bsg);
+    (void)hipFree(d_class_score); (void)hipFree(d_species_keep); (void)hipFree(d_bsg);
 }
 
 namespace {
@@ -292,14 +292,7 @@ int bh_classifier_create(const bh_config *cfg, bh_classifier **out) try {
     c->sched = build_schedule(*c, true, true);
     c->sched_layers = build_schedule(*c, false, false);
     c->sched_keep_fused = build_schedule(*c, true, false);
-    // Phase 6: the experiment switches (A/B aids; BH_XENV names exist in the EXPERIMENTS build only)
-    if (const char *e = BH_XENV("BIRDA_HIP_MB_NARROW_MAX")) c->narrow_max_workgroups = atoi(e);   // (A/B aid: 0 = never)
     if (const char *e = getenv("BIRDA_HIP_SE_GROUP_MB")) c->se_group_bytes = (size_t)atol(e) << 20;   // (MB of D per group of segments; 0: whole launches)
-    if (const char *st = BH_XENV("BIRDA_HIP_MB_STAMPS"); st && st[0] == '1' && !c->mb.empty()) {
-        HIPCHK(hipMalloc((void **)&c->d_stamps, c->mb.size() * 8 * sizeof(unsigned long long)));
-        HIPCHK(hipMemset(c->d_stamps, 0, c->mb.size() * 8 * sizeof(unsigned long long)));
-        for (size_t i = 0; i < c->mb.size(); i++) { c->mb[i].stamps = c->d_stamps + i * 8; c->mb_small[i].stamps = c->mb[i].stamps; c->mb_narrow[i].stamps = c->mb[i].stamps; }
-    }
     *out = c.release();
     return BH_OK;
 } catch (...) { return on_exception(); }

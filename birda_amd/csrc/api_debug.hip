@@ -137,7 +137,7 @@ int mb_debug_plan(const int32_t *shape, int force_cfg, int variant, bh::MbDesc &
     const int nfam = bh::mb_config_families(), nbase = bh::mb_config_count() / nfam;   // (the activation copies of one list: kernels_mbconv.hip)
     for (int k = 0; rec && force_cfg >= 0 && force_cfg < nbase && k < nfam; k++) {   // the row's own facts, whatever becomes of the shape
         int th = 0, has_se = 0, act = -1;
-        if (bh::mb_config_row(force_cfg + k * nbase, &th, &has_se, nullptr, &act) && act == shape[11]) { rec[6] = has_se; rec[7] = th; }
+        if (bh::mb_config_row(force_cfg + k * nbase, &th, &has_se, &act) && act == shape[11]) { rec[6] = has_se; rec[7] = th; }
     }
     if (!mb_desc_of_shape(shape, d)) return fail(BH_ERR_INVALID, "debug_mbconv: not a block's shape");
     bh::MbDesc planned = d;
@@ -153,9 +153,9 @@ int mb_debug_plan(const int32_t *shape, int force_cfg, int variant, bh::MbDesc &
     if (variant == 2 && !has_narrow) return fail(BH_ERR_UNSUPPORTED, "debug_mbconv: the planned entry has no narrow-tile twin");
     d = variant == 1 ? tw : variant == 2 ? nw : planned;
     if (rec) {
-        int th = 0, has_se = 0, persist = 0;
-        bh::mb_config_row(d.cfg, &th, &has_se, &persist, nullptr);
-        rec[20] = persist;
+        int th = 0, has_se = 0;
+        bh::mb_config_row(d.cfg, &th, &has_se, nullptr);
+        rec[20] = 0;   // (the PERSIST template argument: always 0, the record keeps its place)
         rec[0] = d.cfg; rec[1] = d.TH; rec[2] = d.tiles_y; rec[3] = d.tiles_x; rec[4] = d.nchunks; rec[5] = d.KG; rec[6] = has_se; rec[7] = th;
         rec[8] = d.S; rec[9] = d.CE; rec[10] = d.NTOP; rec[11] = (int32_t)d.lds_bytes; rec[12] = mb_ksplit_of(d); rec[13] = has_twin;
         rec[14] = has_narrow; rec[15] = sums; rec[16] = d.IH; rec[17] = d.IW; rec[18] = d.mpad_max;
@@ -622,9 +622,7 @@ int bh_debug_mbconv_block(int device, const int32_t *shape, size_t n_seg, const 
     if (x_fl > (size_t)INT32_MAX || y_fl > (size_t)INT32_MAX || d_fl > (size_t)INT32_MAX)
         return fail(BH_ERR_INVALID, "debug_mbconv_block: tensors past 2^31 elements");
     if (d.dblk && (n_seg * P) % 16) return fail(BH_ERR_INVALID, "debug_mbconv_block: blocked D needs whole row tiles");
-    int persist = 0;
-    bh::mb_config_row(d.cfg, nullptr, nullptr, &persist, nullptr);
-    const int ksp = (ksplit && !persist) ? mb_ksplit_of(d) : 1;   // (the persistent instantiations have no channel split: mbconv_kernel.hpp)
+    const int ksp = ksplit ? mb_ksplit_of(d) : 1;
     if (record) record[12] = ksp;
     HIPCHK(hipSetDevice(device));
     MbHostWeights hw;
@@ -636,7 +634,6 @@ int bh_debug_mbconv_block(int device, const int32_t *shape, size_t n_seg, const 
     d.Y = d.se ? nullptr : h.out(y_fl, "Y", Y);
     d.Dout = d.se && D ? h.out(d_fl, "D", D) : nullptr;
     d.pool_part = d.se ? h.out(pp_fl, "pool_part", pool_part) : nullptr;
-    d.stamps = nullptr; d.dbg = 0;
     d.ksplit = ksp > 1 ? ksp : 0; d.partial = ksp > 1 ? h.out((size_t)ksp * y_fl, "partial", nullptr) : nullptr;
     if (!h.ok) return h.no_memory();
     bh::launch_mbconv(d, (int)n_seg, nullptr);

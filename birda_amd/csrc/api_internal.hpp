@@ -155,7 +155,6 @@ struct bh_classifier {
     bh_classifier *fb = nullptr;
     std::mutex fb_mu;
     std::atomic<unsigned long long> fallback_segments{0};
-    unsigned long long *d_stamps = nullptr;  // BIRDA_HIP_MB_STAMPS=1: [mb.size()][8] phase counters
     uint64_t mel_flops = 0;
     bh::TopkFilter filter;                   // range filter / species list applied to the kept top-k (device tables below)
     float *d_class_score = nullptr;

@@ -356,7 +356,6 @@ bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, s
         d.Ho = (int)D.out_h; d.Wo = (int)D.out_w; d.pad_t = (int)D.pad_t; d.pad_l = (int)D.pad_l;
         d.KS = (int)D.kh; d.ST = (int)D.sh;
         d.act_e = (int)D.act; d.act_d = (int)D.act; d.act_p = (int)P.act;   // (no expand activation: the kernel template is keyed on one)
-        if (const char *dbg = BH_XENV("BIRDA_HIP_MB_DBG")) d.dbg = atoi(dbg);
         d.prec = precision;
         return plan_in_some_precision(d, force_cfg);
     }
@@ -378,11 +377,9 @@ bool describe_fused_block(const bh::Model &m, const std::vector<int> &readers, s
     d.Ho = (int)D.out_h; d.Wo = (int)D.out_w; d.pad_t = (int)D.pad_t; d.pad_l = (int)D.pad_l;
     d.KS = (int)D.kh; d.ST = (int)D.sh;
     d.act_e = (int)E.act; d.act_d = (int)D.act; d.act_p = (int)P.act;
-    if (const char *dbg = BH_XENV("BIRDA_HIP_MB_DBG")) d.dbg = atoi(dbg);
     d.prec = precision;
-    // The split-f16 MFMA and the f32 MFMA agree to ~1e-7 of sum|a b|; measured (profiles/), f16x3 is
-    // the faster one on every block, the stem's 18-column im2col GEMM included.
-    if (d.stem && precision == 3 && BH_XENV("BIRDA_HIP_STEM_F32")) d.prec = 0;   // A/B aid
+    // (the split-f16 MFMA and the f32 MFMA agree to ~1e-7 of sum|a b|; measured (profiles/), f16x3 is the faster one on every
+    //  block, the stem's 18-column im2col GEMM included: the stem block takes the model's precision like every other)
     return plan_in_some_precision(d, force_cfg);
 }
 
@@ -515,7 +512,6 @@ void mb_prepare_weights(bh::MbDesc &d, const float *We, const float *be, const f
     // |se| <= 21 (weights 2^7 away from the usual He-normal sizes still land within 2^-8 of the top of the f16 range).
     d.e_fold = 0;
     d.gelu = bh::GeluScaled{0.f, 0.f, 0.f, 0.f, 0.f};
-#if BH_GELU_DEGREE == 5
     if (d.noexp) se = 0;
     if (h16 && d.act_e == bh::ACT_GELU_ERF && !d.noexp) {
         se = std::max(-21, std::min(21, se));
@@ -524,15 +520,7 @@ void mb_prepare_weights(bh::MbDesc &d, const float *We, const float *be, const f
         for (int k = 1; k <= 5; k++) gc[k - 1] = std::ldexp(bh::kGeluCoef[k - 1], -k * se);
         d.gelu = bh::GeluScaled{gc[0], gc[1], gc[2], gc[3], gc[4]};
     }
-#endif
-    // ... and both GELUs of such a block leave TWICE their value (gelu2x_fast4, kernels.hpp): the expand one's factor joins the
-    // 2^-se in the depthwise taps (x2e), the depthwise one's raises the exponent the project accumulators live at (x2d).
-    int x2e = 0, x2d = 0;
-#if BH_GELU_DEGREE == 5 && BH_GELU_2X
-    if (h16 && d.act_d == bh::ACT_GELU_ERF) x2d = 1;
-    x2e = d.e_fold;
-#endif
-    const int spa = sp + x2d;   // the project accumulators hold 2^spa times the output
+    const int spa = sp;   // the project accumulators hold 2^spa times the output
     d.e_unscale = std::ldexp(1.0f, -se); d.p_scale = std::ldexp(1.0f, spa); d.p_unscale = std::ldexp(1.0f, -spa);
     const size_t frag = h16 ? 512 : 256, psteps = h16 ? (CE + 31) / 32 : NTE;
     const bool p16 = h16 && CE == 16;   // project GEMM as one 16-deep step: [column tile]{hi, lo}[64 lanes][4 halves]
@@ -605,7 +593,7 @@ void mb_prepare_weights(bh::MbDesc &d, const float *We, const float *be, const f
                 }
         for (int tap = 0; tap < KK; tap++)
             for (int n = 0; n < CE; n++)
-                wdf[ch * wd_fl + (size_t)tap * CE + n] = ch * CE + n < d.Cexp ? std::ldexp(Wd[(size_t)tap * d.Cexp + ch * CE + n], d.e_fold ? -se - x2e : 0) : 0.0f;
+                wdf[ch * wd_fl + (size_t)tap * CE + n] = ch * CE + n < d.Cexp ? std::ldexp(Wd[(size_t)tap * d.Cexp + ch * CE + n], d.e_fold ? -se : 0) : 0.0f;
         for (int n = 0; n < CE; n++) wdf[ch * wd_fl + (size_t)KK * CE + n] = ch * CE + n < d.Cexp ? bd[ch * CE + n] : 0.0f;
     }
     out.spa = spa;
@@ -648,15 +636,14 @@ int plan_fusion(bh_classifier *c) {
         {
             bh::MbDesc tw{};
             tw.cfg = -1;
-            static const bool no_twin = BH_XENV("BIRDA_HIP_MB_TWIN") && BH_XENV("BIRDA_HIP_MB_TWIN")[0] == '0';   // (A/B aid)
             // (squeeze-excite blocks keep ONE tiling -- the pooled sums are added tile by tile, and a segment's logits must not depend
             //  on the size of the launch it ran in -- except where the one-segment twin adds them in the very same order:
             //  mb_twin_sums_match, the 4x16 stages' whole-image tiles)
-            if (force_cfg < 0 && !no_twin && bh::mb_plan_twin(d, tw) && (!d.se || bh::mb_twin_sums_match(d, tw))) c->mb_small.push_back(tw);
+            if (force_cfg < 0 && bh::mb_plan_twin(d, tw) && (!d.se || bh::mb_twin_sums_match(d, tw))) c->mb_small.push_back(tw);
             else { tw.cfg = -1; c->mb_small.push_back(tw); }
             bh::MbDesc nw{};
             nw.cfg = -1;
-            if (!(force_cfg < 0 && !no_twin && !d.se && bh::mb_plan_narrow(d, nw))) nw.cfg = -1;
+            if (!(force_cfg < 0 && !d.se && bh::mb_plan_narrow(d, nw))) nw.cfg = -1;
             c->mb_narrow.push_back(nw);
             // (squeeze-excite: the slot of the per-tile channel sums holds whichever of the three tilings has the most tiles)
             size_t tiles = (size_t)d.tiles_x * d.tiles_y;

@@ -12,13 +12,8 @@
 // Environment switches.  The PRODUCT library reads a short, documented list (tests/test_abi_and_host.py holds the shipped .so to
 // it): BIRDA_HIP_PRECISION, BIRDA_HIP_COPY_THREADS, BIRDA_HOST_PIPELINE_DEPTH, BIRDA_INFERENCE_TIMEOUT, BIRDA_HIP_ROCTX,
 // BIRDA_HOST_TIMING, and the switches the parity tests drive it with (BIRDA_HIP_KEEP_TENSORS, _KEEP_FUSED, _MB_CFG, _MB_PREFER,
-// _FUSE, _MEL32, _MEL_F32, _HEAD_GAP).  Everything else -- ablation bits, A/B aids of experiments DESIGN.md reports -- goes through
-// BH_XENV and exists only in the EXPERIMENTS build (`make EXPERIMENTS=1`): in the product the name is not even in the binary.
-#ifdef BIRDA_HIP_EXPERIMENTS
-#define BH_XENV(name) getenv(name)
-#else
-#define BH_XENV(name) (static_cast<const char *>(nullptr))
-#endif
+// _FUSE, _MEL32, _MEL_F32, _HEAD_GAP).  There are no others: an alternative is measured as a second build of the library
+// (tools/ab.sh lib), not through a switch kept in this one.
 
 namespace bh {
 
@@ -74,26 +69,10 @@ constexpr int MAX_BRANCHES = 4;
 // is negative, so Q falls monotonically to -inf beyond the fit range, where Phi(-a) < 3e-10 rounds away.  Per value: 1 v_med3,
 // 3.5 packed FMAs and ONE transcendental (v_exp_f32, quarter rate).  Round 2 carried a degree-8 fit (1.7e-7, three more packed
 // FMAs per pair: 102 cycles per pair of values against ~80 now, tools/microbench/pk_fma_rate.hip); the logits sat 10x inside
-// their tolerance with it.  -DBH_GELU_DEGREE=8 restores it (A/B aid).
+// their tolerance with it (its code: in git up to commit 2004492).
 // Exp-free forms were priced and rejected: a polynomial for a Phi(-a) itself needs degree >= 15 on [0, 5.3] for the same
 // tolerance (Chebyshev interpolation: 4.4e-7 at degree 15, 1.0e-6 at 14) -- seven more packed FMAs per pair (39 cycles) plus
 // two clamps (11) to remove two v_exp_f32 (30).
-#ifndef BH_GELU_DEGREE
-#define BH_GELU_DEGREE 5
-#endif
-#if BH_GELU_DEGREE == 8
-#define BH_GELU_C1 -1.1511051654815674f
-#define BH_GELU_C2 -0.4592081904411316f
-#define BH_GELU_C3 -0.052496183663606644f
-#define BH_GELU_C4 0.007063428405672312f
-#define BH_GELU_C5 -0.00013694142398890108f
-#define BH_GELU_C6 -0.00018617883324623108f
-#define BH_GELU_C7 3.93775844713673e-05f
-#define BH_GELU_C8 -2.834923634509323e-06f
-#define BH_GELU_CTOP BH_GELU_C8
-#define BH_GELU_CNEXT BH_GELU_C7
-#define BH_GELU_MID(STEP) STEP(BH_GELU_C6) STEP(BH_GELU_C5) STEP(BH_GELU_C4) STEP(BH_GELU_C3) STEP(BH_GELU_C2) STEP(BH_GELU_C1)
-#else
 #define BH_GELU_C1 -1.1510556936264038f
 #define BH_GELU_C2 -0.45938199758529663f
 #define BH_GELU_C3 -0.05241312459111214f
@@ -102,7 +81,6 @@ constexpr int MAX_BRANCHES = 4;
 #define BH_GELU_CTOP BH_GELU_C5
 #define BH_GELU_CNEXT BH_GELU_C4
 #define BH_GELU_MID(STEP) STEP(BH_GELU_C3) STEP(BH_GELU_C2) STEP(BH_GELU_C1)
-#endif
 // max(v, 0) as ONE instruction (v_med3_f32 v, 0, 3e38: the finite bound keeps hipcc from rewriting it as a canonicalise + max pair): fmaxf() in IEEE mode first canonicalises its operand
 // (a second v_max).  NOT inline asm: the operand is usually an MFMA result, and hipcc places the wait
 // states an MFMA -> VALU read needs only in front of instructions it knows -- an inline-asm v_max_f32
@@ -192,64 +170,11 @@ __device__ __forceinline__ void gelu_erf_fast4_scaled(bh_f32x2 &v0, bh_f32x2 &v1
     v0 = __builtin_elementwise_fma(-a0, e0, m0);
     v1 = __builtin_elementwise_fma(-a1, e1, m1);
 }
-// -DBH_GELU_2X=1 builds the fused blocks with the "twice the GELU" form below instead of round 3's gelu_erf_fast4 (max(v, 0) form,
-// no factor two to fold).  Built, parity-green and MEASURED in round 4 -- and off: in isolation the packed 2x form is 12 % cheaper
-// per pair (22.5 against 25.6 ns, profiles/r4_d_valu_throughput.txt), inside the kernels it is 0.7 % SLOWER on every one of five
-// alternations on one box (fused blocks 5.861 -> 5.902 us per segment, profiles/r4_e_gelu2x_packed_ab.txt: tools/ab.sh lib with
-// the two builds of one tree); a scalar spelling with |v| as a free source modifier measured 31.2 ns per pair.
-#ifndef BH_GELU_2X
-#define BH_GELU_2X 0
-#endif
-#if BH_GELU_DEGREE == 5
-// TWICE the GELU, for the fused blocks of the f16 modes (round 4): 2 GELU(v) = (v + |v|) - |v| 2 Phi(-|v|), with
-// 2 Phi(-a) = exp2(Q(a) + 1) and Q(a) + 1 = a (c1 + a (c2 + ... + a c5)) -- the constant term is gone, so the Horner chain ends in a
-// multiply -- and v + |v| = 2 max(v, 0) replaces the v_med3_f32 (1.8 v_fma_f32 at the occupancy these kernels run at) and the
-// packed FMA that made |v| from it: |v| is a v_and_b32 per value.  Per PAIR of values: 2 v_and + 4 packed FMAs + 1 packed multiply +
-// 2 v_exp + 1 packed add + 1 packed FMA = 11 instructions, as many as gelu_erf_fast4's (2 v_med3 + 7 packed FMAs + 2 v_exp), with
-// the two dearest non-transcendental ones replaced by the two cheapest: 22.5 ns per pair and SIMD against 25.6
-// (tools/microbench/valu_throughput.hip at 4 waves per SIMD, profiles/r4_d_valu_throughput.txt).  A scalar spelling with |v| as
-// a free VOP3 source modifier (8 instructions per value instead of 5.5) was built first and measured SLOWER in isolation, 31.2 ns:
-// at this occupancy the instruction count, not the issue cycles, is what the SIMD charges for.
-// The factor two is a power of two and is folded on the host into the next linear stage (depthwise taps after the expand GELU,
-// the exponent the project accumulators live at after the depthwise GELU: api.hip plan_fusion).  Same polynomial, same rounding
-// points but the last: against float64 erfc the worst point is 0.63 of the activation's stated tolerance, as for gelu_erf_fast.
-// gc = c_k 2^(-k s) when the argument arrives multiplied by 2^s (gelu_erf_fast4_scaled's convention), c_k otherwise.
-__device__ __forceinline__ bh_f32x2 bh_abs2(bh_f32x2 v) {
-    bh_f32x2 a;
-    a[0] = __builtin_fabsf(v[0]); a[1] = __builtin_fabsf(v[1]);
-    return a;
-}
-__device__ __forceinline__ void gelu2x_fast4(bh_f32x2 &v0, bh_f32x2 &v1, const GeluScaled &gc) {
-    const bh_f32x2 a0 = bh_abs2(v0), a1 = bh_abs2(v1);
-    bh_f32x2 q0 = __builtin_elementwise_fma(a0, BH_PK(gc.c5), BH_PK(gc.c4));
-    bh_f32x2 q1 = __builtin_elementwise_fma(a1, BH_PK(gc.c5), BH_PK(gc.c4));
-#define BH_GELU_STEP(c)                                       \
-    q0 = __builtin_elementwise_fma(q0, a0, BH_PK(c));         \
-    q1 = __builtin_elementwise_fma(q1, a1, BH_PK(c));
-    BH_GELU_STEP(gc.c3) BH_GELU_STEP(gc.c2) BH_GELU_STEP(gc.c1)
-#undef BH_GELU_STEP
-    q0 = q0 * a0; q1 = q1 * a1;
-    bh_f32x2 e0, e1;
-    e0[0] = __builtin_amdgcn_exp2f(q0[0]); e0[1] = __builtin_amdgcn_exp2f(q0[1]);
-    e1[0] = __builtin_amdgcn_exp2f(q1[0]); e1[1] = __builtin_amdgcn_exp2f(q1[1]);
-    v0 = __builtin_elementwise_fma(-a0, e0, v0 + a0);
-    v1 = __builtin_elementwise_fma(-a1, e1, v1 + a1);
-}
-__device__ __forceinline__ bh_f32x2 gelu2x_fast2(bh_f32x2 v, const GeluScaled &gc) {
-    const bh_f32x2 a = bh_abs2(v);
-    bh_f32x2 q = __builtin_elementwise_fma(a, BH_PK(gc.c5), BH_PK(gc.c4));
-    q = __builtin_elementwise_fma(q, a, BH_PK(gc.c3));
-    q = __builtin_elementwise_fma(q, a, BH_PK(gc.c2));
-    q = __builtin_elementwise_fma(q, a, BH_PK(gc.c1));
-    q = q * a;
-    bh_f32x2 e;
-    e[0] = __builtin_amdgcn_exp2f(q[0]); e[1] = __builtin_amdgcn_exp2f(q[1]);
-    return __builtin_elementwise_fma(-a, e, v + a);
-}
-// the unscaled polynomial's coefficients, for the host (c_k 2^-ks is computed there) and for the unscaled 2 GELU
+// (A "twice the GELU" form for the fused blocks -- |v| by v_and, the factor two folded into the next linear stage -- was built and
+//  measured in round 4: 12 % cheaper per pair in isolation, 0.7 % SLOWER inside the kernels on every one of five alternations,
+//  profiles/r4_e_gelu2x_packed_ab.txt.  Its code: in git up to commit 2004492.)
+// the unscaled polynomial's coefficients, for the host (c_k 2^-ks is computed there)
 constexpr float kGeluCoef[5] = {BH_GELU_C1, BH_GELU_C2, BH_GELU_C3, BH_GELU_C4, BH_GELU_C5};
-constexpr GeluScaled kGeluUnscaled = {BH_GELU_C1, BH_GELU_C2, BH_GELU_C3, BH_GELU_C4, BH_GELU_C5};
-#endif
 
 // a + b as a plain v_add_f32 that hipcc cannot fuse with its neighbour.  Written as `fwd[j] + rev[-j]`
 // in C, the folded-frame sums of the split-f16 mel kernel are SLP-vectorised into
@@ -642,17 +567,11 @@ struct MbDesc {
     // spectrogram X [n][stem_c][stem_h][stem_w]; then H, W are the stem's OUTPUT size and
     // Cin = stem_k * stem_k * stem_c im2col columns (We rows in [kh][kw][cin] order)
     int stem, stem_c, stem_h, stem_w, stem_k, stem_s, stem_pt, stem_pl;
-    // diagnostic: 8 phase counters (wave-cycles: setup, dw-weight stage, P1, barrier, P2, barrier, P3,
-    // epilogue) or nullptr
-    unsigned long long *stamps;
-    int dbg;  // ablation bits for tuning (BIRDA_HIP_MB_DBG): 1 no GELU in P1, 2 no P2, 4 no P3, 8 no P1 MFMA,
-              // 16 no weight DMA, 32 no output store.  Results are wrong when non-zero.
     // filled by mb_plan()
     int cfg, CE, TH, S, tiles_y, tiles_x, IH, IW, KG, nchunks, NTOP, mpad_max;
     // floor(2^32 / tiles_x) + 1 and floor(2^32 / (tiles_x tiles_y)) + 1 (saturated at 2^32 - 1): the kernel decodes its tile index with
     // them instead of dividing (mbconv_kernel.hpp BH_MB_HOSTRCP)
     unsigned rcp_tiles_x, rcp_tiles_xy;
-    int ring;  // 1: the chunk weights go through rings of LDS buffers (We x 2, Wp x 3, Wd x 2), refilled a whole chunk ahead
     size_t lds_bytes;
     // Squeeze-excite blocks (round 5; EfficientNet's gate between the depthwise and the project convolution: pool -> 1x1 -> act ->
     // 1x1 -> sigmoid -> scale).  The gate needs the pool of the WHOLE depthwise output, so the block runs as pass A (se = 1: this
@@ -686,7 +605,7 @@ int mb_config_families();   // activation copies of the list (4: GELU, swish, Re
 int mb_config_name(int ci, char *out, size_t cap);
 // picks the instantiation (force_cfg >= 0: that entry or fail) and fills the derived fields
 bool mb_plan(MbDesc &d, int force_cfg);
-bool mb_config_row(int ci, int *th, int *has_se, int *persist, int *act);   // the row's own tile height; pass A instantiated and reachable (mb_try_th); PERSIST; ACT
+bool mb_config_row(int ci, int *th, int *has_se, int *act);   // the row's own tile height; pass A instantiated and reachable (mb_try_th); ACT
 int mb_plan_refusal(const MbDesc &d, int force_cfg, char *out, size_t cap);   // the planner's reason in words
 bool mb_plan_twin(const MbDesc &d, MbDesc &twin);
 bool mb_twin_sums_match(const MbDesc &d, const MbDesc &twin);   // squeeze-excite pass A: the twin's pooled sums are the block's, bit for bit   // one-segment-per-workgroup twin of a two-segment configuration (small launches)

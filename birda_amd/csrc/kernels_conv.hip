@@ -1030,8 +1030,7 @@ const char *launch_pw_gemm16(const float *A, const void *Wf, const float *bias, 
     const int n_xb = (n_tiles + 7) / 8, n_yb = (M + 127) / 128;
     dim3 grid((unsigned)(8 * ((n_xb + 7) / 8) * n_yb)), block(256);   // (one-dimensional: the kernel deals the blocks XCD by XCD)
     // (the LDS-staged kernel wherever a workgroup's 128 rows exist; a handful of rows stream as before: nothing to share)
-    static const bool stream_only = [] { const char *e = BH_XENV("BIRDA_HIP_GEMM_STREAM"); return e && e[0] == '1'; }();   // A/B aid
-    const bool staged = M >= 64 && !stream_only;
+    const bool staged = M >= 64;
     // (round 6: a launch of a few hundred rows has one or two row blocks, and with eight column tiles a workgroup the dense layers
     //  leave half the CUs idle and every workgroup alone on its CU, its step a bare HBM round trip + its MFMAs: four or two column
     //  tiles a workgroup while the grid stays under ~1.5 workgroups a CU.  The same products in the same order: the same bits.)

@@ -148,27 +148,14 @@ void launch_segment_pcm(const void *d_pcm_origin, int sample_format, size_t n_fr
 // B = folded frames from LDS.  The four partial sums meet in LDS (reusing xs); wave w then
 // owns frame tile w for the epilogue (square, power law, affine, flip, store).
 // ---------------------------------------------------------------------------------------
-// BH_MEL_PIPE = 1: a software-pipelined main loop for the split-f16 kernel (the frame fragments of step s + 1 built under the
-// MFMAs of step s, sched_group_barrier groups of {BH_MEL_GM MFMA, BH_MEL_GD LDS reads, BH_MEL_GV VALU}).  Round 4 measured it
-// because the kernel turned out to be ISSUE-bound, not bound by the operator stream from L2 (with every step reading the same
-// operator fragments, BIRDA_HIP_MEL_DBG=16 in the EXPERIMENTS build, it is as slow: 713.9 against 712.7 us per launch): 0.704 ->
-// 0.683 us per segment (-3 %, profiles/r4_l_mel_pipe.txt).  Not the product: two full operator sets, two sets of frame fragments
-// and 72 accumulator registers leave hipcc 3-26 registers short whatever the group sizes; it spills thread-invariant offsets and
-// reloads them behind `s_waitcnt vmcnt(0)` in the reduction (or, with other group sizes, inside the MFMA tail: 1.05 us).
-// BH_MEL_PIPE = 2 (round 6, THE PRODUCT): the same pipeline with the operator held half a step at a time -- one register set per half
-// of the mel tiles instead of two whole sets (48 registers instead of 96): 16 bytes of scratch instead of 148, and the loop that
-// round 4 could only measure ships: 0.706 -> 0.678 us per segment on a box in its slow mode, -4.2 % with the fused blocks of the same
-// runs as the clock reference (profiles/r6_g_mel_pipe_tuning.txt: group sizes 3 / 6 / 9 and the split of the fragment build over the
-// two phases within 1 % of each other; round 4's form on today's compiler 1.17 us -- it spills inside the MFMA tail).  0 restores the
-// plain loop (two operator sets, fragments built in front of their MFMAs).
-#ifndef BH_MEL_PIPE
-#define BH_MEL_PIPE 2
-#endif
-#ifndef BH_MEL_GM
-#define BH_MEL_GM 6
-#define BH_MEL_GD 6
-#define BH_MEL_GV 8
-#endif
+// The main loop of the split-f16 kernel is software-pipelined (the frame fragments of step s + 1 built under the MFMAs of step s,
+// sched_group_barrier groups of BH_MEL_GM MFMAs with their share of LDS reads and VALU) because the kernel is ISSUE-bound, not
+// bound by the operator stream from L2.  Round 4's first form (BH_MEL_PIPE = 1 in the measurements) held two full operator sets
+// and spilled: -3 % only (profiles/r4_l_mel_pipe.txt).  The form below (BH_MEL_PIPE = 2, round 6) holds the operator half a step
+// at a time -- one register set per half of the mel tiles instead of two whole sets (48 registers instead of 96), 16 bytes of
+// scratch instead of 148: 0.706 -> 0.678 us per segment against the plain loop (profiles/r6_g_mel_pipe_tuning.txt: group sizes
+// 3 / 6 / 9 and the split of the fragment build over the two phases within 1 % of each other).
+constexpr int BH_MEL_GM = 6;      // MFMAs per scheduling group of the pipelined loop
 constexpr int MEL_FT = 3;           // 16-frame tiles per block: 3 keeps the span at 60 KB -> two blocks per CU
 constexpr int MEL_TN = 16 * MEL_FT;
 
@@ -176,31 +163,23 @@ constexpr int MEL_TN = 16 * MEL_FT;
 // 64-KB span of the 128-mel one, whose workgroups have the whole register file
 
 // (128-mel front-ends need 98 KB of LDS for the reduction: one workgroup per CU, so they get the whole register file)
-// HALVES = 2 (round 4): ONE workgroup of 8 waves per CU works a 96-frame item -- waves 0-3 the first 48 frames,
-// waves 4-7 the last 48, each four splitting K as before.  Wave w and wave w + 4 sit on the same SIMD and read the SAME operator
-// fragments within a few hundred cycles of each other, so the second read is served by the CU's L1 instead of the L2 -> CU
-// fabric (the stream that bounds this kernel: 6.5 MB per segment with 48-frame items); the staged span is shared by both
-// halves (96 frames: 115 KB), and the cross-wave reduction buffer (2 x 74 KB) aliases it.
+// HALVES is always 1.  (2 was ONE workgroup of 8 waves per CU on a 96-frame item; it lost)  The parameter is
+// kept so that kernel symbols stay the ones profiles/, the tools, bench.py's labels and the tests know.
 template <int MT, int PREC, int HALVES = 1>
-__global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) void mel_kernel(const float *__restrict__ x, const float *__restrict__ mm,
+__global__ __launch_bounds__(256, MT <= 6 ? 2 : 1) void mel_kernel(const float *__restrict__ x, const float *__restrict__ mm,
                                                       float *__restrict__ spec, const FrontendParams *__restrict__ pp,
                                                       const float *__restrict__ gf0, const float *__restrict__ gf1,
                                                       const float *__restrict__ gf2, const float *__restrict__ gf3,
-                                                      const int dbg_arg, const int n_tiles, const int n_items, const int paired) {
+                                                      const int n_tiles, const int n_items, const int paired) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    // (the ablation bits, BIRDA_HIP_MEL_DBG, exist in the EXPERIMENTS build only: a compile-time zero in the product)
-#ifdef BIRDA_HIP_EXPERIMENTS
-    const int dbg = dbg_arg;
-#else
-    constexpr int dbg = 0; (void)dbg_arg;
-#endif
+    static_assert(HALVES == 1, "the 8-wave form on 96-frame items lost (DESIGN.md section 8)");
     const int n_branches = pp->n_branches;
     const int S = pp->sample_count;
     float *xs = smem;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int half = HALVES == 2 ? tid >> 8 : 0, wave = (tid >> 6) & 3;   // wave: the K quarter, as in the 4-wave kernel
+    const int wave = (tid >> 6) & 3;   // the wave's K quarter (256 threads: the mask changes no value; it is in the code hipcc has always emitted here)
     const int li = lane & 15, kq = lane >> 4;
-    constexpr int TNW = MEL_TN * HALVES, NTHR = 256 * HALVES;             // frames per item, threads
+    constexpr int TNW = MEL_TN, NTHR = 256;             // frames per item, threads
 
     // PERSISTENT workgroups: each walks the work items (segment, branch, frame tile) with stride gridDim.x, and
     // the sample span of its NEXT item is fetched into registers (MEL_SU x 16 B per thread, free at that point)
@@ -208,7 +187,7 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
     // it started (two per CU) exposed one HBM round trip per tile, 0.37 of this kernel's 0.95 us per segment.
     // item = (seg * n_branches + branch) * n_tiles + tile
     static_assert(MM_SPLIT == 8, "16 floats of min / max partials per segment");
-    constexpr int MEL_SU = HALVES == 2 ? 14 : (MT <= 6 ? 15 : 16);   // (two halves: 28 460 floats of span over 512 threads)
+    constexpr int MEL_SU = MT <= 6 ? 15 : 16;
     float4 q[MEL_SU], mmq[4];
     // Work items and the XCD-aware pairing.  Unpaired: item = (seg * n_branches + branch) * n_tiles + tile, workgroup b takes
     // b, b + gridDim.x, ...  Paired (n_branches > 1, grid a multiple of 8 n_branches): the branches of one (segment, tile)
@@ -331,14 +310,13 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
         const f16x8 *gA = reinterpret_cast<const f16x8 *>(gfp) + lane;
         [[maybe_unused]] f16x8 a0h[MT], a0l[MT], a1h[MT], a1l[MT];
         [[maybe_unused]] auto load = [&](int st, f16x8 (&ah)[MT], f16x8 (&al)[MT]) {
-            if (dbg & 16) st = sbeg;   // (ablation: every step reads the wave's FIRST operator fragments -- the kernel without the L2 -> CU operator stream)
 #pragma unroll
             for (int m = 0; m < MT; m++) {
                 ah[m] = gA[(((size_t)st * MT + m) * 2 + 0) * 64];
                 al[m] = gA[(((size_t)st * MT + m) * 2 + 1) * 64];
             }
         };
-        const float *xf = xs + (half * MEL_TN + li) * H;
+        const float *xf = xs + li * H;
         [[maybe_unused]] auto step = [&](int st, const f16x8 (&ah)[MT], const f16x8 (&al)[MT]) {
             // element jj of the lane's operand fragment is k = 32 st + 4 jj + kq (the operator planes are packed to match,
             // api.hip build_gf): the four lane groups read NEIGHBOURING samples, so the 32 lanes of an LDS access spread over
@@ -370,72 +348,6 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
                     acc[f][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[m], bh[f], acc[f][m], 0, 0, 0);
                 }
         };
-#if BH_MEL_PIPE == 1
-        // Software-pipelined form (round 4, -DBH_MEL_PIPE=1; measured alternative, not the product -- see the note at BH_MEL_PIPE):
-        // the folded-and-split frame fragments of step s + 1 are built WHILE the MFMAs of step s issue.
-        auto build = [&](int st, f16x8 (&bh)[MEL_FT], f16x8 (&bl)[MEL_FT]) {
-            const int j0 = st * 32 + kq;
-#pragma unroll
-            for (int f = 0; f < MEL_FT; f++) {
-                float y[8];
-#pragma unroll
-                for (int jj = 0; jj < 8; jj++)
-                    y[jj] = bh_add_unpacked(xf[f * 16 * H + j0 + 4 * jj + 1], xf[f * 16 * H + L - 1 - j0 - 4 * jj]);
-                bh_split8(y, bh[f], bl[f]);
-            }
-        };
-        auto mma = [&](const f16x8 (&ah)[MT], const f16x8 (&al)[MT], const f16x8 (&bh)[MEL_FT], const f16x8 (&bl)[MEL_FT]) {
-#pragma unroll
-            for (int m = 0; m < MT; m++)
-#pragma unroll
-                for (int f = 0; f < MEL_FT; f++) {
-                    acc[f][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[m], bh[f], acc[f][m], 0, 0, 0);
-                    acc[f][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[m], bl[f], acc[f][m], 0, 0, 0);
-                    acc[f][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[m], bh[f], acc[f][m], 0, 0, 0);
-                }
-        };
-        // 54 MFMAs, 72 vector instructions and 48 LDS reads per step, dealt in groups of {GM MFMA, GD DS read, GV VALU}
-        auto interleave = [&]() {
-#pragma unroll
-            for (int g = 0; g < 9 * MT / BH_MEL_GM; g++) {
-                __builtin_amdgcn_sched_group_barrier(0x008, BH_MEL_GM, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, BH_MEL_GD, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, BH_MEL_GV, 0);
-            }
-        };
-        f16x8 b0h[MEL_FT], b0l[MEL_FT], b1h[MEL_FT], b1l[MEL_FT];
-        load(sbeg, a0h, a0l);
-        if (!(dbg & 1) && (HALVES == 1 || t0 + half * MEL_TN < bp.n_frames)) {
-            build(sbeg, b0h, b0l);
-            __builtin_amdgcn_sched_barrier(0);
-            int si = 0;
-            for (; si + 2 < spw; si += 2) {
-                load(sbeg + si + 1, a1h, a1l);
-                __builtin_amdgcn_sched_barrier(0);
-                build(sbeg + si + 1, b1h, b1l);
-                mma(a0h, a0l, b0h, b0l);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-                load(sbeg + si + 2, a0h, a0l);
-                __builtin_amdgcn_sched_barrier(0);
-                build(sbeg + si + 2, b0h, b0l);
-                mma(a1h, a1l, b1h, b1l);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (si + 1 < spw) {
-                load(sbeg + si + 1, a1h, a1l);
-                __builtin_amdgcn_sched_barrier(0);
-                build(sbeg + si + 1, b1h, b1l);
-                mma(a0h, a0l, b0h, b0l);
-                interleave();
-                __builtin_amdgcn_sched_barrier(0);
-                mma(a1h, a1l, b1h, b1l);
-            } else {
-                mma(a0h, a0l, b0h, b0l);
-            }
-        }
-#elif BH_MEL_PIPE == 2
         // Round 6: the pipelined loop with the operator held HALF a step at a time.  Round 4's form kept two whole
         // operator sets (96 registers) beside two sets of frame fragments (48) and the accumulators (72) and was 3-26 registers
         // short of two workgroups per CU.  Here the step's mel tiles are two halves L and H with ONE register set each (48 in all):
@@ -444,15 +356,11 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
         //     phase 2   MFMAs of half H                           |  frame tile 2 built beside them
         //               -> half H of the next step is fetched
         // so every operator fragment is in flight for half a step (27 MFMAs, ~450 cycles: an L2 round trip) instead of a whole one.
-        #ifndef BH_MEL_FT1
-#define BH_MEL_FT1 ((MEL_FT + 1) / 2)
-#endif
         // (an odd number of mel tiles -- 48, 80, 112 mels -- splits as MH + (MH - 1): the register sets are MH wide, the short half leaves
         //  its last slot unused)
-        constexpr int MH = (MT + 1) / 2, FT1 = BH_MEL_FT1;
+        constexpr int MH = (MT + 1) / 2, FT1 = (MEL_FT + 1) / 2;
         f16x8 aLh[MH], aLl[MH], aHh[MH], aHl[MH];
         auto load_half = [&](int st, int h, f16x8 (&ah)[MH], f16x8 (&al)[MH]) {
-            if (dbg & 16) st = sbeg;
 #pragma unroll
             for (int m = 0; m < MH; m++) {
                 if (h * MH + m >= MT) continue;
@@ -499,64 +407,34 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
         f16x8 b0h[MEL_FT], b0l[MEL_FT], b1h[MEL_FT], b1l[MEL_FT];
         load_half(sbeg, 0, aLh, aLl);
         load_half(sbeg, 1, aHh, aHl);
-        if (!(dbg & 1) && (HALVES == 1 || t0 + half * MEL_TN < bp.n_frames)) {
-            build_f(sbeg, 0, MEL_FT, b0h, b0l);
+        build_f(sbeg, 0, MEL_FT, b0h, b0l);
+        __builtin_amdgcn_sched_barrier(0);
+        // one step: MFMAs on (cur), fragments of the next step into (nxt); `more`: there is a next step (compile-time per call site)
+        auto one = [&](int st, const f16x8 (&ch)[MEL_FT], const f16x8 (&cl)[MEL_FT], f16x8 (&nh)[MEL_FT], f16x8 (&nl)[MEL_FT], bool more) __attribute__((always_inline)) {
+            if (more) build_f(st + 1, 0, FT1, nh, nl);
+            mma_half(0, aLh, aLl, ch, cl);
+            if (more) interleave(FT1);
             __builtin_amdgcn_sched_barrier(0);
-            // one step: MFMAs on (cur), fragments of the next step into (nxt); `more`: there is a next step (compile-time per call site)
-            auto one = [&](int st, const f16x8 (&ch)[MEL_FT], const f16x8 (&cl)[MEL_FT], f16x8 (&nh)[MEL_FT], f16x8 (&nl)[MEL_FT], bool more) __attribute__((always_inline)) {
-                if (more) build_f(st + 1, 0, FT1, nh, nl);
-                mma_half(0, aLh, aLl, ch, cl);
-                if (more) interleave(FT1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) load_half(st + 1, 0, aLh, aLl);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) build_f(st + 1, FT1, MEL_FT, nh, nl);
-                mma_half(1, aHh, aHl, ch, cl);
-                if (more) interleave(MEL_FT - FT1);
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) load_half(st + 1, 1, aHh, aHl);
-                __builtin_amdgcn_sched_barrier(0);
-            };
-            int si = 0;
-            for (; si + 2 < spw; si += 2) {
-                one(sbeg + si, b0h, b0l, b1h, b1l, true);
-                one(sbeg + si + 1, b1h, b1l, b0h, b0l, true);
-            }
-            if (si + 1 < spw) {
-                one(sbeg + si, b0h, b0l, b1h, b1l, true);
-                one(sbeg + si + 1, b1h, b1l, b0h, b0l, false);
-            } else {
-                one(sbeg + si, b0h, b0l, b1h, b1l, false);
-            }
+            if (more) load_half(st + 1, 0, aLh, aLl);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) build_f(st + 1, FT1, MEL_FT, nh, nl);
+            mma_half(1, aHh, aHl, ch, cl);
+            if (more) interleave(MEL_FT - FT1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (more) load_half(st + 1, 1, aHh, aHl);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        int si = 0;
+        for (; si + 2 < spw; si += 2) {
+            one(sbeg + si, b0h, b0l, b1h, b1l, true);
+            one(sbeg + si + 1, b1h, b1l, b0h, b0l, true);
         }
-#else
-        // The last one or two steps are peeled so that no load inside the loop is conditional: with
-        // `if (si + 2 < spw) load(...)` in the loop, hipcc turned the register sets into loop-carried
-        // selects and waited for every load right after issuing it.
-        load(sbeg, a0h, a0l);
-        if (!(dbg & 1) && (HALVES == 1 || t0 + half * MEL_TN < bp.n_frames)) {   // (a half wholly past the last frame has nothing to add)
-            int si = 0;
-            for (; si + 2 < spw; si += 2) {
-                load(sbeg + si + 1, a1h, a1l);
-                __builtin_amdgcn_sched_barrier(0);
-                step(sbeg + si, a0h, a0l);
-                __builtin_amdgcn_sched_barrier(0);
-                load(sbeg + si + 2, a0h, a0l);
-                __builtin_amdgcn_sched_barrier(0);
-                step(sbeg + si + 1, a1h, a1l);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (si + 1 < spw) {
-                load(sbeg + si + 1, a1h, a1l);
-                __builtin_amdgcn_sched_barrier(0);
-                step(sbeg + si, a0h, a0l);
-                __builtin_amdgcn_sched_barrier(0);
-                step(sbeg + si + 1, a1h, a1l);
-            } else {
-                step(sbeg + si, a0h, a0l);
-            }
+        if (si + 1 < spw) {
+            one(sbeg + si, b0h, b0l, b1h, b1l, true);
+            one(sbeg + si + 1, b1h, b1l, b0h, b0l, false);
+        } else {
+            one(sbeg + si, b0h, b0l, b1h, b1l, false);
         }
-#endif
     } else {
     // Two operator register sets, used alternately (no copies): set B is loaded while set A feeds
     // the MFMAs and vice versa.  The scheduling fences keep each load a full group (96 MFMAs)
@@ -584,30 +462,28 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
                     acc[f][m] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, b[c][f], acc[f][m], 0, 0, 0);
             }
     };
-    if (!(dbg & 1)) {   // last one or two groups peeled: no conditional loads inside the loop
-        int gi = 0;
-        for (; gi + 2 < gpw; gi += 2) {
+    int gi = 0;
+    for (; gi + 2 < gpw; gi += 2) {
 #pragma unroll
-            for (int m = 0; m < MT; m++) a1[m] = gA[((size_t)(gbeg + gi + 1) * MT + m) * 64];
-            __builtin_amdgcn_sched_barrier(0);
-            group(gbeg + gi, a0);
-            __builtin_amdgcn_sched_barrier(0);
+        for (int m = 0; m < MT; m++) a1[m] = gA[((size_t)(gbeg + gi + 1) * MT + m) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+        group(gbeg + gi, a0);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int m = 0; m < MT; m++) a0[m] = gA[((size_t)(gbeg + gi + 2) * MT + m) * 64];
-            __builtin_amdgcn_sched_barrier(0);
-            group(gbeg + gi + 1, a1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (gi + 1 < gpw) {
+        for (int m = 0; m < MT; m++) a0[m] = gA[((size_t)(gbeg + gi + 2) * MT + m) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+        group(gbeg + gi + 1, a1);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (gi + 1 < gpw) {
 #pragma unroll
-            for (int m = 0; m < MT; m++) a1[m] = gA[((size_t)(gbeg + gi + 1) * MT + m) * 64];
-            __builtin_amdgcn_sched_barrier(0);
-            group(gbeg + gi, a0);
-            __builtin_amdgcn_sched_barrier(0);
-            group(gbeg + gi + 1, a1);
-        } else {
-            group(gbeg + gi, a0);
-        }
+        for (int m = 0; m < MT; m++) a1[m] = gA[((size_t)(gbeg + gi + 1) * MT + m) * 64];
+        __builtin_amdgcn_sched_barrier(0);
+        group(gbeg + gi, a0);
+        __builtin_amdgcn_sched_barrier(0);
+        group(gbeg + gi + 1, a1);
+    } else {
+        group(gbeg + gi, a0);
     }
 
     }  // PREC
@@ -620,11 +496,11 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
     float4 *red = reinterpret_cast<float4 *>(smem);
 #pragma unroll
     for (int f = 0; f < MEL_FT; f++) {
-        if (f == wave || (dbg & 4)) continue;
+        if (f == wave) continue;
         const int slot = f - (f > wave ? 1 : 0);
 #pragma unroll
         for (int m = 0; m < MT; m++)
-            red[(((half * 4 + wave) * 3 + slot) * MT + m) * 64 + lane] = make_float4(acc[f][m][0], acc[f][m][1], acc[f][m][2], acc[f][m][3]);
+            red[((wave * 3 + slot) * MT + m) * 64 + lane] = make_float4(acc[f][m][0], acc[f][m][1], acc[f][m][2], acc[f][m][3]);
     }
     __syncthreads();
     if (wave < MEL_FT) {   // waves beyond the frame tiles own no epilogue tile
@@ -635,16 +511,16 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
         f32x4 v = wave == 0 ? acc[0][m] : wave == 1 ? acc[1][m] : wave == 2 ? acc[2][m] : acc[MEL_FT - 1][m];
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            if (s == wave || (dbg & 4)) continue;
+            if (s == wave) continue;
             const int slot = wave - (wave > s ? 1 : 0);
-            const float4 q = red[(((half * 4 + s) * 3 + slot) * MT + m) * 64 + lane];
+            const float4 q = red[((s * 3 + slot) * MT + m) * 64 + lane];
             v[0] += q.x; v[1] += q.y; v[2] += q.z; v[3] += q.w;
         }
         tot[m] = v;
     }
 
     // epilogue: square, power law, folded-BN affine, mel flip, [mel][time] store
-    const int t = t0 + half * MEL_TN + wave * 16 + li;
+    const int t = t0 + wave * 16 + li;
     if (t < bp.n_frames) {
         float *out = spec + ((size_t)seg * n_branches + branch) * bp.n_mels * bp.n_frames;
 #pragma unroll
@@ -656,10 +532,10 @@ __global__ __launch_bounds__(256 * HALVES, (MT <= 6 || HALVES == 2) ? 2 : 1) voi
                     const float v = tot[m][r];
                     // (v^2)^expo = exp2(expo * log2(v^2)): v_log_f32 + v_mul + v_exp_f32 instead of ocml powf
                     // (~70 instructions); relative error <= ~5e-7 for v^2 down to 1e-12, 0 -> 0
-                    float o = (dbg & 2) ? v : __builtin_amdgcn_exp2f(__builtin_fmaf(bp.expo, __builtin_amdgcn_logf(v * v), bp.log2_bias));
+                    float o = __builtin_amdgcn_exp2f(__builtin_fmaf(bp.expo, __builtin_amdgcn_logf(v * v), bp.log2_bias));
                     o = o * bp.out_scale + bp.out_shift;
                     const int row = bp.flip ? (bp.n_mels - 1 - mel) : mel;
-                    if (!(dbg & 8) || o == 12345.678f) out[__mul24(row, bp.n_frames) + t] = o;   // (24-bit product: a branch's [mel][time] plane is < 2^24 elements; v_mad_i64_i32 is quarter-rate)
+                    out[__mul24(row, bp.n_frames) + t] = o;   // (24-bit product: a branch's [mel][time] plane is < 2^24 elements; v_mad_i64_i32 is quarter-rate)
                 }
             }
     }
@@ -684,6 +560,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int MEL32_TN = 32;
 constexpr int MEL32_YP = 36;   // dwords per staged Y row (32 + 4: 16-byte row pieces of 16 frames tile the 64 banks)
 
+// (dbg: the launcher passes 0.  Bit 0 once switched the main loop off; it is a RUN-TIME test here, so taking the argument out changes
+//  the kernel's code -- two lane spills and, at 64 mels, a register -- and is left to a change that measures it.)
 template <int MT32>
 __global__ __launch_bounds__(256, 2) void mel32_kernel(const float *__restrict__ x, const float *__restrict__ mm,
                                                         float *__restrict__ spec, const FrontendParams *__restrict__ pp,
@@ -784,7 +662,7 @@ __global__ __launch_bounds__(256, 2) void mel32_kernel(const float *__restrict__
             for (int m = 0; m < MT32; m++) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bh, acc[m], 0, 0, 0);
         };
         const int st0 = kw / 16;
-        if (!(dbg & 1)) {
+        if (!(dbg & 1)) {   // (dbg is always 0: see the argument)
             load(st0, a0h, a0l);
             for (int c = 0; c < nch; c++) {
                 const int kc = kw + 64 * c;
@@ -887,7 +765,6 @@ const char *launch_mel(const float *x, const float *minmax, float *spec, const F
         max_span = span > max_span ? span : max_span;
         max_frames = p.br[b].n_frames > max_frames ? p.br[b].n_frames : max_frames;
     }
-    static const int dbg = [] { const char *e = BH_XENV("BIRDA_HIP_MEL_DBG"); return e ? atoi(e) : 0; }();  // tuning ablations
     if (p.prec == 32) {
         int span32 = 0;
         for (int b = 0; b < p.n_branches; b++) span32 = std::max(span32, (MEL32_TN - 1) * p.br[b].H + p.br[b].L);
@@ -901,7 +778,7 @@ const char *launch_mel(const float *x, const float *minmax, float *spec, const F
     case MTV: {                                                                                                                \
         static DeviceOnce set32;                                                                                               \
         set32.run([] { (void)hipFuncSetAttribute((const void *)mel32_kernel<MTV>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
-        hipLaunchKernelGGL((mel32_kernel<MTV>), g32, b32, smem32, s, x, minmax, spec, d_p, p.br[0].gf, p.br[1].gf, p.br[2].gf, p.br[3].gf, dbg, ybuf_off, nt32, ni32); \
+        hipLaunchKernelGGL((mel32_kernel<MTV>), g32, b32, smem32, s, x, minmax, spec, d_p, p.br[0].gf, p.br[1].gf, p.br[2].gf, p.br[3].gf, 0, ybuf_off, nt32, ni32); \
         return "bh::mel32_kernel<" #MTV ">";                                                                                   \
     }
         switch (mt32) {
@@ -915,37 +792,17 @@ const char *launch_mel(const float *x, const float *minmax, float *spec, const F
         return nullptr;
     }
     const int mt = nmp / 16;
-    // 8-wave workgroups on 96-frame items (HALVES = 2 above) for the split-f16 96-mel front-ends: built, parity-green, measured and
-    // REJECTED (round 4): 0.714 against 0.661 us per segment on every one of four alternations on one box
-    // (profiles/r4_h_mel_halves.txt) -- the twin waves' second reads of the operator fragments do not come cheaper out of L1 than
-    // the one workgroup per CU loses by its eight waves meeting at every barrier of an item.  EXPERIMENTS build only,
-    // BIRDA_HIP_MEL_HALVES=2.
-    static const bool halves_on = BH_XENV("BIRDA_HIP_MEL_HALVES") && BH_XENV("BIRDA_HIP_MEL_HALVES")[0] == '2';
-    int max_span2 = 0;
-    for (int b = 0; b < p.n_branches; b++) max_span2 = std::max(max_span2, (2 * MEL_TN - 1) * p.br[b].H + p.br[b].L);
-    const bool two = halves_on && p.prec == 3 && mt == 6 && ((size_t)((max_span2 + 3) & ~3) * 4 <= 160 * 1024) && ((max_span2 + 3) & ~3) <= 14 * 2048;
-    const int tnw = two ? 2 * MEL_TN : MEL_TN;
-    const size_t span_bytes = (size_t)(((two ? max_span2 : max_span) + 3) & ~3) * sizeof(float);
-    const size_t red_bytes = (size_t)(two ? 8 : 4) * 3 * mt * 64 * sizeof(float4);
+    const size_t span_bytes = (size_t)((max_span + 3) & ~3) * sizeof(float);
+    const size_t red_bytes = (size_t)4 * 3 * mt * 64 * sizeof(float4);
     const size_t smem = span_bytes > red_bytes ? span_bytes : red_bytes;
-    const int n_tiles = (max_frames + tnw - 1) / tnw, n_items = n_tiles * p.n_branches * n_seg;
+    const int n_tiles = (max_frames + MEL_TN - 1) / MEL_TN, n_items = n_tiles * p.n_branches * n_seg;
     const int n_cu = device_cu_count();
-    int n_wg = std::min(n_items, ((mt <= 6 && !two) ? 2 : 1) * n_cu);   // persistent: as many workgroups as fit at once
+    int n_wg = std::min(n_items, (mt <= 6 ? 2 : 1) * n_cu);   // persistent: as many workgroups as fit at once
     // branch partners on one XCD (see the kernel): needs whole groups of 8 n_branches workgroups
-    static const bool pair_off = BH_XENV("BIRDA_HIP_MEL_PAIR") && BH_XENV("BIRDA_HIP_MEL_PAIR")[0] == '0';
     const int pair_group = 8 * p.n_branches;
-    const int paired = (!pair_off && p.n_branches > 1 && n_wg >= pair_group) ? 1 : 0;
+    const int paired = (p.n_branches > 1 && n_wg >= pair_group) ? 1 : 0;
     if (paired) n_wg -= n_wg % pair_group;
     dim3 grid((unsigned)n_wg), block(256);
-#ifdef BIRDA_HIP_EXPERIMENTS
-    if (two) {
-        static DeviceOnce attr2;
-        attr2.run([] { (void)hipFuncSetAttribute((const void *)mel_kernel<6, 3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-        hipLaunchKernelGGL((mel_kernel<6, 3, 2>), grid, dim3(512), smem, s, x, minmax, spec, d_p, p.br[0].gf, p.br[1].gf, p.br[2].gf, p.br[3].gf,
-                           dbg, n_tiles, n_items, paired);
-        return "bh::mel_kernel<6, 3, 2>";
-    }
-#endif
 #define BH_MEL_CASE(MTV)                                                                                   \
     case MTV: {                                                                                            \
         static DeviceOnce attr_set;                                                                        \
@@ -957,11 +814,11 @@ const char *launch_mel(const float *x, const float *minmax, float *spec, const F
         });                                                                                                \
         if (p.prec == 3) {                                                                                 \
             hipLaunchKernelGGL((mel_kernel<MTV, 3>), grid, block, smem, s, x, minmax, spec, d_p, p.br[0].gf,   \
-                               p.br[1].gf, p.br[2].gf, p.br[3].gf, dbg, n_tiles, n_items, paired);                 \
+                               p.br[1].gf, p.br[2].gf, p.br[3].gf, n_tiles, n_items, paired);                      \
             return "bh::mel_kernel<" #MTV ", 3, 1>";                                                       \
         }                                                                                                  \
         hipLaunchKernelGGL((mel_kernel<MTV, 0>), grid, block, smem, s, x, minmax, spec, d_p, p.br[0].gf,       \
-                           p.br[1].gf, p.br[2].gf, p.br[3].gf, dbg, n_tiles, n_items, paired);                     \
+                           p.br[1].gf, p.br[2].gf, p.br[3].gf, n_tiles, n_items, paired);                          \
         return "bh::mel_kernel<" #MTV ", 0, 1>";                                                           \
     }
     switch (mt) {      // (32, 96 and 128 mels are the published families'; 48 / 64 / 80 / 112 -- round 6 -- whatever else a model file holds)

@@ -57,7 +57,7 @@ double mb_try_th(MbDesc &d, int ci, int th, bool relax_kg = false) {
     if ((long)c.S * d.H * d.W * std::max(d.Cin, 1) >= (1L << 24) || (long)c.S * d.Ho * d.Wo * d.Cout >= (1L << 24) ||
         (d.stem && (long)d.stem_c * d.stem_h * d.stem_w >= (1L << 24))) return -1;
     if (d.stem && d.stem_k != 3) MB_NO(3);
-    if (d.se && (!c.launch_se || c.PERSIST)) MB_NO(4);   // pass A of a squeeze-excite block: only where it is instantiated (mbconv_kernel.hpp MB_WITH_SE)
+    if (d.se && !c.launch_se) MB_NO(4);   // pass A of a squeeze-excite block: only where it is instantiated (mbconv_kernel.hpp MB_WITH_SE)
     if (c.KG == 0) { if (!d.noexp || d.stem) return -1; }   // the no-expand entries serve the no-expand blocks, and only them
     else {
         // k steps of the expand GEMM: the entry's own number, or (relax_kg: a block no entry was shaped for) any number up to it --
@@ -95,26 +95,9 @@ double mb_try_th(MbDesc &d, int ci, int th, bool relax_kg = false) {
     const size_t we_fl = (size_t)c.KG * (c.CE / 16) * frag + c.CE, wp_fl = p16 ? (size_t)t.NTOP * 256 : psteps * t.NTOP * frag;
     const size_t wd_fl = (size_t)c.KS * c.KS * c.CE + c.CE;
     const size_t ds_fl = c.PREC ? (size_t)pout_pad * (p16 ? 24 : psteps * 32 + 8) : (size_t)pout_pad * ces;
-    if (c.PERSIST == 2) {   // strip-walking workgroups: more than one tile row to walk, one segment, a halo the step inherits
-        if (t.tiles_y < 2 || c.S != 1 || c.KS <= c.ST || th * c.ST < c.KS - c.ST || d.pad_t > th * c.ST) return -1;
-    }
-    const size_t halo_bytes = c.PERSIST == 2 ? (size_t)t.nchunks * (c.KS - c.ST) * t.IW * ces * 4 : 0;   // [chunk][KS - ST rows][IW][ces]
-    const size_t lds_base = (((size_t)c.S * t.IH * t.IW + 1) * ces + ds_fl) * 4 + (size_t)pout_pad * 4 + halo_bytes;
-    t.lds_bytes = lds_base + (we_fl + wp_fl + wd_fl) * 4 * (c.PERSIST == 1 ? (size_t)t.nchunks : 1);   // persistent: every chunk resident
+    // the grid (+ its trash row), the D planes, the output map and one buffer each of We, Wp and Wd
+    t.lds_bytes = (((size_t)c.S * t.IH * t.IW + 1) * ces + ds_fl) * 4 + (size_t)pout_pad * 4 + (we_fl + wp_fl + wd_fl) * 4;
     if (t.lds_bytes > 160 * 1024) MB_NO(10);
-    if (c.PERSIST == 1 && t.lds_bytes > 80 * 1024) return -1;   // one workgroup per CU cannot hide its own set-up
-    // weight ring (We x 2, Wp x 3, Wd x 2, a whole chunk of prefetch distance): for 16-channel chunks, when the workgroups the
-    // entry's register budget allows per CU still fit in LDS with it.  BIRDA_HIP_MB_RING=0/1 forces it off / on where it fits.
-    t.ring = 0;
-    {
-        const size_t lds_ring = lds_base + (2 * we_fl + 3 * wp_fl + 2 * wd_fl) * 4;
-        const char *re = BH_XENV("BIRDA_HIP_MB_RING");
-        // Measured (profiles/r2 notes): the ring removes the wait in front of B1 (22 % -> 3 % of a wave's
-        // cycles) but the time moves to B2 and the launch does not get shorter, and wherever it costs a workgroup per CU it is
-        // slower (7.31 -> 8.02 us per segment over all blocks when forced).  Off unless BIRDA_HIP_MB_RING=1.
-        const bool want = !c.PERSIST && re && re[0] == '1' && c.CE == 16 && t.nchunks > 2 && lds_ring <= 160 * 1024;
-        if (want) { t.ring = 1; t.lds_bytes = lds_ring; }
-    }
     d = t;
     const double tiles = (double)t.tiles_y * t.tiles_x / c.S;
     // (relaxed pass: the weights every workgroup streams count too -- 1 / 192 of an MFMA step per byte: 64 bytes a clock into a CU's
@@ -123,8 +106,6 @@ double mb_try_th(MbDesc &d, int ci, int th, bool relax_kg = false) {
     if (relax_kg)
         return tiles * ((double)t.mpad_max / 16 * t.KG * 4 * (d.Cexp / 16) + (double)pout_pad / 16 * t.NTOP * (d.Cexp / 4) +
                         (double)t.nchunks * (double)(we_fl + wp_fl + wd_fl) * 4.0 / 192.0);
-    if (c.PERSIST == 2)   // (the halo rows are not expanded again: TH * ST new rows per step)
-        return tiles * ((double)(c.S * std::min(th * c.ST, d.H) * std::min(t.IW, d.W) + 15) / 16 * t.KG * 4 * (d.Cexp / 16) + (double)pout_pad / 16 * t.NTOP * (d.Cexp / 4));
     return tiles * ((double)t.mpad_max / 16 * t.KG * 4 * (d.Cexp / 16) + (double)pout_pad / 16 * t.NTOP * (d.Cexp / 4));
 }
 
@@ -162,18 +143,18 @@ int mb_config_families() { return kNActs; }
 int mb_config_name(int ci, char *out, size_t cap) {
     if (ci < 0 || ci >= kNCfgs) return 0;
     const MbCfg &c = kCfgs[ci];
-    // the first 19 template arguments, as a profiler prints them (the last three: persistent instantiation, activation, column tasks);
+    // the first 19 template arguments, as a profiler prints them (the last three: PERSIST, always 0 and kept for the symbols' sake,
+    // activation, column tasks);
     // the twentieth, SE, belongs to the launch, not the table entry: the caller appends it (classifier.py fused_kernel_name)
     return snprintf(out, cap, "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", c.KS, c.ST, c.CE, c.KG, c.RT_W, c.NCS, c.WM,
-                    c.WN, c.MT_W, c.NT_W, c.TWL, c.XBL, c.S, c.OCC, c.STEM, c.PREC, c.PERSIST, c.ACT, c.COLTH);
+                    c.WN, c.MT_W, c.NT_W, c.TWL, c.XBL, c.S, c.OCC, c.STEM, c.PREC, 0, c.ACT, c.COLTH);
 }
 
 // the row's tile height and whether pass A of a squeeze-excite block is instantiated for it (the block diagnostics' plan record)
-bool mb_config_row(int ci, int *th, int *has_se, int *persist, int *act) {
+bool mb_config_row(int ci, int *th, int *has_se, int *act) {
     if (ci < 0 || ci >= kNCfgs) return false;
     if (th) *th = kCfgs[ci].TH;
-    if (has_se) *has_se = kCfgs[ci].KS != 0 && kCfgs[ci].launch_se != nullptr && !kCfgs[ci].PERSIST;
-    if (persist) *persist = kCfgs[ci].PERSIST;
+    if (has_se) *has_se = kCfgs[ci].KS != 0 && kCfgs[ci].launch_se != nullptr;
     if (act) *act = kCfgs[ci].ACT;
     return true;
 }
@@ -221,19 +202,11 @@ bool mb_plan(MbDesc &d, int force_cfg) {
     static const int kPreferred[] = {11, 12, 13, 14, 15, 16, 17, 18, 19, 9, 10, 20, 21};
     // split-f16 with 16-channel chunks (two or more workgroups per CU): the early blocks, and the 6x32
     // blocks whose depthwise phase is light enough (3x3, and the stride-2 5x5)
-    // 79..84: persistent twins of 48, 49, 65, 66, 50, 51.  Measured (us per 1000 segments, same box): the two 5x5 blocks gain
-    // (741 -> 686, 576 -> 536); the stem, 16 -> 96 -> 24 and 24 -> 144 -> 24 blocks LOSE (928 -> 1161, 1032 -> 1504, 737 -> 953):
-    // with every chunk's weights resident they fit two workgroups per CU instead of four, and without a prefetch of the next
-    // tile's rows nothing hides a tile's set-up.  Off by default; BIRDA_HIP_MB_PERSIST=1 all six, =2 the 5x5 pair.
-    static const int kPreferred16a[] = {79, 80, 81, 82, 83, 84, 48, 49, 50, 51, 52, 113, 55, 58, 65, 66, 99, 101, 103, 105, 107, 109, 111, 85, 87, 89, 91, 95, 97};
-    static const int kPreferred16p[] = {83, 84, 48, 49, 50, 51, 52, 113, 55, 58, 65, 66, 99, 101, 103, 105, 107, 109, 111, 85, 87, 89, 91, 95, 97};
-    static const int kPreferred16n[] = {48, 49, 50, 51, 52, 113, 55, 58, 65, 66, 99, 101, 103, 105, 107, 109, 111, 85, 87, 89, 91, 95, 97};
-    // 99..110: the 8-wave twins of 85..92 and 95..98 (two waves per SIMD inside the one workgroup a CU holds): 307 -> 257,
-    // 426 -> 391, 258 -> 224, 292 -> 254 us per 1 000 segments (old and new library in one run, tools/ab_lib.sh); Perch-shaped
-    // model 410 -> 256, 407 -> 298
-    static const int kPreferred1[] = {100, 102, 104, 106, 108, 110, 112, 114, 86, 88, 90, 92, 96, 98};   // plain f16: the column-task twins where they apply, else the work rule
-    const char *pe = BH_XENV("BIRDA_HIP_MB_PERSIST");
-    const int persist_mode = !pe ? 0 : pe[0] == '1' ? 2 : pe[0] == '2' ? 1 : 0;
+    static const int kPreferred16n[] = {48, 49, 50, 51, 52, 113, 55, 58, 65, 66, 99, 101, 103, 105, 107, 109, 111};
+    // 99..110: the 8-wave column-task entries (two waves per SIMD inside the one workgroup a CU holds); against their 4-wave
+    // forerunners 85..92 and 95..98: 307 -> 257, 426 -> 391, 258 -> 224, 292 -> 254 us per 1 000 segments (old and new library in
+    // one run, tools/ab.sh lib); Perch-shaped model 410 -> 256, 407 -> 298
+    static const int kPreferred1[] = {100, 102, 104, 106, 108, 110, 112, 114};   // plain f16: the column-task twins where they apply, else the work rule
     if (d.prec == 0)
         for (int base : kPreferred) {  // at the entry's own tile height: the shapes it was measured on
             const int ci = mb_act_index(d, base);
@@ -247,11 +220,8 @@ bool mb_plan(MbDesc &d, int force_cfg) {
             if (ci >= 0 && mb_try_th(t, ci, kCfgs[ci].TH) >= 0) { d = t; return true; }
         }
     if (d.prec == 3) {
-        const int *list = persist_mode == 2 ? kPreferred16a : persist_mode == 1 ? kPreferred16p : kPreferred16n;
-        const int nlist = persist_mode == 2 ? (int)(sizeof kPreferred16a / sizeof(int))
-                        : persist_mode == 1 ? (int)(sizeof kPreferred16p / sizeof(int)) : (int)(sizeof kPreferred16n / sizeof(int));
-        for (int q = 0; q < nlist; q++) {
-            const int ci = mb_act_index(d, list[q]);
+        for (int base : kPreferred16n) {
+            const int ci = mb_act_index(d, base);
             MbDesc t = d;
             if (ci >= 0 && mb_try_th(t, ci, kCfgs[ci].TH) >= 0) { d = t; return true; }
         }
@@ -265,7 +235,6 @@ bool mb_plan(MbDesc &d, int force_cfg) {
         MbDesc bestd = d;
         if (why) std::fill(g_why, g_why + 16, 0);
         for (int ci = 0; ci < kNCfgs; ci++) {
-            if (kCfgs[ci].PERSIST) continue;   // persistent entries only through the preferred list (measured shapes)
             // (the generic entries, mbconv_cfgs.inc from 211 on, belong to the relaxed pass whatever their k steps: there a hand-shaped
             //  entry that fits the block by relaxation competes with them on cost, weights streamed included)
             if (!relax && ci % kNBase >= 211) continue;
@@ -287,8 +256,7 @@ bool mb_plan(MbDesc &d, int force_cfg) {
                 const double tiles = (double)bestd.tiles_y * bestd.tiles_x / c.S, pout_pad = c.WM * c.MT_W * 16;
                 const double steps = tiles * ((double)bestd.mpad_max / 16 * bestd.KG * 4 * (d.Cexp / 16.0) + pout_pad / 16 * bestd.NTOP * (d.Cexp / 4.0));
                 const double own = (double)d.H * d.W / 16 * ((d.noexp ? 0 : d.Cin) / 4.0) * (d.Cexp / 16.0) + (double)d.Ho * d.Wo / 16 * (d.Cout / 16.0) * (d.Cexp / 4.0);
-                static const double pad_max = [] { const char *e = BH_XENV("BIRDA_HIP_MB_F32_PAD"); return e ? atof(e) : 2.5; }();   // (A/B aid)
-                if (steps > pad_max * own && d.Cin >= 64 && d.Cexp >= 192) {   // (narrow blocks pad as much on the layer path's GEMM tiles)
+                if (steps > 2.5 * own && d.Cin >= 64 && d.Cexp >= 192) {   // (narrow blocks pad as much on the layer path's GEMM tiles)
                     if (why)
                         fprintf(stderr, "mb_plan: %d -> %d -> %d k%d s%d %dx%d left to the layer kernels on the f32 MFMA: best entry %d issues %.1f x the block's own MFMA steps\n",
                                 d.Cin, d.Cexp, d.Cout, d.KS, d.ST, d.H, d.W, bestd.cfg % kNBase, steps / own);
@@ -316,7 +284,7 @@ bool mb_plan_twin(const MbDesc &d, MbDesc &twin) {
     for (int b = 0; b < kNBase; b++) {
         const MbCfg &q = kCfgs[k0 + b];
         if (q.S != 1 || q.COLTH != c.COLTH || q.KS != c.KS || q.ST != c.ST || q.CE != c.CE || q.KG != c.KG || q.PREC != c.PREC ||
-            q.TWL != c.TWL || q.WM * q.WN != 8 || q.WN * q.NT_W != c.WN * c.NT_W || q.STEM != c.STEM || q.PERSIST) continue;
+            q.TWL != c.TWL || q.WM * q.WN != 8 || q.WN * q.NT_W != c.WN * c.NT_W || q.STEM != c.STEM) continue;
         MbDesc t = d;
         // (relaxed: the block may have come to its entry through the relaxed pass -- fewer k steps than the entry's, a lower image)
         if (mb_try_th(t, k0 + b, q.TH, true) >= 0 && t.NTOP == d.NTOP && t.nchunks == d.nchunks && t.KG == d.KG && t.CE == d.CE) { twin = t; return true; }
@@ -346,13 +314,13 @@ bool mb_twin_sums_match(const MbDesc &d, const MbDesc &tw) {
 bool mb_plan_narrow(const MbDesc &d, MbDesc &narrow) {
     if (d.cfg < 0 || d.cfg >= kNCfgs) return false;
     const MbCfg &c = kCfgs[d.cfg];
-    if (c.PERSIST || d.tiles_x * d.tiles_y != 1) return false;
+    if (d.tiles_x * d.tiles_y != 1) return false;
     const int k0 = (d.cfg / kNBase) * kNBase;   // the same activation's copy of the list
     int best_twl = 99;
     for (int b = 0; b < kNBase; b++) {
         const MbCfg &q = kCfgs[k0 + b];
         if (q.S != 1 || q.COLTH != c.COLTH || q.KS != c.KS || q.ST != c.ST || q.CE != c.CE || q.KG != c.KG || q.PREC != c.PREC ||
-            q.TWL >= c.TWL || q.TWL >= best_twl || q.WM * q.WN != c.WM * c.WN || q.WN * q.NT_W != c.WN * c.NT_W || q.STEM != c.STEM || q.PERSIST) continue;
+            q.TWL >= c.TWL || q.TWL >= best_twl || q.WM * q.WN != c.WM * c.WN || q.WN * q.NT_W != c.WN * c.NT_W || q.STEM != c.STEM) continue;
         MbDesc t = d;
         if (mb_try_th(t, k0 + b, q.TH, true) >= 0 && t.NTOP == d.NTOP && t.nchunks == d.nchunks && t.KG == d.KG && t.CE == d.CE && t.tiles_y == 1 && t.tiles_x >= 2) {
             narrow = t; best_twl = q.TWL;

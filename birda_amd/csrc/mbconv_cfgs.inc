@@ -4,15 +4,15 @@
 // Tile configurations of the fused MBConv kernel (kernels_mbconv_<activation>.hip include this list once each, with MB_A set).
 // MB_ENTRY* rows are the product: exactly the configurations mb_plan() reaches for the BirdNET-v2.4-shaped, Perch-sized (B3) and
 // Perch-shaped (B0) stacks and the small test models in the three precisions (tools/plan_models.py;
-// tests/test_abi_and_host.py::test_shipped_tile_configurations_are_the_reachable_ones holds the list to that).  MB_XENTRY* rows are
-// measured alternatives that lost (DESIGN.md section 3): they keep their index but are only built with -DBIRDA_HIP_EXPERIMENTS
-// (make EXPERIMENTS=1), for A/B runs through BIRDA_HIP_MB_CFG / BIRDA_HIP_MB_PREFER.
+// tests/test_abi_and_host.py::test_shipped_tile_configurations_are_the_reachable_ones holds the list to that).  MB_NONE / MB_NONE2 rows
+// hold the place of measured alternatives that lost (DESIGN.md sections 3 and 8 have the numbers, and the table of section 8 the
+// commit that last held their code): indices are ABI, so the place stays and matches no block.
 //        KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC
-    MB_XENTRY(3, 2, 48, 1, 5, 1, 4, 1, 1, 2, 4, 0, 4, 1, 2),    // 0: 16 -> 96 -> 24, 48x256 -> 24x128
-    MB_XENTRY(3, 1, 48, 2, 3, 1, 4, 1, 2, 2, 4, 1, 8, 1, 2),    // 1: 24 -> 144 -> 24, 24x128
-    MB_XENTRY(5, 2, 48, 2, 7, 1, 4, 1, 1, 3, 4, 0, 4, 1, 1),    // 2: 24 -> 144 -> 40, 24x128 -> 12x64
+    MB_NONE,    // 0: lost -- was 16 -> 96 -> 24, 48x256 -> 24x128
+    MB_NONE,    // 1: lost -- was 24 -> 144 -> 24, 24x128
+    MB_NONE,    // 2: lost -- was 24 -> 144 -> 40, 24x128 -> 12x64
     MB_ENTRY(5, 1, 48, 3, 4, 1, 4, 1, 3, 3, 4, 2, 12, 1, 1),   // 3: 40 -> 240 -> 40, 12x64, full-height tiles
-    MB_XENTRY(3, 2, 48, 3, 7, 1, 2, 2, 3, 3, 4, 1, 6, 1, 1),    // 4: 40 -> 240 -> 80, 12x64 -> 6x32
+    MB_NONE,    // 4: lost -- was 40 -> 240 -> 80, 12x64 -> 6x32
     MB_ENTRY(3, 1, 32, 5, 3, 1, 4, 1, 3, 5, 5, 1, 6, 1, 2),    // 5: 80 -> 480 -> 80, 6x32 whole image
     MB_ENTRY(5, 1, 32, 5, 3, 1, 4, 1, 3, 7, 5, 1, 6, 1, 1),    // 6: 80 -> 480 -> 112, 6x32
     MB_ENTRY(5, 1, 32, 7, 3, 1, 4, 1, 3, 7, 5, 1, 6, 1, 1),    // 7: 112 -> 672 -> 112, 6x32
@@ -34,19 +34,19 @@
     MB_ENTRY_S(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 3, 1),  // 21: 1-channel spectrogram (K = 9)
     // f16 MFMA twins (even index: split hi/lo x3, odd: plain f16), 32-channel chunks
     //         KS ST KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM
-    MB_XENTRY_P(3, 2, 32, 1, 5, 1, 4, 1, 1, 2, 4, 1, 4, 1, 2, 0, 3), MB_ENTRY_P(3, 2, 32, 1, 5, 1, 4, 1, 1, 2, 4, 1, 4, 1, 2, 0, 1),    // 22/23: Cin <= 32, 3x3 s2 (16 -> 96 -> 24)
-    MB_XENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 2, 4, 2, 8, 1, 2, 0, 3), MB_ENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 2, 4, 2, 8, 1, 2, 0, 1),    // 24/25: Cin <= 32, 3x3 s1
-    MB_XENTRY_P(5, 2, 32, 1, 7, 1, 4, 1, 1, 3, 4, 1, 4, 1, 2, 0, 3), MB_ENTRY_P(5, 2, 32, 1, 7, 1, 4, 1, 1, 3, 4, 1, 4, 1, 2, 0, 1),    // 26/27: Cin <= 32, 5x5 s2
-    MB_XENTRY_P(5, 1, 32, 2, 4, 1, 4, 1, 3, 3, 4, 3, 12, 1, 1, 0, 3), MB_ENTRY_P(5, 1, 32, 2, 4, 1, 4, 1, 3, 3, 4, 3, 12, 1, 1, 0, 1),   // 28/29: Cin <= 64, 5x5 s1, 12x64
-    MB_XENTRY_P(3, 2, 32, 2, 7, 1, 2, 2, 3, 3, 4, 0, 6, 1, 1, 0, 3), MB_ENTRY_P(3, 2, 32, 2, 7, 1, 2, 2, 3, 3, 4, 0, 6, 1, 1, 0, 1),    // 30/31: Cin <= 64, 3x3 s2
-    MB_XENTRY_P(3, 1, 32, 3, 3, 1, 4, 1, 3, 5, 5, 3, 6, 1, 2, 0, 3), MB_ENTRY_P(3, 1, 32, 3, 3, 1, 4, 1, 3, 5, 5, 3, 6, 1, 2, 0, 1),    // 32/33: 80 -> 480 -> 80, 6x32
-    MB_XENTRY_P(5, 1, 32, 3, 3, 1, 4, 1, 3, 7, 5, 3, 6, 1, 1, 0, 3), MB_ENTRY_P(5, 1, 32, 3, 3, 1, 4, 1, 3, 7, 5, 3, 6, 1, 1, 0, 1),    // 34/35: 80 -> 480 -> 112
-    MB_XENTRY_P(5, 1, 32, 4, 3, 1, 4, 1, 3, 7, 5, 3, 6, 1, 1, 0, 3), MB_ENTRY_P(5, 1, 32, 4, 3, 1, 4, 1, 3, 7, 5, 3, 6, 1, 1, 0, 1),    // 36/37: 112 -> 672 -> 112
-    MB_XENTRY_P(5, 2, 32, 4, 3, 1, 1, 4, 3, 3, 4, 1, 3, 1, 1, 0, 3), MB_ENTRY_P(5, 2, 32, 4, 3, 1, 1, 4, 3, 3, 4, 1, 3, 1, 1, 0, 1),    // 38/39: 112 -> 672 -> 192 stride 2
+    MB_NONE, MB_ENTRY_P(3, 2, 32, 1, 5, 1, 4, 1, 1, 2, 4, 1, 4, 1, 2, 0, 1),    // 22/23: Cin <= 32, 3x3 s2 (16 -> 96 -> 24); the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 2, 4, 2, 8, 1, 2, 0, 1),    // 24/25: Cin <= 32, 3x3 s1; the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(5, 2, 32, 1, 7, 1, 4, 1, 1, 3, 4, 1, 4, 1, 2, 0, 1),    // 26/27: Cin <= 32, 5x5 s2; the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(5, 1, 32, 2, 4, 1, 4, 1, 3, 3, 4, 3, 12, 1, 1, 0, 1),    // 28/29: Cin <= 64, 5x5 s1, 12x64; the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(3, 2, 32, 2, 7, 1, 2, 2, 3, 3, 4, 0, 6, 1, 1, 0, 1),    // 30/31: Cin <= 64, 3x3 s2; the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(3, 1, 32, 3, 3, 1, 4, 1, 3, 5, 5, 3, 6, 1, 2, 0, 1),    // 32/33: 80 -> 480 -> 80, 6x32; the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(5, 1, 32, 3, 3, 1, 4, 1, 3, 7, 5, 3, 6, 1, 1, 0, 1),    // 34/35: 80 -> 480 -> 112; the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(5, 1, 32, 4, 3, 1, 4, 1, 3, 7, 5, 3, 6, 1, 1, 0, 1),    // 36/37: 112 -> 672 -> 112; the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(5, 2, 32, 4, 3, 1, 1, 4, 3, 3, 4, 1, 3, 1, 1, 0, 1),    // 38/39: 112 -> 672 -> 192 stride 2; the split-f16 twin lost
     MB_ENTRY_H(5, 1, 6, 3, 2, 2, 2, 3, 6, 4, 2, 3, 2, 1, 0),    // 40/41: 192 -> 1152 -> 192, 3x16 x 2
     MB_ENTRY_H(3, 1, 6, 3, 2, 2, 2, 3, 10, 4, 2, 3, 2, 1, 0),   // 42/43: 192 -> 1152 -> 320
-    MB_XENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 1, 4, 2, 8, 1, 2, 2, 3), MB_ENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 1, 4, 2, 8, 1, 2, 2, 1),    // 44/45: stem (2-channel spectrogram) block
-    MB_XENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 1, 4, 2, 8, 1, 2, 1, 3), MB_ENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 1, 4, 2, 8, 1, 2, 1, 1),    // 46/47: stem (1-channel spectrogram) block
+    MB_NONE, MB_ENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 1, 4, 2, 8, 1, 2, 2, 1),    // 44/45: stem (2-channel spectrogram) block; the split-f16 twin lost
+    MB_NONE, MB_ENTRY_P(3, 1, 32, 1, 3, 1, 4, 1, 2, 1, 4, 2, 8, 1, 2, 1, 1),    // 46/47: stem (1-channel spectrogram) block; the split-f16 twin lost
     // split-f16 with 16-channel chunks (k of the project GEMM zero-padded to 32): the large early images
     //         KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
     MB_ENTRY_P(3, 2, 16, 1, 5, 1, 4, 1, 1, 2, 4, 0, 4, 1, 4, 0, 3),    // 48: as 11
@@ -54,55 +54,55 @@
     MB_ENTRY_P(5, 2, 16, 1, 7, 1, 4, 1, 1, 3, 4, 0, 4, 1, 2, 0, 3),    // 50: as 13
     MB_ENTRY_P(5, 1, 16, 2, 4, 1, 4, 1, 3, 3, 4, 2, 12, 1, 2, 0, 3),   // 51: as 14
     MB_ENTRY_P(3, 2, 16, 2, 7, 1, 2, 2, 3, 3, 4, 1, 6, 1, 2, 0, 3),    // 52: as 15
-    MB_XENTRY_P(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 3, 2, 3),    // 53: as 20 (2-channel stem)
-    MB_XENTRY_P(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 3, 1, 3),    // 54: as 21 (1-channel stem)
+    MB_NONE,    // 53: lost -- was as 20 (2-channel stem)
+    MB_NONE,    // 54: lost -- was as 21 (1-channel stem)
     MB_ENTRY_P(3, 1, 16, 3, 3, 1, 4, 1, 3, 5, 5, 2, 6, 1, 2, 0, 3),    // 55: as 16 (80 -> 480 -> 80, 6x32)
-    MB_XENTRY_P(5, 1, 16, 3, 3, 1, 4, 1, 3, 7, 5, 2, 6, 1, 2, 0, 3),    // 56: as 17
-    MB_XENTRY_P(5, 1, 16, 4, 3, 1, 4, 1, 3, 7, 5, 2, 6, 1, 2, 0, 3),    // 57: as 18 (112 -> 672 -> 112)
+    MB_NONE,    // 56: lost -- was as 17
+    MB_NONE,    // 57: lost -- was as 18 (112 -> 672 -> 112)
     MB_ENTRY_P(5, 2, 16, 4, 3, 1, 1, 4, 3, 3, 4, 0, 3, 1, 2, 0, 3),    // 58: as 19
     // half-image tiles (3x32 of a 6x32 image) for the 5x5 blocks: 1.67x the expand work (cheap on the f16
     // MFMA) buys two or three workgroups per CU, whose phases then overlap
     MB_ENTRY_P(5, 1, 16, 4, 3, 1, 2, 2, 3, 4, 5, 2, 3, 1, 2, 0, 3),    // 59: 112 -> 672 -> 112
     MB_ENTRY_P(5, 1, 16, 3, 3, 1, 2, 2, 3, 4, 5, 2, 3, 1, 2, 0, 3),    // 60: 80 -> 480 -> 112
     // 32-wide tiles for the large early images: half the workgroups, half the per-workgroup set-up
-    MB_XENTRY_P(3, 2, 16, 1, 10, 1, 4, 1, 2, 2, 5, 1, 4, 1, 2, 0, 3),   // 61: as 48, tile 4x32
-    MB_XENTRY_P(3, 1, 16, 1, 6, 1, 4, 1, 4, 2, 5, 2, 8, 1, 2, 0, 3),    // 62: as 49, tile 8x32
-    MB_XENTRY_S(3, 1, 16, 2, 6, 1, 4, 1, 4, 1, 5, 2, 8, 1, 2, 2),       // 63: as 20 (stem, f32), tile 8x32
+    MB_NONE,    // 61: lost -- was as 48, tile 4x32
+    MB_NONE,    // 62: lost -- was as 49, tile 8x32
+    MB_NONE,    // 63: lost -- was as 20 (stem, f32), tile 8x32
     // four workgroups per CU for the gather-latency-bound stem block
-    MB_XENTRY_S(3, 1, 16, 2, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 4, 2),       // 64: as 20, 4 waves per SIMD
+    MB_NONE,    // 64: lost -- was as 20, 4 waves per SIMD
     MB_ENTRY_P(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 4, 2, 3),    // 65: as 53, 4 waves per SIMD
     MB_ENTRY_P(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 4, 1, 3),    // 66: as 54, 4 waves per SIMD
     // 16-channel chunks for the 3x16 blocks: with the 16-deep project step the workgroup needs < 80 KB of LDS,
     // so two share a CU
-    MB_XENTRY_P(5, 1, 16, 6, 2, 1, 2, 2, 3, 6, 4, 2, 3, 2, 2, 0, 3),    // 67: as 40 (192 -> 1152 -> 192, 3x16 x 2)
-    MB_XENTRY_P(3, 1, 16, 6, 2, 1, 2, 2, 3, 10, 4, 2, 3, 2, 2, 0, 3),   // 68: as 42 (192 -> 1152 -> 320)
-    MB_XENTRY_P(3, 2, 16, 1, 9, 1, 4, 1, 2, 2, 4, 1, 8, 1, 2, 0, 3),    // 69: as 48, tile 8x16 (17x33 source rows: 10 % halo; the one entry whose last expand group is a single row tile)
+    MB_NONE,    // 67: lost -- was as 40 (192 -> 1152 -> 192, 3x16 x 2)
+    MB_NONE,    // 68: lost -- was as 42 (192 -> 1152 -> 320)
+    MB_NONE,    // 69: lost -- was as 48, tile 8x16 (17x33 source rows: 10 % halo; the one entry whose last expand group is a single row tile)
     // whole-image tiles for the Perch-shaped stack (128 mel x 497 frames -> 8x32 and 4x16 images in the late stages)
     //         KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
     MB_ENTRY_P(3, 1, 16, 3, 4, 1, 4, 1, 4, 5, 5, 2, 8, 1, 1, 0, 3),    // 70: 80 -> 480 -> 80, 8x32
     //         KS ST KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM
-    MB_XENTRY_H(5, 1, 3, 4, 1, 4, 1, 4, 7, 5, 3, 8, 1, 1, 0),           // 71/72: 80 -> 480 -> 112, 8x32
+    MB_NONE2,    // 71/72: lost -- was 80 -> 480 -> 112, 8x32
     MB_ENTRY_H(5, 1, 4, 4, 1, 4, 1, 4, 7, 5, 3, 8, 1, 1, 0),           // 73/74: 112 -> 672 -> 112, 8x32
-    MB_XENTRY_H(5, 1, 6, 2, 2, 2, 2, 2, 6, 4, 2, 4, 1, 1, 0),           // 75/76: 192 -> 1152 -> 192, 4x16 (one segment: no spills)
-    MB_XENTRY_H(3, 1, 6, 2, 2, 2, 2, 2, 10, 4, 2, 4, 1, 1, 0),          // 77/78: 192 -> 1152 -> 320, 4x16
+    MB_NONE2,    // 75/76: lost -- was 192 -> 1152 -> 192, 4x16 (one segment: no spills)
+    MB_NONE2,    // 77/78: lost -- was 192 -> 1152 -> 320, 4x16
     // persistent twins of the early-block entries (48, 49, 65, 66, 50, 51): indices 79..84
     //          KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
-    MB_XENTRY_PP(3, 2, 16, 1, 5, 1, 4, 1, 1, 2, 4, 0, 4, 1, 4, 0, 3),    // 79: as 48 (16 -> 96 -> 24, 48x256 -> 24x128)
-    MB_XENTRY_PP(3, 1, 16, 1, 3, 1, 4, 1, 2, 2, 4, 1, 8, 1, 3, 0, 3),    // 80: as 49 (24 -> 144 -> 24, 24x128)
-    MB_XENTRY_PP(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 4, 2, 3),    // 81: as 65 (stem block, 2-channel spectrogram)
-    MB_XENTRY_PP(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 4, 1, 3),    // 82: as 66 (stem block, 1-channel spectrogram)
-    MB_XENTRY_PP(5, 2, 16, 1, 7, 1, 4, 1, 1, 3, 4, 0, 4, 1, 2, 0, 3),    // 83: as 50 (24 -> 144 -> 40, 5x5 s2)
-    MB_XENTRY_PP(5, 1, 16, 2, 4, 1, 4, 1, 3, 3, 4, 2, 12, 1, 2, 0, 3),   // 84: as 51 (40 -> 240 -> 40, 5x5 s1)
+    MB_NONE,    // 79: lost -- was as 48 (16 -> 96 -> 24, 48x256 -> 24x128)
+    MB_NONE,    // 80: lost -- was as 49 (24 -> 144 -> 24, 24x128)
+    MB_NONE,    // 81: lost -- was as 65 (stem block, 2-channel spectrogram)
+    MB_NONE,    // 82: lost -- was as 66 (stem block, 1-channel spectrogram)
+    MB_NONE,    // 83: lost -- was as 50 (24 -> 144 -> 40, 5x5 s2)
+    MB_NONE,    // 84: lost -- was as 51 (40 -> 240 -> 40, 5x5 s1)
     // column-task depthwise phase for the whole-image late blocks (kernels_mbconv.hip, COLTH): 85..92.  Measured (us per 1 000
     // segments, same box): 344 -> 309 (80 -> 480 -> 112), 493 -> 453 (112 -> 672 -> 112), 337 -> 286 (192 -> 1152 -> 192),
     // 335 -> 298 (192 -> 1152 -> 320).  Tried and dropped: the 3x3 6x32 block with 32-channel chunks (279 against 239 for
     // entry 55's 16-channel chunks) and the Perch-sized 8x32 blocks (8 rows x 5 columns of E in registers: 417 / 604 against
     // 384 / 557).
     //          KS ST KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM
-    MB_XENTRY_HC(5, 1, 3, 3, 1, 4, 1, 3, 7, 5, 3, 6, 1, 1, 0),           // 85/86: as 34/35 (80 -> 480 -> 112, 6x32)
-    MB_XENTRY_HC(5, 1, 4, 3, 1, 4, 1, 3, 7, 5, 3, 6, 1, 1, 0),           // 87/88: as 36/37 (112 -> 672 -> 112, 6x32)
-    MB_XENTRY_HC(5, 1, 6, 3, 2, 2, 2, 3, 6, 4, 2, 3, 2, 1, 0),           // 89/90: as 40/41 (192 -> 1152 -> 192, 3x16 x 2)
-    MB_XENTRY_HC(3, 1, 6, 3, 2, 2, 2, 3, 10, 4, 2, 3, 2, 1, 0),          // 91/92: as 42/43 (192 -> 1152 -> 320, 3x16 x 2)
+    MB_NONE2,    // 85/86: lost -- was as 34/35 (80 -> 480 -> 112, 6x32)
+    MB_NONE2,    // 87/88: lost -- was as 36/37 (112 -> 672 -> 112, 6x32)
+    MB_NONE2,    // 89/90: lost -- was as 40/41 (192 -> 1152 -> 192, 3x16 x 2)
+    MB_NONE2,    // 91/92: lost -- was as 42/43 (192 -> 1152 -> 320, 3x16 x 2)
     // Perch-sized images (16x63, 8x32 -> 4x16): the entries above need tile heights that leave a ragged second tile row there
     //         KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
     MB_ENTRY_P(5, 1, 16, 2, 4, 1, 4, 1, 2, 3, 4, 1, 8, 1, 2, 0, 3),    // 93: 40 -> 240 -> 40 at 16x63: 8-row tiles, 16-channel chunks
@@ -110,8 +110,8 @@
     //          KS ST KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM
     // (measured on the Perch-shaped model, us per 1 000 segments: 1 283 -> 862 with 93, 1 058 -> 555 with 94, 500 -> 431 and
     //  441 -> 393 with 95 / 97; config 4 82 -> 91 k segments/s)
-    MB_XENTRY_HC(5, 1, 6, 2, 2, 2, 2, 2, 6, 4, 2, 4, 1, 1, 0),           // 95/96: as 75/76 (192 -> 1152 -> 192, 4x16), column tasks
-    MB_XENTRY_HC(3, 1, 6, 2, 2, 2, 2, 2, 10, 4, 2, 4, 1, 1, 0),          // 97/98: as 77/78 (192 -> 1152 -> 320, 4x16), column tasks
+    MB_NONE2,    // 95/96: lost -- was as 75/76 (192 -> 1152 -> 192, 4x16), column tasks
+    MB_NONE2,    // 97/98: lost -- was as 77/78 (192 -> 1152 -> 320, 4x16), column tasks
     // 8-wave workgroups (WM x WN = 8: two waves per SIMD inside the ONE workgroup a CU holds of these whole-image tiles), column
     // tasks of two channels per lane (512 per chunk); P1 with the chunk's two column tiles on two waves
     MB_ENTRY_HC(5, 1, 3, 3, 2, 4, 2, 3, 4, 5, 3, 6, 1, 2, 0),           // 99/100: as 85/86 (80 -> 480 -> 112, 6x32)
@@ -155,18 +155,18 @@
 
     // Larger tiles for the two early stride-2 / stride-1 3x3 blocks, re-measured with the degree-5 GELU (round 2's 61 / 62 / 69 lost
     // with the dearer activation): less halo and half the per-tile set-up against a workgroup per CU less.  They lose again
-    // (EXPERIMENTS build, tools/ab_prefer_x.sh, us per 1 000 segments): 16 -> 96 -> 24 890-906 -> 1 016-1 023 (137) / 961-985 (69);
+    // (us per 1 000 segments): 16 -> 96 -> 24 890-906 -> 1 016-1 023 (137) / 961-985 (69);
     // 24 -> 144 -> 24 644-654 -> 685-701 (138) / 759-768 (139) -- occupancy hides more than the halo costs.
     //          KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
-    MB_XENTRY_P(3, 2, 16, 1, 9, 1, 4, 1, 2, 2, 4, 1, 8, 1, 3, 0, 3),    // 137: as 69 (16 -> 96 -> 24, tile 8x16) at three waves per SIMD
-    MB_XENTRY_P(3, 1, 16, 1, 4, 1, 4, 1, 3, 2, 4, 2, 12, 1, 3, 0, 3),   // 138: 24 -> 144 -> 24, tile 12x16 (halo 1.31 against 1.41)
-    MB_XENTRY_P(3, 1, 16, 1, 8, 1, 4, 1, 6, 2, 4, 3, 24, 1, 2, 0, 3),   // 139: 24 -> 144 -> 24, tile 24x16 = the image's height (halo 1.125)
+    MB_NONE,    // 137: lost -- was as 69 (16 -> 96 -> 24, tile 8x16) at three waves per SIMD
+    MB_NONE,    // 138: lost -- was 24 -> 144 -> 24, tile 12x16 (halo 1.31 against 1.41)
+    MB_NONE,    // 139: lost -- was 24 -> 144 -> 24, tile 24x16 = the image's height (halo 1.125)
 
 
-    // STRIP-WALKING twins (PERSIST = 2, mbconv_kernel.hpp) of the early-block entries 48 / 49 / 65 / 66 / 50: a workgroup walks one
+    // Tile-row-walking twins (the kernel's PERSIST = 2 form, gone with them) of the early-block entries 48 / 49 / 65 / 66 / 50: a workgroup walks one
     // tile column of one segment from the top of the image to the bottom and inherits the last KS - ST expanded rows of every tile
     // from the tile above through an LDS halo store instead of expanding them again (VERDICT r3 next #1).  Parity-green
-    // (tools/gpu_block_debug.py), measured (EXPERIMENTS build, tools/ab_blocks.sh, profiles/r4_b_strip_ab.txt, us per 1 000 segments,
+    // (tools/gpu_block_debug.py), measured (profiles/r4_b_strip_ab.txt, us per 1 000 segments,
     // same box) and REJECTED: stem block 724 -> 767-782, 16 -> 96 -> 24 824 -> 1 037-1 056, 24 -> 144 -> 24 610 -> 842-895,
     // 5x5 stride 2 522 -> 1 014-1 104.  The halo store (5.8 / 15.8 / 25.9 / 75.6 KB) costs workgroups per CU (4 -> 4 / 3 / 2 / 1) and
     // these kernels' time follows the workgroups per CU almost proportionally; at EQUAL occupancy (the stem block) the walk still
@@ -174,18 +174,18 @@
     // plain tile), so the rows that are no longer expanded shorten no phase, while the halo copies and the barrier that ends a
     // tile row lengthen each step (DESIGN.md section 3).
     //          KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
-    MB_XENTRY_PW(3, 2, 16, 1, 5, 1, 4, 1, 1, 2, 4, 0, 4, 1, 4, 0, 3),    // 140: as 48 (16 -> 96 -> 24, 48x256 -> 24x128)
-    MB_XENTRY_PW(3, 1, 16, 1, 3, 1, 4, 1, 2, 2, 4, 1, 8, 1, 3, 0, 3),    // 141: as 49 (24 -> 144 -> 24, 24x128)
-    MB_XENTRY_PW(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 4, 2, 3),    // 142: as 65 (stem block, 2-channel spectrogram)
-    MB_XENTRY_PW(3, 1, 16, 1, 3, 1, 4, 1, 2, 1, 4, 1, 8, 1, 4, 1, 3),    // 143: as 66 (stem block, 1-channel spectrogram)
-    MB_XENTRY_PW(5, 2, 16, 1, 7, 1, 4, 1, 1, 3, 4, 0, 4, 1, 2, 0, 3),    // 144: as 50 (24 -> 144 -> 40, 5x5 stride 2, 24x128 -> 12x64)
+    MB_NONE,    // 140: lost -- was as 48 (16 -> 96 -> 24, 48x256 -> 24x128)
+    MB_NONE,    // 141: lost -- was as 49 (24 -> 144 -> 24, 24x128)
+    MB_NONE,    // 142: lost -- was as 65 (stem block, 2-channel spectrogram)
+    MB_NONE,    // 143: lost -- was as 66 (stem block, 1-channel spectrogram)
+    MB_NONE,    // 144: lost -- was as 50 (24 -> 144 -> 40, 5x5 stride 2, 24x128 -> 12x64)
 
     // Occupancy twins (round 4, once the strip walk had shown how closely these kernels' time follows the workgroups per CU): the
     // same tiles with one more wave per SIMD allowed where LDS has room for the extra workgroup.
     //         KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
-    MB_XENTRY_P(3, 1, 16, 1, 3, 1, 4, 1, 2, 2, 4, 1, 8, 1, 4, 0, 3),    // 145: as 49 (24 -> 144 -> 24) at four waves per SIMD (33 KB of LDS: four fit)
-    MB_XENTRY_P(5, 2, 16, 1, 7, 1, 4, 1, 1, 3, 4, 0, 4, 1, 3, 0, 3),    // 146: as 50 (5x5 stride 2) at three
-    MB_XENTRY_P(5, 1, 16, 2, 4, 1, 4, 1, 3, 3, 4, 2, 12, 1, 3, 0, 3),   // 147: as 51 (5x5 at 12x64) at three
+    MB_NONE,    // 145: lost -- was as 49 (24 -> 144 -> 24) at four waves per SIMD (33 KB of LDS: four fit)
+    MB_NONE,    // 146: lost -- was as 50 (5x5 stride 2) at three
+    MB_NONE,    // 147: lost -- was as 51 (5x5 at 12x64) at three
     // Two-wave workgroups on half-width tiles (round 4): twice the independent barrier domains per CU at the same waves per SIMD
     // (7 workgroups of 128 threads fit: 20 KB of LDS each), 3 % more halo for the stride-2 block, 11 % for the stride-1 ones.
     // REJECTED, measured (us per 1 000 segments, medians of 3 alternations on one box, parity green): 780 -> 863 (stem), 890 -> 925,
@@ -193,11 +193,11 @@
     // (ACTIVE_INST_VALU x waves ~ 0.9, profiles/r4_z_sq_counters.txt), so more barrier domains buy nothing and every extra
     // expanded pixel costs its share.
     //         KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
-    MB_XENTRY_P(3, 2, 16, 1, 5, 1, 2, 1, 1, 2, 3, 0, 4, 1, 4, 0, 3),    // 148: 16 -> 96 -> 24, tile 4x8 (9 x 17 source rows = 10 row tiles)
-    MB_XENTRY_P(3, 1, 16, 1, 4, 1, 2, 1, 2, 1, 3, 1, 8, 1, 4, 2, 3),    // 149: stem block, tile 8x8 (10 x 10 = 7 row tiles)
-    MB_XENTRY_P(3, 1, 16, 1, 4, 1, 2, 1, 2, 2, 3, 1, 8, 1, 4, 0, 3),    // 150: 24 -> 144 -> 24, tile 8x8
-    // The Perch-sized late-block entries that 119-130 replaced in round 4, and the alternatives measured beside them (EXPERIMENTS
-    // build; us per 1 000 segments on one box, bench.py --config c4, profiles/r4_k_perch_blocks.txt).  Two things were wrong with
+    MB_NONE,    // 148: lost -- was 16 -> 96 -> 24, tile 4x8 (9 x 17 source rows = 10 row tiles)
+    MB_NONE,    // 149: lost -- was stem block, tile 8x8 (10 x 10 = 7 row tiles)
+    MB_NONE,    // 150: lost -- was 24 -> 144 -> 24, tile 8x8
+    // The Perch-sized late-block entries that 119-130 replaced in round 4, and the alternatives measured beside them
+    // (us per 1 000 segments on one box, bench.py --config c4, profiles/r4_k_perch_blocks.txt).  Two things were wrong with
     // them: (1) hipcc sank each window column's FMAs of the 5x5 column tasks below the loads of the next two columns (three columns
     // and their taps in flight, +60 registers; fixed for every 8-wave column task by pinning the sums after each column,
     // mbconv_kernel.hpp MB_P2_PIN): 96 -> 576 -> 136 679 -> 408, 232 -> 1392 -> 232 642 -> 366 with the entries unchanged; (2) the
@@ -207,23 +207,23 @@
     //   384 -> 2304 -> 384 1 110 -> 1 052 (two segments, 396 B of scratch: 161) / 890 (one segment, column pair: now 129)
     // config 4: 46.5 k -> 50.8 k (pin alone) -> 54.4 k segments/s.
     //          KS ST KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM
-    MB_XENTRY_HC(5, 1, 5, 2, 1, 4, 2, 4, 5, 5, 3, 8, 1, 2, 0),           // 151/152: 136 -> 816 -> 136 with the project phase as 4 x 2 waves (561 against 544)
-    MB_XENTRY_HC(5, 1, 3, 4, 2, 4, 2, 4, 5, 5, 3, 8, 1, 2, 0),           // 153/154: 119 until round 4
-    MB_XENTRY_HC(3, 1, 3, 2, 1, 4, 2, 4, 3, 5, 3, 8, 1, 2, 0),           // 155/156: 96 -> 576 -> 96 without the column split (290 against 117's 296: noise)
-    MB_XENTRY_HC(5, 1, 8, 2, 2, 4, 2, 2, 8, 4, 2, 4, 2, 2, 0),           // 157/158: 125 until round 4
-    MB_XENTRY_HC(3, 1, 8, 2, 2, 2, 2, 2, 12, 4, 2, 4, 1, 1, 0),          // 159/160: 127 until round 4
-    MB_XENTRY_HC(3, 1, 12, 1, 1, 4, 2, 2, 12, 4, 2, 4, 2, 2, 0),         // 161/162: 384 -> 2304 -> 384, two segments, no column split (1 052)
-    MB_XENTRY_H(5, 1, 5, 4, 1, 4, 1, 4, 9, 5, 3, 8, 1, 1, 0),            // 163/164: 121 until round 4 (4 waves, row tasks)
+    MB_NONE2,    // 151/152: lost -- was 136 -> 816 -> 136 with the project phase as 4 x 2 waves (561 against 544)
+    MB_NONE2,    // 153/154: lost -- was 119 until round 4
+    MB_NONE2,    // 155/156: lost -- was 96 -> 576 -> 96 without the column split (290 against 117's 296: noise)
+    MB_NONE2,    // 157/158: lost -- was 125 until round 4
+    MB_NONE2,    // 159/160: lost -- was 127 until round 4
+    MB_NONE2,    // 161/162: lost -- was 384 -> 2304 -> 384, two segments, no column split (1 052)
+    MB_NONE2,    // 163/164: lost -- was 121 until round 4 (4 waves, row tasks)
     // the same for the BirdNET-v2.4-shaped late blocks (no-split twins of 99 / 101 / 113 / 103 / 105): within +-1 % of the split
     // entries there (three k steps: the fragments fit either way), not taken; and the 8-wave twins of 129 / 127
-    MB_XENTRY_HC(5, 1, 3, 2, 1, 4, 2, 3, 4, 5, 3, 6, 1, 2, 0),           // 165/166: as 99 (80 -> 480 -> 112, 6x32)
-    MB_XENTRY_HC(5, 1, 4, 2, 1, 4, 2, 3, 4, 5, 3, 6, 1, 2, 0),           // 167/168: as 101 (112 -> 672 -> 112, 6x32)
-    MB_XENTRY_HC(3, 1, 3, 2, 1, 4, 2, 3, 3, 5, 3, 6, 1, 2, 0),           // 169/170: as 113 (80 -> 480 -> 80, 3x3 at 6x32)
-    MB_XENTRY_HC(5, 1, 6, 1, 1, 2, 4, 3, 3, 4, 2, 3, 2, 2, 0),           // 171/172: as 103 (192 -> 1152 -> 192, 3x16 x 2)
-    MB_XENTRY_HC(3, 1, 6, 2, 2, 2, 4, 3, 5, 4, 2, 3, 2, 2, 0),           // 173/174: 105 until round 4 (column split)
-    MB_XENTRY_HC(3, 1, 12, 2, 2, 2, 2, 2, 12, 4, 2, 4, 1, 1, 0),         // 175/176: 129 until round 4 (4 waves)
-    MB_XENTRY_HC(3, 1, 8, 1, 2, 2, 4, 2, 6, 4, 2, 4, 1, 2, 0),           // 177/178: 232 -> 1392 -> 384 at 4x16, one segment, 8 waves (483)
-    MB_XENTRY_HC(3, 1, 6, 2, 2, 4, 2, 2, 10, 4, 2, 4, 2, 2, 0),          // 179/180: 109 until round 4 (column split)
+    MB_NONE2,    // 165/166: lost -- was as 99 (80 -> 480 -> 112, 6x32)
+    MB_NONE2,    // 167/168: lost -- was as 101 (112 -> 672 -> 112, 6x32)
+    MB_NONE2,    // 169/170: lost -- was as 113 (80 -> 480 -> 80, 3x3 at 6x32)
+    MB_NONE2,    // 171/172: lost -- was as 103 (192 -> 1152 -> 192, 3x16 x 2)
+    MB_NONE2,    // 173/174: lost -- was 105 until round 4 (column split)
+    MB_NONE2,    // 175/176: lost -- was 129 until round 4 (4 waves)
+    MB_NONE2,    // 177/178: lost -- was 232 -> 1392 -> 384 at 4x16, one segment, 8 waves (483)
+    MB_NONE2,    // 179/180: lost -- was 109 until round 4 (column split)
     // Perch-sized stack on the f32 MFMA (v_mfma_f32_16x16x4_f32; the path BH_FLAG_AUTO re-runs a row on): round 3 fused 6 of its 26
     // blocks there.  KG counts 16-deep k steps; 816 and 1392 expanded channels are not multiples of 32, so those blocks run 16-channel
     // chunks (256 column tasks on 512 threads).
@@ -250,25 +250,25 @@
     MB_ENTRY_HC(3, 1, 3, 1, 2, 4, 2, 1, 3, 3, 3, 6, 1, 2, 0),           // 197/198: 80 -> 480 -> 80, 3x3
     MB_ENTRY_HC(5, 1, 6, 1, 2, 2, 4, 1, 3, 3, 2, 3, 1, 2, 0),           // 199/200: 192 -> 1152 -> 192, 3x16 in two 3x8 tiles
     MB_ENTRY_HC(3, 1, 6, 1, 2, 2, 4, 1, 5, 3, 2, 3, 1, 2, 0),           // 201/202: 192 -> 1152 -> 320
-    // Measured (tools/gpu_narrow_check.py, tools/gpu_quick_bench.py under rocprofv3 at 20 segments, us per launch): 76.6 -> 47.8
+    // Measured (tools/gpu_quick_bench.py under rocprofv3 at 20 segments, us per launch): 76.6 -> 47.8
     // (112 -> 672 -> 112), 53.0 -> 33.6, 46.0 -> 24.9 (3x3), 69.7 -> 58.4 and 83.6 -> 66.8 (the 3x16 pair: 36 chunks of weights are
     // the chain there, not the pixels); a forward of 20 segments 1.011 -> 0.824 ms, of 64 1.163 -> 0.973; taken while the narrow
     // tiles number at most 256 (round 5: at 512 launches of 96-256 segments lost 2-4 %, profiles/r5_g_narrow_tiles_sweep.txt; at
     // 1 024 a launch of 192 segments loses 10 %).
     //         KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
-    MB_XENTRY_P(5, 2, 16, 4, 2, 1, 1, 4, 2, 3, 3, 0, 3, 1, 2, 0, 3),    // 203: 112 -> 672 -> 192, 5x5 stride 2, 6x32 -> 3x16 in two 3x8 tiles (as 58): 87 -> 91 us, not taken
+    MB_NONE,    // 203: lost -- was 112 -> 672 -> 192, 5x5 stride 2, 6x32 -> 3x16 in two 3x8 tiles (as 58): 87 -> 91 us, not taken
     // 8-wave workgroups on DOUBLE tiles for the three early blocks (round 4, late): a workgroup's fixed cost -- tile decode, output
     // map, grid zero fill, weight DMA, accumulator set-up: ~1 000 instructions a wave, 39 % of the stem block's time with nothing
     // else running (profiles/r4_m_setup_share.txt) -- paid once per 256 (128) output pixels instead of 128 (64), at the SAME four
     // waves per SIMD (two workgroups of 512 threads per CU instead of four of 256) and less halo (1.27 / 1.10 / 1.27 against 1.41 /
-    // 1.16 / 1.41 expanded pixels per output pixel).  REJECTED, measured (us per 1 000 segments, medians of 3 alternations, EXPERIMENTS
-    // build, parity green): stem 778 -> 822, 16 -> 96 -> 24 905 -> 970, 24 -> 144 -> 24 651 -> 920.  Eight waves that meet at every barrier
+    // 1.16 / 1.41 expanded pixels per output pixel).  REJECTED, measured (us per 1 000 segments, medians of 3 alternations,
+    // parity green): stem 778 -> 822, 16 -> 96 -> 24 905 -> 970, 24 -> 144 -> 24 651 -> 920.  Eight waves that meet at every barrier
     // of the chunk loop lose more than the halved fixed cost returns: four independent 4-wave workgroups per CU remain the best
     // shape found for these blocks (strip walking, two-wave tiles, larger 4-wave tiles and these all lost to it).
     //         KS ST CE KG RT NCS WM WN MT NT TWL XBL TH S OCC STEM PREC
-    MB_XENTRY_P(3, 1, 16, 1, 3, 1, 8, 1, 2, 1, 4, 1, 16, 1, 4, 2, 3),   // 204: stem block, tile 16x16
-    MB_XENTRY_P(3, 2, 16, 1, 5, 1, 8, 1, 1, 2, 4, 0, 8, 1, 4, 0, 3),    // 205: 16 -> 96 -> 24, tile 8x16 (17 x 33 source pixels = 36 row tiles)
-    MB_XENTRY_P(3, 1, 16, 1, 3, 1, 8, 1, 2, 2, 4, 1, 16, 1, 4, 0, 3),   // 206: 24 -> 144 -> 24, tile 16x16
+    MB_NONE,    // 204: lost -- was stem block, tile 16x16
+    MB_NONE,    // 205: lost -- was 16 -> 96 -> 24, tile 8x16 (17 x 33 source pixels = 36 row tiles)
+    MB_NONE,    // 206: lost -- was 24 -> 144 -> 24, tile 16x16
     // One-segment twins of 125-128 (the Perch-sized plan's 4x16 stages, two segments per workgroup), round 5: as 133-136 for the
     // 3x16 blocks -- and the only twins a squeeze-excite block takes: its pooled sums come out of the one-segment tile in the very
     // order the two-segment tile adds them (kernels_mbconv.hip mb_twin_sums_match: 64 pixels a segment on 64 thread rows), so a

@@ -37,7 +37,7 @@ def test_library_exports_every_declared_symbol(L):
     names = _declared("birda_hip.h") + _declared("birda_host.h") + _declared("birda_hip_debug.h")
     assert len(names) >= 40
     # the diagnostic entry points live in their own header: the one birda binds (and the Rust text generated from it) has none
-    assert _declared("birda_hip_debug.h") == ["bh_debug_gated_gemm", "bh_debug_mb_stamps", "bh_debug_read_tensor"]
+    assert _declared("birda_hip_debug.h") == ["bh_debug_gated_gemm", "bh_debug_read_tensor"]
     assert not [n for n in _declared("birda_hip.h") if "debug" in n]
     assert "bh_debug" not in open(os.path.join(ROOT, "include", "birda_hip_sys.rs")).read()
     bound = {n for n, _, _ in _lib.SYMBOLS + _lib.HOST_SYMBOLS}
@@ -347,7 +347,7 @@ def test_shipped_tile_configurations_are_the_reachable_ones():
     """the product library ships what the planner can reach, nothing else.  tools/plan_models.py walks every
     synthetic model (BirdNET-v2.4-shaped, Perch-sized, Perch-shaped, the small test stacks) in the three precisions and the three
     templated activations through bh_plan_fused_blocks (host logic, no GPU); every MB_ENTRY row of mbconv_cfgs.inc must be picked
-    somewhere, and the rejected experiments (MB_XENTRY rows, kernels_mbwave.hip, the persistent variants) must not be in the
+    somewhere, and the rejected experiments (the MB_NONE placeholder rows, kernels_mbwave.hip, the persistent variants) must not be in the
     build."""
     import ctypes as C
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -460,8 +460,8 @@ def test_directory_mode_assignment_by_duration():
 
 
 def test_environment_names_in_the_shipped_library_are_the_documented_ones():
-    """debug / A-B getenv knobs are compiled out of the product build (BH_XENV, kernels.hpp: they exist behind
-    `make EXPERIMENTS=1`).  What `strings` finds in the shipped .so must be the documented list."""
+    """the library has no debug / A-B getenv knobs (kernels.hpp lists what it reads).  What `strings` finds
+    in the shipped .so must be the documented list."""
     import re
     import subprocess
     so = os.path.join(ROOT, "birda_amd", "libbirda_hip.so")

@@ -543,7 +543,7 @@ def test_column_task_late_blocks_against_the_row_task_ones(full_model, oracle_li
     scale = max(1.0, float(np.abs(ref).max()))
     out = {}
     # row-task entries that ship: 59 / 60 (half-image tiles of the 5x5 6x32 blocks), 40-43 (3x16 x 2), 55 / 33 (3x3 at 6x32) -- their
-    # 4-wave whole-image twins 34 / 36 are measured alternatives now (mbconv_cfgs.inc MB_XENTRY, make EXPERIMENTS=1)
+    # 4-wave whole-image twins 34 / 36 are measured alternatives that lost (mbconv_cfgs.inc: MB_NONE placeholder rows)
     for tag, prefer in (("column", None), ("row", "59,60,40,42,55" if precision == "f16x3" else "35,37,41,43,33")):
         if prefer:
             monkeypatch.setenv("BIRDA_HIP_MB_PREFER", prefer)
@@ -620,8 +620,8 @@ def test_fused_block_outputs_match_oracle_tensor_by_tensor(model_dir, oracle_lib
 
 
 def test_every_fused_tile_configuration(model_dir, oracle_lib, monkeypatch):
-    """Force each SHIPPED tile configuration in turn (mbconv_cfgs.inc MB_ENTRY rows; the MB_XENTRY rows are not part of the product
-    build); blocks it cannot run fall back to the layer kernels.  The precision is the configuration's own (template argument 15:
+    """Force each SHIPPED tile configuration in turn (mbconv_cfgs.inc MB_ENTRY rows; the MB_NONE rows are placeholders of
+    alternatives that lost); blocks it cannot run fall back to the layer kernels.  The precision is the configuration's own (template argument 15:
     0 f32 MFMA, 3 split f16, 1 plain f16)."""
     from birda_amd import synth
     from birda_amd._lib import load

@@ -8,20 +8,14 @@
 #   tools/ab.sh legs "A=1 B=2" "A=0" ... the host-fed legs of bench.py (h2d_inclusive, end_to_end) under each set of assignments
 #   tools/ab.sh prof VAR v1 v2 ...       rocprofv3 --kernel-trace --stats of tools/gpu_quick_bench.py per value: per-kernel averages
 #   tools/ab.sh pmc TAG VAR v1 v2 ...    FETCH_SIZE / WRITE_SIZE passes per value (tools/pmc_summary.py)
-#   tools/ab.sh x CMD ...                CMD with the EXPERIMENTS build swapped in (see LIBX)
 #
-# Environment: REPS (2), STEPS (10), BENCH_ARGS (extra bench.py arguments), MODEL / NSEG for prof (birdnet_v24 / 1000), LIBX=1 =
-# run with the EXPERIMENTS build of the library swapped in (tools/ab/libbirda_hip_x.so, built with
-#   make -C birda_amd/csrc EXPERIMENTS=1 BUILD=_build_x LIB=../../tools/ab/libbirda_hip_x.so
-# -- it carries the measured alternatives of mbconv_cfgs.inc, the phase clock and the A/B switches that the product build compiles
-# out: BIRDA_HIP_MB_DBG / _MEL_DBG ablation bits, _LANES, _NLANES, _SUBSLICES, _FIRST_SUBSLICE, _MB_TWIN, _MB_RING, _MB_PERSIST,
-# _MEL_PAIR, _EVENT_FENCE, _RESAMPLE_F32, _STEM_F32, BIRDA_HOST_PACK_SUBSLICES; kernels.hpp BH_XENV).
+# Environment: REPS (2), STEPS (10), BENCH_ARGS (extra bench.py arguments), MODEL / NSEG for prof (birdnet_v24 / 1000).
+# An alternative that is not an environment name of the library is measured as a second BUILD: `lib`.
 cd ${GRAFT_REPO_ROOT:-.}
 root=$(pwd)
 mode=$1; shift
 swap_in() { cp birda_amd/libbirda_hip.so /tmp/libbirda_hip_keep.so; cp "$1" birda_amd/libbirda_hip.so; }
 swap_out() { cp /tmp/libbirda_hip_keep.so birda_amd/libbirda_hip.so; }
-[ -n "$LIBX" ] && [ "$mode" != lib ] && swap_in tools/ab/libbirda_hip_x.so
 row() {   # label -> one line: value, median of five, mel, mbconv, per-block times
   python bench.py --full --no-cpu-baseline --no-extra-legs --steps ${STEPS:-10} --warmup 2 $BENCH_ARGS "${@:2}" 2>/tmp/ab_err.txt | python -c "
 import json,sys
@@ -75,8 +69,6 @@ pmc)  tag=$1; var=$2; shift 2; cd /tmp && export TMPDIR=/tmp
         rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/pmc_write -- python3 $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra-legs > /dev/null 2> $out/pmc_write.log
         python3 $root/tools/pmc_summary.py $out $out/traffic.json > $out/traffic.txt; echo "== $var=$v"; head -4 $out/traffic.txt; rm -rf $out/pmc_fetch $out/pmc_write
       done; cd $root ;;
-x)    [ -z "$LIBX" ] && swap_in tools/ab/libbirda_hip_x.so; "$@"; [ -z "$LIBX" ] && swap_out ;;
-*)    sed -n 2,22p $0 ;;
+*)    sed -n 2,13p $0 ;;
 esac
-[ -n "$LIBX" ] && [ "$mode" != lib ] && swap_out
 exit 0

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds A/B variants of libbirda_hip.so that differ in the compile-time switches of ONE translation unit (default: the GELU copy of
 # the fused MBConv kernel, the one the BirdNET-v2.4-shaped model runs): tools/ab/libbirda_hip_<tag>.so for every "tag:-DFLAG=.. .."
-#   tools/build_variants.sh "base:-DBH_MB_BUFLOAD=0 -DBH_MB_HOSTRCP=0 -DBH_MB_CONSTDIV=0" "buf:-DBH_MB_BUFLOAD=1 -DBH_MB_HOSTRCP=0 -DBH_MB_CONSTDIV=0" ...
+#   tools/build_variants.sh "a:-DSWITCH=0" "b:-DSWITCH=1"   (SWITCH: a compile-time switch of that unit) ...
 # UNIT=kernels_frontend builds variants of another unit.  The other objects are the current build's (make first).
 cd "$(dirname "$0")/../birda_amd/csrc" || exit 1
 unit=${UNIT:-kernels_mbconv_gelu}
