@@ -338,6 +338,13 @@ REDUCE_DEBUG_SYMBOLS = [
     ("bh_debug_reduce_on_device", C.c_int, [C.c_int, _VP, _VP, _SZ, _VP, C.c_int, C.c_int, _VP, _SZ]),
 ]
 
+# include/birda_hip_bnact_debug.h: one norm + activation launch (OP_BNACT) alone, for the tests that hold it to float64
+BNACT_DEBUG_SYMBOLS = [
+    ("bh_debug_bnact", C.c_int, [C.c_int, _VP, _VP, _VP, C.c_int, _VP, _SZ, _SZ, _VP, _SZ]),
+    ("bh_debug_bnact_on_device", C.c_int, [C.c_int, _VP, _VP, _VP, C.c_int, _VP, _SZ, _SZ, _SZ, _VP, _SZ]),
+    ("bh_debug_scale_on_device", C.c_int, [C.c_int, _VP, _VP, _VP, _SZ, _SZ, _SZ, _VP, _SZ]),
+]
+
 _lib = None
 
 
@@ -350,7 +357,7 @@ def load():
         raise RuntimeError(f"{LIB_PATH} is missing: build it with `make -C birda_amd/csrc` "
                            "(the HIP hot path has no CPU fallback)")
     L = C.CDLL(LIB_PATH)
-    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS + GCONV_DEBUG_SYMBOLS + GATE_DEBUG_SYMBOLS + PCM_DEBUG_SYMBOLS + RESAMPLE_DEBUG_SYMBOLS + CONCAT_DEBUG_SYMBOLS + CUSTOM_DEBUG_SYMBOLS + GATED_DEBUG_SYMBOLS + DILATED_DEBUG_SYMBOLS + LNORM_DEBUG_SYMBOLS + REDUCE_DEBUG_SYMBOLS:
+    for name, res, args in SYMBOLS + HOST_SYMBOLS + AUDIT_SYMBOLS + LAYER_DEBUG_SYMBOLS + BLOCK_DEBUG_SYMBOLS + TERMS_DEBUG_SYMBOLS + POOL_DEBUG_SYMBOLS + RESACT_DEBUG_SYMBOLS + GCONV_DEBUG_SYMBOLS + GATE_DEBUG_SYMBOLS + PCM_DEBUG_SYMBOLS + RESAMPLE_DEBUG_SYMBOLS + CONCAT_DEBUG_SYMBOLS + CUSTOM_DEBUG_SYMBOLS + GATED_DEBUG_SYMBOLS + DILATED_DEBUG_SYMBOLS + LNORM_DEBUG_SYMBOLS + REDUCE_DEBUG_SYMBOLS + BNACT_DEBUG_SYMBOLS:
         fn = getattr(L, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

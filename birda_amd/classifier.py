@@ -194,8 +194,9 @@ class BirdClassifier:
 
     def layer_kernel(self, layer: int) -> str:
         """bh_debug_layer_kernel: the split-f16 GEMM instantiation model layer `layer` launched in the last forward ('' if none); a
-        grouped convolution, a concat, a dilated or 7x7 depthwise layer, a LayerNorm and a reduce layer name their kernels in every mode
-        ("lnorm_kernel<32,3>": lanes a pixel, 16-byte pieces a lane; "reduce_kernel<MAXMEAN,8>": the mode, lanes a value)."""
+        grouped convolution, a concat, a dilated or 7x7 depthwise layer, a LayerNorm, a reduce layer and a norm + activation layer name their
+        kernels in every mode ("lnorm_kernel<32,3>": lanes a pixel, 16-byte pieces a lane; "reduce_kernel<MAXMEAN,8>": the mode, lanes a
+        value; "bnact_kernel": one instantiation, the activation a run-time argument)."""
         buf = C.create_string_buffer(160)
         self._L.bh_debug_layer_kernel(self._h, layer, buf, 160)
         return buf.value.decode()

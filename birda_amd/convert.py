@@ -2,7 +2,7 @@
 
 `model_from_graph` turns the classifier part of an ONNX graph -- from the spectrogram tensor
 [N, C, H, W] to the logits -- into the layer table `modelfile.py` describes: Conv (group 1 / depthwise
-/ 1x1 / any other group count: OP_GCONV) with BatchNormalization folded, the activation that follows folded into the producing layer
+/ 1x1 / any other group count: OP_GCONV) with BatchNormalization folded (or, with its activation, on a pool output, a concat, a residual sum or an activated convolution, one OP_BNACT record: DenseNet, pre-activation ResNets), the activation that follows folded into the producing layer
 (Relu, Clip 0..6, Sigmoid*x, the Div-Erf-Add-Mul-Mul spelling of exact GELU, a fused `Gelu`; MobileNetV3's hard swish as `HardSwish`,
 as HardSigmoid(1/6, 1/2)*x or as the Add 3 - Clip 0..6 - Mul x - Mul 1/6 chain, its hard-sigmoid gate as HardSigmoid(1/6, 1/2) or that
 chain without the Mul x),
@@ -152,7 +152,7 @@ REDUCE_SPELLING_OPTIONS = {"keep", "input", "neg", "gmp", "swap", "argmax"}
 
 
 def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op",
-                     spell_lnorm: str = "node", spell_reduce: str = "") -> ox.Graph:
+                     spell_lnorm: str = "node", spell_reduce: str = "", spell_concat: str = "pair") -> ox.Graph:
     """The conv stack of a BHM1 model as an ONNX graph over `spectrogram` [N, C, H, W] -- or, with `frontend_spelling`
     (see `frontend_nodes`), the whole model over `audio` [N, S].
     spell_gelu: 'erf' = Div, Erf, Add, Mul, Mul (what exporters emit below opset 20); 'gelu' = one Gelu node.
@@ -166,9 +166,17 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
     spell_reduce: how an OP_REDUCE record is written, comma-separated options over PyTorch's default spelling -- x.mean(dim) / torch.max(x,
     dim) as ReduceMean / ReduceMax(axes = [2] or [3], keepdims = 0) with the axes as an attribute, the pair as Add(max, mean) --: 'keep'
     (keepdims = 1), 'input' (the axes as the opset-18 input), 'neg' (negative axes), 'gmp' (a max over both axes as GlobalMaxPool), 'swap'
-    (Add(mean, max)), 'argmax' (the ArgMax that torch.max leaves behind, read by nothing)."""
+    (Add(mean, max)), 'argmax' (the ArgMax that torch.max leaves behind, read by nothing).
+    spell_concat: 'pair' = an OP_CONCAT record as a Concat of its own one or two sources; 'list' = a dense block's concats as the growing
+    list -- a plain two-source record whose first source is the whole output of an earlier such record lists that record's inputs in its
+    place, Concat([f0, f1, ..., fk]) over every earlier feature (what torchvision and timm export of a DenseNet layer).
+    An OP_BNACT record is written as BatchNormalization(scale = scale, B = shift, mean = 0, var = 1, epsilon = 0) and the activation's
+    spelling: either reader folds that back to the same bits (scale / sqrt(1 + 0), shift - 0 scale)."""
     if spell_lnorm not in ("node", "chain"):
         raise ConvertError(f"unknown LayerNorm spelling {spell_lnorm!r}")
+    if spell_concat not in ("pair", "list"):
+        raise ConvertError(f"unknown concat spelling {spell_concat!r}")
+    cat_parts: Dict[int, List[str]] = {}   # tensor of a plain two-source concat record -> the names its Concat node lists ('list')
     red_opts = set(filter(None, spell_reduce.split(",")))
     if not red_opts <= REDUCE_SPELLING_OPTIONS:
         raise ConvertError(f"unknown reduce spelling {spell_reduce!r}")
@@ -218,6 +226,9 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
             return tag + "_gelu"
         if act in (mf.ACT_HSWISH, mf.ACT_HSIGMOID):
             return hard_activation(x, act == mf.ACT_HSWISH, tag)
+        if act == mf.ACT_GELU_TANH:      # (opset 20's node is its one spelling either reader knows)
+            g.nodes.append(ox.Node("Gelu", [x], [tag + "_gelu"], {"approximate": "tanh"}))
+            return tag + "_gelu"
         raise ConvertError(f"activation {act} has no ONNX spelling here")
 
     def hard_activation(x: str, swish: bool, tag: str) -> str:
@@ -332,6 +343,10 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
             # (a lone Slice that only concats read would be folded into their windows: a one-input Concat keeps it a record)
             only_concats = all(M.op == mf.OP_CONCAT for M in m.layers if i + 1 in (M.in_tensor, M.res_tensor))
             if len(parts) == 2 or (L.reserved <= 1 and (y == names[L.in_tensor] or only_concats)):
+                if spell_concat == "list" and len(parts) == 2 and L.reserved <= 1:
+                    if parts[0] == names[L.in_tensor] and L.in_tensor in cat_parts:
+                        parts = cat_parts[L.in_tensor] + parts[1:]
+                    cat_parts[i + 1] = list(parts)
                 g.nodes.append(ox.Node("Concat", parts, [tag + "_cat"], {"axis": 1}, name=tag))
                 y = tag + "_cat"
             if L.reserved > 1:
@@ -362,6 +377,13 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
                 g.nodes.append(ox.Node("Flatten", [y], [tag + "_flat"], {"axis": 1}))
                 y = tag + "_flat"
                 flat.add(i + 1)
+        elif L.op == mf.OP_BNACT:
+            if L.in_tensor == 0:
+                raise ConvertError(f"layer {i}: a norm + activation layer on the spectrogram has no ONNX spelling here")
+            g.nodes.append(ox.Node("BatchNormalization", [x, const(tag + "_scale", m.weight(L.w_off, L.cout)), const(tag + "_shift", m.weight(L.b_off, L.cout)),
+                                                          const(tag + "_mean", np.zeros(L.cout, np.float32)), const(tag + "_var", np.ones(L.cout, np.float32))],
+                                   [tag + "_bn"], {"epsilon": 0.0}, name=tag))
+            y = activation(tag + "_bn", L.act, tag)
         elif L.op == mf.OP_REDUCE:
             if L.in_tensor == 0:
                 raise ConvertError(f"layer {i}: a reduction of the spectrogram has no ONNX spelling here")
@@ -430,9 +452,9 @@ def graph_from_model(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Op
 
 
 def model_to_onnx(m: mf.Model, spell_gelu: str = "erf", frontend_spelling: Optional[str] = None, spell_hswish: str = "op",
-                  spell_lnorm: str = "node", spell_reduce: str = "") -> bytes:
+                  spell_lnorm: str = "node", spell_reduce: str = "", spell_concat: str = "pair") -> bytes:
     """`graph_from_model` serialised: the bytes of the `.onnx` file `bh_classifier_create` opens."""
-    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling, spell_hswish, spell_lnorm, spell_reduce))
+    return ox.dump(graph_from_model(m, spell_gelu, frontend_spelling, spell_hswish, spell_lnorm, spell_reduce, spell_concat))
 
 
 # ---------------------------------------------------------------------------------------
@@ -873,6 +895,17 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         if L is not None and L.op == mf.OP_REDUCE:
             raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer: directly after a ReduceMax / ReduceMean / "
                                "GlobalMaxPool (a reduce layer carries no activation)")
+        if L is not None and L.op == mf.OP_BNACT:
+            # the activation that completes a tentative norm + activation record (the BatchNormalization branch below); anything but one of
+            # the record's activations as the ONLY reader of the norm's output leaves the norm where it was: refused, in the words stored
+            if t[0] not in bn_pending:
+                raise ConvertError(f"activation after {name_in!r} cannot be folded into its producer")
+            if act not in mf.BNACT_ACTS or name_in in graph_out or any(name_in in q.inputs for k, q in enumerate(g.nodes) if k not in own):
+                raise ConvertError(bn_pending[t[0]])
+            del bn_pending[t[0]]
+            L.act = act
+            tmap[name_out] = t
+            return
         if name_in in nhwc:
             nhwc.add(name_out)
         if L is not None and name_in in sums and L.res_tensor != mf.NO_TENSOR and L.reserved != mf.RES_ACT_AFTER:
@@ -891,6 +924,8 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         L.act = act
         tmap[name_out] = t
 
+    bn_pending: Dict[int, str] = {}   # tensor of a norm + activation record that has no activation yet -> the refusal its BatchNormalization gets without one
+    cat_lists: List[Tuple[tuple, tuple]] = []   # (the resolved input list of a Concat, its output tensor), in graph order: prefix reuse
     first_of_pattern = {}   # applied when the walk reaches the pattern's input (below)
     for out_name, (x, act, own) in act_of.items():
         first_of_pattern.setdefault(x, []).append((out_name, act, own))
@@ -1007,6 +1042,12 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         op = n.op_type
         if op == "Constant":      # (the library's parser turns these into initializers; _const_ints reads them where they are)
             continue
+        for x in n.inputs if bn_pending else ():
+            if x in tmap and tmap[x][0] in bn_pending:
+                relu6 = op == "Clip" and (_scalar(g, n.inputs[1]) if len(n.inputs) > 1 else n.attrs.get("min")) == 0.0 and \
+                    (_scalar(g, n.inputs[2]) if len(n.inputs) > 2 else n.attrs.get("max")) == 6.0
+                if not (op in ("Relu", "Gelu", "HardSwish") or relu6):
+                    raise ConvertError(bn_pending[tmap[x][0]])
         view_in = next((x for x in n.inputs if x in nhwc), None)
         if view_in is not None and i in ln_deferred:
             raise ConvertError(ln_deferred[i])
@@ -1105,9 +1146,20 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
                 src.append(x)
             if sum(x[1] for x in src) > 65536:
                 raise ConvertError(who + "more than 65 536 channels")
-            y = concat_rec(src[0], src[1] if len(src) > 1 else None, 0)
-            for x in src[2:]:
+            # prefix reuse (a DenseNet layer's Concat over the whole list of earlier features): where the leading j >= 2 inputs are, in order,
+            # the complete input list of an earlier Concat whose output is still a plain whole tensor, the chain starts from that output
+            # (the longest such prefix; j < the inputs, so that a Concat always is a record of its own)
+            start, y = 0, None
+            for lst, out_t in cat_lists:
+                j = len(lst)
+                if 2 <= j < len(src) and j > start and tuple(src[:j]) == lst and layers[out_t[0] - 1].reserved <= 1:
+                    start, y = j, out_t
+            if y is None:
+                y = concat_rec(src[0], src[1] if len(src) > 1 else None, 0)
+                start = 2
+            for x in src[start:]:
                 y = concat_rec(y + (0,), x, 0)
+            cat_lists.append((tuple(src), y))
             tmap[n.outputs[0]] = y
             flush_patterns(n.outputs[0])
         elif op in ("Split", "Slice"):
@@ -1265,15 +1317,40 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
         elif op == "BatchNormalization":
             t = tmap.get(n.inputs[0])
             L = layers[t[0] - 1] if t and t[0] > 0 else None
+            conv_type = L is not None and L.op in (mf.OP_CONV, mf.OP_DWCONV, mf.OP_PWCONV, mf.OP_GCONV)
+            # the refusal this norm has had so far, by its producer; it stands unless the norm becomes a record of its own (below)
+            refusal = None
             if L is not None and L.op == mf.OP_CONCAT:
-                raise ConvertError(f"BatchNormalization {n.name!r} directly after a Concat, Split, Slice or channel shuffle cannot be folded "
-                                   "(the record carries neither a scale nor an activation)")
-            if L is None or L.op not in (mf.OP_CONV, mf.OP_DWCONV, mf.OP_PWCONV, mf.OP_GCONV) or L.act != mf.ACT_NONE:
-                raise ConvertError("BatchNormalization that does not follow a convolution directly")
+                refusal = (f"BatchNormalization {n.name!r} directly after a Concat, Split, Slice or channel shuffle cannot be folded "
+                           "(the record carries neither a scale nor an activation)")
+            elif not conv_type or L.act != mf.ACT_NONE:
+                refusal = "BatchNormalization that does not follow a convolution directly"
             # folding rewrites the convolution's weights: a residual already folded into the layer (BN(conv + x)) or another
             # reader of the convolution's output (a skip taken before the BN) would silently see the wrong values
-            if L.res_tensor != mf.NO_TENSOR:
-                raise ConvertError("BatchNormalization after a residual Add (BN(conv + x)) cannot be folded into the convolution")
+            elif L.res_tensor != mf.NO_TENSOR:
+                refusal = "BatchNormalization after a residual Add (BN(conv + x)) cannot be folded into the convolution"
+            if refusal is not None:
+                # act(bn(x)) on a tensor no convolution can take the norm into -- a pool's, a concat's, an activated convolution's, a sum's,
+                # another such record's -- is one OP_BNACT record (DenseNet, pre-activation ResNets; csrc/onnx_conv.hpp has the same branch).
+                # The record is tentative, without an activation, until set_act completes it.
+                ok = L is not None and t[2] > 0 and t[3] > 0 and t[1] % 4 == 0 and n.inputs[0] not in nhwc and n.inputs[0] not in r3 and \
+                    (L.op in (mf.OP_POOL, mf.OP_CONCAT) or (L.op == mf.OP_BNACT and t[0] not in bn_pending) or
+                     (conv_type and (L.res_tensor == mf.NO_TENSOR or n.inputs[0] in sums)))
+                if not ok:
+                    raise ConvertError(refusal)
+                C = t[1]
+                par = [g.initializers.get(a) for a in n.inputs[1:5]]
+                if len(par) != 4 or any(a is None or a.dtype not in (np.float32, np.float16) or a.size != C for a in par):
+                    raise ConvertError(f"BatchNormalization {n.name!r}: scale, B, mean and var must be float32 or float16 initializers of the {C} channels")
+                gamma, beta, mean, var = (a.reshape(-1).astype(np.float64) for a in par)
+                scale = gamma / np.sqrt(var + float(np.float32(n.attrs.get("epsilon", 1e-5))))      # (the attribute is an f32: its default too)
+                shift = beta - mean * scale
+                layers.append(mf.Layer(mf.OP_BNACT, mf.ACT_NONE, t[0], mf.NO_TENSOR, C, C, 1, 1, 1, 1, 0, 0, t[2], t[3], t[2], t[3], 0,
+                                       blob.put(scale.astype(np.float32)), blob.put(shift.astype(np.float32))))
+                bn_pending[len(layers)] = refusal
+                tmap[n.outputs[0]] = (len(layers), C, t[2], t[3])
+                flush_patterns(n.outputs[0])
+                continue
             if sum(n.inputs[0] in q.inputs for q in g.nodes) != 1 or n.inputs[0] in graph_out:
                 raise ConvertError("BatchNormalization of a convolution output that has other readers cannot be folded")
             gamma, beta, mean, var = (g.initializers[a].astype(np.float64) for a in n.inputs[1:5])
@@ -1544,6 +1621,8 @@ def model_from_graph(g: ox.Graph, frontend: Optional[mf.Model] = None, spectrogr
             tmap[n.outputs[0]] = tmap[n.inputs[0]]
         else:
             raise ConvertError(f"unsupported operator {op} ({n.name!r})")
+    if bn_pending:
+        raise ConvertError(bn_pending[min(bn_pending)])
     if first_of_pattern or ln_of_pattern:
         raise ConvertError(f"activation patterns on tensors that were never produced: {sorted(set(first_of_pattern) | set(ln_of_pattern))}")
     if not layers or layers[-1].op != mf.OP_DENSE:

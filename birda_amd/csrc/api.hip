@@ -271,18 +271,24 @@ int SliceRun::layer(const Step &st) const {
         launched = bh::launch_reduce(in, out, p, (int)L.reserved, (int)n, s);
         ctx_mark(ctx, ST_GAP, (int)i);
         break;
+    case bh::OP_BNACT:    // a folded BatchNormalization + activation: f32 in every precision mode (w_off: scale[C], b_off: shift[C])
+        launched = bh::launch_bnact(in, c->d_blob + L.w_off, bias, out, (unsigned long long)n * L.out_h * L.out_w, (int)L.cout, (int)L.act, s);
+        ctx_mark(ctx, ST_GAP, (int)i);
+        break;
     default: return fail(BH_ERR_UNSUPPORTED, "layer %u: unsupported op %u", i, L.op);
     }
     // (bh_debug_layer_kernel: the split-f16 launchers' names; a grouped convolution's and a concat's f32 kernels are kept too)
     // (... and a dilated depthwise layer's, the dilated form of dwconv_kernel)
     // (... and a 7x7 depthwise layer's and a LayerNorm's: the layers of a ConvNeXt block)
     // (... and a reduce layer's: the split is part of the name)
-    if (f16 || L.op == bh::OP_GCONV || L.op == bh::OP_CONCAT || L.op == bh::OP_LNORM || L.op == bh::OP_REDUCE || (L.op == bh::OP_DWCONV && (bh::conv_dilated(p) || L.kh == 7)))
+    // (... and a norm + activation layer's)
+    if (f16 || L.op == bh::OP_GCONV || L.op == bh::OP_CONCAT || L.op == bh::OP_LNORM || L.op == bh::OP_REDUCE || L.op == bh::OP_BNACT || (L.op == bh::OP_DWCONV && (bh::conv_dilated(p) || L.kh == 7)))
         S.kernel.store(launched, std::memory_order_relaxed);
     // (create's predicates and validate_model keep this from happening; if it does, the output tensor was not written)
     if (!launched && n) {
         if (L.op == bh::OP_LNORM) return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for a layer norm over %u channels", i, L.cout);
         if (L.op == bh::OP_REDUCE) return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for a reduce of mode %u over a %ux%u window", i, L.reserved, L.kh, L.kw);
+        if (L.op == bh::OP_BNACT) return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for a norm + activation layer over %u channels with activation %u", i, L.cout, L.act);
         if (L.op == bh::OP_DWCONV || (L.op == bh::OP_CONV && L.in_layout == 1))
             return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for a %ux%u stride %ux%u window, %u -> %u channels", i, L.kh, L.kw, L.sh, L.sw, L.cin, L.cout);
         return fail(BH_ERR_INTERNAL, "layer %u: no kernel instantiation for activation %u %s the residual add", i, L.act, after ? "after" : "before");

@@ -208,6 +208,10 @@ int prepare_layer(bh_classifier *c, size_t i, bool in_block, bool se_project) {
         if (!bh::reduce_supports(p, (int)L.reserved))
             return fail(BH_ERR_UNSUPPORTED, "layer %zu: reduce of a %ux%u image over a %ux%u window, %u channels, mode %u not built", i, L.in_h, L.in_w, L.kh, L.kw, L.cout, L.reserved);
         return BH_OK;
+    case bh::OP_BNACT:   // (the op needs nothing but the blob: what validate_model accepts, the launcher takes)
+        if (!bh::bnact_supports((int)L.cout, (int)L.act))
+            return fail(BH_ERR_UNSUPPORTED, "layer %zu: norm + activation over %u channels with activation %u not built", i, L.cout, L.act);
+        return BH_OK;
     case bh::OP_CONCAT: {
         const auto src = concat_sources(m, L, nullptr, nullptr);
         if (!bh::concat_supports((int)L.out_h, (int)L.out_w, src.data(), L.res_tensor == bh::NO_TENSOR ? 1 : 2, (int)L.reserved))
@@ -242,9 +246,9 @@ int prepare_layers(bh_classifier *c) {
     // residual sits on its project convolution; the planner fuses no depthwise layer that carries one) and the NCHW stem
     for (size_t i = 0; i < m.layers.size(); i++) {
         const auto &L = m.layers[i];
-        if (L.res_tensor != bh::NO_TENSOR && (L.op == bh::OP_DWCONV || L.op == bh::OP_GAP || L.op == bh::OP_POOL || L.op == bh::OP_REDUCE || L.op == bh::OP_GCONV || (L.op == bh::OP_CONV && L.in_layout == 1)))
+        if (L.res_tensor != bh::NO_TENSOR && (L.op == bh::OP_DWCONV || L.op == bh::OP_GAP || L.op == bh::OP_POOL || L.op == bh::OP_REDUCE || L.op == bh::OP_BNACT || L.op == bh::OP_GCONV || (L.op == bh::OP_CONV && L.in_layout == 1)))
             return fail(BH_ERR_UNSUPPORTED, "layer %zu: a residual on a %s layer is not supported (only convolutions, 1x1 and full NHWC, "
-                        "and dense layers add one)", i, L.op == bh::OP_DWCONV ? "depthwise" : (L.op == bh::OP_GAP || L.op == bh::OP_POOL) ? "pool" : L.op == bh::OP_REDUCE ? "reduce"
+                        "and dense layers add one)", i, L.op == bh::OP_DWCONV ? "depthwise" : (L.op == bh::OP_GAP || L.op == bh::OP_POOL) ? "pool" : L.op == bh::OP_REDUCE ? "reduce" : L.op == bh::OP_BNACT ? "norm + activation"
                                                         : L.op == bh::OP_GCONV ? "grouped convolution" : "stem convolution");
     }
     return BH_OK;

@@ -16,6 +16,7 @@
 #include "../../include/birda_hip_dilated_debug.h"
 #include "../../include/birda_hip_lnorm_debug.h"
 #include "../../include/birda_hip_reduce_debug.h"
+#include "../../include/birda_hip_bnact_debug.h"
 
 using namespace bhi;
 
@@ -335,6 +336,57 @@ int bh_debug_lnorm(int device, const float *X, const float *gamma, const float *
     const char *kn = bh::launch_lnorm(dx, dg, db, dy, (unsigned long long)n_pixels_total, (int)C, eps, nullptr);
     if (!kn) return fail(BH_ERR_INTERNAL, "debug_lnorm: the launcher has no instantiation for a width lnorm_supports accepts");
     return h.finish(kn, name, name_len);
+} catch (...) { return on_exception(); }
+
+// One norm + activation launch alone on operands of the caller's, through the launcher a forward pass takes
+// (include/birda_hip_bnact_debug.h).
+int bh_debug_bnact(int device, const float *X, const float *scale, const float *shift, int act, float *out, size_t n_pixels_total, size_t C,
+                   char *name, size_t name_len) try {
+    if (!X || !scale || !shift || !out || !n_pixels_total || !C) return fail(BH_ERR_INVALID, "debug_bnact: bad arguments");
+    if (C > (size_t)(1 << 16) || C % 4)
+        return fail(BH_ERR_UNSUPPORTED, "debug_bnact: norm + activation over %zu channels not built (a multiple of 4, 4 .. 65 536)", C);
+    if (!bh::bnact_supports((int)C, act))
+        return fail(BH_ERR_INVALID, "debug_bnact: activation %d (RELU, RELU6, SWISH, GELU_ERF, GELU_TANH or HSWISH: 1 .. 5, 7)", act);
+    if (n_pixels_total > (size_t)INT32_MAX || n_pixels_total * C > (size_t)INT32_MAX) return fail(BH_ERR_INVALID, "debug_bnact: tensors past 2^31 elements");
+    HIPCHK(hipSetDevice(device));
+    DebugLaunch h{"debug_bnact"};
+    const float *dx = h.in(X, n_pixels_total * C * 4), *da = h.in(scale, C * 4), *db = h.in(shift, C * 4);
+    float *dy = h.out(n_pixels_total * C, "out", out);
+    if (!h.ok) return h.no_memory();
+    const char *kn = bh::launch_bnact(dx, da, db, dy, (unsigned long long)n_pixels_total, (int)C, act, nullptr);
+    if (!kn) return fail(BH_ERR_INTERNAL, "debug_bnact: the launcher has no instantiation for a width and an activation bnact_supports accepts");
+    return h.finish(kn, name, name_len);
+} catch (...) { return on_exception(); }
+
+// The same launch on DEVICE buffers of the caller's, for the timing tool (include/birda_hip_bnact_debug.h): no copies, no guard bands.
+int bh_debug_bnact_on_device(int device, const float *dX, const float *dScale, const float *dShift, int act, float *dOut, size_t n_seg, size_t pixels,
+                             size_t C, char *name, size_t name_len) try {
+    if (!dX || !dScale || !dShift || !dOut || !n_seg || !pixels || !C) return fail(BH_ERR_INVALID, "debug_bnact_on_device: bad arguments");
+    if (C > (size_t)(1 << 16) || C % 4) return fail(BH_ERR_UNSUPPORTED, "debug_bnact_on_device: %zu channels not built (a multiple of 4, 4 .. 65 536)", C);
+    if (n_seg > (size_t)INT32_MAX || pixels > (size_t)INT32_MAX || n_seg * pixels > ((size_t)1 << 40) / C)
+        return fail(BH_ERR_INVALID, "debug_bnact_on_device: tensors past 2^40 elements");
+    if (!bh::bnact_supports((int)C, act)) return fail(BH_ERR_INVALID, "debug_bnact_on_device: activation %d (RELU, RELU6, SWISH, GELU_ERF, GELU_TANH or HSWISH: 1 .. 5, 7)", act);
+    HIPCHK(hipSetDevice(device));
+    const char *kn = bh::launch_bnact(dX, dScale, dShift, dOut, (unsigned long long)n_seg * pixels, (int)C, act, nullptr);
+    if (!kn) return fail(BH_ERR_INTERNAL, "debug_bnact_on_device: the launcher has no instantiation for this shape");
+    HIPCHK(hipGetLastError());
+    if (name && name_len) snprintf(name, name_len, "%s", kn);
+    return BH_OK;
+} catch (...) { return on_exception(); }
+
+// The timing tool's yardstick, an entry of its own: scale_kernel (launch_scale, the squeeze-excite layer's x times a [n_seg][C] gate), the nearest
+// existing kernel, over the same tensor on DEVICE buffers of the caller's (include/birda_hip_bnact_debug.h).
+int bh_debug_scale_on_device(int device, const float *dX, const float *dGate, float *dOut, size_t n_seg, size_t pixels, size_t C, char *name,
+                             size_t name_len) try {
+    if (!dX || !dGate || !dOut || !n_seg || !pixels || !C) return fail(BH_ERR_INVALID, "debug_scale_on_device: bad arguments");
+    if (C > (size_t)(1 << 16) || C % 4) return fail(BH_ERR_UNSUPPORTED, "debug_scale_on_device: %zu channels not built (a multiple of 4, 4 .. 65 536)", C);
+    if (n_seg > (size_t)INT32_MAX || pixels > (size_t)INT32_MAX || pixels * (C / 4) > (size_t)INT32_MAX || n_seg * pixels > ((size_t)1 << 40) / C)
+        return fail(BH_ERR_INVALID, "debug_scale_on_device: tensors past 2^40 elements (or a segment past 2^31 float4s)");
+    HIPCHK(hipSetDevice(device));
+    const char *kn = bh::launch_scale(dX, dGate, dOut, (int)n_seg, (int)pixels, (int)C, nullptr);
+    HIPCHK(hipGetLastError());
+    if (name && name_len) snprintf(name, name_len, "%s", kn);
+    return BH_OK;
 } catch (...) { return on_exception(); }
 
 // One grouped convolution alone on operands of the caller's, with create's weight preparation (gconv_matrix, gconv_fragments,

@@ -196,7 +196,9 @@ void plan_arena(const bh::Model &m, const std::vector<Step> &sched, size_t max_b
 // launches all compute the undilated layer.  Every matcher below asks here; such a block runs layer by layer.
 static bool layer_dilated(const bh::LayerRec &L) { return L.skip_h != 0 || L.skip_w != 0; }
 // (An OP_REDUCE record -- like OP_POOL and OP_LNORM -- is in none of the op lists the matchers below accept, the global pool's places
-//  included: a gate or a head whose pool is a reduce runs layer by layer, and its tensors have ordinary liveness.)
+//  included: a gate or a head whose pool is a reduce runs layer by layer, and its tensors have ordinary liveness.  The same holds for
+//  an OP_BNACT record: a run that contains one is no block any matcher knows, the 1x1 -> global pool head behind one included, and the
+//  arena planner sees an ordinary layer that reads in_tensor and writes its own.)
 
 // The pool layer i opens a squeeze-excite gate that runs as the two gate launches (se_hidden_kernel, se_gate16_kernel) instead of pool
 // + two GEMMs: an image of at most 64 pixels, at least BH_SE_GATE16_MIN channels, pool -> 1x1 (C -> Cr) -> 1x1 (Cr -> C) with no

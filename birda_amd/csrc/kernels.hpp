@@ -485,6 +485,13 @@ constexpr int kReduceSplitMin = 32, kReduceKeptMax = 4096;
 bool reduce_supports(const ConvParams &p, int mode);
 int reduce_split(const ConvParams &p);
 const char *launch_reduce(const float *in, float *out, const ConvParams &p, int mode, int n_seg, hipStream_t s, int split = 0);
+// a folded BatchNormalization + activation on an NHWC f32 tensor (kernels_bnact.hip; model.hpp OP_BNACT): out[p][c] = act(fma(in[p][c],
+// scale[c], shift[c])), one __fmaf_rn and the NaN-keeping run-time activation (act_apply_pos(v, act, true)); C % 4 == 0, 4 .. 65 536;
+// act RELU, RELU6, SWISH, GELU_ERF, GELU_TANH or HSWISH.  f32 in every precision mode, one read and one write; an element's bits are
+// the same at every launch size.  Returns the kernel's name ("bnact_kernel": one instantiation, the activation a run-time argument);
+// nullptr when C or act is not supported and nothing was launched.
+bool bnact_supports(int C, int act);
+const char *launch_bnact(const float *in, const float *scale, const float *shift, float *out, unsigned long long n_pix, int C, int act, hipStream_t s);
 // head 1x1 conv + activation (GELU / swish / ReLU6) + global average pool fused (f16 hi / lo weight planes as for launch_pw_gemm16)
 bool head_gap16_supports(int P, int K, int N, int act);
 const char *launch_head_gap16(const float *A, const void *Wf, const float *bias, float *out, int n_seg, int P, int K, int N,

@@ -9,7 +9,7 @@
 
 namespace bh {
 
-enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8, OP_CONCAT = 10, OP_LNORM = 12, OP_REDUCE = 13 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
+enum Op : uint32_t { OP_CONV = 1, OP_DWCONV = 2, OP_PWCONV = 3, OP_GAP = 4, OP_DENSE = 5, OP_SCALE = 6, OP_POOL = 7, OP_GCONV = 8, OP_CONCAT = 10, OP_LNORM = 12, OP_REDUCE = 13, OP_BNACT = 14 };   // OP_SCALE: x * gate[n][c] (squeeze-excite; gate = res_tensor)
 // OP_POOL (ONNX MaxPool / AveragePool, floor mode): the record's `reserved` word is the mode.  No weights, no bias, no activation.
 enum PoolMode : uint32_t { POOL_MAX = 0, POOL_AVG = 1, POOL_AVG_PAD = 2 };   // AVG: over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 // OP_CONV (NHWC), OP_PWCONV, OP_DENSE: the record's `reserved` word is where `act` stands relative to the residual.  0: act(conv + b) + R
@@ -36,6 +36,13 @@ constexpr uint32_t RES_ACT_AFTER = 1;
 // 65 536 taps.  `reserved` is the mode; REDUCE_MAXMEAN is max + mean of the same window as one value.  One spelling each: the mean
 // over both axes stays OP_GAP, and a 1x1 window is no reduction.
 enum ReduceMode : uint32_t { REDUCE_MAX = 0, REDUCE_MEAN = 1, REDUCE_MAXMEAN = 2 };
+// OP_BNACT = 14 (ONNX BatchNormalization + an activation on a tensor no convolution can take the BN into: the relu(bn(cat(..))) that opens
+// every DenseNet layer and transition, the relu(bn(sum)) that opens a pre-activation ResNet block): y[p][c] = act(fma(x[p][c], scale[c],
+// shift[c])) on an NHWC f32 tensor, f32 in every precision mode.  cin == cout == C (a multiple of 4), kernel / stride 1, pads 0, out
+// image == in image, in_layout 0, never on tensor 0; w_off -> scale[C], b_off -> shift[C] (gamma / sqrt(var + eps) and beta - mean scale,
+// folded by the writer), both at offsets that are multiples of 4; no residual, no dilation, `reserved` 0; `act` is RELU, RELU6, SWISH, GELU_ERF, GELU_TANH or HSWISH -- a norm
+// without an activation folds into a convolution or is refused, and the gate activations are no layer's.  A code-14 record with a
+// window other than 1x1 is no norm + activation layer at all: it stays "unknown layer op", as does code 15.
 constexpr uint32_t NO_TENSOR = 0xFFFFFFFFu;
 // Dilation (OP_CONV on an NHWC tensor, OP_DWCONV): the record's words at bytes 88 .. 95, skip_h and skip_w, are the rows and the columns
 // SKIPPED between neighbouring taps, dilation - 1 per axis -- tap (dy, dx) reads pixel (oy sh - pad_t + dy (skip_h + 1),
@@ -124,7 +131,7 @@ inline bool validate_model(Model &m, std::string &err) {
         m.tensor_floats[i + 1] = (uint64_t)L.out_h * L.out_w * L.cout;
         if (L.in_tensor > i || (L.res_tensor != NO_TENSOR && L.res_tensor > i)) { err = "layer reads a later tensor"; return false; }
         // what the layer reads must be what its input tensor holds (a pool reads in_h x in_w x cout, a dense layer cin values)
-        const uint64_t in_floats = L.op == OP_GAP || L.op == OP_DWCONV || L.op == OP_SCALE || L.op == OP_POOL || L.op == OP_REDUCE ? (uint64_t)L.in_h * L.in_w * L.cout
+        const uint64_t in_floats = L.op == OP_GAP || L.op == OP_DWCONV || L.op == OP_SCALE || L.op == OP_POOL || L.op == OP_REDUCE || L.op == OP_BNACT ? (uint64_t)L.in_h * L.in_w * L.cout
                                  : L.op == OP_DENSE ? (uint64_t)L.cin
                                  : L.op == OP_CONCAT ? m.tensor_floats[L.in_tensor]   // (a window of its source: held below)
                                  : (uint64_t)L.in_h * L.in_w * L.cin;
@@ -132,7 +139,10 @@ inline bool validate_model(Model &m, std::string &err) {
         if (L.res_tensor != NO_TENSOR && L.op != OP_SCALE && L.op != OP_CONCAT && m.tensor_floats[L.res_tensor] != m.tensor_floats[i + 1]) {
             err = "residual shape does not match the layer output"; return false;
         }
-        if (L.op < OP_CONV || L.op > OP_REDUCE || L.op == 9 || L.op == 11) { err = "unknown layer op"; return false; }
+        if (L.op < OP_CONV || L.op > OP_BNACT || L.op == 9 || L.op == 11) { err = "unknown layer op"; return false; }
+        // (a norm + activation layer has no window: a code-14 record with one is not this op, and is refused first and in the words of an
+        //  unknown code, whatever else the record says)
+        if (L.op == OP_BNACT && (L.kh != 1 || L.kw != 1)) { err = "unknown layer op: a norm + activation layer with a window other than 1x1"; return false; }
         if (L.op == OP_GCONV) {
             const uint32_t G = L.reserved;
             if (G < 2) { err = "grouped convolution with fewer than two groups (one group is a full convolution)"; return false; }
@@ -205,6 +215,23 @@ inline bool validate_model(Model &m, std::string &err) {
                 err = "reduce layer that is the mean over both axes (OP_GAP is its one spelling)"; return false;
             }
         }
+        if (L.op == OP_BNACT) {
+            if (L.sh != 1 || L.sw != 1 || L.pad_t != 0 || L.pad_l != 0) { err = "norm + activation layer with a stride or padding other than 1 / 0"; return false; }
+            if (L.in_h != L.out_h || L.in_w != L.out_w) { err = "norm + activation layer whose output image is not its input image"; return false; }
+            if (L.cin != L.cout) { err = "norm + activation layer that changes the channel count"; return false; }
+            if (L.cout % 4) { err = "norm + activation layer over a channel count that is not a multiple of 4"; return false; }
+            if (L.in_layout != 0 || L.in_tensor == 0) { err = "norm + activation layer on the planar spectrogram (tensor 0)"; return false; }
+            if (L.res_tensor != NO_TENSOR) { err = "norm + activation layer with a residual"; return false; }
+            if (L.reserved != 0) { err = "norm + activation layer with a reserved word that is not 0"; return false; }
+            if (L.act == 0) { err = "norm + activation layer without an activation"; return false; }
+            if (L.act == 6 || L.act == 8) { err = "norm + activation layer with a gate activation (sigmoid / hard sigmoid)"; return false; }
+            if (L.act > 8) { err = "norm + activation layer with an unknown activation"; return false; }
+            if (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.cout > m.h.blob_floats - L.w_off || L.cout > m.h.blob_floats - L.b_off) {
+                err = "norm + activation layer scale / shift outside the blob"; return false;
+            }
+            // (the kernel reads both as float4: every writer puts them on 16-float boundaries, and a file is untrusted input)
+            if (L.w_off % 4 || L.b_off % 4) { err = "norm + activation layer scale / shift at an offset that is not a multiple of 4"; return false; }
+        }
         if (L.op == OP_CONV && L.in_layout != 0) {
             if (L.reserved == RES_ACT_AFTER) { err = "activation after the residual on the NCHW stem convolution"; return false; }
         } else if (L.op == OP_CONV || L.op == OP_PWCONV || L.op == OP_DENSE) {
@@ -213,14 +240,14 @@ inline bool validate_model(Model &m, std::string &err) {
             if (L.reserved == RES_ACT_AFTER && L.act == 0) { err = "activation after the residual without an activation (a plain residual is position 0)"; return false; }
         }
         if (L.skip_h || L.skip_w) {
-            static const char *const names[] = {"?", "stem convolution", "depthwise", "pointwise", "global pool", "dense", "scale", "pool", "grouped convolution", "?", "concat", "?", "layer norm", "reduce"};
+            static const char *const names[] = {"?", "stem convolution", "depthwise", "pointwise", "global pool", "dense", "scale", "pool", "grouped convolution", "?", "concat", "?", "layer norm", "reduce", "norm + activation"};
             if (!(L.op == OP_DWCONV || (L.op == OP_CONV && L.in_layout == 0))) {
                 err = std::string("dilation on a ") + names[L.op] + " layer"; return false;
             }
             if (L.skip_h >= MAX_DILATION || L.skip_w >= MAX_DILATION) { err = "dilation above 16"; return false; }
             if ((L.kh == 1 && L.skip_h) || (L.kw == 1 && L.skip_w)) { err = "dilation on an axis with one tap (dilation 1 is its one spelling)"; return false; }
         }
-        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && L.op != OP_CONCAT && L.op != OP_LNORM && L.op != OP_REDUCE && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
+        if (L.op != OP_GAP && L.op != OP_SCALE && L.op != OP_POOL && L.op != OP_CONCAT && L.op != OP_LNORM && L.op != OP_REDUCE && L.op != OP_BNACT && (L.w_off > m.h.blob_floats || L.b_off > m.h.blob_floats || L.w_off + wn > m.h.blob_floats ||
                                                    L.b_off + L.cout > m.h.blob_floats)) {
             err = "layer weights outside blob"; return false;
         }

@@ -5,7 +5,8 @@
 //   * the CONV STACK is read off the graph (round 4; a C++ port of birda_amd/convert.py model_from_graph, which stays as the
 //     second witness: tests/test_onnx_native.py holds the two to the same layer table and the same weights, bit for bit):
 //     Conv (1x1 -> pointwise, group == channels -> depthwise, any other group count -> OP_GCONV, else full), BatchNormalization folded into the convolution in
-//     front of it, the activation spellings exporters emit (Relu, Clip(0, 6), Sigmoid x Mul = swish, Div / Erf / Add / Mul / Mul
+//     front of it -- or, with its activation, on a pool output, a concat, a residual sum or an activated convolution, one OP_BNACT record (DenseNet,
+//     pre-activation ResNets) --, the activation spellings exporters emit (Relu, Clip(0, 6), Sigmoid x Mul = swish, Div / Erf / Add / Mul / Mul
 //     = GELU, the Gelu operator; HardSwish, HardSigmoid(1/6, 1/2) x Mul and Add 3 / Clip(0, 6) / Mul / Mul 1/6 = hard swish; HardSigmoid(1/6,
 //     1/2) or that chain without its Mul(., x) on a pooled tensor = the hard-sigmoid gate), residual Add folded into its 1x1 convolution, MaxPool / AveragePool (floor mode; OP_POOL),
 //     GlobalAveragePool / ReduceMean over H, W, ReduceMax / ReduceMean over H or W or both, GlobalMaxPool and the max + mean pair Add(ReduceMax,
@@ -527,6 +528,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
     for (const auto &o : outputs) graph_out.insert(o);
     auto find = [&](const std::string &name, T &t) { auto it = tmap.find(name); if (it == tmap.end()) return false; t = it->second; return true; };
     std::set<std::string> sums;   // the outputs of the residual Adds folded into a layer
+    std::vector<std::pair<std::vector<T>, T>> cat_lists;   // (the resolved input list of a Concat, its output tensor), in graph order: prefix reuse
     // ---- the channel shuffle (convert.py _find_shuffles): Reshape [N, g, C / g, H, W] -> Transpose (0, 2, 1, 3, 4) -> Reshape
     // [N, C, H, W], each with one reader, the shapes constants.  Found here, where the activation spellings are; the walk makes an
     // OP_CONCAT record (or the `reserved` word of the Concat in front) of the first Reshape and skips the other two nodes.
@@ -575,10 +577,26 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
         if (it != cons.end()) for (size_t k : it->second) if (nodes[k].op != "Concat") return true;
         return false;
     };
+    // tensor of a norm + activation record (OP_BNACT) that has no activation yet -> the refusal its BatchNormalization gets without one
+    std::map<uint32_t, std::string> bn_pending;
     // (own: the nodes of the activation itself -- one, or a multi-node spelling's)
     auto set_act = [&](const std::string &name_in, const std::string &name_out, uint32_t act, const std::vector<size_t> &own) {
         T t;
         if (!find(name_in, t)) return fail("activation on unknown tensor '" + name_in + "'");
+        if (t.idx != 0 && layers[t.idx - 1].op == OP_BNACT) {
+            // the activation that completes a tentative norm + activation record (the BatchNormalization branch below); anything but one of
+            // the record's activations as the ONLY reader of the norm's output leaves the norm where it was: refused, in the words stored
+            auto pit = bn_pending.find(t.idx);
+            if (pit == bn_pending.end()) return fail("activation after '" + name_in + "' cannot be folded into its producer");
+            bool other = graph_out.count(name_in) != 0;
+            auto cit = cons.find(name_in);
+            if (cit != cons.end()) for (size_t k : cit->second) if (std::find(own.begin(), own.end(), k) == own.end()) other = true;
+            if (other || !(act == A_RELU || act == A_RELU6 || act == A_SWISH || act == A_GELU_ERF || act == A_GELU_TANH || act == A_HSWISH)) return fail(pit->second);
+            bn_pending.erase(pit);
+            layers[t.idx - 1].act = act;
+            tmap[name_out] = t;
+            return true;
+        }
         // (the hard sigmoid stands where the Sigmoid inside the graph may: on a pooled [N, C, 1, 1] tensor -- the gate's second 1x1, a dense layer)
         if (act == A_HSIGMOID && (uint64_t)t.h * t.w != 1) return fail("HardSigmoid inside the graph that is neither HardSigmoid * x nor a squeeze-excite gate");
         if (t.idx != 0 && layers[t.idx - 1].op == OP_POOL)
@@ -743,6 +761,22 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 return fail(op + " '" + n.name + "': input '" + xn + "' is a rank-3 tensor [N, C, T] (behind a reduction with keepdims = 0): only further reductions, the max + mean "
                             "Add, and Squeeze / Unsqueeze / Flatten / Reshape once one pixel is left read one (1-D convolutions and pools are not supported)");
         }
+        // a norm + activation record without its activation yet among the inputs: only an activation reads one (set_act completes it)
+        if (!bn_pending.empty())
+            for (const auto &xn : n.in) {
+                T t;
+                if (!find(xn, t)) continue;
+                auto pit = bn_pending.find(t.idx);
+                if (pit == bn_pending.end()) continue;
+                bool relu6 = false;
+                if (op == "Clip") {
+                    float lo = 0.f, hi = 0.f;
+                    const bool has_lo = n.in.size() > 1 && !n.in[1].empty() ? scalar(n.in[1], lo) : (n.a.count("min") ? (lo = n.getf("min", 0.f), true) : false);
+                    const bool has_hi = n.in.size() > 2 && !n.in[2].empty() ? scalar(n.in[2], hi) : (n.a.count("max") ? (hi = n.getf("max", 0.f), true) : false);
+                    relu6 = has_lo && has_hi && lo == 0.0f && hi == 6.0f;
+                }
+                if (!(op == "Relu" || op == "Gelu" || op == "HardSwish" || relu6)) return fail(pit->second);
+            }
         bool folded = false;
         if (op == "Mul" && !fold_layer_scale(n, folded)) return false;
         if (folded) continue;
@@ -923,14 +957,43 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             T t;
             if (!find(n.in[0], t) || t.idx == 0) return fail("BatchNormalization that does not follow a convolution directly");
             LayerRec &L = layers[t.idx - 1];
+            const bool conv_type = L.op == OP_CONV || L.op == OP_DWCONV || L.op == OP_PWCONV || L.op == OP_GCONV;
+            // the refusal this norm has had so far, by its producer; it stands unless the norm becomes a record of its own (below)
+            std::string refusal;
             if (L.op == OP_CONCAT)
-                return fail("BatchNormalization '" + n.name + "' directly after a Concat, Split, Slice or channel shuffle cannot be folded (the record carries neither a scale nor an activation)");
-            if ((L.op != OP_CONV && L.op != OP_DWCONV && L.op != OP_PWCONV && L.op != OP_GCONV) || L.act != A_NONE || n.in.size() < 5)
-                return fail("BatchNormalization that does not follow a convolution directly");
+                refusal = "BatchNormalization '" + n.name + "' directly after a Concat, Split, Slice or channel shuffle cannot be folded (the record carries neither a scale nor an activation)";
+            else if (!conv_type || L.act != A_NONE || n.in.size() < 5)
+                refusal = "BatchNormalization that does not follow a convolution directly";
             // folding rewrites the convolution's weights, so the BN must be the ONLY reader of the convolution's
             // output (a skip taken before the BN would see scaled values), and a residual already folded into the layer means the BN
             // normalises conv + residual, which no rescaling of the conv's weights expresses
-            if (L.res_tensor != NO_TENSOR) return fail("BatchNormalization after a residual Add (BN(conv + x)) cannot be folded into the convolution");
+            else if (L.res_tensor != NO_TENSOR) refusal = "BatchNormalization after a residual Add (BN(conv + x)) cannot be folded into the convolution";
+            if (!refusal.empty()) {
+                // act(bn(x)) on a tensor no convolution can take the norm into -- a pool's, a concat's, an activated convolution's, a sum's,
+                // another such record's -- is one OP_BNACT record (DenseNet, pre-activation ResNets; convert.py has the same branch, the two
+                // are held to the same records).  The record is tentative, without an activation, until set_act completes it.
+                const bool ok = n.in.size() >= 5 && t.h > 0 && t.w > 0 && t.c % 4 == 0 && !t.nhwc && !t.r3 && !t.view &&
+                                (L.op == OP_POOL || L.op == OP_CONCAT || (L.op == OP_BNACT && !bn_pending.count(t.idx)) ||
+                                 (conv_type && (L.res_tensor == NO_TENSOR || sums.count(n.in[0]))));
+                if (!ok) return fail(refusal);
+                const Tensor *p[4];
+                init_refusal.clear();
+                for (int q = 0; q < 4; q++) { p[q] = finit(n.in[1 + q]); if (!p[q] || p[q]->count != t.c) return fail("BatchNormalization '" + n.name + "': scale, B, mean and var must be float32 or float16 initializers of the " + std::to_string(t.c) + " channels" + init_refusal); }
+                const double eps = (double)n.getf("epsilon", 1e-5f);
+                tmp.resize(t.c); tmpb.resize(t.c);
+                for (uint32_t c = 0; c < t.c; c++) {
+                    const double gamma = p[0]->at(c), beta = p[1]->at(c), mean = p[2]->at(c), var = p[3]->at(c);
+                    const double scale = gamma / std::sqrt(var + eps);
+                    tmp[c] = (float)scale;
+                    tmpb[c] = (float)(beta - mean * scale);
+                }
+                const uint64_t wo = blob.put(tmp), bo = blob.put(tmpb);
+                const uint32_t li = new_layer(OP_BNACT, t.idx, NO_TENSOR, t.c, t.c, 1, 1, 1, 1, 0, 0, t.h, t.w, t.h, t.w, 0, wo, bo);
+                bn_pending[li] = refusal;
+                tmap[n.out[0]] = T{li, t.c, t.h, t.w};
+                if (!flush_patterns(n.out[0])) return false;
+                continue;
+            }
             { auto cit = cons.find(n.in[0]); if ((cit != cons.end() && cit->second.size() != 1) || graph_out.count(n.in[0])) return fail("BatchNormalization of a convolution output that has other readers cannot be folded"); }
             const Tensor *p[4];
             init_refusal.clear();
@@ -1145,8 +1208,22 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
                 src.push_back(x);
             }
             if (sum > DIM_MAX) return fail(who + "more than 65 536 channels");
-            T y = concat_rec(src[0], src.size() > 1 ? &src[1] : nullptr, 0);
-            for (size_t k = 2; k < src.size(); k++) y = concat_rec(y, &src[k], 0);
+            // prefix reuse (a DenseNet layer's Concat over the whole list of earlier features): where the leading j >= 2 inputs are, in order,
+            // the complete input list of an earlier Concat whose output is still a plain whole tensor, the chain starts from that output
+            // (the longest such prefix; j < the inputs, so that a Concat always is a record of its own)
+            size_t start = 0;
+            T y{};
+            for (const auto &cl : cat_lists) {
+                const size_t j = cl.first.size();
+                if (j < 2 || j >= src.size() || j <= start || layers[cl.second.idx - 1].reserved > 1) continue;
+                bool same = true;
+                for (size_t k = 0; k < j && same; k++)
+                    same = cl.first[k].idx == src[k].idx && cl.first[k].c == src[k].c && cl.first[k].off == src[k].off;
+                if (same) { start = j; y = cl.second; }
+            }
+            if (!start) { y = concat_rec(src[0], src.size() > 1 ? &src[1] : nullptr, 0); start = 2; }
+            for (size_t k = start; k < src.size(); k++) y = concat_rec(y, &src[k], 0);
+            cat_lists.emplace_back(src, y);
             tmap[n.out[0]] = y;
             if (!flush_patterns(n.out[0])) return false;
         } else if (op == "Split" || op == "Slice") {
@@ -1288,6 +1365,7 @@ inline bool model_from_graph(const Graph &g, Model &m, std::string &err) {
             return fail("unsupported operator " + op + " ('" + n.name + "')");
         }
     }
+    if (!bn_pending.empty()) return fail(bn_pending.begin()->second);
     if (!first_of_pattern.empty()) return fail("activation pattern on a tensor that was never produced: '" + first_of_pattern.begin()->first + "'");
     if (!ln_of_pattern.empty()) return fail("activation pattern on a tensor that was never produced: '" + ln_of_pattern.begin()->first + "'");
     if (layers.empty() || layers.back().op != OP_DENSE) return fail("the graph does not end in a dense layer");

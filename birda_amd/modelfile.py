@@ -46,12 +46,17 @@ OP_LNORM = 12   # LayerNorm over the channels of an NHWC tensor, pixel by pixel 
 OP_REDUCE = 13  # ReduceMax / ReduceMean over H, over W or over both of an NHWC tensor, GlobalMaxPool, and max + mean of one window (the PANNs
                 # head): spelled like OP_GAP -- cin == cout == C (a multiple of 4), kh = in_h or 1, kw = in_w or 1, stride 1, pads 0, out = in / window;
                 # Layer.reserved is the mode.  The mean over both axes stays OP_GAP and a 1x1 window is refused: one spelling each.
+OP_BNACT = 14   # a folded BatchNormalization + activation on a tensor no convolution can take the norm into (relu(bn(cat(..))), DenseNet; relu(bn(sum)),
+                # pre-activation ResNets): y = act(fma(x, scale[c], shift[c])), f32 in every mode -- cin == cout == C (a multiple of 4), kernel / stride 1,
+                # pads 0, the image kept; w_off -> scale[C], b_off -> shift[C]; no residual or dilation, Layer.reserved 0; Layer.act is one of
+                # BNACT_ACTS (never ACT_NONE, never a gate activation).  A code-14 record with a window stays "unknown layer op", as does 15.
 REDUCE_MAX, REDUCE_MEAN, REDUCE_MAXMEAN = 0, 1, 2  # MAXMEAN: max + mean of the same window, as one value
 POOL_MAX, POOL_AVG, POOL_AVG_PAD = 0, 1, 2  # AVG: mean over the in-image taps (count_include_pad = 0); AVG_PAD: over kh * kw
 # OP_CONV (NHWC), OP_PWCONV, OP_DENSE: Layer.reserved is where `act` stands relative to the residual -- 0: act(conv + b) + R (every
 # file written before the flag existed); RES_ACT_AFTER: act(conv + b + R), the end of a ResNet block
 RES_ACT_AFTER = 1
 ACT_NONE, ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_SIGMOID, ACT_HSWISH, ACT_HSIGMOID = range(9)
+BNACT_ACTS = (ACT_RELU, ACT_RELU6, ACT_SWISH, ACT_GELU_ERF, ACT_GELU_TANH, ACT_HSWISH)  # what an OP_BNACT record's `act` may be
 OUT_NONE, OUT_SIGMOID, OUT_SOFTMAX = 0, 1, 2
 NO_TENSOR = 0xFFFFFFFF
 

@@ -189,6 +189,19 @@ class _Builder:
                      0, self.put(gamma), self.put(beta), reserved=mf.lnorm_eps_bits(eps))
         return self.add(L)
 
+    def bnact(self, tin, h, w, c, act):
+        """a folded BatchNormalization + activation (mf.OP_BNACT): y = act(x * scale[c] + shift[c]).  scale around 1 with a negative entry,
+        an exact zero and a large one (above 3), shift around 0; act one of mf.BNACT_ACTS"""
+        assert act in mf.BNACT_ACTS and c % 4 == 0
+        scale = (1.0 + 0.3 * self.rng.standard_normal(c)).astype(np.float32)
+        i0, i1, i2 = (int(v) for v in self.rng.choice(c, 3, replace=False))
+        scale[i0] = 0.0
+        scale[i1] *= np.float32(-1.0)
+        scale[i2] = np.float32(3.0) + np.abs(scale[i2])
+        shift = (0.2 * self.rng.standard_normal(c)).astype(np.float32)
+        L = mf.Layer(mf.OP_BNACT, act, tin, mf.NO_TENSOR, c, c, 1, 1, 1, 1, 0, 0, h, w, h, w, 0, self.put(scale), self.put(shift))
+        return self.add(L)
+
     def dense(self, tin, cin, cout, gain=1.0, act=mf.ACT_NONE, logits=True):
         wt = self.he((cin, cout), cin) * np.float32(gain)
         b = (self.rng.standard_normal(cout) * 0.5 - 2.0).astype(np.float32) if logits else self.bias(cout)
@@ -257,9 +270,16 @@ def build_model(kind: str = "birdnet_v24", seed: int = WEIGHT_SEED,
     two pointwise layers with the layer scale folded into the second, the residual -- on the mini front end: _build_convnext.
     'convnext_audio' (ConvNeXt-T's layout, widths 96 / 192 / 384 / 768 and depths 3 / 3 / 9 / 3, on the v2.4 front end, for timing the
     LayerNorm and 7x7 depthwise layers).  Both carry the un-folded layer scales in Model.convnext_scales.
+    'dense_plan' (plan = random_dense_plan(seed)) builds that plan's DenseNet blocks, transitions and pre-activation ResNet blocks around
+    norm + activation layers (mf.OP_BNACT) on the mini front end: _build_dense_plan.  'densenet_audio' (DenseNet-121's plan on the v2.4 front
+    end, for timing those layers and the concats between them: _build_densenet_audio).
     A stage tuple (expand, kernel, stride, cout, repeats) may carry a sixth element `fused`: True makes it Fused-MBConv.
     act: the activation between the convolutions (default: exact GELU, the north star's; mf.ACT_SWISH / ACT_RELU6 give the
     EfficientNet / MobileNet spellings of the same stack)."""
+    if kind == "dense_plan":
+        return _build_dense_plan(plan or random_dense_plan(seed), seed)
+    if kind == "densenet_audio":
+        return _build_densenet_audio(seed, n_classes)
     if kind == "cnn_pool":
         return _build_cnn_pool(seed, n_classes)
     if kind == "cnn14_audio":
@@ -535,6 +555,137 @@ def _cnn_pool_body(seed: int):
         c = width
     t = b.pwconv(t, h, w, c, 512, mf.ACT_RELU)
     return b, branches, sr, n, t, h, w
+
+
+# ---- DenseNet and pre-activation ResNets: norm + activation layers (mf.OP_BNACT) on concats, pool outputs and residual sums --------------
+def _dense_layer(b: _Builder, t, h, w, c, growth, bottleneck, act, conv_act=None):
+    """one DenseNet layer: act(bn(x)) -> [1x1 to `bottleneck` channels, its norm folded, act ->] 3x3 to `growth` channels -> cat(x, new)"""
+    y = b.bnact(t, h, w, c, act)
+    cy = c
+    if bottleneck:
+        y, cy = b.pwconv(y, h, w, c, bottleneck, act if conv_act is None else conv_act), bottleneck
+    y, _, _ = b.conv(y, h, w, cy, growth, 3, 1, mf.ACT_NONE)
+    return b.concat([(t, 0, c), (y, 0, growth)], h, w)
+
+
+def _preact_block(b: _Builder, t, h, w, c, kind, shortcut, cout, mid, act, conv_act=None):
+    """one pre-activation (v2) ResNet block at stride 1: p = act(bn(x)); basic: 3x3 (act) -> 3x3, bottleneck: 1x1 (act) -> 3x3 (act) -> 1x1;
+    + the shortcut -- x itself ('identity', cout == c) or a 1x1 convolution of p, the pre-activated tensor ('proj').  The sum carries no
+    activation: the next block's norm + activation layer reads it."""
+    assert shortcut in ("identity", "proj") and (shortcut == "proj" or cout == c)
+    p = b.bnact(t, h, w, c, act)
+    act = act if conv_act is None else conv_act
+    res = t if shortcut == "identity" else b.pwconv(p, h, w, c, cout, mf.ACT_NONE)
+    if kind == "basic":
+        y, _, _ = b.conv(p, h, w, c, mid, 3, 1, act)
+        y, _, _ = b.conv(y, h, w, mid, cout, 3, 1, mf.ACT_NONE, res=res, gain=0.5)
+    elif kind == "bottleneck":
+        y = b.pwconv(p, h, w, c, mid, act)
+        y, _, _ = b.conv(y, h, w, mid, mid, 3, 1, act)
+        y = b.pwconv(y, h, w, mid, cout, mf.ACT_NONE, res, gain=0.5)
+    else:
+        raise ValueError(kind)
+    return y
+
+
+def random_dense_plan(seed: int) -> dict:
+    """A small seeded DenseNet / pre-activation ResNet on the mini front end (one 32-mel branch, 115 frames of a quarter-second segment): a
+    3x3 stem and MaxPool 3x3 stride 2 pad 1 (a 16 x 58 image), a dense block, a transition (norm + activation, 1x1, AveragePool 2x2), then
+    pre-activation blocks -- basic and bottleneck, identity and projection shortcut --, an MBConv block with a residual and a second dense
+    block in a seeded order, and the tail: norm + activation, the global pool, the dense classes.  Every norm + activation layer reads a
+    pool output, a concat, a residual sum or (behind the first dense block's growth) a tensor of 20 .. 200 channels.  The activation is ReLU
+    on the even seeds and ReLU6 / swish / GELU (erf) / GELU (tanh) / hard swish in turn on the odd ones.  Feed to build_model("dense_plan",
+    plan=...).  plan["items"]: ("dense", layers, growth, bottleneck) | ("trans", cout) | ("preact", kind, shortcut, cout, mid) |
+    ("mb", expand, k, cout) -- an MBConv block keeps its width, so that it ends in a sum."""
+    rng = np.random.default_rng(0xDE25 + seed)
+    pick = lambda seq: seq[int(rng.integers(0, len(seq)))]
+    act = mf.ACT_RELU if seed % 2 == 0 else (mf.ACT_RELU6, mf.ACT_SWISH, mf.ACT_GELU_ERF, mf.ACT_GELU_TANH, mf.ACT_HSWISH)[(seed // 2) % 5]
+    c = stem_c = pick((16, 24))
+    growth = pick((8, 12, 16))
+    items = [("dense", int(rng.integers(2, 5)), growth, pick((0, 32, 4 * growth)))]
+    c += items[0][1] * growth
+    c = max(16, c // 2 // 4 * 4)
+    items.append(("trans", c))
+    tail = [("preact", "basic", "identity", c, c), ("preact", "bottleneck", "proj", pick((40, 72)), 32), ("mb", pick((4, 6)), pick((3, 5)), 0),
+            ("dense", int(rng.integers(2, 4)), pick((8, 16)), pick((0, 32)))]
+    for k in rng.permutation(len(tail)):
+        it = tail[int(k)]
+        if it[0] == "preact" and it[2] == "identity":
+            it = ("preact", pick(("basic", "bottleneck")), "identity", c, c if c <= 48 else 32)
+        elif it[0] == "mb":
+            it = ("mb", it[1], it[2], c)
+        items.append(it)
+        c = c + it[1] * it[2] if it[0] == "dense" else it[3]
+    # (the convolutions of a tanh-GELU plan take the erf form: the norm + activation layers alone carry the code the MFMA epilogues lack)
+    return {"items": items, "stem_c": stem_c, "act": int(act), "conv_act": int(mf.ACT_GELU_ERF if act == mf.ACT_GELU_TANH else act), "mb_act": int(mf.ACT_RELU6 if act == mf.ACT_RELU else mf.ACT_GELU_ERF if act == mf.ACT_GELU_TANH else act),
+            "classes": int(rng.integers(20, 61)), "out_act": int(pick((mf.OUT_SIGMOID, mf.OUT_SOFTMAX)))}
+
+
+def _build_dense_plan(plan: dict, seed: int = WEIGHT_SEED) -> mf.Model:
+    """random_dense_plan's stack on the mini front-end of one branch (512-sample frames at hop 100: 32 mels x 115 frames)."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 12000
+    br = mf.Branch(512, 100, 32, (n - 512) // 100 + 1, 0.0, 3000.0, 1.23)
+    br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+    br.out_scale, br.out_shift = 0.8, -0.4
+    act, mb_act, c = int(plan["act"]), int(plan["mb_act"]), int(plan["stem_c"])
+    conv_act = int(plan.get("conv_act", act))
+    t, h, w = b.conv(0, br.n_mels, br.n_frames, 1, c, 3, 1, conv_act, in_layout=1)
+    t, h, w = b.pool(t, h, w, c, 3, 3, 2, 2, mf.POOL_MAX, (1, 1, 1, 1))
+    for it in plan["items"]:
+        if it[0] == "dense":
+            _, layers, growth, bottleneck = it
+            for _ in range(layers):
+                t, c = _dense_layer(b, t, h, w, c, growth, bottleneck, act, conv_act)
+        elif it[0] == "trans":
+            t = b.bnact(t, h, w, c, act)
+            t = b.pwconv(t, h, w, c, it[1], mf.ACT_NONE)
+            c = it[1]
+            t, h, w = b.pool(t, h, w, c, 2, 2, 2, 2, mf.POOL_AVG, "valid")
+        elif it[0] == "preact":
+            _, kind, shortcut, cout, mid = it
+            t = _preact_block(b, t, h, w, c, kind, shortcut, cout, mid, act, conv_act)
+            c = cout
+        elif it[0] == "mb":
+            _, e, k, cout = it
+            assert cout == c, "an MBConv block of a dense plan keeps its width (it must end in a sum)"
+            t = _mb_block(b, t, h, w, c, e, k, cout, mb_act)
+        else:
+            raise ValueError(it[0])
+    t = b.bnact(t, h, w, c, act)
+    t = emb = b.gap(t, h, w, c)
+    ncls = int(plan["classes"])
+    b.dense(t, c, ncls, gain=1.5)
+    return _finish(b, [br], sr, n, ncls, c, emb, int(plan["out_act"]))
+
+
+def _build_densenet_audio(seed: int = WEIGHT_SEED, n_classes: Optional[int] = None) -> mf.Model:
+    """DenseNet-121 (Huang et al. 2017) on the v2.4 front-end (96 mels x 511 frames, two branches): a 7x7 stride-2 NCHW stem to 64 channels
+    with ReLU, MaxPool 3x3 stride 2 pad 1, four dense blocks of 6 / 12 / 24 / 16 layers -- relu(bn(x)) -> 1x1 to 128 -> relu -> 3x3 to 32,
+    cat --, between them the transitions relu(bn(x)) -> 1x1 to half the channels -> AveragePool 2x2, and the tail relu(bn(x)) -> global
+    pool -> dense: 1 024 features.  Seeded weights: a model for TIMING the norm + activation and concat layers, not for accuracy."""
+    b = _Builder(np.random.default_rng(seed))
+    sr, n = 48000, 144000
+    branches = [mf.Branch(2048, 278, 96, 511, 0.0, 3000.0, 1.23), mf.Branch(1024, 280, 96, 511, 500.0, 15000.0, 1.23)]
+    for br in branches:
+        br.mel_w_off = b.put(linear_to_mel_weight_matrix(br.n_mels, br.n_bins, sr, br.fmin, br.fmax))
+        br.out_scale, br.out_shift = 0.8, -0.4
+    t, h, w = b.conv(0, 96, 511, 2, 64, 7, 2, mf.ACT_RELU, in_layout=1)
+    t, h, w = b.pool(t, h, w, 64, 3, 3, 2, 2, mf.POOL_MAX, (1, 1, 1, 1))
+    c = 64
+    for bi, layers in enumerate((6, 12, 24, 16)):
+        for _ in range(layers):
+            t, c = _dense_layer(b, t, h, w, c, 32, 128, mf.ACT_RELU)
+        if bi < 3:
+            t = b.bnact(t, h, w, c, mf.ACT_RELU)
+            t = b.pwconv(t, h, w, c, c // 2, mf.ACT_NONE)
+            c //= 2
+            t, h, w = b.pool(t, h, w, c, 2, 2, 2, 2, mf.POOL_AVG, "valid")
+    t = b.bnact(t, h, w, c, mf.ACT_RELU)
+    t = emb = b.gap(t, h, w, c)
+    ncls = n_classes or 6522
+    b.dense(t, c, ncls, gain=1.5)
+    return _finish(b, branches, sr, n, ncls, c, emb, mf.OUT_SIGMOID)
 
 
 REDUCE_HEADS = ("panns", "global_max", "mean_then_max", "maxmean_both")

@@ -1,6 +1,6 @@
 """Byte-level fuzz of the library's model readers (FUZZ_BHM=1: also the flat BHM1 container through bh_plan_fused_blocks; bh_onnx_to_bhm: protobuf walk, conv-stack reader, front-end recovery with its
 float64 evaluator; FUZZ_F16=1: the seed files are float16 files -- convert.graph_to_float16 of the same graphs, front-end in float16 and in
-float32 by turns; FUZZ_BRANCHY=1: the seed files are synth's multi-branch plans, as graphs and as containers; FUZZ_MNV3=1: MobileNetV3-style plans -- HardSwish / HardSigmoid in every spelling the readers take; FUZZ_CONVNEXT=1: ConvNeXt plans -- Transpose, LayerNormalization as a node and as the decomposed chain, OP_LNORM records; FUZZ_REDUCE=1: reduce heads -- ReduceMax / ReduceMean over one axis or both, GlobalMaxPool, the max + mean Add, a leftover ArgMax, in every spelling the readers take, OP_REDUCE records) -- CPU only.  A model file is untrusted input: whatever the bytes, the call must RETURN (an error code and a
+float32 by turns; FUZZ_BRANCHY=1: the seed files are synth's multi-branch plans, as graphs and as containers; FUZZ_MNV3=1: MobileNetV3-style plans -- HardSwish / HardSigmoid in every spelling the readers take; FUZZ_CONVNEXT=1: ConvNeXt plans -- Transpose, LayerNormalization as a node and as the decomposed chain, OP_LNORM records; FUZZ_REDUCE=1: reduce heads -- ReduceMax / ReduceMean over one axis or both, GlobalMaxPool, the max + mean Add, a leftover ArgMax, in every spelling the readers take, OP_REDUCE records; FUZZ_BNACT=1: DenseNet / pre-activation ResNet plans -- BatchNormalization + activation nodes behind pools, concats and sums, the concats as pairs and as the growing list, OP_BNACT records) -- CPU only.  A model file is untrusted input: whatever the bytes, the call must RETURN (an error code and a
 message), never crash or hang.  Mutations of a small valid file: byte flips, varint bumps, truncations, spliced ranges.  Each batch
 runs in a child process so that a crash is seen as a signal, and every mutant has a time limit.
     python tools/fuzz_onnx_reader.py [n_mutants] [seed]"""
@@ -64,6 +64,13 @@ def main():
             m = synth.build_model("reduce_plan", seed=k)
             bases.append((".onnx", ox.dump(convert.graph_from_model(m, frontend_spelling=sp, spell_reduce=red))))
             q = os.path.join(d, f"reduce_{k}.bhm"); mf.write_model(q, m); bases.append((".bhm", open(q, "rb").read()))
+    if os.environ.get("FUZZ_BNACT"):   # ONLY dense plans: BatchNormalization + activation behind pools, concats and residual sums, both Concat spellings; containers with OP_BNACT records
+        from birda_amd import modelfile as mf
+        bases = []
+        for k, (sp, cat) in enumerate((("conv1d", "pair"), ("stft", "list"), ("conv1d", "list"), ("stft", "pair"))):
+            m = synth.build_model("dense_plan", seed=k)
+            bases.append((".onnx", ox.dump(convert.graph_from_model(m, frontend_spelling=sp, spell_concat=cat))))
+            q = os.path.join(d, f"dense_{k}.bhm"); mf.write_model(q, m); bases.append((".bhm", open(q, "rb").read()))
     paths = []
     for i in range(n):
         ext, raw = rng.choice(bases)
