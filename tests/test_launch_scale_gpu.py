@@ -5,13 +5,23 @@ most launches is resident at once.  A race between workgroups of one launch -- o
 share arena bytes (tests/test_arena_plan_gpu.py) -- stays hidden there: all of them are still in their read phase when the first
 ones write.  Here each model forces one path of forward_slice (birda_amd/csrc/api.hip) and 8 192 distinct segments go through it
 in ONE launch; every row must be bit-identical to the same segment run in launches of 16, and a spread of rows (the last ones
-included) must match the C oracle at the fp32 logit tolerance.
+included) must match the C oracle at the fp32 logit tolerance -- for the two families the oracle has no layers for, a multi-branch
+plan (OP_CONCAT, the one-launch chain) and a DenseNet / pre-activation plan (OP_BNACT), the float64 forwards of tests/test_concat.py
+and tests/test_bnact.py, at the same tolerance.
 
 Residency: 256 CUs x at most 8 workgroups of 256 threads (32 waves a CU) = 2 048 workgroups at once, an upper bound.  At 8 192
 segments the front end's min/max launch alone has at least one such workgroup per segment (4x that bound) and
   * the gate launches of a 3 840-channel chain: ceil(8 192 / 16) x ceil(3 840 / 256) = 512 x 15 = 7 680 workgroups (3.75x);
   * of a 672-channel chain: 512 x 3 = 1 536 -- not past the bound on their own, but behind the fused passes of 8 192 segments;
 so every forward below runs launches of at least 3x what the chip can hold.
+
+branchy_plan0 and dense_plan0 (synth.random_branchy_plan(0), synth.random_dense_plan(0): 44 layers each on 16 x 58-pixel images) run
+at N_BIG = 8 192 as well.  Their concat, pool and norm + activation launches are grid-stride loops capped at 256 x 8 = 2 048
+workgroups -- the bound itself, every one of them resident, each walking rows of many segments --, and the 1x1 convolutions between
+them are GEMMs of 8 192 x 928 rows at no more than 128 rows a workgroup: at least 59 392 workgroups a launch, 29x the bound.
+Time allowance of a new case: twice the slowest case the file had before, measured in the same run on one MI355X (the library and
+those cases are the parent commit's, unchanged): mini_b0 [f32] 1.15 s, so 2.30 s.  Measured: branchy_plan0 0.84 s (f32) and 0.56 s
+(f16x3), dense_plan0 0.52 s and 0.32 s, the float64 forward of 15 rows included -- no segment count had to be halved.
 """
 import os
 import time
@@ -19,8 +29,9 @@ import time
 import numpy as np
 import pytest
 
-from test_arena_plan_gpu import (FUSED_WIDE_SE_PLAN, PATH_FUSED, PATH_FUSED_SE, PATH_HEAD_GAP, PATH_SE_GATE, WIDE_GATE_PLAN,
-                                 arena_plan, tail_gate_model)
+from birda_amd import modelfile as mf
+from test_arena_plan_gpu import (FUSED_WIDE_SE_PLAN, PATH_CONCAT, PATH_FUSED, PATH_FUSED_SE, PATH_HEAD_GAP, PATH_LAYER, PATH_SE_GATE,
+                                 WIDE_GATE_PLAN, arena_plan, tail_gate_model)
 
 pytestmark = pytest.mark.gpu
 
@@ -34,6 +45,8 @@ def _build(kind, d):
     from birda_amd import modelfile as mf, synth
     m = {"wide_gate": lambda: synth.build_model("custom", plan=WIDE_GATE_PLAN),
          "fused_wide_se": lambda: synth.build_model("custom", plan=FUSED_WIDE_SE_PLAN),
+         "branchy_plan0": lambda: synth.build_model("branchy_plan", plan=synth.random_branchy_plan(0)),
+         "dense_plan0": lambda: synth.build_model("dense_plan", plan=synth.random_dense_plan(0)),
          "tail_gate": tail_gate_model}.get(kind, lambda: synth.build_model(kind))()
     path = os.path.join(str(d), f"{kind}.bhm")
     mf.write_model(path, m)
@@ -75,7 +88,21 @@ CASES = {
     "mini_se": _takes(PATH_FUSED_SE),                                                           # (c) se_gate_kernel
     "mini_hg": _takes(PATH_HEAD_GAP),                                                           # (d) head conv + pool
     "mini_b0": _takes(PATH_FUSED),                                                              # (e) plain fused blocks
+    "branchy_plan0": _takes(PATH_CONCAT),                                                       # (f) the one-launch concat chain
+    "dense_plan0": _takes(PATH_LAYER, lambda m, i: m.layers[i].op == mf.OP_BNACT),              # (g) norm + activation layers
 }
+
+
+def _reference(kind, path, m, x, oracle_lib):
+    """The yardstick's logits for the rows x: the C oracle, and for the two families it has no layers for (OP_CONCAT, OP_BNACT) the
+    float64 forwards of tests/test_concat.py and tests/test_bnact.py"""
+    if kind == "branchy_plan0":
+        from test_concat import forward64
+        return forward64(m, x)
+    if kind == "dense_plan0":
+        from test_bnact import forward64
+        return forward64(m, x)
+    return oracle_lib.OracleModel(path).forward(x)
 
 
 @pytest.mark.parametrize("precision", ["f32", "f16x3"])
@@ -97,11 +124,11 @@ def test_launch_past_residency_matches_small_launches_and_oracle(kind, precision
         big.close(); small.close(); clf.close()
     bad = np.flatnonzero((got != want).any(axis=1))
     rows = np.unique(np.concatenate([np.linspace(0, N_BIG - 1, N_ORACLE - 2).astype(int), [N_BIG - 2, N_BIG - 1]]))
-    ref = oracle_lib.OracleModel(path).forward(x[rows])
+    ref = _reference(kind, path, m, x[rows], oracle_lib)
     scale = max(1.0, float(np.abs(ref).max()))
     err = float(np.abs(got[rows] - ref).max())
     print(f"{kind} [{precision}]: {N_BIG} segments in one launch {t_big * 1e3:.1f} ms, in launches of {N_SMALL} {t_small * 1e3:.1f} ms; "
-          f"{len(bad)} rows differ; oracle max|dlogit| {err:.3e} on {len(rows)} rows (max|logit| {scale:.3f})")
+          f"{len(bad)} rows differ; reference max|dlogit| {err:.3e} on {len(rows)} rows (max|logit| {scale:.3f})")
     assert np.isfinite(got).all()
     assert len(bad) == 0, f"{len(bad)} of {N_BIG} rows differ from launches of {N_SMALL}, first {bad[:8].tolist()}"
     assert err <= LOGIT_RTOL * scale, (err, LOGIT_RTOL * scale)
